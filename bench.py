@@ -18,9 +18,18 @@ Workloads (config.workload in the JSON line)
               a step is one abr_mpc_select over all lanes; metric = combos/s.
   env_mpc     (configs[2]) MPC-driven rollout: every step = mpc_select + env step.
 
-Timing: W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both
-sides, max over ranks.  When K < --min-timed-steps that region is repeated (`repeats`) and the
-median repeat is reported, every repeat bracketed the same way.
+Timing: W untimed warm-up steps, then ONE region of EXACTLY K timed steps between barrier +
+synchronize on both sides, max over ranks; ms_per_step = that region's time / K.  Before it, one
+region of the same K steps with HIP events around every launch measures the kernel's own duration
+(`roofline`); it is instrumentation and no part of the timed figure.  Opt-in: when K <
+--min-timed-steps both regions are repeated (`repeats`) and the median repeat is reported, every
+repeat bracketed the same way (`timed_steps` = K x repeats).
+
+--dump-outputs DIR: after the timed steps, what the timed path computed in its LAST step -- the
+arrays its caller receives (env_random / env_mpc: obs [8, N], reward [N], done [N]; mpc: bitrate
+[N]) -- is written as DIR/<name>.npy in float32, a seeded sample of lanes (lane_index.npy) when
+all of it would exceed 64 MB.  Inputs depend on the arguments alone, so two builds run with the same
+arguments can be compared array for array.
 
 Output (rank 0, stdout): the JSON line of the task's contract -- printed as soon as the headline is measured (at N = 1 together
 with `roofline`, `cpu_baseline` and `selfcheck`, so that this first line is already complete), then printed AGAIN, grown by one
@@ -391,6 +400,33 @@ def _load_traffic(workload, kernel, lanes, fuse):
     return None
 
 
+DUMP_BUDGET_BYTES = 60 * 10 ** 6       # array bytes: under 64 MB however counted, the .npy headers included
+
+
+def write_dump(d, arrays, suffix="", budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: {name: array whose LAST axis is the lane} -> d/<name><suffix>.npy, float32 (float64 stays float64).
+    When the arrays would exceed `budget` bytes together, the same fixed, seeded sample of lanes is taken from every one of
+    them and its indices are written as lane_index.npy (float64).  Returns what was written, for the JSON line."""
+    arrays = {k: np.asarray(v) for k, v in arrays.items()}
+    arrays = {k: v if v.dtype == np.float64 else v.astype(np.float32) for k, v in arrays.items()}
+    n = {v.shape[-1] for v in arrays.values()}
+    assert len(n) == 1, {k: v.shape for k, v in arrays.items()}
+    n = n.pop()
+    total = sum(v.nbytes for v in arrays.values())
+    sampled = total > budget
+    if sampled:
+        per_lane = total // n + 8                          # + the lane index itself
+        idx = np.sort(np.random.default_rng(0).choice(n, budget // per_lane, replace=False))
+        arrays = {k: v[..., idx] for k, v in arrays.items()}
+        arrays["lane_index"] = idx.astype(np.float64)
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + suffix + ".npy"), np.ascontiguousarray(v))
+    return {"dir": d, "lanes": n, "sampled": sampled,
+            "arrays": {k + suffix: list(v.shape) for k, v in arrays.items()},
+            "bytes": int(sum(v.nbytes for v in arrays.values()))}
+
+
 # =====================================================================================================================
 # the run: one object holds what the blocks share; one method per block
 # =====================================================================================================================
@@ -410,10 +446,13 @@ def parse_args(argv=None):
     ap.add_argument("--mixed-traces", action="store_true", help="trace lengths 300..3000 (configs[4])")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--impl", default="auto", choices=["auto", "async", "split", "split3", "ring3", "pair3", "jump", "tick"])
-    ap.add_argument("--min-timed-steps", type=int, default=960,
-                    help="when --steps is smaller than this the timed region of exactly --steps steps is "
+    ap.add_argument("--min-timed-steps", type=int, default=0,
+                    help="opt-in: when --steps is smaller than this the timed region of exactly --steps steps is "
                          "repeated (each repeat bracketed by barrier + synchronize) and the MEDIAN repeat "
-                         "is reported, so that one sub-millisecond launch is not the whole sample")
+                         "is reported, so that one sub-millisecond launch is not the whole sample.  Default 0: "
+                         "one timed region of --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-sustained", action="store_true", help="env_random, N=1: skip the sustained block")
     ap.add_argument("--no-single-step", action="store_true", help="env_random, N=1: skip the single_step block (abr_env_step launches)")
@@ -571,6 +610,7 @@ class Run:
                        done=torch.empty(1, N, dtype=torch.uint8, device=dev), actions=None)
 
         pool = []
+        last = {}
 
         def run(n_steps, timed):
             if not timed:                                 # warm-up call: HIP events are created on their first record()
@@ -584,10 +624,17 @@ class Run:
                 if drive_env:
                     self.env.step_mpc(ctl, 1, out=mpc_out)       # K3 + K1 on the device, no host glue
                 else:
-                    ctl.next_bitrate()
+                    last["bitrate"] = ctl.next_bitrate()
                 if timed == "events":
                     e1 = pool.pop() if pool else torch.cuda.Event(enable_timing=True); e1.record()
                     events.append((e0, e1, 1))
+
+        def last_outputs():
+            """What the caller of the last step received: env_mpc obs [8, N], reward [N], done [N]; mpc bitrate [N]."""
+            if drive_env:
+                return {k: mpc_out[k][0] for k in ("obs", "reward", "done")}
+            return dict(last)
+        run.last_outputs = last_outputs
         return run
 
     def make_random_runner(self, env_, N_, F_, events_, use_graph, gather_on=True, total_lanes=None):
@@ -641,19 +688,27 @@ class Run:
                     e1 = take(); e1.record()
                     events_.append((e0, e1, F_))
                 info["last"] = (0, F_, info["n_done"]); info["n_done"] += F_
+                info["last_out"] = (sh._outs[0], F_)
                 left -= F_
             while left > 0:
                 f = min(F_, left)
                 evp = (take(), take()) if ev_on else None
                 b = sh._it & 1
-                sh.step_random(f, a.seed, events=evp)     # wait for the slab, launch, enqueue the all-gather
+                st = sh.step_random(f, a.seed, events=evp)     # wait for the slab, launch, enqueue the all-gather
                 if ev_on:
                     events_.append((evp[0], evp[1], f))
                 info["last"] = (b, f, info["n_done"]) if f == F_ else None
+                info["last_out"] = (st.local, f)
                 info["n_done"] += f
                 left -= f
             sh.finish()
+
+        def last_outputs():
+            """What the caller of the last step received (this rank's lanes): obs [8, N], reward [N], done [N]."""
+            out, f = info["last_out"]
+            return {k: out[k][f - 1] for k in ("obs", "reward", "done")}
         run_.info = info
+        run_.last_outputs = last_outputs
         return run_, gat_
 
     # ---- block: the headline ----
@@ -697,6 +752,7 @@ class Run:
         # records cost a region that is one launch ~7 us (5 % of the driver's 20-decision region, tools/gpu_event_cost.py), and
         # that is instrumentation, not workload.  Both series are in the line (repeat_seconds, repeat_seconds_with_events).
         self.times, self.times_ev = self.measure(self.run, K, self.repeats, phase="timed_region")
+        dump = self.dump_outputs() if a.dump_outputs else None
         self.elapsed = float(np.median(self.times))
         self.avg_launch_s, self.f_per_launch = self.launch_stats(self.ev)
         roof = self.env_roofline() if a.workload == "env_random" else self.mpc_roofline(self.avg_launch_s)
@@ -717,12 +773,22 @@ class Run:
                                  f"{self.gat.n_collectives if self.gat else 0}x" if gathering else "none")}
         if self.overrides:
             config["overrides"] = self.overrides
+        if dump:
+            config["dump_outputs"] = dump
         self.em.update(metric=self.metric, value=self.units_per_step * K / self.elapsed, unit=self.unit, n_gpus=self.world,
-                       steps=K, warmup=W, ms_per_step=self.elapsed / K * 1e3, higher_is_better=True,
+                       steps=K, warmup=W, timed_steps=K * self.repeats, ms_per_step=self.elapsed / K * 1e3,
+                       higher_is_better=True,
                        scaling="strong" if a.total_lanes else "weak", vs_baseline=None, dtype="f64", data="synthetic",
                        repeats=self.repeats, repeat_seconds=self.times, repeat_seconds_with_events=self.times_ev,
                        value_with_events=self.units_per_step * K / float(np.median(self.times_ev)),
                        config=config, roofline=roof, cpu_baseline=None)
+
+    def dump_outputs(self):
+        """--dump-outputs: the last timed step's outputs, read right after the timed regions (before any later block reuses
+        the buffers).  More than one rank: each rank writes its own lanes, <name>.rank<r>.npy."""
+        with self.wd.phase("dump_outputs"):
+            arrays = {k: v.cpu().numpy() for k, v in self.run.last_outputs().items()}
+            return write_dump(self.a.dump_outputs, arrays, suffix=f".rank{self.rank}" if self.world > 1 else "")
 
     def env_roofline(self):
         # algorithmic bytes per launch (DESIGN.md "Roofline"): per lane, state in + out once per

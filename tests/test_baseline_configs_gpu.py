@@ -555,3 +555,40 @@ def test_bench_default_line_carries_both_scaling_curves_two_ranks():
     cmd2 = [c for c in cmd if c != "--allow-overrides"]
     refused = subprocess.run(cmd2, env=env, capture_output=True, text=True, timeout=300)
     assert refused.returncode != 0 and "allow-overrides" in refused.stderr and not refused.stdout.strip()
+
+
+def test_bench_dump_outputs_is_the_last_timed_step_and_repeats(tmp_path):
+    """bench.py --dump-outputs: two runs with the same arguments write the same arrays, and they are what the LAST timed
+    decision handed its caller -- every lane replayed through the C oracle (bench.selfcheck_env).  Decisions run before it:
+    the warm-up (W), the region with HIP events (K) and the timed region (K), so the dumped one is decision W + 2K - 1."""
+    import json
+
+    import bench
+    N, K, W = 4096, 20, 5
+    lean = ["--no-cpu-baseline", "--no-secondary", "--no-sustained", "--no-single-step", "--no-mpc-rollout", "--no-strong"]
+
+    def run(d, *extra):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--lanes-per-gpu", str(N),
+               "--dump-outputs", d] + lean + list(extra)
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        return json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+
+    dumps = []
+    for i in range(2):
+        d = str(tmp_path / f"env{i}")
+        line = run(d, "--steps", str(K), "--warmup", str(W))
+        assert line["steps"] == K and line["timed_steps"] == K and line["repeats"] == 1 and line["ms_per_step"] > 0
+        assert line["config"]["dump_outputs"]["arrays"] == {"obs": [8, N], "reward": [N], "done": [N]}
+        dumps.append({k: np.load(os.path.join(d, k + ".npy")) for k in ("obs", "reward", "done")})
+    for k in dumps[0]:
+        assert dumps[0][k].dtype == np.float32 and np.array_equal(dumps[0][k], dumps[1][k]), k
+    g = dumps[0]
+    sc = dict(pick=np.arange(N), n0=W + 2 * K - 1, f=1, obs=g["obs"][None], reward=g["reward"][None], done=g["done"][None])
+    res = bench.selfcheck_env(sc, bench.synth_traces(), 0, 1)
+    assert res["mismatches"] == 0 and res["elements"] == 10 * N, res["first_mismatch"]
+
+    line = run(str(tmp_path / "mpc"), "--workload", "mpc", "--steps", "3", "--warmup", "1")
+    assert line["timed_steps"] == 3 and line["config"]["dump_outputs"]["arrays"] == {"bitrate": [N]}
+    b = np.load(str(tmp_path / "mpc" / "bitrate.npy"))
+    assert b.dtype == np.float32 and np.all((b >= 0) & (b < len(LADDER)) & (b == np.round(b)))

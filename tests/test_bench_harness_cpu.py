@@ -103,3 +103,40 @@ def test_workload_overrides_need_the_flag():
     assert bench.check_overrides(False, {"ABR_BENCH_INTERVAL": ""}) == {}          # unset-by-empty does not count
     a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
     assert not a.allow_overrides and a.dist_timeout == 90.0 and a.phase_timeout == 150.0
+
+
+def test_steps_alone_set_the_timed_steps():
+    """`--steps K` times exactly K steps: repeating a short region is opt-in (--min-timed-steps)."""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "20", "--warmup", "5"])
+    assert a.steps == 20 and a.min_timed_steps == 0 and a.dump_outputs is None
+    assert bench.parse_args(["--steps", "20", "--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float32_and_samples_lanes_over_budget(tmp_path):
+    """--dump-outputs' writer: every array as <name>.npy in float32 (float64 kept), lanes on the last axis; over the budget,
+    ONE fixed seeded lane sample taken from every array, its indices in lane_index.npy, and the files within the budget."""
+    import numpy as np
+
+    import bench
+    n = 1000
+    obs = np.arange(8 * n, dtype=np.float32).reshape(8, n)
+    arrays = {"obs": obs, "reward": np.linspace(0, 1, n), "done": (np.arange(n) % 3 == 0).astype(np.uint8)}
+    r = bench.write_dump(str(tmp_path / "all"), arrays)
+    assert not r["sampled"] and r["lanes"] == n and sorted(os.listdir(tmp_path / "all")) == ["done.npy", "obs.npy", "reward.npy"]
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "all" / (k + ".npy"))
+        assert got.dtype == (np.float64 if v.dtype == np.float64 else np.float32) and np.array_equal(got, v)
+    budget = 20000
+    r1 = bench.write_dump(str(tmp_path / "s1"), arrays, budget=budget)
+    r2 = bench.write_dump(str(tmp_path / "s2"), arrays, budget=budget)
+    assert r1["sampled"] and r1["arrays"] == r2["arrays"] and r1["bytes"] <= budget
+    idx = np.load(tmp_path / "s1" / "lane_index.npy")
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "lane_index.npy"))
+    li = idx.astype(np.int64)
+    assert len(li) > 0 and np.all(np.diff(li) > 0) and li[-1] < n
+    assert np.array_equal(np.load(tmp_path / "s1" / "obs.npy"), obs[:, li])
+    assert np.array_equal(np.load(tmp_path / "s1" / "done.npy"), arrays["done"][li].astype(np.float32))
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) < budget + 4 * 256
+    assert bench.write_dump(str(tmp_path / "r"), {"obs": obs}, suffix=".rank1")["arrays"] == {"obs.rank1": [8, n]}
+    assert os.path.exists(tmp_path / "r" / "obs.rank1.npy")
