@@ -78,6 +78,14 @@ class MpcOptions(C.Structure):
                 ("mask_is_done", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class RuleConfig(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("window", C.c_int32), ("reservoir", C.c_double), ("cushion", C.c_double),
+                ("safety", C.c_double), ("bola_v", C.c_double), ("bola_gp", C.c_double), ("utility_dev", C.c_void_p)]
+
+
+RULE_BUFFER, RULE_RATE, RULE_BOLA = 1, 2, 3
+
+
 class StateView(C.Structure):
     _fields_ = [("n_lanes", C.c_int64), ("chunk_id", C.c_void_p), ("last_bitrate", C.c_void_p),
                 ("buffer_level", C.c_void_p), ("hist_n", C.c_void_p), ("hist_sum_inv", C.c_void_p),
@@ -114,6 +122,8 @@ SYMBOLS = [
     ("abr_mpc_select_opt", C.c_int, [C.POINTER(MpcConfig), C.POINTER(MpcOptions), _P, _P, _P, _P, _P, _P,
                                      _P, _P, _P, _P, _P, C.c_int64, _P]),
     ("abr_env_step_mpc", C.c_int, [_P, C.POINTER(MpcConfig), _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("abr_env_step_rule", C.c_int, [_P, C.POINTER(RuleConfig), C.c_int32, _P, _P, _P, _P, _P]),
+    ("abr_env_rule_select", C.c_int, [_P, C.POINTER(RuleConfig), _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

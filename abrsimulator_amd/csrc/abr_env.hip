@@ -3,7 +3,9 @@
 // Hot path restated from the reference (file:line into Elliotshui/ABRSimulator):
 //   K1/K2 env_jump_kernel<MODE>     Simulator.py:95-133,135-208   event-driven, one thread per lane: the
 //         tick loop's float64 sequences advanced in exact closed form (abr_lane_jump.h,
-//         abr_exact_jump.h); MODE 0 reset, 1 step, 2 fused random-policy rollout, 3 fused scripted rollout
+//         abr_exact_jump.h); MODE 0 reset, 1 step, 2 fused random-policy rollout, 3 fused scripted rollout,
+//         4 fused rollout under a bitrate rule (BUFFER / RATE / BOLA: abr_lane_jump.h rule_select; rule_select_kernel
+//         is the same decision without a step)
 //   K1    env_split3_kernel<MODE>   the same lane functions on three waves per 64 lanes (download / player /
 //         service; abr_env_roles.h): what impl 3 (auto) runs up to kSplit3MaxLanes (65 536) lanes -- for launches of more
 //         than one decision; a single decision per launch goes to env_jump_kernel at every size
@@ -333,16 +335,26 @@ __device__ inline void write_obs(const Lane &s, const EnvParams &p, int64_t i, f
 // ep_qoe_terms[3] when the episode ends.  (Rounds 1-4 copied the episode's 48 actions aside at every auto-reset for K4 to
 // loop over: six dependent rounds of byte loads and stores per lane, ~10 us per episode end for the whole workgroup.)
 
+// MODE 4's action: a standard bitrate rule (abr_lane_jump.h: rule_select) on the lane's call-site state -- chunk_id,
+// buffer_level, and previous_bandwidths read back from the lane's bw_hist rows (coalesced: row stride n_lanes; the rows
+// of this launch's earlier decisions are the lane's own stores)
+__device__ inline int32_t rule_action(const EnvParams &p, const abrx::RuleParams &rule, int64_t i, int32_t c, double B) {
+    const auto br = [&](int32_t m) { return chunk_bitrate(p, c, m); };
+    const auto hist = [&](int32_t j) { return p.bw_hist[(int64_t)j * p.n_lanes + i]; };
+    return abrx::rule_select(rule, br, hist, p.n_rates, c, B);
+}
+
 // MODE 0: reset (fresh lanes run to their first call site)
 // MODE 1: step  (one externally supplied action per lane)
 // MODE 2: fused random-policy rollout of n_steps decisions per lane
 // MODE 3: fused rollout of n_steps scripted decisions per lane, actions[step][lane]
+// MODE 4: fused rollout of n_steps decisions per lane taken by a bitrate rule (`rule`; the other modes ignore it)
 template <int MODE>
 __global__ __launch_bounds__(64) void env_advance_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -457,10 +469,11 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                 int32_t a;
                 if (MODE == 1) a = actions[i];
                 else if (MODE == 3) a = actions[(int64_t)step_idx * p.n_lanes + i];
+                else if (MODE == 4) a = rule_action(p, rule, i, s.chunk_id, s.buf);
                 else a = (int32_t)philox_action(seed, (uint64_t)(p.lane_id_base + i),
                                                 (uint32_t)s.chunk_id, (uint32_t)episode_no,
                                                 (uint32_t)p.n_rates);
-                if (MODE == 2 && actions_out) actions_out[(int64_t)step_idx * p.n_lanes + i] = a;
+                if ((MODE == 2 || MODE == 4) && actions_out) actions_out[(int64_t)step_idx * p.n_lanes + i] = a;
                 need_action = false;
                 if (a < 0 || a >= p.n_rates) {
                     done |= ABR_DONE_BADACT;
@@ -551,7 +564,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                 const int64_t o = (int64_t)t * p.n_lanes + i;
                 if (reward_out) reward_out[o] = 0.0f;
                 if (done_out) done_out[o] = done;
-                if (MODE == 2 && actions_out) actions_out[o] = -1;
+                if ((MODE == 2 || MODE == 4) && actions_out) actions_out[o] = -1;
                 if (obs_out)
                     write_obs(s, p, i, obs_out + (int64_t)t * ABR_OBS_DIM * p.n_lanes, last_bw);
             }
@@ -656,14 +669,15 @@ __device__ inline void write_obs_vals(const LaneJ &s, const EnvParams &p, int64_
 #endif
 // MODE 1 (ONE decision per launch: abr_env_step, the K1 launches of abr_env_step_mpc -- what `auto` runs at every size) is
 // compiled for four waves: a single pass through a decision gains nothing from the fifth wave, and the 102-VGPR bound
-// cost it 12 B of scratch per lane (round 5).
-#define ABR_JUMP_BOUNDS(MODE) __launch_bounds__(64, ((MODE) == 1 ? 4 : ABR_JUMP_WAVES))
+// cost it 12 B of scratch per lane (round 5).  MODE 4 (a rule rollout) too: at five waves its rule loops push the
+// register bound into 36 B of spills, at four it keeps none.
+#define ABR_JUMP_BOUNDS(MODE) __launch_bounds__(64, ((MODE) == 1 || (MODE) == 4 ? 4 : ABR_JUMP_WAVES))
 template <int MODE>
 __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -713,6 +727,9 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
             const int64_t o = (int64_t)step * p.n_lanes + i;
             float *obs = obs_out ? obs_out + (int64_t)step * ABR_OBS_DIM * p.n_lanes : nullptr;
             if (active) {
+                // MODE 4: the rule runs BEFORE the step's burst of loads, so that its loops do not hold the burst's
+                // registers live (it decides chunk_id's download: nothing of the step is needed)
+                const int32_t a_rule = (MODE == 4) ? rule_action(p, rule, i, s.chunk_id, s.buf) : 0;
                 // one burst of loads for everything the step needs (issued before the
                 // policy arithmetic so that the two overlap)
                 const abrx::StepStart st = abrx::lanej_begin_step(s.cur, tb, s.k, s.chunk_id);
@@ -720,10 +737,11 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
                 int32_t a;
                 if (MODE == 1) a = actions[i];
                 else if (MODE == 3) a = actions[o];
+                else if (MODE == 4) a = a_rule;
                 else a = (int32_t)philox_action(seed, (uint64_t)(p.lane_id_base + i),
                                                 (uint32_t)s.chunk_id, (uint32_t)episode_no,
                                                 (uint32_t)p.n_rates);
-                if (MODE == 2 && actions_out) ABR_OUT(actions_out[o], a);
+                if ((MODE == 2 || MODE == 4) && actions_out) ABR_OUT(actions_out[o], a);
                 if (a < 0 || a >= p.n_rates) {
                     done |= ABR_DONE_BADACT;
                     if (reward_out) ABR_OUT(reward_out[o], 0.0f);
@@ -785,7 +803,7 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
                 // lanes already finished report their terminal record again
                 if (reward_out) ABR_OUT(reward_out[o], 0.0f);
                 if (done_out) ABR_OUT(done_out[o], (uint8_t)done);
-                if (MODE == 2 && actions_out) ABR_OUT(actions_out[o], (int32_t)-1);
+                if ((MODE == 2 || MODE == 4) && actions_out) ABR_OUT(actions_out[o], (int32_t)-1);
                 write_obs_j(s, p, i, obs, last_bw);
             }
         }
@@ -1251,7 +1269,7 @@ extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
     env->armed = true;
     hipLaunchKernelGGL(env->impl == 1 ? env_advance_kernel<0> : env_jump_kernel<0>, dim3(grid64(env->p.n_lanes)), dim3(64), 0,
                        (hipStream_t)stream, env->p, nullptr, trace_id_dev, start_offset_dev,
-                       lane_mask_dev, obs_out_dev, nullptr, nullptr, nullptr, 0, 0ull);
+                       lane_mask_dev, obs_out_dev, nullptr, nullptr, nullptr, 0, 0ull, abrx::RuleParams{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
@@ -1267,7 +1285,7 @@ extern "C" int abr_env_step(abr_env *env, const int32_t *actions_dev, float *obs
     else
         hipLaunchKernelGGL(impl ? env_advance_kernel<1> : env_jump_kernel<1>, dim3(grid64(env->p.n_lanes)), dim3(64), 0,
                            (hipStream_t)stream, env->p, actions_dev, nullptr, nullptr, nullptr,
-                           obs_out_dev, reward_out_dev, done_out_dev, nullptr, 1, 0ull);
+                           obs_out_dev, reward_out_dev, done_out_dev, nullptr, 1, 0ull, abrx::RuleParams{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
@@ -1299,7 +1317,8 @@ static int launch_fused(abr_env *env, const int32_t *script, int32_t n_steps, ui
         launch_split<MODE>(impl, env->p, script, obs, rew, dn, acts, n_steps, seed, st);
     else
         hipLaunchKernelGGL(impl ? env_advance_kernel<MODE> : env_jump_kernel<MODE>, dim3(grid64(N)), dim3(64), 0,
-                           st, env->p, script, nullptr, nullptr, nullptr, obs, rew, dn, acts, n_steps, seed);
+                           st, env->p, script, nullptr, nullptr, nullptr, obs, rew, dn, acts, n_steps, seed,
+                           abrx::RuleParams{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
@@ -1323,6 +1342,63 @@ extern "C" int abr_env_step_script(abr_env *env, int32_t n_steps, const int32_t 
     if (!actions_dev) return fail(ABR_E_INVALID, "actions_dev is NULL");
     return launch_fused<3>(env, actions_dev, n_steps, 0ull, obs_out_dev, reward_out_dev, done_out_dev,
                            nullptr, (hipStream_t)stream);
+}
+
+// ---------------------------------------------------------------------------
+// bitrate rules (include/abr_env.h: abr_rule_config)
+// ---------------------------------------------------------------------------
+static int validate_rule(const abr_rule_config *r, abrx::RuleParams *out) {
+    if (!r) return fail(ABR_E_INVALID, "rule is NULL");
+    if (r->kind != ABR_RULE_BUFFER && r->kind != ABR_RULE_RATE && r->kind != ABR_RULE_BOLA)
+        return fail(ABR_E_INVALID, "unknown rule kind %d", r->kind);
+    const double v[5] = {r->reservoir, r->cushion, r->safety, r->bola_v, r->bola_gp};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(ABR_E_INVALID, "rule parameters must be finite");
+    if (r->kind == ABR_RULE_BUFFER && !(r->reservoir >= 0.0 && r->cushion > 0.0))
+        return fail(ABR_E_INVALID, "BUFFER needs reservoir >= 0 and cushion > 0 (got %g, %g)", r->reservoir, r->cushion);
+    if (r->kind == ABR_RULE_RATE && r->window < 1) return fail(ABR_E_INVALID, "RATE needs window >= 1 (got %d)", r->window);
+    if (r->kind == ABR_RULE_RATE && !(r->safety > 0.0)) return fail(ABR_E_INVALID, "RATE needs safety > 0 (got %g)", r->safety);
+    if (r->kind == ABR_RULE_BOLA && !(r->bola_v > 0.0)) return fail(ABR_E_INVALID, "BOLA needs bola_v > 0 (got %g)", r->bola_v);
+    if (r->kind == ABR_RULE_BOLA && !r->utility_dev) return fail(ABR_E_INVALID, "BOLA needs utility_dev");
+    out->kind = r->kind; out->window = r->window;
+    out->reservoir = r->reservoir; out->cushion = r->cushion; out->safety = r->safety;
+    out->bola_v = r->bola_v; out->bola_gp = r->bola_gp; out->utility = r->utility_dev;
+    return ABR_OK;
+}
+
+// A rule rollout runs where the call-site state is at hand: the one-thread-per-lane kernel (`auto` at every size -- the
+// role-split kernels' download wave speculates ahead of the player, abr_env_roles.h) or the tick kernel (impl 1).
+extern "C" int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int32_t n_steps, float *obs_out_dev,
+                                 float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
+    abrx::RuleParams rp;
+    int rc = validate_rule(rule, &rp);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (env->impl != 0 && env->impl != 1 && env->impl != 3)
+        return fail(ABR_E_UNSUPPORTED, "rule rollouts run on impl 0 (jump), 1 (tick) or 3 (auto), not %d", env->impl);
+    hipLaunchKernelGGL(env->impl == 1 ? env_advance_kernel<4> : env_jump_kernel<4>, dim3(grid64(env->p.n_lanes)), dim3(64),
+                       0, (hipStream_t)stream, env->p, nullptr, nullptr, nullptr, nullptr, obs_out_dev, reward_out_dev,
+                       done_out_dev, actions_out_dev, n_steps, 0ull, rp);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+__global__ __launch_bounds__(256) void rule_select_kernel(EnvParams p, abrx::RuleParams rule, int32_t *__restrict__ action_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n_lanes) return;
+    action_out[i] = p.done[i] ? -1 : rule_action(p, rule, i, p.chunk_id[i], p.buf[i]);
+}
+
+extern "C" int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, int32_t *action_out_dev, void *stream) {
+    abrx::RuleParams rp;
+    int rc = validate_rule(rule, &rp);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument");
+    hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, env->p, rp, action_out_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
 }
 
 extern "C" int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out) {
@@ -2052,7 +2128,7 @@ extern "C" int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg,
             launch_split<1>(effective_impl(env), env->p, act, obs, rew, dn, nullptr, 1, 0ull, st);
         else
             hipLaunchKernelGGL(env_jump_kernel<1>, dim3(grid64(N)), dim3(64), 0, st, env->p, act, nullptr,
-                               nullptr, nullptr, obs, rew, dn, nullptr, 1, 0ull);
+                               nullptr, nullptr, obs, rew, dn, nullptr, 1, 0ull, abrx::RuleParams{});
         HIP_TRY(hipGetLastError());
     }
     return ABR_OK;

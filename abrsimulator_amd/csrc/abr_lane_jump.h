@@ -592,5 +592,69 @@ ABR_HD StepResult lanej_step(LaneJ &s, const Tables &t, double target, int32_t a
     return lanej_download_and_wait(s, t, st, target, action);
 }
 
+// ---- the standard bitrate rules, evaluated at a call site (include/abr_env.h: abr_rule_config) ----
+// Inputs are the arguments of get_next_bitrate (Simulator.py:155): c = chunk_id, B = buffer_level, h[0..c) =
+// previous_bandwidths oldest first, and br(m) = chunk c's bitrate m (per-chunk table or the ladder).  Everything is
+// float64 in a fixed operation order (the library builds with -ffp-contract=off), so a numpy twin written in the same
+// order reproduces every answer bit for bit.  `br` and `hist` are accessors, so that the kernels read the ladder and the
+// history rows straight from where they live (no copy into a local array, which would cost scratch).
+enum { kRuleBuffer = 1, kRuleRate = 2, kRuleBola = 3 };
+
+struct RuleParams {
+    int32_t kind, window;                    // kRule*; RATE: W >= 1
+    double reservoir, cushion;               // BUFFER: r >= 0, k > 0 [s]
+    double safety;                           // RATE: s > 0
+    double bola_v, bola_gp;                  // BOLA: V > 0, gp
+    const double *utility;                   // BOLA: [video_length][n_rates]
+};
+
+// the highest index m in 1..M-1 with br(m) <= X, else 0 (on an ascending ladder: the highest rate not above X)
+template <class BR>
+ABR_HD int32_t rule_hi(const BR &br, int32_t M, double X) {
+    int32_t a = 0;
+    for (int32_t m = 1; m < M; m++) a = br(m) <= X ? m : a;
+    return a;
+}
+
+// BBA-0 rate map (Huang et al. 2014) without hysteresis
+template <class BR>
+ABR_HD int32_t rule_buffer(const RuleParams &r, const BR &br, int32_t M, double B) {
+    if (B <= r.reservoir) return 0;
+    if (B >= r.reservoir + r.cushion) return M - 1;
+    const double lo = br(0);
+    return rule_hi(br, M, lo + ((B - r.reservoir) / r.cushion) * (br(M - 1) - lo));
+}
+
+// safety * harmonic mean of the last min(W, c) throughputs, summed oldest first
+template <class BR, class HIST>
+ABR_HD int32_t rule_rate(const RuleParams &r, const BR &br, const HIST &hist, int32_t M, int32_t c) {
+    const int32_t n = r.window < c ? r.window : c;
+    if (n <= 0) return 0;
+    double S = 0.0;
+    for (int32_t j = c - n; j < c; j++) S = S + 1.0 / hist(j);
+    return rule_hi(br, M, r.safety * ((double)n / S));
+}
+
+// BOLA-BASIC (Spiteri et al. 2016): argmax_m (V (u[c][m] + gp) - B) / br(m), the FIRST index of the maximum
+template <class BR>
+ABR_HD int32_t rule_bola(const RuleParams &r, const BR &br, int32_t M, int32_t c, double B) {
+    const double *u = r.utility + (int64_t)c * M;
+    double best = (r.bola_v * (u[0] + r.bola_gp) - B) / br(0);
+    int32_t a = 0;
+    for (int32_t m = 1; m < M; m++) {
+        const double sc = (r.bola_v * (u[m] + r.bola_gp) - B) / br(m);
+        a = sc > best ? m : a;
+        best = sc > best ? sc : best;
+    }
+    return a;
+}
+
+template <class BR, class HIST>
+ABR_HD int32_t rule_select(const RuleParams &r, const BR &br, const HIST &hist, int32_t M, int32_t c, double B) {
+    if (r.kind == kRuleBuffer) return rule_buffer(r, br, M, B);
+    if (r.kind == kRuleRate) return rule_rate(r, br, hist, M, c);
+    return rule_bola(r, br, M, c, B);
+}
+
 }  // namespace abrx
 #endif

@@ -276,6 +276,18 @@ class ShardedABREnv:
             return self.env.step_mpc(controller, n, out=out)
         return self._launch(n, call)
 
+    def step_rule(self, controller, n_steps):
+        """n_steps decisions taken by a bitrate rule (rules.py) on this shard's own state; as step_mpc, only (obs, reward)
+        is gathered."""
+        n = int(n_steps)
+
+        def call(out):
+            if out is not None and out.get("actions") is None:
+                out = dict(out)
+                out["actions"] = torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
+            return self.env.step_rule(controller, n, out=out)
+        return self._launch(n, call)
+
     @property
     def n_collectives(self):
         return self._gather.n_collectives if self._gather is not None else 0

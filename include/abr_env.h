@@ -400,6 +400,38 @@ int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg, const double *br_t
                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
                      void *stream);
 
+/*
+ * The standard ABR baselines as get_next_bitrate (Simulator.py:155), evaluated on the device at each lane's call site on
+ * exact float64 state: c = chunk_id, B = buffer_level, h[0..c) = previous_bandwidths oldest first, br[m] = chunk c's
+ * bitrate m (the abr_env_set_bitrate_table row, else config.ladder), M = n_rates.
+ * hi(X) = the last m in 1..M-1 with br[m] <= X, else 0 (on an ascending ladder: the highest rate not above X).
+ *  ABR_RULE_BUFFER  BBA-0 rate map (Huang et al. 2014), no hysteresis: B <= reservoir -> 0; B >= reservoir + cushion -> M-1;
+ *                   else hi(br[0] + ((B - reservoir) / cushion) * (br[M-1] - br[0])).
+ *  ABR_RULE_RATE    n = min(window, c); n == 0 -> 0; else S = sum over j = c-n .. c-1 (in that order) of 1.0 / h[j],
+ *                   hi(safety * (n / S)).
+ *  ABR_RULE_BOLA    BOLA-BASIC (Spiteri et al. 2016): the FIRST m maximising (bola_v * (u[c][m] + bola_gp) - B) / br[m],
+ *                   u = utility_dev [video_length][n_rates] float64 (caller-computed, e.g. ln(br[c][m] / br[c][0])).
+ * Every operation is float64 in the order written (the library is built with -ffp-contract=off).  Validation (before the
+ * handle is looked at; ABR_E_INVALID, nothing launched): kind, finite parameters, reservoir >= 0, cushion > 0, window >= 1,
+ * safety > 0, bola_v > 0, utility_dev != NULL for BOLA, n_steps >= 1.
+ */
+enum { ABR_RULE_BUFFER = 1, ABR_RULE_RATE = 2, ABR_RULE_BOLA = 3 };
+typedef struct abr_rule_config {
+    int32_t kind, window;
+    double reservoir, cushion, safety, bola_v, bola_gp;
+    const double *utility_dev;      /* BOLA: [video_length][n_rates] float64 */
+} abr_rule_config;
+
+/* n_steps fused decisions per lane taken by the rule, with no host work between decisions.  Outputs (all nullable) as
+ * abr_env_step_random; lanes whose done bits are set take no decision (action -1) and stay frozen.  Kernels: `auto` (3) and
+ * 0 run the one-thread-per-lane kernel at every size, 1 the tick kernel; 2 and 5 answer ABR_E_UNSUPPORTED (their download
+ * wave runs ahead of the player and does not know the call-site buffer level). */
+int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int32_t n_steps, float *obs_out_dev,
+                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream);
+/* The rule's answer for each lane on the environment's current state, no step: action_out_dev int32 [n_lanes], -1 for a
+ * lane whose done bits are set. */
+int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, int32_t *action_out_dev, void *stream);
+
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
 int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t prev_bitrate,
