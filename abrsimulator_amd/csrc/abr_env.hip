@@ -1489,6 +1489,7 @@ struct MpcParams {
     const uint8_t *mask;
     int32_t mask_is_done;      // mask[] holds ABR_DONE_* bits: a lane is active iff its byte is 0
     int32_t neg_to_zero;       // report "no decision" (-1: D13 / D12) as bitrate 0 in action_out
+    int32_t careful_all;       // L, max_buffer or a weight is outside the fast path's range: every lane takes mpc_scan_careful
     int32_t *action_out, *flat_out;
     double *J_out;
 };
@@ -1644,6 +1645,51 @@ __device__ inline int32_t mpc_resolve_group(const MpcLds &t, int H, int32_t gfla
     return 0x7fffffff;    // not in this group
 }
 
+// The search above keeps x = -J in registers with fmax and strict `>`: exact while every x is finite,
+// but fmax drops a NaN and an all -inf lane never takes a winner.  It is used only where every value
+// it forms is provably finite: each table entry and the buffer at most 2^960 in magnitude, L and
+// max_buffer too, and each weight at most 2^40 (then no partial sum of the H <= 8 levels, nor a
+// weighted one, exceeds 2^1010).  Every other lane takes this scan.
+constexpr double kMpcFastEntryMax = 0x1p960;
+constexpr double kMpcFastWeightMax = 0x1p40;
+constexpr int kMpcCareful = 0x100;    // flag bit beside the effective horizon (heff_s) of a lane that takes the scan below
+
+// The careful scan: thread `pre` of the lane's T evaluates its contiguous share of the B^heff
+// combinations, each from scratch in objective()'s operation order (mpc.py:144-162, the startup
+// term included), and keeps what numpy's argmin over the raveled grid keeps (scipy brute,
+// finish=None): its first NaN, else its first maximum of x = -J (the first leaf is always taken,
+// so an all -inf share has a winner).  best.idx is the leaf itself; phase 4 ranks a NaN above
+// every number.
+__device__ inline void mpc_scan_careful(const MpcLds &t, double ws, int prev0, double buf0, int pre, int T,
+                                        Best &best) {
+    const int B = t.B, he = t.heff;
+    int32_t total = 1;
+    for (int i = 0; i < he; i++) total *= B;                 // <= 2e9 (validate_mpc)
+    const int32_t share = total / T + (total % T != 0);
+    const int32_t f0 = (int32_t)min((int64_t)pre * share, (int64_t)total);
+    const int32_t f1 = (int32_t)min((int64_t)f0 + share, (int64_t)total);
+    for (int32_t f = f0; f < f1; f++) {
+        int32_t pw = total / B;
+        double q = 0.0, v = 0.0, rb = 0.0, buf = buf0;
+        double bp = t.brv[prev0];
+        for (int lvl = 0; lvl < he; lvl++) {
+            const int r = (f / pw) % B;
+            pw = (pw >= B) ? pw / B : 1;
+            const double b = t.brv[lvl * B + r];
+            q = q + b; v = v + fabs(b - bp); rb = rb + (t.rbt[lvl * B + r] - buf);
+            if (lvl + 1 < he) {
+                const double tmp = pymax0(buf - t.tdl[lvl * B + r]);
+                const double wait = pymax0(tmp + t.L - t.max_buffer);
+                buf = pymax0(tmp + t.L - wait);
+                bp = t.brv[(lvl + 1) * B + r];
+            }
+        }
+        const double x = ((q - t.wv * v) - t.wr * rb) - ws * 0.0;
+        if (x != x) { best.x = x; best.idx = f; return; }
+        if (best.idx == 0x7fffffff || x > best.x) { best.x = x; best.idx = f; }
+    }
+}
+
 // Phase 1 of K3 for one lane: validates chunk / previous_bitrate, runs the throughput predictor
 // (growing the caller's history, D9, in the harmonic branch) and writes the H predictions to
 // pred[i * stride].  Returns the effective horizon (0 = no decision); prev_out = previous_bitrate
@@ -1692,12 +1738,18 @@ __device__ inline int mpc_predict_lane(const MpcParams &p, int64_t lane, int B, 
         // here as "no decision": history untouched, action -1.
         return 0;
     }
+    bool zero = false;
     for (int i = 0; i < H; i++) {
         double tp = n / S;            // history_size / sum_inverse  (:90)
+        zero = zero || !(tp > 0.0);
         pred[(int64_t)i * stride] = tp;
         S = S + 1.0 / tp;             // throughput_values.append(tp): next pass sums it last
         n = n + 1.0;
     }
+    // a zero prediction (S overflowed to inf): the reference divides by it -- 1/x of the appended value on
+    // the next pass (:88) or size/bandwidth in objective() (:151) -- and raises ZeroDivisionError.  Defined
+    // as for D13: no decision, history untouched.
+    if (zero) return 0;
     p.hist_n[lane] = n; p.hist_s[lane] = S;    // D9: the caller's list has grown by H
     return he;
 }
@@ -1726,7 +1778,7 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
     // layout per lane-in-block: brv[HB] rbt[HB] tdl[HB] pred[H]
     const int per_lane = 3 * HB + H;
     double *tab = lds;
-    __shared__ int32_t heff_s[16];
+    __shared__ int32_t heff_s[16];    // effective horizon; phase 2 sets the kMpcCareful bit of a lane that takes mpc_scan_careful
     __shared__ int32_t prev_s[16];    // previous_bitrate as the index Python would use (mpc.py:132,148)
     __shared__ unsigned long long bestK[16];   // phase 4: the lane's maximum of x = -J as an ordered key
     __shared__ int32_t bestF[16];              //          and the smallest flat index that reaches it
@@ -1760,7 +1812,8 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
     // ---- phase 2: the per-(level, rate) tables, 60 divisions per lane spread over T threads ----
     if (valid) {
         const int c = p.chunk[lane];
-        const int he = heff_s[li];
+        const int he = heff_s[li] & (kMpcCareful - 1);
+        bool careful = p.careful_all || (pre == 0 && !(fabs(p.buffer[lane]) <= kMpcFastEntryMax));
         for (int e = pre; e < HB; e += T) {
             const int i = e / B, r = e - i * B;
             if (i < he) {
@@ -1772,17 +1825,26 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
                 const double bre = p.br[(int64_t)(c + i) * B + r];
                 // utility 1: log_bitrate_utility with the arity its call sites need (mpc.py:99-102,
                 // :146-149): u = log(bitrate / top bitrate of that chunk).  PARITY UNPINNED.
-                my[e] = p.utility == 1 ? log(bre / p.br[(int64_t)(c + i) * B + (B - 1)]) : bre;
-                my[HB + e] = m / pr;
-                my[2 * HB + e] = p.sz[(int64_t)c * B + r] / pr;
+                const double u = p.utility == 1 ? log(bre / p.br[(int64_t)(c + i) * B + (B - 1)]) : bre;
+                const double rt = m / pr, td = p.sz[(int64_t)c * B + r] / pr;
+                my[e] = u; my[HB + e] = rt; my[2 * HB + e] = td;
+                careful |= !(fabs(u) <= kMpcFastEntryMax) | !(rt <= kMpcFastEntryMax) | !(fabs(td) <= kMpcFastEntryMax);
             }
         }
+        // (every writer stores the same value; an LDS atomic here measured 3 % slower on the whole kernel)
+        if (careful && he > 0) heff_s[li] = he | kMpcCareful;
     }
     __syncthreads();
     K3_STAMP(27);
     // ---- phase 3: each thread walks its prefix, then enumerates its subtree ----
     Best best; best.x = -INFINITY; best.idx = 0x7fffffff; best.m = -INFINITY;
-    if (valid && heff_s[li] > 0) {
+    if (valid && heff_s[li] > kMpcCareful) {
+        MpcLds t;
+        t.brv = my; t.rbt = my + HB; t.tdl = my + 2 * HB;
+        t.L = p.L; t.max_buffer = p.max_buffer; t.wv = p.wv; t.wr = p.wr; t.B = B;
+        t.heff = heff_s[li] - kMpcCareful;
+        mpc_scan_careful(t, p.ws, prev_s[li], p.buffer[lane], pre, T, best);
+    } else if (valid && heff_s[li] > 0) {
         MpcLds t;
         t.brv = my; t.rbt = my + HB; t.tdl = my + 2 * HB;
         t.L = p.L; t.max_buffer = p.max_buffer; t.wv = p.wv; t.wr = p.wr; t.B = B;
@@ -1845,7 +1907,8 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
     //      and two barriers: the maximum of x as an order-preserving 64-bit key (ds_max_u64), then
     //      the smallest flat index among the threads that hold it (ds_min_i32) -- the same winner
     //      as a left-to-right scan with strict `>` (round 2 used a pairwise tree: six barriers).
-    //      x + 0.0 folds -0.0 into +0.0 so that equal values have equal keys; a NaN never wins. ----
+    //      x + 0.0 folds -0.0 into +0.0 so that equal values have equal keys.  A NaN (only the careful
+    //      scan keeps one) takes the largest key: numpy's argmin returns the first NaN. ----
     if (!valid && pre == 0 && li < LPB && lane < p.n_lanes && p.mask_is_done)
         p.action_out[lane] = -1;          // a finished lane of the fused rollout takes no decision
     unsigned long long key = 0;
@@ -1853,7 +1916,8 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
         const double xc = best.x + 0.0;
         const unsigned long long u = (unsigned long long)__double_as_longlong(xc);
         key = (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-        if (!(xc == xc) || best.idx == 0x7fffffff) key = 0;
+        if (!(xc == xc)) key = ~0ull;
+        if (best.idx == 0x7fffffff) key = 0;
     }
     if (li < LPB && key) atomicMax(&bestK[li], key);
     __syncthreads();
@@ -1871,7 +1935,7 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
             const unsigned long long bk = bestK[l2];
             const int32_t bf = bestF[l2];
             // (a masked or out-of-range lane has bk == 0: none of its threads entered a key)
-            if (bk != 0 && bf != 0x7fffffff && heff_s[l2] == H) {
+            if (bk != 0 && bf != 0x7fffffff && heff_s[l2] == H) {     // (never a careful lane: its bestF is the leaf)
                 const unsigned long long bu = (bk >> 63) ? (bk & 0x7fffffffffffffffull) : ~bk;
                 const double *my2 = tab + l2 * per_lane;
                 MpcLds t;
@@ -1897,7 +1961,7 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
             const int he = heff_s[l2];
             int32_t act = -1;
             if (have) {
-                if (he == H) {
+                if (he == H) {                      // (not a careful lane: its bestF is the leaf itself)
                     if (H >= 4) {
                         // always found: the maximum came out of this very arithmetic (else: the node's first leaf)
                         const int32_t fl = bestL[l2];
@@ -1912,7 +1976,7 @@ void mpc_select_kernel(MpcParams p, int T, int D, int LPB) {
                     }
                 }
                 int32_t lead = 1;
-                for (int i = 1; i < he; i++) lead *= B;
+                for (int i = 1; i < (he & (kMpcCareful - 1)); i++) lead *= B;
                 act = bf / lead;                                   // int(result[0])  mpc.py:186
             }
             p.action_out[lane2] = (p.neg_to_zero && act < 0) ? 0 : act;
@@ -1979,6 +2043,9 @@ static void fill_mpc_params(MpcParams &p, const abr_mpc_config *cfg, int64_t n_l
     p.L = cfg->chunk_length; p.max_buffer = cfg->max_buffer; p.wv = cfg->variance_weight;
     p.wr = cfg->rebuffer_weight; p.ws = cfg->startup_weight; p.n_lanes = n_lanes;
     p.mask = nullptr; p.mask_is_done = 0; p.neg_to_zero = 0;
+    p.careful_all = !(fabs(p.L) <= kMpcFastEntryMax && fabs(p.max_buffer) <= kMpcFastEntryMax &&
+                      fabs(p.wv) <= kMpcFastWeightMax && fabs(p.wr) <= kMpcFastWeightMax &&
+                      fabs(p.ws) <= kMpcFastWeightMax);
     p.predictor = 0; p.utility = 0; p.hist = nullptr; p.hist_stride = 0; p.hist_len = nullptr;
     p.pre_pred = nullptr; p.pre_he = nullptr; p.pre_prev = nullptr;
     p.pre_pred_w = nullptr; p.pre_he_w = nullptr; p.pre_prev_w = nullptr;

@@ -314,9 +314,14 @@ typedef struct abr_mpc_config {
  *  previous_bitrate indexes the ladder as Python does (mpc.py:132,148): -n_rates..-1 wrap to
  *  the top (the env's "no previous chunk" value -1 means the highest rate).
  *  Lanes the reference would raise on report action -1 (flat -1, J NaN) and keep their
- *  history: an empty or zero history (ZeroDivisionError, mpc.py:88,90, D13), a
- *  previous_bitrate outside [-n_rates, n_rates) (IndexError) and, without clip_horizon,
- *  chunk + horizon > video_length (IndexError, mpc.py:126, D12).
+ *  history: an empty or zero history (ZeroDivisionError, mpc.py:88,90, D13), a predicted
+ *  throughput of 0.0 (the sum of reciprocals overflowed: ZeroDivisionError at mpc.py:88 on
+ *  the next pass or at mpc.py:151), a previous_bitrate outside [-n_rates, n_rates)
+ *  (IndexError) and, without clip_horizon, chunk + horizon > video_length (IndexError,
+ *  mpc.py:126, D12).
+ *  Non-finite objectives follow np.argmin over the grid, as scipy's brute does: the first
+ *  combination whose J is NaN wins (flat >= 0, J NaN); with no NaN the first minimum wins,
+ *  so a grid where every J is +inf gives combination 0 (J = +inf).
  */
 int abr_mpc_select(const abr_mpc_config *cfg, const int32_t *chunk_dev,
                    const int32_t *prev_bitrate_dev, const double *buffer_dev, double *hist_n_dev,

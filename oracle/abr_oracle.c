@@ -381,9 +381,10 @@ double oracle_mpc_objective(const oracle_mpc_cfg *c, const double *br, const dou
     return -qoe_sum;
 }
 
-/* optimize_qoe + scipy.optimize.brute(finish=None): C-order grid, first
- * minimum (mpc.py:171-179).  J_out (B^H doubles) may be
- * NULL.  Returns the flat arg-min; *Jmin its value. */
+/* optimize_qoe + scipy.optimize.brute(finish=None): C-order grid, np.argmin of
+ * the raveled grid (mpc.py:171-179): the first NaN if the
+ * grid holds one, else the first minimum (an all-+inf grid gives 0).  J_out
+ * (B^H doubles) may be NULL.  Returns the flat arg-min; *Jmin its value. */
 int64_t oracle_mpc_brute(const oracle_mpc_cfg *c, const double *br, const double *sz,
                          int chunk, int prev_bitrate, double buffer_level, const double *pred,
                          double *J_out, double *Jmin)
@@ -399,7 +400,7 @@ int64_t oracle_mpc_brute(const oracle_mpc_cfg *c, const double *br, const double
         for (int i = H - 1; i >= 0; i--) { R[i] = (int32_t)(t % B); t /= B; }
         double J = oracle_mpc_objective(c, br, sz, chunk, prev_bitrate, buffer_level, pred, R);
         if (J_out) J_out[f] = J;
-        if (J < bestJ || f == 0) { bestJ = J; best = f; }     /* numpy argmin: first minimum */
+        if (f == 0 || (bestJ == bestJ && (J < bestJ || J != J))) { bestJ = J; best = f; }
     }
     if (Jmin) *Jmin = bestJ;
     return best;

@@ -151,6 +151,26 @@ def test_mpc_validation(L):
     assert lib.abr_mpc_select(C.byref(m), None, *args[1:], 4, None) == -1   # NULL pointer
 
 
+def test_mpc_grid_size_boundary(L):
+    """validate_mpc accepts n_rates^horizon up to 2e9 -- the largest such grid, 14^8 = 1 475 789 056, keeps every flat
+    index inside int32 -- and refuses every larger one (15^8, 16^8, ..) with ABR_E_UNSUPPORTED."""
+    lib = L.lib()
+    m = L.MpcConfig()
+    m.video_length = 48
+    need = C.c_size_t()
+    accepted = []
+    for B in range(1, 17):
+        for H in range(2, 9):
+            m.n_rates, m.horizon = B, H
+            rc = lib.abr_mpc_scratch_bytes(C.byref(m), 4, C.byref(need))
+            assert rc == (-4 if B ** H > 2e9 else 0), (B, H, rc)
+            if rc == 0:
+                accepted.append(B ** H)
+    assert max(accepted) == 14 ** 8 < 2 ** 31 - 1
+    m.n_rates, m.horizon = 15, 8
+    assert lib.abr_mpc_scratch_bytes(C.byref(m), 4, C.byref(need)) == -4
+
+
 def test_product_never_imports_the_oracle():
     """The oracle is test infrastructure; the product path must not reach it: no
     import, include, dlopen or path reference anywhere under abrsimulator_amd/."""

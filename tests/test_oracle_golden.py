@@ -134,6 +134,36 @@ def test_mpc_sweep_bit_exact(oracle, name):
         assert f == g["flat"][i]
 
 
+def test_mpc_nonfinite_bit_exact(oracle):
+    """Objective grids holding +inf or NaN (tools/gen_golden.py: NONFINITE_LANES): the brute force keeps what
+    np.argmin keeps -- the first NaN, else the first minimum, index 0 when every J is +inf -- and its grid equals the
+    reference's element for element.  Lanes the reference raises on predict a bandwidth of exactly 0.0."""
+    m, g = load_golden("mpc_nonfinite")
+    B, kinds = m["n_rates"], m["kinds"]
+    assert {k: kinds.count(k) for k in set(kinds)} == {"finite": 5, "all_inf": 2, "some_inf": 3, "all_nan": 2,
+                                                       "mixed": 6, "raises": 3}
+    for i, kind in enumerate(kinds):
+        H = int(g["H"][i])
+        cfg = oracle.mpc_cfg(B, H, m["video_length"], m["chunk_length"], m["max_buffer"], g["wv"][i], g["wr"][i],
+                             m["startup_weight"])
+        pred, n_after, s_after = oracle.mpc_predict_ns(H, g["hist_n"][i], g["hist_s"][i])
+        if kind == "raises":
+            assert g["raises"][i] == 1 and (pred == 0.0).any(), i
+            assert g["action"][i] == -1 and g["flat"][i] == -1 and np.isnan(g["Jmin"][i])
+            continue
+        assert g["raises"][i] == 0
+        assert np.array_equal(pred, g["pred"][i, :H]), i
+        assert n_after == g["hist_n_after"][i] and s_after == g["hist_s_after"][i], i
+        f, Jm, J = oracle.mpc_brute(cfg, g["br"], g["sz"], g["chunk"][i], g["prev"][i], g["buf"][i], pred)
+        assert np.array_equal(J, g["Jfull"][i, :B ** H], equal_nan=True), i
+        assert f == g["flat"][i] and f // B ** (H - 1) == g["action"][i], (i, kind, f, g["flat"][i])
+        assert np.array_equal(Jm, g["Jmin"][i], equal_nan=True), i
+        if kind == "mixed":
+            assert np.isnan(Jm) and np.isfinite(J).any()
+        if kind == "all_inf":
+            assert f == 0 and Jm == np.inf
+
+
 @pytest.mark.parametrize("name", ["env_bench_shape", "env_starved_i03", "env_speed125", "env_l3_i07"])
 def test_pure_python_restatement_bit_exact(name):
     """oracle/pyloop.py (the interpreter-baseline twin) against the same fixtures."""

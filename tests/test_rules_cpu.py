@@ -266,9 +266,9 @@ def test_controller_defaults_and_errors():
     assert np.array_equal(A.BolaController(_Stub(vbr)).utility[:, 1], np.log([2.0, 4.0, 3.0]))
 
 
-def test_mode4_instances_have_no_scratch_and_no_calls():
-    """make asm: env_jump_kernel<4>, env_advance_kernel<4> and rule_select_kernel exist with a 0 B private segment and no
-    calls."""
+def _product_asm():
+    """The product's ISA (`make asm`: abrsimulator_amd/csrc/abr_env.s), regenerated when older than its sources; skips
+    without hipcc."""
     src = os.path.join(ROOT, "abrsimulator_amd", "csrc")
     asm = os.path.join(src, "abr_env.s")
     deps = [os.path.join(src, f) for f in os.listdir(src) if f.endswith((".hip", ".h"))]
@@ -277,7 +277,13 @@ def test_mode4_instances_have_no_scratch_and_no_calls():
         if not (shutil.which("hipcc") or os.path.exists("/opt/rocm/bin/hipcc")):
             pytest.skip("no hipcc here: the ISA cannot be regenerated")
         subprocess.run(["make", "-C", src, "-s", "asm"], check=True, capture_output=True, timeout=600)
-    text = open(asm).read()
+    return open(asm).read()
+
+
+def test_mode4_instances_have_no_scratch_and_no_calls():
+    """make asm: env_jump_kernel<4>, env_advance_kernel<4> and rule_select_kernel exist with a 0 B private segment and no
+    calls."""
+    text = _product_asm()
     found = set()
     for name, desc in re.findall(r"^\s*\.amdhsa_kernel\s+(\S+)\n(.*?)\.end_amdhsa_kernel", text, re.S | re.M):
         k = re.search(r"env_(jump|advance)_kernelILi4E|rule_select_kernel", name)
@@ -288,3 +294,14 @@ def test_mode4_instances_have_no_scratch_and_no_calls():
         body = re.search(r"^" + re.escape(name) + r":.*?^\.Lfunc_end\d+:", text, re.S | re.M).group(0)
         assert "s_swappc" not in body and "s_setpc" not in body, name
     assert found == {"jump", "advance", "select"}
+
+
+def test_mpc_case_table_covers_every_compiled_search_instance():
+    """tests/mpc_matrix.py: the mpc_select_kernel<H, BC, WVM> instances the case table dispatches to (launch_mpc's rule
+    as data) are exactly the ones compiled -- 52 today.  An instance added to the dispatch, or a case dropped from the
+    table, fails here until the GPU parity tests (test_mpc_instances_gpu.py) run it."""
+    from mpc_matrix import MPC_CASES, isa_instances, mpc_instance
+    compiled = isa_instances(_product_asm())
+    covered = {mpc_instance(B, H, wv) for B, H, wv in MPC_CASES}
+    assert covered == compiled, (sorted(compiled - covered), sorted(covered - compiled))
+    assert len(compiled) == 52

@@ -418,6 +418,106 @@ def gen_mpc(mpc, a_only=""):
         ties = sum(1 for g in rec["gap"] if g == 0.0)
         print(f"{name}: {n} cases, exact ties in {ties}, smallest nonzero gap "
               f"{min([g for g in rec['gap'] if g > 0] or [0]):.3e}")
+    if a_only in ("", "mpc_nonfinite"):
+        gen_mpc_nonfinite(mpc)
+
+
+# Non-finite objectives.  A throughput history of one tiny value x predicts x at every step
+# (S_i = (i + 1) / x): max(size, L) / x overflows, or the rebuffer sum over the H levels does, so
+# every J is +inf with rebuffer_weight > 0 and NaN (0 * inf) with rebuffer_weight = 0.  Chunks
+# HUGE_FROM and HUGE_FROM + 1 carry sizes near 1e306 at the upper three rates: there a small x
+# overflows only the combinations that pick one of them, so the grid mixes finite values with
+# +inf or NaN.  When S itself overflows a prediction is 0.0 and the reference raises
+# ZeroDivisionError: in the predictor (1/0.0, mpc.py:88) or in objective() (size/0.0, mpc.py:151).
+HUGE_FROM = 16
+#   kind        H  (wr, wv)    history              chunk (None: drawn below HUGE_FROM)
+NONFINITE_LANES = [
+    ("finite",   3, (4.3, 1.0), None,                None),
+    ("finite",   3, (4.3, 1.0), None,                None),
+    ("all_inf",  3, (4.3, 1.0), [2.0e-308],          None),
+    ("all_inf",  3, (4.3, 1.0), [3.3e-308],          None),
+    ("some_inf", 3, (4.3, 1.0), [1e-3],              HUGE_FROM - 1),
+    ("raises",   3, (4.3, 1.0), [1.0e-310],          None),   # S = inf: the second pass divides by 0.0
+    ("raises",   3, (4.3, 1.0), [1.4e-308],          None),   # S_2 = inf: objective() divides by 0.0
+    ("finite",   3, (0.0, 1.0), None,                None),
+    ("all_nan",  3, (0.0, 1.0), [2.0e-308],          None),
+    ("mixed",    3, (0.0, 1.0), [1e-3],              HUGE_FROM - 2),
+    ("mixed",    3, (0.0, 1.0), [5e-4, 2.0],         HUGE_FROM + 1),
+    ("mixed",    3, (0.0, 1.0), [2e-4, 1.0, 3.0],    HUGE_FROM - 1),
+    ("finite",   4, (0.0, 0.5), None,                None),
+    ("all_nan",  4, (0.0, 0.5), [3.0e-308],          None),
+    ("mixed",    4, (0.0, 0.5), [1e-3],              HUGE_FROM - 3),
+    ("mixed",    4, (0.0, 0.5), [4e-4, 2.0],         HUGE_FROM - 1),
+    ("mixed",    4, (0.0, 0.5), [8e-4],              HUGE_FROM + 1),
+    ("finite",   4, (4.3, 1.0), None,                None),
+    ("some_inf", 4, (4.3, 1.0), [1e-3],              HUGE_FROM - 2),
+    ("some_inf", 4, (4.3, 1.0), [4e-4, 0.1],         HUGE_FROM + 1),
+    ("raises",   4, (4.3, 1.0), [2.0e-308],          None),   # S_3 = 4 / x = inf: objective() divides by 0.0
+]
+
+
+def gen_mpc_nonfinite(mpc):
+    """tests/golden/mpc_nonfinite: lanes whose objective grid holds +inf or NaN, and lanes the reference
+    raises on.  Lanes of one (H, wr, wv) form one call of the controller."""
+    name = "mpc_nonfinite"
+    rng = random.Random(31337)
+    lad = [0.3, 0.75, 1.2, 1.85, 2.85, 4.3]
+    B, V, L, mb, ws = len(lad), 24, 4, 20, 0.0
+    br = [[b * rng.uniform(0.8, 1.2) for b in lad] for _ in range(V)]
+    sz = [[b * L * rng.uniform(0.7, 1.3) for b in row] for row in br]
+    for c in (HUGE_FROM, HUGE_FROM + 1):
+        sz[c][3:] = [s * 1e305 for s in sz[c][3:]]
+    HM = 4
+    n = len(NONFINITE_LANES)
+    rec = dict(H=np.zeros(n, np.int32), wr=np.zeros(n), wv=np.zeros(n), chunk=np.zeros(n, np.int32),
+               prev=np.zeros(n, np.int32), buf=np.zeros(n), hist_n=np.zeros(n, np.int32), hist_s=np.zeros(n),
+               raises=np.zeros(n, np.int32), action=np.zeros(n, np.int32), flat=np.zeros(n, np.int32),
+               Jmin=np.zeros(n), pred=np.zeros((n, HM)), hist_n_after=np.zeros(n, np.int32),
+               hist_s_after=np.zeros(n), Jfull=np.zeros((n, B ** HM)))
+    kinds = []
+    for i, (kind, H, (wr, wv), hist, chunk) in enumerate(NONFINITE_LANES):
+        if hist is None:
+            hist = [rng.uniform(0.2, 6.0) for _ in range(rng.randrange(1, 8))]
+        if chunk is None:
+            chunk = rng.randrange(0, HUGE_FROM - H + 1)
+        prev = rng.randrange(-1, B)
+        buf = rng.choice([0.0, rng.uniform(0, mb), float(mb)])
+        rec["H"][i], rec["wr"][i], rec["wv"][i] = H, wr, wv
+        rec["chunk"][i], rec["prev"][i], rec["buf"][i] = chunk, prev, buf
+        rec["hist_n"][i], rec["hist_s"][i] = len(hist), _suminv(hist)
+        try:
+            with np.errstate(all="ignore"):
+                r = mpc_case(mpc, br, sz, L, mb, wr, wv, ws, chunk, prev, hist, buf, H, True)
+        except ZeroDivisionError:
+            r = None
+        if r is None:
+            # the reference raises; the documented answer (include/abr_env.h: abr_mpc_select) is
+            # "no decision": action -1, flat -1, J NaN, history untouched
+            assert kind == "raises", (i, kind)
+            rec["raises"][i] = 1
+            rec["action"][i], rec["flat"][i], rec["Jmin"][i] = -1, -1, np.nan
+            rec["hist_n_after"][i], rec["hist_s_after"][i] = len(hist), _suminv(hist)
+            kinds.append(kind)
+            continue
+        J = r["Jout"]
+        got = ("all_nan" if np.isnan(J).all() else "mixed" if np.isnan(J).any() else
+               "all_inf" if np.isposinf(J).all() else "some_inf" if np.isinf(J).any() else "finite")
+        assert got == kind, (i, kind, got)
+        assert r["flat"] == int(np.argmin(J)) and r["action"] == r["flat"] // B ** (H - 1)
+        assert np.array_equal(J[r["flat"]], r["Jmin"], equal_nan=True)
+        if kind == "mixed":
+            assert r["flat"] == int(np.flatnonzero(np.isnan(J))[0])           # the first NaN, not a finite minimum
+        rec["action"][i], rec["flat"][i], rec["Jmin"][i] = r["action"], r["flat"], r["Jmin"]
+        rec["pred"][i, :H] = r["pred"]
+        rec["hist_n_after"][i], rec["hist_s_after"][i] = r["hist_len_after"], r["hist_sum_inv_after"]
+        rec["Jfull"][i, :B ** H] = J
+        kinds.append(kind)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), br=np.array(br, np.float64),
+                        sz=np.array(sz, np.float64), **rec)
+    with open(os.path.join(OUT, name + ".json"), "w") as f:
+        json.dump(dict(chunk_length=L, max_buffer=mb, startup_weight=ws, video_length=V, n_rates=B,
+                       kinds=kinds), f, indent=1)
+    print(f"{name}: {n} lanes: " + ", ".join(f"{k} {kinds.count(k)}" for k in sorted(set(kinds))))
 
 
 def main():
