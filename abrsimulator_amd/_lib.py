@@ -78,6 +78,15 @@ class MpcOptions(C.Structure):
                 ("mask_is_done", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class MpcRobust(C.Structure):
+    _fields_ = [("window", C.c_int32), ("utility", C.c_int32), ("state_dev", C.c_void_p), ("state_bytes", C.c_size_t),
+                ("hist_dev", C.c_void_p), ("hist_stride", C.c_int64), ("scratch_dev", C.c_void_p),
+                ("scratch_bytes", C.c_size_t), ("mask_is_done", C.c_int32), ("reserved_", C.c_int32 * 5)]
+
+
+ROBUST_MAX_WINDOW = 16
+
+
 class RuleConfig(C.Structure):
     _fields_ = [("kind", C.c_int32), ("window", C.c_int32), ("reservoir", C.c_double), ("cushion", C.c_double),
                 ("safety", C.c_double), ("bola_v", C.c_double), ("bola_gp", C.c_double), ("utility_dev", C.c_void_p)]
@@ -124,6 +133,11 @@ SYMBOLS = [
     ("abr_env_step_mpc", C.c_int, [_P, C.POINTER(MpcConfig), _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("abr_env_step_rule", C.c_int, [_P, C.POINTER(RuleConfig), C.c_int32, _P, _P, _P, _P, _P]),
     ("abr_env_rule_select", C.c_int, [_P, C.POINTER(RuleConfig), _P, _P]),
+    ("abr_mpc_robust_state_bytes", C.c_int, [C.c_int32, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("abr_mpc_select_robust", C.c_int, [C.POINTER(MpcConfig), C.POINTER(MpcRobust), _P, _P, _P, _P, _P, _P, _P, _P,
+                                        _P, C.c_int64, _P]),
+    ("abr_env_step_mpc_robust", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(MpcRobust), _P, _P, C.c_int32, _P, _P,
+                                          _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

@@ -14,6 +14,7 @@
 //   K3    mpc_select_kernel<H, B, WVM>   mpc.py:81-93,104-186   harmonic predictor (mpc_predict_kernel ahead of it when the
 //         caller provides scratch) + exhaustive B^H: B^2 threads per lane; tables in LDS, depth-first enumeration with
 //         prefix sharing, LDS arg-max over the threads, first-leaf search below the winning node
+//   K3r   mpc_robust_predict_kernel      RobustMPC's estimate (abr_lane_jump.h: robust_estimate) ahead of the same search
 //   K4    episode_qoe_kernel        Simulator.py:79-86
 //
 // Exactness contract: every quantity that feeds a decision in the
@@ -2187,6 +2188,163 @@ extern "C" int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg,
         int32_t *act = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
         p.action_out = act;
         rc = launch_mpc_select(p, st, env->mpc_scratch);
+        if (rc) return rc;
+        float *obs = obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr;
+        float *rew = reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr;
+        uint8_t *dn = done_out_dev ? done_out_dev + (int64_t)s * N : nullptr;
+        if (is_split(effective_impl(env)))
+            launch_split<1>(effective_impl(env), env->p, act, obs, rew, dn, nullptr, 1, 0ull, st);
+        else
+            hipLaunchKernelGGL(env_jump_kernel<1>, dim3(grid64(N)), dim3(64), 0, st, env->p, act, nullptr,
+                               nullptr, nullptr, obs, rew, dn, nullptr, 1, 0ull, abrx::RuleParams{});
+        HIP_TRY(hipGetLastError());
+    }
+    return ABR_OK;
+}
+
+// ===========================================================================
+// RobustMPC (include/abr_env.h: abr_mpc_robust): the same search, fed by an error-discounted estimate
+// ===========================================================================
+// The robust predictor for every lane ahead of the unchanged search kernel (one thread per lane): updates the lane's
+// state rows in place (abr_lane_jump.h: robust_estimate) and fills the pre_pred / pre_he / pre_prev scratch exactly as
+// mpc_predict_kernel does -- H_eff 0 is "no decision", previous_bitrate normalised as Python indexes it.  The robust
+// parameters are arguments of this kernel only; MpcParams and the search instances are untouched.
+__global__ __launch_bounds__(256) void mpc_robust_predict_kernel(MpcParams p, int32_t window, uint8_t *__restrict__ state,
+                                                                 const double *__restrict__ hist, int64_t hist_stride) {
+    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= p.n_lanes) return;
+    if (p.mask && ((p.mask[lane] != 0) == (p.mask_is_done != 0))) return;
+    const int64_t N = p.n_lanes;
+    int32_t *cs1_row = (int32_t *)state, *cnt_row = cs1_row + N;
+    double *ps_row = (double *)(state + 2 * sizeof(int32_t) * N), *err_rows = ps_row + N;
+    int32_t cs1 = cs1_row[lane], cnt = cnt_row[lane];
+    double ps = ps_row[lane];
+    const int c = p.chunk[lane];
+    const auto hf = [&](int32_t j) { return hist[(int64_t)j * hist_stride + lane]; };
+    const auto ef = [&](int32_t k) -> double & { return err_rows[(int64_t)k * N + lane]; };
+    const double P = abrx::robust_estimate(window, c, hf, cs1, cnt, ps, ef);
+    cs1_row[lane] = cs1; cnt_row[lane] = cnt; ps_row[lane] = ps;
+    // D12 and previous_bitrate as mpc_predict_lane
+    int he = p.H;
+    if (c + p.H > p.V) he = p.clip ? (p.V - c) : 0;
+    if (he < 0) he = 0;
+    int pv = p.prev[lane];
+    const bool prev_ok = (pv >= -p.B) && (pv < p.B);
+    if (pv < 0) pv += p.B;
+    if (!(P > 0.0) || !prev_ok) he = 0;
+    else
+        for (int i = 0; i < p.H; i++) p.pre_pred_w[(int64_t)i * N + lane] = P;
+    p.pre_he_w[lane] = he; p.pre_prev_w[lane] = prev_ok ? pv : 0;
+}
+
+static size_t robust_state_bytes(int32_t window, int64_t n_lanes) {
+    return (size_t)n_lanes * (2 * sizeof(int32_t) + (size_t)(1 + window) * sizeof(double));
+}
+
+// the checks that need no lane count: window, utility, state pointer
+static int validate_robust(const abr_mpc_robust *r) {
+    if (!r) return fail(ABR_E_INVALID, "robust options are NULL");
+    if (r->window < 1 || r->window > ABR_ROBUST_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "robust window %d outside 1..%d", r->window, ABR_ROBUST_MAX_WINDOW);
+    if (r->utility != ABR_UTILITY_IDENTITY && r->utility != ABR_UTILITY_LOG)
+        return fail(ABR_E_INVALID, "utility must be ABR_UTILITY_IDENTITY or ABR_UTILITY_LOG");
+    if (!r->state_dev) return fail(ABR_E_INVALID, "robust state_dev is NULL");
+    if ((uintptr_t)r->state_dev & 7) return fail(ABR_E_INVALID, "robust state must be 8-byte aligned");
+    return ABR_OK;
+}
+
+// the checks against the lane count; scratch == NULL is accepted only when `scratch_optional`
+static int validate_robust_sizes(const abr_mpc_robust *r, int H, int64_t n_lanes, bool scratch_optional) {
+    if (r->state_bytes < robust_state_bytes(r->window, n_lanes))
+        return fail(ABR_E_INVALID, "robust state has %zu bytes, need %zu", (size_t)r->state_bytes,
+                    robust_state_bytes(r->window, n_lanes));
+    if (!r->scratch_dev && scratch_optional) return ABR_OK;
+    if (!r->scratch_dev) return fail(ABR_E_INVALID, "robust scratch_dev is NULL");
+    if (r->scratch_bytes < mpc_scratch_bytes(H, n_lanes))
+        return fail(ABR_E_INVALID, "robust scratch has %zu bytes, need %zu", (size_t)r->scratch_bytes,
+                    mpc_scratch_bytes(H, n_lanes));
+    if ((uintptr_t)r->scratch_dev & 7) return fail(ABR_E_INVALID, "robust scratch must be 8-byte aligned");
+    return ABR_OK;
+}
+
+extern "C" int abr_mpc_robust_state_bytes(int32_t window, int64_t n_lanes, size_t *bytes_out) {
+    if (window < 1 || window > ABR_ROBUST_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "robust window %d outside 1..%d", window, ABR_ROBUST_MAX_WINDOW);
+    if (n_lanes < 1 || !bytes_out) return fail(ABR_E_INVALID, "n_lanes must be >= 1 and bytes_out non-NULL");
+    *bytes_out = robust_state_bytes(window, n_lanes);
+    return ABR_OK;
+}
+
+// the robust predictor kernel, then the search through its pre_pred path
+static int launch_mpc_robust(MpcParams p, const abr_mpc_robust *r, const double *hist, int64_t hist_stride,
+                             void *scratch, hipStream_t st) {
+    p.pre_pred_w = (double *)scratch;
+    p.pre_he_w = (int32_t *)(p.pre_pred_w + (size_t)p.H * p.n_lanes);
+    p.pre_prev_w = p.pre_he_w + p.n_lanes;
+    p.pre_pred = nullptr;
+    hipLaunchKernelGGL(mpc_robust_predict_kernel, dim3((unsigned)((p.n_lanes + 255) / 256)), dim3(256), 0, st, p,
+                       r->window, (uint8_t *)r->state_dev, hist, hist_stride);
+    p.pre_pred = p.pre_pred_w; p.pre_he = p.pre_he_w; p.pre_prev = p.pre_prev_w;
+    return launch_mpc_select(p, st);
+}
+
+extern "C" int abr_mpc_select_robust(const abr_mpc_config *cfg, const abr_mpc_robust *robust,
+                                     const int32_t *chunk_dev, const int32_t *prev_bitrate_dev,
+                                     const double *buffer_dev, const double *br_table_dev,
+                                     const double *sz_table_dev, const uint8_t *lane_mask_dev,
+                                     int32_t *action_out_dev, int32_t *best_flat_out_dev, double *best_J_out_dev,
+                                     int64_t n_lanes, void *stream) {
+    int rc = validate_mpc(cfg);
+    if (rc) return rc;
+    if ((rc = validate_robust(robust))) return rc;
+    if (!robust->hist_dev || robust->hist_stride < 1)
+        return fail(ABR_E_INVALID, "the robust select needs the history: hist_dev and hist_stride >= 1");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "n_lanes must be >= 1");
+    if ((rc = validate_robust_sizes(robust, cfg->horizon, n_lanes, false))) return rc;
+    if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !br_table_dev || !sz_table_dev || !action_out_dev)
+        return fail(ABR_E_INVALID, "NULL device pointer");
+    MpcParams p;
+    fill_mpc_params(p, cfg, n_lanes);
+    p.utility = robust->utility;
+    p.mask_is_done = robust->mask_is_done != 0;
+    p.chunk = chunk_dev; p.prev = prev_bitrate_dev; p.buffer = buffer_dev;
+    p.hist_n = nullptr; p.hist_s = nullptr; p.br = br_table_dev; p.sz = sz_table_dev;
+    p.mask = lane_mask_dev; p.action_out = action_out_dev; p.flat_out = best_flat_out_dev;
+    p.J_out = best_J_out_dev;
+    return launch_mpc_robust(p, robust, robust->hist_dev, robust->hist_stride, robust->scratch_dev, (hipStream_t)stream);
+}
+
+// abr_env_step_mpc with the robust predictor: per decision the predictor kernel (reading the lane's bw_hist rows), the
+// search, then K1 MODE 1 on the same kernel choice as abr_env_step_mpc
+extern "C" int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_robust *robust,
+                                       const double *br_table_dev, const double *sz_table_dev, int32_t n_steps,
+                                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                       int32_t *actions_out_dev, void *stream) {
+    int rc = validate_mpc(cfg);
+    if (rc) return rc;
+    if ((rc = validate_robust(robust))) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
+    if (cfg->n_rates != env->p.n_rates || cfg->video_length != env->p.video_length)
+        return fail(ABR_E_INVALID, "MPC tables are [%d][%d], the environment has video_length %d, n_rates %d",
+                    cfg->video_length, cfg->n_rates, env->p.video_length, env->p.n_rates);
+    const EnvParams &e = env->p;
+    const int64_t N = e.n_lanes;
+    if ((rc = validate_robust_sizes(robust, cfg->horizon, N, true))) return rc;
+    if (env->impl == 1) return fail(ABR_E_UNSUPPORTED, "the fused MPC rollout needs the event-driven kernels");
+    hipStream_t st = (hipStream_t)stream;
+    void *scratch = robust->scratch_dev ? robust->scratch_dev : env->mpc_scratch;
+    MpcParams p;
+    fill_mpc_params(p, cfg, N);
+    p.utility = robust->utility;
+    p.chunk = e.chunk_id; p.prev = e.last_action; p.buffer = e.buf;
+    p.hist_n = nullptr; p.hist_s = nullptr; p.br = br_table_dev; p.sz = sz_table_dev;
+    p.mask = e.done; p.mask_is_done = 1; p.neg_to_zero = 1;
+    for (int32_t s = 0; s < n_steps; s++) {
+        int32_t *act = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        p.action_out = act;
+        rc = launch_mpc_robust(p, robust, e.bw_hist, N, scratch, st);
         if (rc) return rc;
         float *obs = obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr;
         float *rew = reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr;

@@ -28,6 +28,8 @@
 #ifndef ABR_LANE_JUMP_H
 #define ABR_LANE_JUMP_H
 
+#include <math.h>
+
 #include "abr_exact_jump.h"
 
 #ifndef ABR_STAMP
@@ -625,14 +627,20 @@ ABR_HD int32_t rule_buffer(const RuleParams &r, const BR &br, int32_t M, double 
     return rule_hi(br, M, lo + ((B - r.reservoir) / r.cushion) * (br(M - 1) - lo));
 }
 
+// harmonic mean of the n > 0 throughputs h[c-n .. c-1]: S = sum of 1.0 / h[j] oldest first, then n / S (RATE, RobustMPC)
+template <class HIST>
+ABR_HD double harmonic_tail(const HIST &hist, int32_t c, int32_t n) {
+    double S = 0.0;
+    for (int32_t j = c - n; j < c; j++) S = S + 1.0 / hist(j);
+    return (double)n / S;
+}
+
 // safety * harmonic mean of the last min(W, c) throughputs, summed oldest first
 template <class BR, class HIST>
 ABR_HD int32_t rule_rate(const RuleParams &r, const BR &br, const HIST &hist, int32_t M, int32_t c) {
     const int32_t n = r.window < c ? r.window : c;
     if (n <= 0) return 0;
-    double S = 0.0;
-    for (int32_t j = c - n; j < c; j++) S = S + 1.0 / hist(j);
-    return rule_hi(br, M, r.safety * ((double)n / S));
+    return rule_hi(br, M, r.safety * harmonic_tail(hist, c, n));
 }
 
 // BOLA-BASIC (Spiteri et al. 2016): argmax_m (V (u[c][m] + gp) - B) / br(m), the FIRST index of the maximum
@@ -654,6 +662,55 @@ ABR_HD int32_t rule_select(const RuleParams &r, const BR &br, const HIST &hist, 
     if (r.kind == kRuleBuffer) return rule_buffer(r, br, M, B);
     if (r.kind == kRuleRate) return rule_rate(r, br, hist, M, c);
     return rule_bola(r, br, M, c, B);
+}
+
+// ---- RobustMPC's throughput estimate (Yin et al. 2015; include/abr_env.h: abr_mpc_robust) ----
+// One lane at a decision: c = chunk_number (also the history length), h[0..c) = previous_bandwidths oldest first, window
+// W in 1..16.  The lane's state (include/abr_env.h: ABR_ROBUST_* layout): cs1 = c* + 1 of the last estimate p* (0 = none),
+// cnt = number of stored relative errors, err(0 .. cnt) = those errors oldest first (entries at or past cnt hold no
+// meaning; a count outside 0..W is read as 0).  `err` is an accessor returning a double& so that the kernel updates the state rows in place.  Returns the
+// estimate P the search divides by, or 0.0 for "no decision"; every operation is float64 in the order written.
+template <class HIST, class ERR>
+ABR_HD double robust_estimate(int32_t W, int32_t c, const HIST &hist, int32_t &cs1, int32_t &cnt, double &ps,
+                              const ERR &err) {
+    if (cnt < 0 || cnt > W) cnt = 0;
+    // 1. the error of the previous estimate against the throughput it predicted
+    if (cs1 > 0 && (int64_t)cs1 == (int64_t)c) {
+        const double hc = hist(c - 1);
+        const double e = fabs(ps - hc) / hc;
+        if (cnt < W) {
+            err(cnt) = e;
+            cnt = cnt + 1;
+        } else {
+            for (int32_t k = 1; k < W; k++) err(k - 1) = err(k);
+            err(W - 1) = e;
+        }
+    } else if (!(cs1 > 0 && (int64_t)cs1 == (int64_t)c + 1)) {
+        cnt = 0;                                   // none, a gap, a new episode or a rewind
+    }
+    // 2. the window
+    const int32_t n = W < c ? W : c;
+    if (n <= 0) {
+        cs1 = 0; cnt = 0; ps = 0.0;
+        return 0.0;
+    }
+    // 3. harmonic mean of the last n throughputs (RATE's arithmetic)
+    const double hm = harmonic_tail(hist, c, n);
+    // 4. discount by the largest recent relative error
+    double E = 0.0;
+    if (cnt > 0) {
+        E = err(0);
+        for (int32_t k = 1; k < cnt; k++) E = err(k) > E ? err(k) : E;
+    }
+    const double P = hm / (1.0 + E);
+    // 5. / 6.  (hm <= DBL_MAX: finite; NaN fails both comparisons)
+    if (!(hm > 0.0 && hm <= 1.79769313486231570815e+308)) {
+        cs1 = 0; cnt = 0; ps = 0.0;
+        return 0.0;
+    }
+    ps = hm;
+    cs1 = c + 1;
+    return P > 0.0 ? P : 0.0;
 }
 
 }  // namespace abrx

@@ -288,7 +288,8 @@ class BatchedABREnv:
     def step_mpc(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True):
         """n_steps decisions per lane taken by `controller` (a BatchedMPCController whose
         tables match this environment) on the device: next_bitrate() on each lane's own
-        state, then the download, with no host work between decisions.  Returns
+        state, then the download, with no host work between decisions (a method="robust" controller runs
+        abr_env_step_mpc_robust with its own per-lane state).  Returns
         dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
         n = int(n_steps)
         br, sz = controller._tables()
@@ -301,6 +302,13 @@ class BatchedABREnv:
                 done=torch.empty(n, self.n_lanes, dtype=torch.uint8, device=self.device),
                 actions=(torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
                          if want_actions else None))
+        if getattr(controller, "method", None) == "robust":
+            # RobustMPC: the controller's per-lane state rides along; the estimates go through the workspace's scratch
+            rob = controller.robust_options(self.n_lanes)
+            self._call(self.lib.abr_env_step_mpc_robust, self._h, C.byref(cfg), C.byref(rob), _lib.ptr(br),
+                       _lib.ptr(sz), n, _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")),
+                       _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
+            return out
         self._call(self.lib.abr_env_step_mpc, self._h, C.byref(cfg), _lib.ptr(br), _lib.ptr(sz), n,
                    _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
                    _lib.ptr(out.get("actions")))

@@ -27,13 +27,21 @@ class BatchedMPCController:
     `horizon` predictions), D10 (3-argument max, unclamped rebuffer term), D11
     (lookahead buffer uses the current chunk's sizes).  clip_horizon=True defines
     the behaviour where the reference raises IndexError (D12).
+
+    method="robust" is RobustMPC (Yin et al. 2015; include/abr_env.h: abr_mpc_robust): the same search fed by the
+    harmonic mean of the last `window` measured throughputs divided by 1 + the largest relative error of the last
+    `window` estimates.  It needs the history itself (chunk-info `previous_bandwidths` f64[T, N] with T >= every
+    chunk_number; EnvPlayer provides it), does not grow hist_n / hist_sum_inv, and keeps a per-lane state the controller
+    owns: zero-initialised, rebound (empty) when the lane count or the window changes, cleared by reset_state(), saved
+    and restored by state_dict() / load_state_dict().
     """
 
     METHODS = {"harmonic": 0, "expsmoothing": 1}
+    ROBUST = "robust"
     UTILITIES = {"identity": 0, "log": 1}
 
     def __init__(self, player=None, bitrate_utility=None, horizon=None, clip_horizon=True,
-                 device="cuda", *, method="harmonic", utility="identity"):
+                 device="cuda", *, method="harmonic", utility="identity", window=5):
         self.lib = _lib.lib()
         self.device = torch.device(device)
         self.horizon = 3 if horizon is None else int(horizon)
@@ -42,9 +50,14 @@ class BatchedMPCController:
         # see include/abr_env.h: abr_mpc_options.  method="expsmoothing" needs the throughput
         # history itself: chunk-info fields `previous_bandwidths` f64[T, N] (entry t of lane i)
         # and `history_length` i32[N]  (EnvPlayer provides both).
-        if method not in self.METHODS or utility not in self.UTILITIES:
-            raise ValueError("method is 'harmonic' or 'expsmoothing'; utility is 'identity' or 'log'")
+        if (method not in self.METHODS and method != self.ROBUST) or utility not in self.UTILITIES:
+            raise ValueError("method is 'harmonic', 'expsmoothing' or 'robust'; utility is 'identity' or 'log'")
+        if isinstance(window, bool) or int(window) != window or not 1 <= int(window) <= _lib.ROBUST_MAX_WINDOW:
+            raise ValueError(f"window must be an integer in 1..{_lib.ROBUST_MAX_WINDOW}")
         self.method, self.utility = method, utility
+        self.window = int(window)
+        self._state = None             # RobustMPC's per-lane state (uint8 bytes, include/abr_env.h layout)
+        self._state_key = None         # (n_lanes, window) it was laid out for
         # run the predictor as its own kernel (False: everything in one kernel; same results)
         self.use_scratch = os.environ.get("ABR_MPC_SINGLE_KERNEL") != "1"
         self._scratch = None
@@ -98,9 +111,52 @@ class BatchedMPCController:
     def _bind_key(self, n_lanes):
         """Everything the bound config / options depend on: a change of any of it -- also an in-place change of the MPD's
         chunk_length or max_buffer, which config() reads -- rebinds on the next select."""
-        return (int(n_lanes), self._tables_for, self.horizon, self.clip_horizon, self.method, self.utility,
+        return (int(n_lanes), self._tables_for, self.horizon, self.clip_horizon, self.method, self.utility, self.window,
                 float(self.mpd.chunk_length), float(self.mpd.max_buffer),
                 float(self.qoe.variance_weight), float(self.qoe.rebuffer_weight), float(self.qoe.startup_weight))
+
+    # -- RobustMPC's per-lane state ----------------------------------------
+    def robust_state(self, n_lanes):
+        """The state tensor for n_lanes lanes at the current window: the one in use, or a new all-zero (empty) one when
+        the lane count or the window changed."""
+        key = (int(n_lanes), self.window)
+        if self._state is None or self._state_key != key:
+            need = C.c_size_t()
+            _lib.check(self.lib.abr_mpc_robust_state_bytes(self.window, int(n_lanes), C.byref(need)))
+            self._state = torch.zeros(need.value, dtype=torch.uint8, device=self.device)
+            self._state_key = key
+        return self._state
+
+    def reset_state(self):
+        """Forget every lane's past estimates and errors."""
+        if self._state is not None:
+            self._state.zero_()
+
+    def state_dict(self):
+        return {"window": self.window, "n_lanes": None if self._state_key is None else self._state_key[0],
+                "state": None if self._state is None else self._state.detach().clone()}
+
+    def load_state_dict(self, sd):
+        if int(sd["window"]) != self.window:
+            raise ValueError(f"state was written for window {sd['window']}, this controller has window {self.window}")
+        if sd["state"] is None:
+            self._state, self._state_key = None, None
+            return
+        n = int(sd["n_lanes"])
+        st = self.robust_state(n)
+        if sd["state"].numel() != st.numel() or sd["state"].dtype != torch.uint8:
+            raise ValueError("state does not match the window and lane count it claims")
+        st.copy_(sd["state"])
+
+    def robust_options(self, n_lanes, scratch=None):
+        """The abr_mpc_robust struct for n_lanes lanes (state bound; scratch: a uint8 device tensor or None)."""
+        st = self.robust_state(n_lanes)
+        r = _lib.MpcRobust()
+        r.window, r.utility = self.window, self.UTILITIES[self.utility]
+        r.state_dev, r.state_bytes = st.data_ptr(), st.numel()
+        if scratch is not None:
+            r.scratch_dev, r.scratch_bytes = scratch.data_ptr(), scratch.numel()
+        return r
 
     def next_bitrate(self, want_details=False):
         """mpc.py:181-186, batched: returns int32 [N] bitrate indices."""
@@ -115,11 +171,14 @@ class BatchedMPCController:
         mask, mask_is_done = getattr(ci, "mask", None), 0
         if mask is None and getattr(ci, "done", None) is not None:
             mask, mask_is_done = ci.done, 1
+        robust = self.method == self.ROBUST          # reads the history itself, not its (hist_n, hist_sum_inv) summary
         for t, dt in ((ci.chunk_number, torch.int32), (ci.previous_bitrate, torch.int32),
-                      (ci.buffer_level, torch.float64), (ci.hist_n, torch.float64),
-                      (ci.hist_sum_inv, torch.float64)):
+                      (ci.buffer_level, torch.float64)) + (() if robust else ((ci.hist_n, torch.float64),
+                                                                             (ci.hist_sum_inv, torch.float64))):
             if t.dtype != dt or t.device.type != "cuda":
                 raise TypeError(f"chunk-info tensors must be {dt} on the GPU")
+        if robust:
+            return self._next_bitrate_robust(ci, N, br, sz, action, flat, J, mask, mask_is_done)
         # the config / options structs and the predictor's scratch are bound once per (lane count, tables, weights,
         # method): a select is then the two kernel launches and nothing else on the host (BoundOut's counterpart)
         key = self._bind_key(N)
@@ -152,6 +211,32 @@ class BatchedMPCController:
                 _lib.ptr(ci.buffer_level), _lib.ptr(ci.hist_n), _lib.ptr(ci.hist_sum_inv),
                 _lib.ptr(br), _lib.ptr(sz), _lib.ptr(mask), _lib.ptr(action), _lib.ptr(flat),
                 _lib.ptr(J), N, _lib.current_stream(self.device)))
+        self.last_flat, self.last_J = flat, J
+        return action
+
+    def _next_bitrate_robust(self, ci, N, br, sz, action, flat, J, mask, mask_is_done):
+        key = self._bind_key(N)
+        if self._bound is None or self._bound[0] != key:
+            cfg = self.config()
+            need = C.c_size_t()
+            _lib.check(self.lib.abr_mpc_scratch_bytes(C.byref(cfg), N, C.byref(need)))
+            if self._scratch is None or self._scratch.numel() < need.value:
+                self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._bound = (key, cfg, None)
+        cfg = self._bound[1]
+        hist = ci.previous_bandwidths
+        if hist.dtype != torch.float64 or hist.dim() != 2 or hist.shape[1] != N or hist.stride(1) != 1:
+            raise TypeError("previous_bandwidths must be float64 [T, N] with unit lane stride")
+        if int(ci.chunk_number.max()) > hist.shape[0]:
+            raise TypeError("previous_bandwidths has fewer rows than a lane's chunk_number")
+        r = self.robust_options(N, self._scratch)
+        r.hist_dev, r.hist_stride = hist.data_ptr(), hist.stride(0)
+        r.mask_is_done = mask_is_done
+        with torch.cuda.device(self.device):
+            _lib.check(self.lib.abr_mpc_select_robust(
+                C.byref(cfg), C.byref(r), _lib.ptr(ci.chunk_number), _lib.ptr(ci.previous_bitrate),
+                _lib.ptr(ci.buffer_level), _lib.ptr(br), _lib.ptr(sz), _lib.ptr(mask), _lib.ptr(action),
+                _lib.ptr(flat), _lib.ptr(J), N, _lib.current_stream(self.device)))
         self.last_flat, self.last_J = flat, J
         return action
 

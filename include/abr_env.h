@@ -406,6 +406,70 @@ int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg, const double *br_t
                      void *stream);
 
 /*
+ * RobustMPC (Yin et al., SIGCOMM 2015): the same search as abr_mpc_select (objective, D10, D11, D12 clip, Python's negative
+ * previous_bitrate, first-minimum tie-break, the non-finite rules above) fed by an error-discounted throughput estimate
+ * instead of the reference's harmonic predictor.  For one active lane at a decision: c = chunk_number (also the history
+ * length), h[0..c) = previous_bandwidths oldest first, W = window.  The lane's state holds the last estimate p*, the chunk
+ * c* it was made at (or none) and up to W past relative errors, oldest first.  All float64, in this order:
+ *  1. c* == c - 1: push e = |p* - h[c-1]| / h[c-1], keeping the last W errors; c* == c: errors unchanged (selecting
+ *     twice on the same state gives the same answer); otherwise (none, a gap, a new episode, a rewind) clear them.
+ *  2. n = min(W, c); n == 0: no decision, state := empty.
+ *  3. S = sum over j = c-n .. c-1 (in that order) of 1.0 / h[j]; hm = n / S (ABR_RULE_RATE's arithmetic).
+ *  4. E = the stored errors' maximum, scanned oldest first: E = e[0], then E = e[k] if e[k] > E; 0.0 with no errors.
+ *     P = hm / (1.0 + E).
+ *  5. hm not finite or not > 0: no decision, state := empty.  P not > 0: no decision, but p* = hm, c* = c are recorded.
+ *  6. Otherwise p* = hm, c* = c, and the search runs with C_hat[i] = P for every i < H_eff.
+ * The state is updated whenever step 3 produced an estimate, even if the search then reports no decision (D12, a bad
+ * previous_bitrate).  The history summary hist_n / hist_sum_inv is NOT mutated (no D9).  Masked or finished lanes are
+ * skipped: state, flat and J untouched, and the action too except under mask_is_done, which reports -1.  "No decision" reports action -1, flat -1, J NaN as abr_mpc_select.
+ *
+ * State layout (caller-owned device memory, 8-byte aligned, abr_mpc_robust_state_bytes(window, n_lanes); ALL-ZERO BYTES
+ * ARE THE EMPTY STATE): int32 [2][n_lanes] -- row 0 c* + 1 (0 = none), row 1 the error count (0..W; any other value reads
+ * as 0) -- followed by float64 [1 + window][n_lanes] -- row 0 p*, rows 1 .. 1 + count the errors oldest first (rows at or
+ * past the count hold no meaning).  Lane i's field f is at row f, column i, as everywhere in this ABI.  The layout depends
+ * on the window: a state is only meaningful for the window it was written with.
+ */
+#define ABR_ROBUST_MAX_WINDOW 16
+typedef struct abr_mpc_robust {
+    int32_t window;               /* W, 1..ABR_ROBUST_MAX_WINDOW (RobustMPC's default: 5) */
+    int32_t utility;              /* ABR_UTILITY_* as for abr_mpc_select_opt */
+    void *state_dev;              /* IN-OUT per-lane state, layout above */
+    size_t state_bytes;           /* >= abr_mpc_robust_state_bytes(window, n_lanes) */
+    const double *hist_dev;       /* abr_mpc_select_robust: previous_bandwidths, entry j of lane i at
+                                     hist_dev[j * hist_stride + i], at least chunk_number rows per lane.  Ignored by
+                                     abr_env_step_mpc_robust, which reads the environment's own history */
+    int64_t hist_stride;
+    void *scratch_dev;            /* abr_mpc_scratch_bytes(cfg, n_lanes) of 8-byte aligned device memory for the
+                                     estimates handed to the search.  Required by abr_mpc_select_robust; optional for
+                                     abr_env_step_mpc_robust (NULL: the environment's workspace) */
+    size_t scratch_bytes;
+    int32_t mask_is_done;         /* abr_mpc_select_robust: as abr_mpc_options.mask_is_done */
+    int32_t reserved_[5];         /* set to 0 */
+} abr_mpc_robust;
+
+/* Bytes of the RobustMPC state of n_lanes lanes at `window`. */
+int abr_mpc_robust_state_bytes(int32_t window, int64_t n_lanes, size_t *bytes_out);
+
+/* RobustMPC's next_bitrate for n_lanes independent players; arguments and outputs as abr_mpc_select_opt, without the
+ * history summary.  Validation (ABR_E_INVALID, nothing launched): the config as abr_mpc_select, window in 1..16, the
+ * utility, a non-NULL 8-byte aligned state of at least the size query's bytes, hist_dev != NULL and hist_stride >= 1,
+ * a scratch of at least abr_mpc_scratch_bytes, n_lanes >= 1, then the device pointers. */
+int abr_mpc_select_robust(const abr_mpc_config *cfg, const abr_mpc_robust *robust, const int32_t *chunk_dev,
+                          const int32_t *prev_bitrate_dev, const double *buffer_dev, const double *br_table_dev,
+                          const double *sz_table_dev, const uint8_t *lane_mask_dev, int32_t *action_out_dev,
+                          int32_t *best_flat_out_dev, double *best_J_out_dev, int64_t n_lanes, void *stream);
+
+/* abr_env_step_mpc with RobustMPC's estimate: per decision the robust predictor on each lane's own state (chunk_id,
+ * previous_bitrates[-1], buffer_level, and the environment's previous_bandwidths rows), the search, then the download.
+ * Kernel choice as abr_env_step_mpc (impl 1, tick, answers ABR_E_UNSUPPORTED); finished lanes take no decision and keep
+ * their state; "no decision" downloads bitrate 0.  robust->hist_dev, hist_stride and mask_is_done are ignored.
+ * Validation (ABR_E_INVALID, nothing launched): the config and robust options as above and n_steps >= 1 before the handle
+ * is looked at; then the tables against the environment, the state size and the scratch size (if given) for its lanes. */
+int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_robust *robust,
+                            const double *br_table_dev, const double *sz_table_dev, int32_t n_steps, float *obs_out_dev,
+                            float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream);
+
+/*
  * The standard ABR baselines as get_next_bitrate (Simulator.py:155), evaluated on the device at each lane's call site on
  * exact float64 state: c = chunk_id, B = buffer_level, h[0..c) = previous_bandwidths oldest first, br[m] = chunk c's
  * bitrate m (the abr_env_set_bitrate_table row, else config.ladder), M = n_rates.
