@@ -9,6 +9,7 @@ from .env import BatchedABREnv, obs_dict, pack_traces
 from .mpc import BatchedMPCController, EnvPlayer
 from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
+from .speed import LatencySpeedController
 from .simulator import Simulator
 from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd_file,
                      save_trace_file)
@@ -16,6 +17,6 @@ from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd
 _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
-           "BatchedMPCController", "EnvPlayer", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep",
+           "BatchedMPCController", "EnvPlayer", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

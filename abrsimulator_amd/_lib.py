@@ -94,6 +94,14 @@ class RuleConfig(C.Structure):
 
 RULE_BUFFER, RULE_RATE, RULE_BOLA = 1, 2, 3
 
+SPEED_RULE_MAX_THR = 4
+
+
+class SpeedRule(C.Structure):
+    _fields_ = [("n_lat", C.c_int32), ("n_buf", C.c_int32), ("lat_thr", C.c_double * SPEED_RULE_MAX_THR),
+                ("buf_thr", C.c_double * SPEED_RULE_MAX_THR),
+                ("speed", (C.c_double * (SPEED_RULE_MAX_THR + 1)) * (SPEED_RULE_MAX_THR + 1))]
+
 
 class StateView(C.Structure):
     _fields_ = [("n_lanes", C.c_int64), ("chunk_id", C.c_void_p), ("last_bitrate", C.c_void_p),
@@ -116,6 +124,7 @@ SYMBOLS = [
     ("abr_env_set_lane_speeds", C.c_int, [_P, _P]),
     ("abr_env_set_bitrate_table", C.c_int, [_P, _P]),
     ("abr_env_set_speed_schedule", C.c_int, [_P, _P, C.c_int32]),
+    ("abr_env_set_speed_rule", C.c_int, [_P, C.POINTER(SpeedRule), _P, C.c_int32]),
     ("abr_env_reset", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step_random", C.c_int, [_P, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P]),

@@ -52,6 +52,9 @@
 #define K3_STAMP(n)
 #define K3_STAMP_FLUSH()
 #endif
+// where EnvParams::speed_rule lies in the kernarg segment of every kernel that takes `EnvParams p` as its FIRST argument
+// (asserted below): abr_lane_jump.h reads a speed rule there when a played chunk begins
+#define ABR_RULE_KERNARG_OFFSET 592
 #include "abr_lane_jump.h"
 #include "abr_tick_tables.h"
 
@@ -126,7 +129,18 @@ struct EnvParams {
     // parameter block re-read from the kernarg segment -- is THIS launch's block (it carries `sentinel`), 2 if not
     uint32_t *selfcheck_out;
     uint64_t sentinel;
+    // abr_env_set_speed_rule (appended: everything above keeps its offset; the block grew from 592 to 880 bytes).  A rule
+    // runs as a speed schedule whose rows are computed: speed_rows == abrx::kSpeedRowsRule, and lane_speeds then points at
+    // sd_lane -- non-null, so that every "per-lane speeds" test holds, and never read as speeds.  The kernels read this
+    // block from the kernarg segment only when a played chunk begins (abr_lane_jump.h: sched_begin_chunk).
+    abrx::SpeedRuleBlock speed_rule;
 };
+static_assert(offsetof(EnvParams, speed_rule) == ABR_RULE_KERNARG_OFFSET, "abr_lane_jump.h reads the rule at this offset");
+static_assert(sizeof(EnvParams) == 880, "the parameter block: 592 bytes + 288 of the speed rule");
+static_assert(sizeof(abrx::SpeedRule) == sizeof(abr_speed_rule) &&
+              offsetof(abrx::SpeedRule, lat_thr) == offsetof(abr_speed_rule, lat_thr) &&
+              offsetof(abrx::SpeedRule, buf_thr) == offsetof(abr_speed_rule, buf_thr) &&
+              offsetof(abrx::SpeedRule, speed) == offsetof(abr_speed_rule, speed), "abr_speed_rule: one layout");
 
 // What a workspace says about itself, in its last 256 bytes: written by abr_env_create, compared by abr_env_notify_restore
 // (and by the Python wrapper's load_state_dict before it copies anything).  A checkpoint is a copy of the workspace, and the
@@ -158,6 +172,8 @@ struct abr_env {
     void *mpc_scratch;              // predictor scratch of abr_env_step_mpc (in the workspace)
     const double *pending_speeds;   // abr_env_set_lane_speeds / _speed_schedule: latched by the next full reset
     int32_t pending_speed_rows;
+    bool pending_rule_on;           // abr_env_set_speed_rule: latched the same way (speeds_dirty)
+    abrx::SpeedRuleBlock pending_rule;
     bool speeds_dirty;
     const double *pending_br_table; // abr_env_set_bitrate_table: latched the same way
     bool br_table_dirty;
@@ -170,6 +186,8 @@ static void apply_pending(abr_env *env) {
     if (env->br_table_dirty) { env->p.br_table = env->pending_br_table; env->br_table_dirty = false; }
     if (env->speeds_dirty) {
         env->p.lane_speeds = env->pending_speeds; env->p.speed_rows = env->pending_speed_rows;
+        env->p.speed_rule = env->pending_rule;
+        if (env->pending_rule_on) { env->p.lane_speeds = env->p.sd_lane; env->p.speed_rows = abrx::kSpeedRowsRule; }
         env->speeds_dirty = false;
     }
 }
@@ -704,7 +722,8 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
                 episode_no = (p.flags[i] & kFlagArmed) ? p.episode_no[i] + 1 : 0;
                 p.trace_id[i] = t; p.offset0[i] = offset0;
                 s.cur.tlen = p.trace_len[t]; s.cur.trace = p.traces + p.trace_off[t];
-                s.sd = p.lane_speeds ? p.lane_speeds[i] * kDt : p.sd;     // play_speed * dt (:182)
+                // play_speed * dt (:182); a rule sets it at the lane's first playing tick (sched_begin_chunk)
+                s.sd = (p.lane_speeds && p.speed_rows != abrx::kSpeedRowsRule) ? p.lane_speeds[i] * kDt : p.sd;
                 s.lane = i;
                 abrx::lanej_init(s, tb, offset0);
                 if (!bad && !abrx::lanej_wait_call(s, tb)) done |= ABR_DONE_TIMEOUT;
@@ -1050,6 +1069,7 @@ extern "C" int abr_env_create(const abr_env_config *cfg, const double *traces_de
     p.buf = f; p.last_bw = f + N; p.hist_n = f + 2 * N; p.hist_s = f + 3 * N;
     p.sd_lane = f + 4 * N; p.pt_lane = f + 5 * N; p.pt_sum = f + 6 * N; p.var_run = f + 7 * N; p.lane_speeds = nullptr;
     p.speed_rows = 1;
+    p.speed_rule = abrx::SpeedRuleBlock{};
     p.sumk = (long long *)(w + L.i64_state);
     int32_t *q = (int32_t *)(w + L.i32_state);
     p.k = q; p.chunk_id = q + N; p.n_su = q + 2 * N; p.n_rb = q + 3 * N; p.n_play = q + 4 * N;
@@ -1118,8 +1138,11 @@ extern "C" int abr_env_set_impl(abr_env *env, int32_t impl) {
         return fail(ABR_E_UNSUPPORTED, "impl %d (4: the asynchronous pipeline, 6: the ring-coupled role pipeline, 7: the pair rendezvous) is not part of "
                     "the product library: it is slower than what `auto` selects; the diagnostic build "
                     "tools/diag/lib/libabr_hip_diag.so carries it", impl);
-    if (impl == 1 && (env->p.lane_speeds || (env->speeds_dirty && env->pending_speeds)))
+    if (impl == 1 && (env->p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on))))
         return fail(ABR_E_UNSUPPORTED, "the tick-by-tick kernels take one speed for all lanes");
+    const bool rule = env->speeds_dirty ? env->pending_rule_on : env->p.speed_rows == abrx::kSpeedRowsRule;
+    if (rule && (impl == 4 || impl == 6 || impl == 7))
+        return fail(ABR_E_UNSUPPORTED, "a speed rule needs the event-driven kernels (impl 0, 2, 3 or 5)");
     env->impl = impl;
     return ABR_OK;
 }
@@ -1133,6 +1156,7 @@ extern "C" int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev) {
     // speeds (and the carried play_time) they were started with
     env->pending_speeds = speeds_dev;
     env->pending_speed_rows = 1;
+    env->pending_rule_on = false;
     env->speeds_dirty = true;
     if (!env->armed) apply_pending(env);
     return ABR_OK;
@@ -1146,6 +1170,54 @@ extern "C" int abr_env_set_speed_schedule(abr_env *env, const double *speeds_dev
     if (speeds_dev && n_rows < 1) return fail(ABR_E_INVALID, "n_rows must be >= 1");
     env->pending_speeds = speeds_dev;
     env->pending_speed_rows = speeds_dev ? n_rows : 1;
+    env->pending_rule_on = false;
+    env->speeds_dirty = true;
+    if (!env->armed) apply_pending(env);
+    return ABR_OK;
+}
+
+// a closed-loop speed controller (include/abr_env.h: abr_speed_rule), evaluated where the reference calls get_next_speed()
+static int check_speed_rule(const abr_speed_rule *r) {
+    const int nl = r->n_lat, nb = r->n_buf;
+    if (nl < 0 || nl > ABR_SPEED_RULE_MAX_THR) return fail(ABR_E_INVALID, "speed rule: n_lat must be in 0..4, got %d", nl);
+    if (nb < 0 || nb > ABR_SPEED_RULE_MAX_THR) return fail(ABR_E_INVALID, "speed rule: n_buf must be in 0..4, got %d", nb);
+    for (int q = 0; q < nl; q++) {
+        if (!std::isfinite(r->lat_thr[q])) return fail(ABR_E_INVALID, "speed rule: lat_thr[%d] is not finite", q);
+        if (q > 0 && !(r->lat_thr[q] > r->lat_thr[q - 1]))
+            return fail(ABR_E_INVALID, "speed rule: lat_thr must be strictly ascending (lat_thr[%d])", q);
+    }
+    for (int q = 0; q < nb; q++) {
+        if (!std::isfinite(r->buf_thr[q])) return fail(ABR_E_INVALID, "speed rule: buf_thr[%d] is not finite", q);
+        if (q > 0 && !(r->buf_thr[q] > r->buf_thr[q - 1]))
+            return fail(ABR_E_INVALID, "speed rule: buf_thr must be strictly ascending (buf_thr[%d])", q);
+    }
+    for (int i = 0; i <= nl; i++)
+        for (int j = 0; j <= nb; j++)
+            if (!(std::isfinite(r->speed[i][j]) && r->speed[i][j] > 0.0))
+                return fail(ABR_E_INVALID, "speed rule: speed[%d][%d] must be finite and > 0", i, j);
+    return ABR_OK;
+}
+
+extern "C" int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, double *speed_log_dev, int32_t log_rows) {
+    // the struct before the handle: a CPU test drives every refusal with env == NULL
+    if (rule) {
+        const int rc = check_speed_rule(rule);
+        if (rc != ABR_OK) return rc;
+        if (log_rows < 0) return fail(ABR_E_INVALID, "log_rows must be >= 0, got %d", log_rows);
+        if (log_rows > 0 && !speed_log_dev) return fail(ABR_E_INVALID, "log_rows > 0 needs speed_log_dev");
+    }
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (rule && (env->impl == 1 || env->impl == 4 || env->impl == 6 || env->impl == 7))
+        return fail(ABR_E_UNSUPPORTED, "a speed rule needs the event-driven kernels (impl 0, 2, 3 or 5)");
+    env->pending_speeds = nullptr;
+    env->pending_speed_rows = 1;
+    env->pending_rule_on = rule != nullptr;
+    env->pending_rule = abrx::SpeedRuleBlock{};
+    if (rule) {
+        std::memcpy(&env->pending_rule.rule, rule, sizeof(abr_speed_rule));
+        env->pending_rule.log = log_rows > 0 ? speed_log_dev : nullptr;
+        env->pending_rule.log_rows = log_rows > 0 ? log_rows : 0;
+    }
     env->speeds_dirty = true;
     if (!env->armed) apply_pending(env);
     return ABR_OK;

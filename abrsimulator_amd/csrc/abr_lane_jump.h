@@ -52,6 +52,34 @@ constexpr int kPrologue = 16;               // (the asynchronous pipeline's own 
 constexpr int kPChunks = ABR_PCHUNKS;       // prologue of a download: up to 7 single additions + this many chunks of 8
 constexpr int kPCheck = ABR_PCHECK;         // bit q: a checkpoint after chunk q (the last chunk's bit must be set)
 
+// The stateless speed rule, field for field the layout of include/abr_env.h: abr_speed_rule (abr_env.hip asserts it).
+struct SpeedRule {
+    int32_t n_lat, n_buf;          // 0..4
+    double lat_thr[4], buf_thr[4]; // strictly ascending [s]
+    double speed[5][5];            // speed[i][j], i in 0..n_lat, j in 0..n_buf
+};
+
+// i = thresholds of lat reached, j = thresholds of buf reached; comparisons only, so the host, the device and a numpy twin
+// give the same answer for the same inputs
+ABR_HD double speed_rule_eval(const SpeedRule &r, double lat, double buf) {
+    int32_t i = 0, j = 0;
+    for (int32_t q = 0; q < r.n_lat; q++) i += lat >= r.lat_thr[q] ? 1 : 0;
+    for (int32_t q = 0; q < r.n_buf; q++) j += buf >= r.buf_thr[q] ? 1 : 0;
+    return r.speed[i][j];
+}
+
+// Tables::speed_rows of a speed rule: a "schedule" whose every row is computed (sched_begin_chunk)
+constexpr int32_t kSpeedRowsRule = 0x7fffffff;
+
+// A speed rule's block: the rule, and where its answers go (speed p of lane i to log[p * stride + i] for p < log_rows).
+// In the kernels it lies in the parameter block, at byte ABR_RULE_KERNARG_OFFSET of the kernarg segment, and is read there
+// only when a played chunk begins: held in Tables its pointers would be live scalars across every kernel's loop.
+struct SpeedRuleBlock {
+    SpeedRule rule;
+    double *log;
+    int32_t log_rows, reserved_;
+};
+
 struct Tables {
     const double *G;               // G[n] = dt added n times to 0.0 (global_time, download_time, ...)
     const int32_t *interval_tick;  // first tick k with int(G[k]/interval) >= j          (:158)
@@ -65,6 +93,10 @@ struct Tables {
     int32_t speed_rows;
     int64_t speed_stride;
     const double *speeds;
+    // speed_rows == kSpeedRowsRule: the played chunk's speed is computed by a speed rule (include/abr_env.h:
+    // abr_speed_rule) from the lane's state at that tick; the host harness points `rule` at its block, the kernels read
+    // theirs from the kernarg segment (SpeedRuleBlock)
+    const SpeedRuleBlock *rule = nullptr;
     // the per-binade cascade of buffer_level -= sd at THE one play speed (abr_exact_jump.h: drain_cascade); n == 0 with
     // per-lane speeds or when the speed / buffer range is not covered: the general chains then do the drains
     DrainTab drain;
@@ -181,9 +213,26 @@ ABR_HD bool lanej_drain(const Tables &t, double &b_io, double sd, int32_t m, int
 // The first playing tick of a played chunk (play_length == 0) takes the chunk's speed
 // (:176-177); the chunk then lasts until play_length, `speed*dt` added per tick from 0, is
 // >= chunk_length (:183,:185-187): that many ticks, by the same exact chain.
-ABR_HD void sched_begin_chunk(LaneJ &s, const Tables &t) {
-    const int32_t row = s.play_id < t.speed_rows ? s.play_id : t.speed_rows - 1;
-    s.sd = t.speeds[(int64_t)row * t.speed_stride + s.lane] * kTickDt;     // play_speed * dt (:182)
+// k: the tick, b: buffer_level at that point of it (after :170, before :184) -- what a speed rule reads.
+ABR_HD void sched_begin_chunk(LaneJ &s, const Tables &t, int32_t k, double b) {
+    double v;
+    if (t.speed_rows == kSpeedRowsRule) {
+#if defined(__HIP_DEVICE_COMPILE__) && defined(ABR_RULE_KERNARG_OFFSET)
+        // behind a compiler-only fence, so that the rule's loads stay here instead of being hoisted out of the kernel's
+        // loops as live scalars (abr_env_roles.h: fresh_params)
+        auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(kp));
+        const SpeedRuleBlock &rb = *(const SpeedRuleBlock *)((const char *)kp + ABR_RULE_KERNARG_OFFSET);
+#else
+        const SpeedRuleBlock &rb = *t.rule;
+#endif
+        v = speed_rule_eval(rb.rule, t.G[k] - s.pt, b);                       // lat = instant_latency (:179)
+        if (s.play_id < rb.log_rows) rb.log[(int64_t)s.play_id * t.speed_stride + s.lane] = v;
+    } else {
+        const int32_t row = s.play_id < t.speed_rows ? s.play_id : t.speed_rows - 1;
+        v = t.speeds[(int64_t)row * t.speed_stride + s.lane];
+    }
+    s.sd = v * kTickDt;                                                      // play_speed * dt (:182)
     double x = 0.0;
     int32_t a = 0;
     chain<STOP_GE>(x, s.sd, t.L, t.max_ticks + 1, a);
@@ -210,7 +259,7 @@ ABR_HD bool sched_drain(LaneJ &s, const Tables &t, double &b, double thr, int32_
     int32_t a_tot = 0;
     bool hit = false;
     while (a_tot < m && !hit) {
-        if (s.pl_left == 0) sched_begin_chunk(s, t);
+        if (s.pl_left == 0) sched_begin_chunk(s, t, s.k + a_tot, b);
         const int32_t run = (m - a_tot < s.pl_left) ? m - a_tot : s.pl_left;
         int32_t a = 0;
         if (STOP == STOP_LE) hit = drain_to_zero(b, s.sd, run, a);
@@ -500,7 +549,7 @@ ABR_HD StepResult lanej_after_download(LaneJ &s, const Tables &t, const Download
     if (playing) {                                                            // :176-184
         s.sumk += s.k; s.n_play++;
         if (t.speed_rows >= 2) {
-            if (s.pl_left == 0) sched_begin_chunk(s, t);
+            if (s.pl_left == 0) sched_begin_chunk(s, t, s.k, b);
             b = b - s.sd;
             sched_played(s, t, 1);
         } else { b = b - s.sd; lanej_play(s, t, 1); }

@@ -11,6 +11,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .speed import LatencySpeedController
 from ._lib import F64_DIM, F64_ROWS, OBS_DIM, OBS_ROWS
 from .datamodel import MPD, NetworkInfo, QOEMetric
 
@@ -87,7 +88,13 @@ class BatchedABREnv:
         cfg.startup_weight = float(qoe_metric.startup_weight)
         cfg.latency_weight = float(getattr(qoe_metric, "latency_weight", 0.0))
         self.lane_speeds = None
-        if torch.is_tensor(speed) or hasattr(speed, "__len__"):
+        self.speed_controller = None
+        self._speed_log = None
+        if isinstance(speed, LatencySpeedController):
+            # a closed-loop speed rule, evaluated in the kernels at every played chunk's first playing tick
+            self.speed_controller = speed
+            speed = 1.0
+        elif torch.is_tensor(speed) or hasattr(speed, "__len__"):
             # per-lane play speeds: [N] = one constant speed per lane;
             # [rows, N] = a speed controller's answers, one row per played chunk
             # (Simulator.py:176-177; the last row repeats)
@@ -141,6 +148,8 @@ class BatchedABREnv:
         if self.lane_speeds is not None:
             self._check(self.lib.abr_env_set_speed_schedule(self._h, _lib.ptr(self.lane_speeds),
                                                            int(self.lane_speeds.shape[0])))
+        if self.speed_controller is not None:
+            self.set_speed_controller(self.speed_controller)
         if self.br_table is not None:
             self._check(self.lib.abr_env_set_bitrate_table(self._h, _lib.ptr(self.br_table)))
         self.obs = torch.zeros(OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device)
@@ -148,6 +157,32 @@ class BatchedABREnv:
         self.done = torch.zeros(self.n_lanes, dtype=torch.uint8, device=self.device)
         self.trace_id = None
         self.start_offset = None
+
+    def set_speed_controller(self, controller, log_rows: int = 0):
+        """Install a LatencySpeedController (None: back to the constant config speed).  Latched like the per-lane speeds:
+        the next reset of ALL lanes adopts it; at once on a handle that has not been reset yet.  log_rows > 0 keeps a log
+        of its answers, float64 [log_rows, n_lanes] (speed_log()): row p holds the speed of played chunk p of the lane's
+        current episode.  Replaces per-lane speeds or a schedule given before."""
+        if controller is not None and not isinstance(controller, LatencySpeedController):
+            raise TypeError("set_speed_controller takes a LatencySpeedController or None")
+        log_rows = int(log_rows)
+        if log_rows < 0:
+            raise ValueError("log_rows must be >= 0")
+        log = None
+        if controller is not None and log_rows > 0:
+            log = torch.zeros(log_rows, self.n_lanes, dtype=torch.float64, device=self.device)
+        rule = controller.to_struct() if controller is not None else None
+        self._check(self.lib.abr_env_set_speed_rule(self._h, C.byref(rule) if rule is not None else None,
+                                                    _lib.ptr(log) if log is not None else None,
+                                                    log_rows if log is not None else 0))
+        # the library holds the log's address: keep the tensor alive as long as the rule may write it
+        self._log_keep = getattr(self, "_log_keep", []) + ([log] if log is not None else [])
+        self.speed_controller, self._speed_log = controller, log
+
+    def speed_log(self):
+        """The speed rule's log ([log_rows, n_lanes] float64 view; None without one): row p = the speed answered for
+        played chunk p of each lane's current episode.  Rows a lane has not reached keep their earlier contents."""
+        return self._speed_log
 
     # -- plumbing ----------------------------------------------------------
     def _check(self, rc):

@@ -13,13 +13,16 @@ lanes: chunk_id int32[N]; previous_bitrates uint8[V, N] and previous_bandwidths
 float64[V, N] (rows < chunk_id are the lists' contents); buffer_level float64[N].
 It returns int32[N] bitrate indices.  `speed_controller.get_next_speed()` keeps the
 reference's meaning -- the speed of the next played chunk (Simulator.py:176-177) -- and is asked
-video_length times before the run (see Simulator._speeds).
+video_length times before the run (see Simulator._speeds).  A LatencySpeedController (speed.py) is not
+asked: it is a closed-loop rule over each lane's latency and buffer, evaluated on the device at the
+reference's call point (`Simulator(abr, speed_controller=LatencySpeedController.catch_up(3.0))`).
 """
 import torch
 
 from . import _lib
 from .datamodel import MPD, NetworkInfo, QOEMetric
 from .env import BatchedABREnv
+from .speed import LatencySpeedController
 from .traces import load_mpd_file, load_network_info
 
 
@@ -29,7 +32,11 @@ class _UnitSpeed:
 
 
 class Simulator(object):
-    def __init__(self, AbrController, SpeedController=None, n_lanes=1, device="cuda"):
+    def __init__(self, AbrController, SpeedController=None, n_lanes=1, device="cuda", speed_controller=None):
+        if speed_controller is not None:
+            if SpeedController is not None:
+                raise TypeError("give the speed controller once (SpeedController or speed_controller)")
+            SpeedController = speed_controller
         self.qoe_metric = None
         self.mpd = None
         self.network_info = None
@@ -86,8 +93,10 @@ class Simulator(object):
         return torch.stack(rows)
 
     def run(self):
+        speed = (self.speed_controller if isinstance(self.speed_controller, LatencySpeedController)
+                 else self._speeds())
         self.env = BatchedABREnv(self.mpd, self.qoe_metric, self.network_info, self.n_lanes,
-                                 device=self.device, speed=self._speeds())
+                                 device=self.device, speed=speed)
         env = self.env
         env.reset(self.trace_id, self.start_offset)
         chunk_id, _, buffer_level, _, _, done = env.mpc_inputs()

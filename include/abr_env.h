@@ -162,6 +162,39 @@ int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev);   /* latche
  * abr_env_set_lane_speeds.  Same lifetime and latching rules.  Event-driven kernels only. */
 int abr_env_set_speed_schedule(abr_env *env, const double *speeds_dev, int32_t n_rows);
 
+/* A closed-loop speed controller (ABI 4, additive; BUILD-DEFINED: the reference ships no speed
+ * controller, D8).  A stateless, piecewise-constant table, comparisons only, evaluated on the device
+ * exactly where the reference calls get_next_speed() (Simulator.py:176-177: the first playing tick of
+ * every played chunk, play_length == 0).  At that tick of played chunk p:
+ *   lat = global_time - play_time   float64 G[k] - pt, pt before this tick's += speed*dt: the
+ *                                   reference's instant_latency (:179)
+ *   buf = buffer_level              after this tick's += chunk_length when a download completes on it
+ *                                   (:170), before its -= speed*dt (:184)
+ *   i   = number of q < n_lat with lat >= lat_thr[q]
+ *   j   = number of r < n_buf with buf >= buf_thr[r]
+ * and the chunk plays at speed[i][j].  Everything after that -- the chunk's length in ticks,
+ * play_time, the drains, average_latency -- is the speed schedule's path (abr_env_set_speed_schedule).
+ * Fields: n_lat, n_buf in 0..4; lat_thr[0..n_lat) and buf_thr[0..n_buf) finite and strictly ascending
+ * [s]; speed[0..n_lat][0..n_buf] finite and > 0.  Entries past those counts are ignored. */
+#define ABR_SPEED_RULE_MAX_THR 4
+typedef struct abr_speed_rule {
+    int32_t n_lat, n_buf;
+    double  lat_thr[ABR_SPEED_RULE_MAX_THR];                               /* [s] */
+    double  buf_thr[ABR_SPEED_RULE_MAX_THR];                               /* [s] */
+    double  speed[ABR_SPEED_RULE_MAX_THR + 1][ABR_SPEED_RULE_MAX_THR + 1]; /* [i][j] */
+} abr_speed_rule;                                                          /* 272 bytes */
+
+/* Install a speed rule.  It and abr_env_set_lane_speeds / _speed_schedule are mutually exclusive: the
+ * last call wins; rule == NULL restores config.speed.  Latched like abr_env_set_speed_schedule (the next
+ * reset of ALL lanes adopts it; at once on a handle with no episode in flight).  The rule is copied by
+ * value: the caller's struct may go right after the call.  speed_log_dev: NULL, or caller-owned float64
+ * [log_rows][n_lanes] (same lifetime rules as speeds_dev above): row p receives the speed answered for
+ * played chunk p of the lane's current episode, for p < log_rows; rows never reached keep what they
+ * held.  A bad field (or log_rows < 0, or log_rows > 0 without a log) is ABR_E_INVALID before anything is
+ * stored, and the struct is checked before the handle.  Event-driven kernels only: ABR_E_UNSUPPORTED on
+ * impl 1, and abr_env_set_impl(1) refuses while a rule is set or pending. */
+int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, double *speed_log_dev, int32_t log_rows);
+
 /* Per-chunk bitrate ladders: br_table_dev float64 [video_length][n_rates], caller-owned, valid
  * from this call until the handle is destroyed or another call replaces it; NULL restores
  * config.ladder.  This is the evident intent of set_mpd's one-ladder-per-line file
