@@ -1128,21 +1128,48 @@ extern "C" int abr_env_has_impl(int32_t impl) {
     }
 }
 
+// Which implementation can serve which feature: bit k of `impls` = impl k.  The tick kernels (1) play one speed for all
+// lanes and take no MPC rollout; a speed rule is read where a played chunk begins, which the pipelines 4, 6 and 7 do not
+// do; a bitrate rule needs the call-site state in the thread that decides, which the role-split kernels' download wave
+// (2, 5: it runs ahead of the player) does not have -- `auto` (3) runs the one-thread-per-lane kernel for it.
+enum Feature { kLaneSpeeds, kSpeedRule, kRuleRollout, kMpcRollout };
+static const struct { unsigned impls; const char *what; } kFeatures[] = {
+    {0xFDu, "per-lane speeds and speed schedules need the event-driven kernels"},   // all but 1
+    {0x2Du, "a speed rule needs the event-driven kernels that read it"},            // 0, 2, 3, 5
+    {0x0Bu, "rule rollouts run on the one-thread-per-lane kernels"},                // 0, 1, 3
+    {0xFDu, "the fused MPC rollout needs the event-driven kernels"},                // all but 1
+};
+
+// ABR_OK if `impl` can serve `f`, else ABR_E_UNSUPPORTED with a message that names the impls this build accepts for it
+static int require(Feature f, int impl) {
+    const unsigned ok = kFeatures[f].impls;
+    if (ok >> impl & 1u) return ABR_OK;
+    int ks[8], n = 0, len = 0;
+    for (int k = 0; k < 8; k++)
+        if ((ok >> k & 1u) && abr_env_has_impl(k)) ks[n++] = k;
+    char list[48] = "";
+    for (int i = 0; i < n; i++)
+        len += snprintf(list + len, sizeof(list) - len, "%s%d", i == 0 ? "" : i + 1 < n ? ", " : " or ", ks[i]);
+    return fail(ABR_E_UNSUPPORTED, "%s (impl %s), not impl %d", kFeatures[f].what, list, impl);
+}
+
 // 3 = auto (default), 5 / 2 = role-split event-driven kernels (three / two waves per 64 lanes),
 // 0 = event-driven, one thread per lane, 1 = tick-by-tick kernels (kept as a cross-check)
 extern "C" int abr_env_set_impl(abr_env *env, int32_t impl) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (impl < 0 || impl > 7)
-        return fail(ABR_E_INVALID, "impl must be 0 (jump), 1 (tick), 2 (split), 3 (auto) or 5 (split3)");
+        return fail(ABR_E_INVALID, "impl must be in 0..7: 0 (jump), 1 (tick), 2 (split), 3 (auto) or 5 (split3); 4, 6 "
+                    "and 7 in the diagnostic build; got %d", impl);
     if (!abr_env_has_impl(impl))
         return fail(ABR_E_UNSUPPORTED, "impl %d (4: the asynchronous pipeline, 6: the ring-coupled role pipeline, 7: the pair rendezvous) is not part of "
                     "the product library: it is slower than what `auto` selects; the diagnostic build "
                     "tools/diag/lib/libabr_hip_diag.so carries it", impl);
-    if (impl == 1 && (env->p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on))))
-        return fail(ABR_E_UNSUPPORTED, "the tick-by-tick kernels take one speed for all lanes");
+    // what the running episodes play, or the next full reset will: a rule plays through the per-lane speeds as well
+    const bool speeds = env->p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on));
     const bool rule = env->speeds_dirty ? env->pending_rule_on : env->p.speed_rows == abrx::kSpeedRowsRule;
-    if (rule && (impl == 4 || impl == 6 || impl == 7))
-        return fail(ABR_E_UNSUPPORTED, "a speed rule needs the event-driven kernels (impl 0, 2, 3 or 5)");
+    int rc;
+    if (speeds && (rc = require(kLaneSpeeds, impl))) return rc;
+    if (rule && (rc = require(kSpeedRule, impl))) return rc;
     env->impl = impl;
     return ABR_OK;
 }
@@ -1150,8 +1177,8 @@ extern "C" int abr_env_set_impl(abr_env *env, int32_t impl) {
 // one constant play speed per lane (8f rank 3); nullptr restores the single config speed
 extern "C" int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    if (speeds_dev && env->impl == 1)
-        return fail(ABR_E_UNSUPPORTED, "per-lane speeds need the event-driven kernels (impl 0 or 2)");
+    int rc;
+    if (speeds_dev && (rc = require(kLaneSpeeds, env->impl))) return rc;
     // latched by the next FULL abr_env_reset: until then the running episodes keep the
     // speeds (and the carried play_time) they were started with
     env->pending_speeds = speeds_dev;
@@ -1165,8 +1192,8 @@ extern "C" int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev) {
 // a speed controller's answers, one row per played chunk (8f rank 3): speeds_dev [n_rows][n_lanes]
 extern "C" int abr_env_set_speed_schedule(abr_env *env, const double *speeds_dev, int32_t n_rows) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    if (speeds_dev && env->impl == 1)
-        return fail(ABR_E_UNSUPPORTED, "speed schedules need the event-driven kernels (impl 0 or 2)");
+    int rc;
+    if (speeds_dev && (rc = require(kLaneSpeeds, env->impl))) return rc;
     if (speeds_dev && n_rows < 1) return fail(ABR_E_INVALID, "n_rows must be >= 1");
     env->pending_speeds = speeds_dev;
     env->pending_speed_rows = speeds_dev ? n_rows : 1;
@@ -1207,8 +1234,8 @@ extern "C" int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, 
         if (log_rows > 0 && !speed_log_dev) return fail(ABR_E_INVALID, "log_rows > 0 needs speed_log_dev");
     }
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    if (rule && (env->impl == 1 || env->impl == 4 || env->impl == 6 || env->impl == 7))
-        return fail(ABR_E_UNSUPPORTED, "a speed rule needs the event-driven kernels (impl 0, 2, 3 or 5)");
+    int rc;
+    if (rule && (rc = require(kSpeedRule, env->impl))) return rc;
     env->pending_speeds = nullptr;
     env->pending_speed_rows = 1;
     env->pending_rule_on = rule != nullptr;
@@ -1302,29 +1329,68 @@ static inline int effective_impl(const abr_env *env, bool fused = false) {
     (void)fused;
     return impl;
 }
-static inline bool is_split(int impl) { return impl == 2 || impl == 5 || impl == 6 || impl == 7; }
-// launch of the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5)
+// The implementation that serves one launch of MODE (see launch_env): a reset and a rule rollout run the tick kernel under
+// impl 1 and the one-thread-per-lane kernel otherwise; a launch of one decision (MODE 1, or a fused call with
+// n_steps == 1) follows effective_impl(env, false), a fused rollout of more decisions effective_impl(env, true).
 template <int MODE>
-static void launch_split(int impl, const EnvParams &p, const int32_t *actions, float *obs, float *rew, uint8_t *dn,
-                         int32_t *acts, int32_t n_steps, uint64_t seed, hipStream_t st) {
-#ifdef ABR_WITH_RING
-    if (impl == 7) {
-        hipLaunchKernelGGL(env_pair3_kernel<MODE>, dim3(grid64(p.n_lanes)), dim3(192), 0, st, p, actions, obs, rew,
-                           dn, acts, n_steps, seed);
-        return;
-    }
-    if (impl == 6) {
-        hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(p.n_lanes)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs, rew,
-                           dn, acts, n_steps, seed);
-        return;
+static inline int launch_impl(const abr_env *env, int32_t n_steps) {
+    if (MODE == 0 || MODE == 4) return env->impl == 1 ? 1 : 0;
+    return effective_impl(env, n_steps > 1);
+}
+
+// The one place the environment kernels are launched, on impl = launch_impl<MODE>(...).  MODE 0: reset (trace_id,
+// start_offset, lane_mask); 1: one decision on `actions` [n_lanes]; 2: n_steps decisions of the built-in random policy
+// (`seed`); 3: n_steps decisions scripted in `actions` [n_steps][n_lanes]; 4: n_steps decisions of `rule`.  Outputs
+// obs / rew / dn / acts as abr_env_step_random, all nullable.  A reset and a rule rollout exist only as the tick and the
+// one-thread-per-lane kernel, the asynchronous pipeline only for MODE 2 and 3: the `if constexpr` keeps every other
+// instance out of the build.
+template <int MODE>
+static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
+                      uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule = {},
+                      const int32_t *trace_id = nullptr, const int32_t *start_offset = nullptr,
+                      const uint8_t *lane_mask = nullptr) {
+    const EnvParams &p = env->p;
+    const int64_t N = p.n_lanes;
+#ifdef ABR_WITH_ASYNC
+    if constexpr (MODE == 2 || MODE == 3) {
+        if (impl == 4) {
+            // the pipeline takes at most kMaxFuse decisions per launch (its action table lives in LDS); longer
+            // rollouts are cut into consecutive launches on the same stream
+            for (int32_t s0 = 0; s0 < n_steps; s0 += kMaxFuse) {
+                const int32_t n = n_steps - s0 < kMaxFuse ? n_steps - s0 : kMaxFuse;
+                hipLaunchKernelGGL(env_async_kernel<MODE>, dim3((unsigned)((N + kAW - 1) / kAW)), dim3(3 * kAW), 0, st,
+                                   p, actions ? actions + (int64_t)s0 * N : nullptr,
+                                   obs ? obs + (int64_t)s0 * ABR_OBS_DIM * N : nullptr,
+                                   rew ? rew + (int64_t)s0 * N : nullptr, dn ? dn + (int64_t)s0 * N : nullptr,
+                                   acts ? acts + (int64_t)s0 * N : nullptr, n, seed);
+            }
+            HIP_TRY(hipGetLastError());
+            return ABR_OK;
+        }
     }
 #endif
-    if (impl == 5)
-        hipLaunchKernelGGL(env_split3_kernel<MODE>, dim3(grid64(p.n_lanes)), dim3(192), 0, st, p, actions, obs, rew,
-                           dn, acts, n_steps, seed);
-    else
-        hipLaunchKernelGGL(env_split_kernel<MODE>, dim3(grid64(p.n_lanes)), dim3(128), 0, st, p, actions, obs, rew,
-                           dn, acts, n_steps, seed);
+    if (impl == 0 || impl == 1)
+        hipLaunchKernelGGL(impl == 1 ? env_advance_kernel<MODE> : env_jump_kernel<MODE>, dim3(grid64(N)), dim3(64), 0, st,
+                           p, actions, trace_id, start_offset, lane_mask, obs, rew, dn, acts, n_steps, seed, rule);
+    else if constexpr (MODE >= 1 && MODE <= 3) {
+        // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
+        if (impl == 5)
+            hipLaunchKernelGGL(env_split3_kernel<MODE>, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts,
+                               n_steps, seed);
+        else if (impl == 2)
+            hipLaunchKernelGGL(env_split_kernel<MODE>, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts,
+                               n_steps, seed);
+#ifdef ABR_WITH_RING
+        else if (impl == 6)
+            hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
+                               rew, dn, acts, n_steps, seed);
+        else if (impl == 7)
+            hipLaunchKernelGGL(env_pair3_kernel<MODE>, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts,
+                               n_steps, seed);
+#endif
+    }
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
 }
 
 extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
@@ -1340,69 +1406,26 @@ extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
                     "(lane_mask_dev must be NULL for the first reset after it)");
     apply_pending(env);
     env->armed = true;
-    hipLaunchKernelGGL(env->impl == 1 ? env_advance_kernel<0> : env_jump_kernel<0>, dim3(grid64(env->p.n_lanes)), dim3(64), 0,
-                       (hipStream_t)stream, env->p, nullptr, trace_id_dev, start_offset_dev,
-                       lane_mask_dev, obs_out_dev, nullptr, nullptr, nullptr, 0, 0ull, abrx::RuleParams{});
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    return launch_env<0>(env, launch_impl<0>(env, 0), (hipStream_t)stream, nullptr, obs_out_dev, nullptr, nullptr,
+                         nullptr, 0, 0ull, {}, trace_id_dev, start_offset_dev, lane_mask_dev);
 }
 
 extern "C" int abr_env_step(abr_env *env, const int32_t *actions_dev, float *obs_out_dev,
                             float *reward_out_dev, uint8_t *done_out_dev, void *stream) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (!actions_dev) return fail(ABR_E_INVALID, "actions_dev is NULL");
-    const int impl = effective_impl(env);
-    if (is_split(impl))
-        launch_split<1>(impl, env->p, actions_dev, obs_out_dev, reward_out_dev, done_out_dev, nullptr, 1, 0ull,
-                        (hipStream_t)stream);
-    else
-        hipLaunchKernelGGL(impl ? env_advance_kernel<1> : env_jump_kernel<1>, dim3(grid64(env->p.n_lanes)), dim3(64), 0,
-                           (hipStream_t)stream, env->p, actions_dev, nullptr, nullptr, nullptr,
-                           obs_out_dev, reward_out_dev, done_out_dev, nullptr, 1, 0ull, abrx::RuleParams{});
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    return launch_env<1>(env, launch_impl<1>(env, 1), (hipStream_t)stream, actions_dev, obs_out_dev, reward_out_dev,
+                         done_out_dev, nullptr, 1, 0ull);
 }
 
-// n_steps fused decisions per lane; MODE 2: built-in random policy, MODE 3: scripted actions
-// [n_steps][n_lanes].
-template <int MODE>
-static int launch_fused(abr_env *env, const int32_t *script, int32_t n_steps, uint64_t seed, float *obs,
-                        float *rew, uint8_t *dn, int32_t *acts, hipStream_t st) {
-    const int impl = effective_impl(env, n_steps > 1);
-    const int64_t N = env->p.n_lanes;
-#ifdef ABR_WITH_ASYNC
-    if (impl == 4) {
-        // the pipeline takes at most kMaxFuse decisions per launch (its action table lives in LDS); longer
-        // rollouts are cut into consecutive launches on the same stream
-        for (int32_t s0 = 0; s0 < n_steps; s0 += kMaxFuse) {
-            const int32_t n = n_steps - s0 < kMaxFuse ? n_steps - s0 : kMaxFuse;
-            hipLaunchKernelGGL(env_async_kernel<MODE>, dim3((unsigned)((N + kAW - 1) / kAW)), dim3(3 * kAW), 0, st,
-                               env->p, script ? script + (int64_t)s0 * N : nullptr,
-                               obs ? obs + (int64_t)s0 * ABR_OBS_DIM * N : nullptr,
-                               rew ? rew + (int64_t)s0 * N : nullptr, dn ? dn + (int64_t)s0 * N : nullptr,
-                               acts ? acts + (int64_t)s0 * N : nullptr, n, seed);
-        }
-        HIP_TRY(hipGetLastError());
-        return ABR_OK;
-    }
-#endif
-    if (is_split(impl))
-        launch_split<MODE>(impl, env->p, script, obs, rew, dn, acts, n_steps, seed, st);
-    else
-        hipLaunchKernelGGL(impl ? env_advance_kernel<MODE> : env_jump_kernel<MODE>, dim3(grid64(N)), dim3(64), 0,
-                           st, env->p, script, nullptr, nullptr, nullptr, obs, rew, dn, acts, n_steps, seed,
-                           abrx::RuleParams{});
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
+// n_steps fused decisions per lane under the built-in random policy
 extern "C" int abr_env_step_random(abr_env *env, int32_t n_steps, uint64_t seed,
                                    float *obs_out_dev, float *reward_out_dev,
                                    uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    return launch_fused<2>(env, nullptr, n_steps, seed, obs_out_dev, reward_out_dev, done_out_dev,
-                           actions_out_dev, (hipStream_t)stream);
+    return launch_env<2>(env, launch_impl<2>(env, n_steps), (hipStream_t)stream, nullptr, obs_out_dev, reward_out_dev,
+                         done_out_dev, actions_out_dev, n_steps, seed);
 }
 
 // The same fused rollout with the ABR controller's answers given up front: what run() does with a
@@ -1413,8 +1436,8 @@ extern "C" int abr_env_step_script(abr_env *env, int32_t n_steps, const int32_t 
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
     if (!actions_dev) return fail(ABR_E_INVALID, "actions_dev is NULL");
-    return launch_fused<3>(env, actions_dev, n_steps, 0ull, obs_out_dev, reward_out_dev, done_out_dev,
-                           nullptr, (hipStream_t)stream);
+    return launch_env<3>(env, launch_impl<3>(env, n_steps), (hipStream_t)stream, actions_dev, obs_out_dev, reward_out_dev,
+                         done_out_dev, nullptr, n_steps, 0ull);
 }
 
 // ---------------------------------------------------------------------------
@@ -1448,13 +1471,9 @@ extern "C" int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int3
     if (rc) return rc;
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    if (env->impl != 0 && env->impl != 1 && env->impl != 3)
-        return fail(ABR_E_UNSUPPORTED, "rule rollouts run on impl 0 (jump), 1 (tick) or 3 (auto), not %d", env->impl);
-    hipLaunchKernelGGL(env->impl == 1 ? env_advance_kernel<4> : env_jump_kernel<4>, dim3(grid64(env->p.n_lanes)), dim3(64),
-                       0, (hipStream_t)stream, env->p, nullptr, nullptr, nullptr, nullptr, obs_out_dev, reward_out_dev,
-                       done_out_dev, actions_out_dev, n_steps, 0ull, rp);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    if ((rc = require(kRuleRollout, env->impl))) return rc;
+    return launch_env<4>(env, launch_impl<4>(env, n_steps), (hipStream_t)stream, nullptr, obs_out_dev, reward_out_dev,
+                         done_out_dev, actions_out_dev, n_steps, 0ull, rp);
 }
 
 __global__ __launch_bounds__(256) void rule_select_kernel(EnvParams p, abrx::RuleParams rule, int32_t *__restrict__ action_out) {
@@ -2111,70 +2130,8 @@ static void launch_mpc(const MpcParams &p, int T, int D, hipStream_t st) {
     launch_mpc_b<H, 0, 0>(p, T, D, st);
 }
 
-static void fill_mpc_params(MpcParams &p, const abr_mpc_config *cfg, int64_t n_lanes) {
-    p.B = cfg->n_rates; p.H = cfg->horizon; p.V = cfg->video_length; p.clip = cfg->clip_horizon;
-    p.L = cfg->chunk_length; p.max_buffer = cfg->max_buffer; p.wv = cfg->variance_weight;
-    p.wr = cfg->rebuffer_weight; p.ws = cfg->startup_weight; p.n_lanes = n_lanes;
-    p.mask = nullptr; p.mask_is_done = 0; p.neg_to_zero = 0;
-    p.careful_all = !(fabs(p.L) <= kMpcFastEntryMax && fabs(p.max_buffer) <= kMpcFastEntryMax &&
-                      fabs(p.wv) <= kMpcFastWeightMax && fabs(p.wr) <= kMpcFastWeightMax &&
-                      fabs(p.ws) <= kMpcFastWeightMax);
-    p.predictor = 0; p.utility = 0; p.hist = nullptr; p.hist_stride = 0; p.hist_len = nullptr;
-    p.pre_pred = nullptr; p.pre_he = nullptr; p.pre_prev = nullptr;
-    p.pre_pred_w = nullptr; p.pre_he_w = nullptr; p.pre_prev_w = nullptr;
-    p.flat_out = nullptr; p.J_out = nullptr;
-}
-
 static size_t mpc_scratch_bytes(int H, int64_t n_lanes) {
     return (size_t)n_lanes * ((size_t)H * sizeof(double) + 2 * sizeof(int32_t));
-}
-
-// scratch != nullptr: run phase 1 as its own kernel first
-static int launch_mpc_select(MpcParams p, hipStream_t st, void *scratch = nullptr) {
-    if (scratch) {
-        p.pre_pred_w = (double *)scratch;
-        p.pre_he_w = (int32_t *)(p.pre_pred_w + (size_t)p.H * p.n_lanes);
-        p.pre_prev_w = p.pre_he_w + p.n_lanes;
-        p.pre_pred = nullptr;                      // the predictor kernel itself must not read "pre"
-        hipLaunchKernelGGL(mpc_predict_kernel, dim3((unsigned)((p.n_lanes + 255) / 256)), dim3(256), 0, st, p);
-        p.pre_pred = p.pre_pred_w; p.pre_he = p.pre_he_w; p.pre_prev = p.pre_prev_w;
-    }
-    const int D = (p.H >= 3) ? 2 : 1;
-    int T = p.B; if (D == 2) T *= p.B;
-    switch (p.H) {
-        case 2: launch_mpc<2>(p, T, D, st); break;
-        case 3: launch_mpc<3>(p, T, D, st); break;
-        case 4: launch_mpc<4>(p, T, D, st); break;
-        case 5: launch_mpc<5>(p, T, D, st); break;
-        case 6: launch_mpc<6>(p, T, D, st); break;
-        case 7: launch_mpc<7>(p, T, D, st); break;
-        case 8: launch_mpc<8>(p, T, D, st); break;
-        default: return fail(ABR_E_INVALID, "horizon %d", p.H);
-    }
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
-extern "C" int abr_mpc_select(const abr_mpc_config *cfg, const int32_t *chunk_dev,
-                              const int32_t *prev_bitrate_dev, const double *buffer_dev,
-                              double *hist_n_dev, double *hist_sum_inv_dev,
-                              const double *br_table_dev, const double *sz_table_dev,
-                              const uint8_t *lane_mask_dev, int32_t *action_out_dev,
-                              int32_t *best_flat_out_dev, double *best_J_out_dev, int64_t n_lanes,
-                              void *stream) {
-    int rc = validate_mpc(cfg);
-    if (rc) return rc;
-    if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !hist_n_dev || !hist_sum_inv_dev ||
-        !br_table_dev || !sz_table_dev || !action_out_dev)
-        return fail(ABR_E_INVALID, "NULL device pointer");
-    if (n_lanes < 1) return fail(ABR_E_INVALID, "n_lanes must be >= 1");
-    MpcParams p;
-    fill_mpc_params(p, cfg, n_lanes);
-    p.chunk = chunk_dev; p.prev = prev_bitrate_dev; p.buffer = buffer_dev;
-    p.hist_n = hist_n_dev; p.hist_s = hist_sum_inv_dev; p.br = br_table_dev; p.sz = sz_table_dev;
-    p.mask = lane_mask_dev; p.action_out = action_out_dev; p.flat_out = best_flat_out_dev;
-    p.J_out = best_J_out_dev;
-    return launch_mpc_select(p, (hipStream_t)stream);
 }
 
 static int apply_mpc_options(MpcParams &p, const abr_mpc_options *opt) {
@@ -2201,76 +2158,6 @@ extern "C" int abr_mpc_scratch_bytes(const abr_mpc_config *cfg, int64_t n_lanes,
     if (rc) return rc;
     if (n_lanes < 1 || !bytes_out) return fail(ABR_E_INVALID, "n_lanes must be >= 1 and bytes_out non-NULL");
     *bytes_out = mpc_scratch_bytes(cfg->horizon, n_lanes);
-    return ABR_OK;
-}
-
-extern "C" int abr_mpc_select_opt(const abr_mpc_config *cfg, const abr_mpc_options *opt,
-                                  const int32_t *chunk_dev, const int32_t *prev_bitrate_dev,
-                                  const double *buffer_dev, double *hist_n_dev,
-                                  double *hist_sum_inv_dev, const double *br_table_dev,
-                                  const double *sz_table_dev, const uint8_t *lane_mask_dev,
-                                  int32_t *action_out_dev, int32_t *best_flat_out_dev,
-                                  double *best_J_out_dev, int64_t n_lanes, void *stream) {
-    int rc = validate_mpc(cfg);
-    if (rc) return rc;
-    if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !hist_n_dev || !hist_sum_inv_dev ||
-        !br_table_dev || !sz_table_dev || !action_out_dev)
-        return fail(ABR_E_INVALID, "NULL device pointer");
-    if (n_lanes < 1) return fail(ABR_E_INVALID, "n_lanes must be >= 1");
-    MpcParams p;
-    fill_mpc_params(p, cfg, n_lanes);
-    rc = apply_mpc_options(p, opt);
-    if (rc) return rc;
-    p.chunk = chunk_dev; p.prev = prev_bitrate_dev; p.buffer = buffer_dev;
-    p.hist_n = hist_n_dev; p.hist_s = hist_sum_inv_dev; p.br = br_table_dev; p.sz = sz_table_dev;
-    p.mask = lane_mask_dev; p.action_out = action_out_dev; p.flat_out = best_flat_out_dev;
-    p.J_out = best_J_out_dev;
-    return launch_mpc_select(p, (hipStream_t)stream, opt ? opt->scratch_dev : nullptr);
-}
-
-// The composition the reference leaves unwired (D5/D6): for n_steps decisions,
-// action = MPCBitrateController.next_bitrate() on the lane's own state (mpc.py:181-186 reading
-// chunk_number / previous_bitrate / buffer_level / previous_bandwidths straight from the
-// environment's workspace, history mutation D9 included), then Simulator.run()'s download of
-// that chunk (Simulator.py:155-170).  Two launches per decision, enqueued back to back on
-// `stream`: K3 writes the actions, K1 consumes them; finished lanes are masked by their
-// done bits and "no decision" (empty history at chunk 0, D13) downloads bitrate 0.
-extern "C" int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg,
-                                const double *br_table_dev, const double *sz_table_dev,
-                                int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
-                                uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    int rc = validate_mpc(cfg);
-    if (rc) return rc;
-    if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (cfg->n_rates != env->p.n_rates || cfg->video_length != env->p.video_length)
-        return fail(ABR_E_INVALID, "MPC tables are [%d][%d], the environment has video_length %d, n_rates %d",
-                    cfg->video_length, cfg->n_rates, env->p.video_length, env->p.n_rates);
-    if (env->impl == 1) return fail(ABR_E_UNSUPPORTED, "the fused MPC rollout needs the event-driven kernels");
-    const EnvParams &e = env->p;
-    const int64_t N = e.n_lanes;
-    hipStream_t st = (hipStream_t)stream;
-    MpcParams p;
-    fill_mpc_params(p, cfg, N);
-    p.chunk = e.chunk_id; p.prev = e.last_action; p.buffer = e.buf;
-    p.hist_n = e.hist_n; p.hist_s = e.hist_s; p.br = br_table_dev; p.sz = sz_table_dev;
-    p.mask = e.done; p.mask_is_done = 1; p.neg_to_zero = 1;
-    for (int32_t s = 0; s < n_steps; s++) {
-        int32_t *act = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        p.action_out = act;
-        rc = launch_mpc_select(p, st, env->mpc_scratch);
-        if (rc) return rc;
-        float *obs = obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr;
-        float *rew = reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr;
-        uint8_t *dn = done_out_dev ? done_out_dev + (int64_t)s * N : nullptr;
-        if (is_split(effective_impl(env)))
-            launch_split<1>(effective_impl(env), env->p, act, obs, rew, dn, nullptr, 1, 0ull, st);
-        else
-            hipLaunchKernelGGL(env_jump_kernel<1>, dim3(grid64(N)), dim3(64), 0, st, env->p, act, nullptr,
-                               nullptr, nullptr, obs, rew, dn, nullptr, 1, 0ull, abrx::RuleParams{});
-        HIP_TRY(hipGetLastError());
-    }
     return ABR_OK;
 }
 
@@ -2347,17 +2234,94 @@ extern "C" int abr_mpc_robust_state_bytes(int32_t window, int64_t n_lanes, size_
     return ABR_OK;
 }
 
-// the robust predictor kernel, then the search through its pre_pred path
-static int launch_mpc_robust(MpcParams p, const abr_mpc_robust *r, const double *hist, int64_t hist_stride,
-                             void *scratch, hipStream_t st) {
-    p.pre_pred_w = (double *)scratch;
-    p.pre_he_w = (int32_t *)(p.pre_pred_w + (size_t)p.H * p.n_lanes);
-    p.pre_prev_w = p.pre_he_w + p.n_lanes;
-    p.pre_pred = nullptr;
-    hipLaunchKernelGGL(mpc_robust_predict_kernel, dim3((unsigned)((p.n_lanes + 255) / 256)), dim3(256), 0, st, p,
-                       r->window, (uint8_t *)r->state_dev, hist, hist_stride);
-    p.pre_pred = p.pre_pred_w; p.pre_he = p.pre_he_w; p.pre_prev = p.pre_prev_w;
-    return launch_mpc_select(p, st);
+// ===========================================================================
+// The host side of K3: the selects, and the rollouts that interleave them with K1
+// ===========================================================================
+// The search's parameters for n_lanes lanes: the config, the decision state (hist_n / hist_s: the harmonic history
+// summary, NULL under the robust predictor, which reads the history itself), the tables, the lane mask and the outputs.
+static MpcParams mpc_params(const abr_mpc_config *cfg, int64_t n_lanes, const int32_t *chunk, const int32_t *prev,
+                            const double *buffer, double *hist_n, double *hist_s, const double *br, const double *sz,
+                            const uint8_t *mask, int32_t *action_out, int32_t *flat_out, double *J_out) {
+    MpcParams p;
+    p.B = cfg->n_rates; p.H = cfg->horizon; p.V = cfg->video_length; p.clip = cfg->clip_horizon;
+    p.L = cfg->chunk_length; p.max_buffer = cfg->max_buffer; p.wv = cfg->variance_weight;
+    p.wr = cfg->rebuffer_weight; p.ws = cfg->startup_weight; p.n_lanes = n_lanes;
+    p.mask_is_done = 0; p.neg_to_zero = 0;
+    p.careful_all = !(fabs(p.L) <= kMpcFastEntryMax && fabs(p.max_buffer) <= kMpcFastEntryMax &&
+                      fabs(p.wv) <= kMpcFastWeightMax && fabs(p.wr) <= kMpcFastWeightMax &&
+                      fabs(p.ws) <= kMpcFastWeightMax);
+    p.predictor = 0; p.utility = 0; p.hist = nullptr; p.hist_stride = 0; p.hist_len = nullptr;
+    p.pre_pred = nullptr; p.pre_he = nullptr; p.pre_prev = nullptr;
+    p.pre_pred_w = nullptr; p.pre_he_w = nullptr; p.pre_prev_w = nullptr;
+    p.chunk = chunk; p.prev = prev; p.buffer = buffer; p.hist_n = hist_n; p.hist_s = hist_s; p.br = br; p.sz = sz;
+    p.mask = mask; p.action_out = action_out; p.flat_out = flat_out; p.J_out = J_out;
+    return p;
+}
+
+// The predictor, then the search.  scratch == nullptr: the search kernel predicts itself (harmonic or exponential
+// smoothing); otherwise the predictor runs first as its own kernel into `scratch`: mpc_predict_kernel, or, with `robust`,
+// mpc_robust_predict_kernel on the throughput history `hist` (row stride hist_stride).
+static int launch_mpc_select(MpcParams p, hipStream_t st, void *scratch, const abr_mpc_robust *robust = nullptr,
+                             const double *hist = nullptr, int64_t hist_stride = 0) {
+    if (scratch) {
+        p.pre_pred_w = (double *)scratch;
+        p.pre_he_w = (int32_t *)(p.pre_pred_w + (size_t)p.H * p.n_lanes);
+        p.pre_prev_w = p.pre_he_w + p.n_lanes;
+        p.pre_pred = nullptr;                      // the predictor kernel itself must not read "pre"
+        const dim3 grid((unsigned)((p.n_lanes + 255) / 256));
+        if (robust)
+            hipLaunchKernelGGL(mpc_robust_predict_kernel, grid, dim3(256), 0, st, p, robust->window,
+                               (uint8_t *)robust->state_dev, hist, hist_stride);
+        else
+            hipLaunchKernelGGL(mpc_predict_kernel, grid, dim3(256), 0, st, p);
+        p.pre_pred = p.pre_pred_w; p.pre_he = p.pre_he_w; p.pre_prev = p.pre_prev_w;
+    }
+    const int D = (p.H >= 3) ? 2 : 1;
+    int T = p.B; if (D == 2) T *= p.B;
+    switch (p.H) {
+        case 2: launch_mpc<2>(p, T, D, st); break;
+        case 3: launch_mpc<3>(p, T, D, st); break;
+        case 4: launch_mpc<4>(p, T, D, st); break;
+        case 5: launch_mpc<5>(p, T, D, st); break;
+        case 6: launch_mpc<6>(p, T, D, st); break;
+        case 7: launch_mpc<7>(p, T, D, st); break;
+        case 8: launch_mpc<8>(p, T, D, st); break;
+        default: return fail(ABR_E_INVALID, "horizon %d", p.H);
+    }
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+extern "C" int abr_mpc_select_opt(const abr_mpc_config *cfg, const abr_mpc_options *opt,
+                                  const int32_t *chunk_dev, const int32_t *prev_bitrate_dev,
+                                  const double *buffer_dev, double *hist_n_dev,
+                                  double *hist_sum_inv_dev, const double *br_table_dev,
+                                  const double *sz_table_dev, const uint8_t *lane_mask_dev,
+                                  int32_t *action_out_dev, int32_t *best_flat_out_dev,
+                                  double *best_J_out_dev, int64_t n_lanes, void *stream) {
+    int rc = validate_mpc(cfg);
+    if (rc) return rc;
+    if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !hist_n_dev || !hist_sum_inv_dev ||
+        !br_table_dev || !sz_table_dev || !action_out_dev)
+        return fail(ABR_E_INVALID, "NULL device pointer");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "n_lanes must be >= 1");
+    MpcParams p = mpc_params(cfg, n_lanes, chunk_dev, prev_bitrate_dev, buffer_dev, hist_n_dev, hist_sum_inv_dev,
+                             br_table_dev, sz_table_dev, lane_mask_dev, action_out_dev, best_flat_out_dev, best_J_out_dev);
+    rc = apply_mpc_options(p, opt);
+    if (rc) return rc;
+    return launch_mpc_select(p, (hipStream_t)stream, opt ? opt->scratch_dev : nullptr);
+}
+
+extern "C" int abr_mpc_select(const abr_mpc_config *cfg, const int32_t *chunk_dev,
+                              const int32_t *prev_bitrate_dev, const double *buffer_dev,
+                              double *hist_n_dev, double *hist_sum_inv_dev,
+                              const double *br_table_dev, const double *sz_table_dev,
+                              const uint8_t *lane_mask_dev, int32_t *action_out_dev,
+                              int32_t *best_flat_out_dev, double *best_J_out_dev, int64_t n_lanes,
+                              void *stream) {
+    return abr_mpc_select_opt(cfg, nullptr, chunk_dev, prev_bitrate_dev, buffer_dev, hist_n_dev, hist_sum_inv_dev,
+                              br_table_dev, sz_table_dev, lane_mask_dev, action_out_dev, best_flat_out_dev,
+                              best_J_out_dev, n_lanes, stream);
 }
 
 extern "C" int abr_mpc_select_robust(const abr_mpc_config *cfg, const abr_mpc_robust *robust,
@@ -2375,19 +2339,62 @@ extern "C" int abr_mpc_select_robust(const abr_mpc_config *cfg, const abr_mpc_ro
     if ((rc = validate_robust_sizes(robust, cfg->horizon, n_lanes, false))) return rc;
     if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !br_table_dev || !sz_table_dev || !action_out_dev)
         return fail(ABR_E_INVALID, "NULL device pointer");
-    MpcParams p;
-    fill_mpc_params(p, cfg, n_lanes);
+    MpcParams p = mpc_params(cfg, n_lanes, chunk_dev, prev_bitrate_dev, buffer_dev, nullptr, nullptr, br_table_dev,
+                             sz_table_dev, lane_mask_dev, action_out_dev, best_flat_out_dev, best_J_out_dev);
     p.utility = robust->utility;
     p.mask_is_done = robust->mask_is_done != 0;
-    p.chunk = chunk_dev; p.prev = prev_bitrate_dev; p.buffer = buffer_dev;
-    p.hist_n = nullptr; p.hist_s = nullptr; p.br = br_table_dev; p.sz = sz_table_dev;
-    p.mask = lane_mask_dev; p.action_out = action_out_dev; p.flat_out = best_flat_out_dev;
-    p.J_out = best_J_out_dev;
-    return launch_mpc_robust(p, robust, robust->hist_dev, robust->hist_stride, robust->scratch_dev, (hipStream_t)stream);
+    return launch_mpc_select(p, (hipStream_t)stream, robust->scratch_dev, robust, robust->hist_dev, robust->hist_stride);
 }
 
-// abr_env_step_mpc with the robust predictor: per decision the predictor kernel (reading the lane's bw_hist rows), the
-// search, then K1 MODE 1 on the same kernel choice as abr_env_step_mpc
+// The composition the reference leaves unwired (D5/D6), behind abr_env_step_mpc (robust == nullptr: the harmonic
+// predictor on the workspace's scratch) and abr_env_step_mpc_robust, whose arguments have been checked up to the
+// handle: for n_steps decisions, action = MPCBitrateController.next_bitrate() on the lane's own state (mpc.py:181-186
+// reading chunk_number / previous_bitrate / buffer_level / previous_bandwidths straight from the environment's
+// workspace, history mutation D9 included), then Simulator.run()'s download of that chunk (Simulator.py:155-170).
+// Per decision the predictor, the search and K1 MODE 1, enqueued back to back on `st`: finished lanes are masked by
+// their done bits and "no decision" (empty history at chunk 0, D13) downloads bitrate 0.
+static int mpc_rollout(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_robust *robust, const double *br_table_dev,
+                       const double *sz_table_dev, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                       uint8_t *done_out_dev, int32_t *actions_out_dev, hipStream_t st) {
+    const EnvParams &e = env->p;
+    const int64_t N = e.n_lanes;
+    if (cfg->n_rates != e.n_rates || cfg->video_length != e.video_length)
+        return fail(ABR_E_INVALID, "MPC tables are [%d][%d], the environment has video_length %d, n_rates %d",
+                    cfg->video_length, cfg->n_rates, e.video_length, e.n_rates);
+    int rc;
+    if (robust && (rc = validate_robust_sizes(robust, cfg->horizon, N, true))) return rc;
+    if ((rc = require(kMpcRollout, env->impl))) return rc;
+    MpcParams p = mpc_params(cfg, N, e.chunk_id, e.last_action, e.buf, robust ? nullptr : e.hist_n,
+                             robust ? nullptr : e.hist_s, br_table_dev, sz_table_dev, e.done, nullptr, nullptr, nullptr);
+    p.mask_is_done = 1; p.neg_to_zero = 1;
+    if (robust) p.utility = robust->utility;
+    void *scratch = robust && robust->scratch_dev ? robust->scratch_dev : env->mpc_scratch;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        p.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        if ((rc = launch_mpc_select(p, st, scratch, robust, e.bw_hist, N))) return rc;
+        rc = launch_env<1>(env, impl, st, p.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
+    return ABR_OK;
+}
+
+extern "C" int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg,
+                                const double *br_table_dev, const double *sz_table_dev,
+                                int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                                uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    int rc = validate_mpc(cfg);
+    if (rc) return rc;
+    if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    return mpc_rollout(env, cfg, nullptr, br_table_dev, sz_table_dev, n_steps, obs_out_dev, reward_out_dev, done_out_dev,
+                       actions_out_dev, (hipStream_t)stream);
+}
+
+// abr_env_step_mpc with the robust predictor (reading the lane's bw_hist rows): the options before the handle
 extern "C" int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_robust *robust,
                                        const double *br_table_dev, const double *sz_table_dev, int32_t n_steps,
                                        float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
@@ -2398,37 +2405,8 @@ extern "C" int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, 
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
-    if (cfg->n_rates != env->p.n_rates || cfg->video_length != env->p.video_length)
-        return fail(ABR_E_INVALID, "MPC tables are [%d][%d], the environment has video_length %d, n_rates %d",
-                    cfg->video_length, cfg->n_rates, env->p.video_length, env->p.n_rates);
-    const EnvParams &e = env->p;
-    const int64_t N = e.n_lanes;
-    if ((rc = validate_robust_sizes(robust, cfg->horizon, N, true))) return rc;
-    if (env->impl == 1) return fail(ABR_E_UNSUPPORTED, "the fused MPC rollout needs the event-driven kernels");
-    hipStream_t st = (hipStream_t)stream;
-    void *scratch = robust->scratch_dev ? robust->scratch_dev : env->mpc_scratch;
-    MpcParams p;
-    fill_mpc_params(p, cfg, N);
-    p.utility = robust->utility;
-    p.chunk = e.chunk_id; p.prev = e.last_action; p.buffer = e.buf;
-    p.hist_n = nullptr; p.hist_s = nullptr; p.br = br_table_dev; p.sz = sz_table_dev;
-    p.mask = e.done; p.mask_is_done = 1; p.neg_to_zero = 1;
-    for (int32_t s = 0; s < n_steps; s++) {
-        int32_t *act = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        p.action_out = act;
-        rc = launch_mpc_robust(p, robust, e.bw_hist, N, scratch, st);
-        if (rc) return rc;
-        float *obs = obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr;
-        float *rew = reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr;
-        uint8_t *dn = done_out_dev ? done_out_dev + (int64_t)s * N : nullptr;
-        if (is_split(effective_impl(env)))
-            launch_split<1>(effective_impl(env), env->p, act, obs, rew, dn, nullptr, 1, 0ull, st);
-        else
-            hipLaunchKernelGGL(env_jump_kernel<1>, dim3(grid64(N)), dim3(64), 0, st, env->p, act, nullptr,
-                               nullptr, nullptr, obs, rew, dn, nullptr, 1, 0ull, abrx::RuleParams{});
-        HIP_TRY(hipGetLastError());
-    }
-    return ABR_OK;
+    return mpc_rollout(env, cfg, robust, br_table_dev, sz_table_dev, n_steps, obs_out_dev, reward_out_dev, done_out_dev,
+                       actions_out_dev, (hipStream_t)stream);
 }
 
 // Diagnostic: the exact chain (abr_exact_jump.h) on arbitrary inputs, one case per thread, so

@@ -220,6 +220,17 @@ class BatchedABREnv:
             raise ValueError(f"{name} must have shape ({self.n_lanes},), got {tuple(t.shape)}")
         return t
 
+    def _rollout_out(self, n, want_obs=True, want_actions=True, actions_key=True):
+        """Fresh output tensors of n fused decisions: dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N]); an
+        entry that is not wanted is None, and actions_key=False leaves the actions key out (step_script)."""
+        N, dev = self.n_lanes, self.device
+        out = dict(obs=torch.empty(n, OBS_DIM, N, dtype=torch.float32, device=dev) if want_obs else None,
+                   reward=torch.empty(n, N, dtype=torch.float32, device=dev),
+                   done=torch.empty(n, N, dtype=torch.uint8, device=dev))
+        if actions_key:
+            out["actions"] = torch.empty(n, N, dtype=torch.int32, device=dev) if want_actions else None
+        return out
+
     # -- the step surface --------------------------------------------------
     def reset(self, trace_id=None, start_offset=None, mask=None, check=False):
         """Simulator.py:95-133 + idle ticks to the first ABR call.  Default assignment: lane i -> trace
@@ -271,12 +282,7 @@ class BatchedABREnv:
         random policy.  Returns dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
         n = int(n_steps)
         if out is None:
-            out = dict(
-                obs=torch.empty(n, OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device),
-                reward=torch.empty(n, self.n_lanes, dtype=torch.float32, device=self.device),
-                done=torch.empty(n, self.n_lanes, dtype=torch.uint8, device=self.device),
-                actions=(torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
-                         if want_actions else None))
+            out = self._rollout_out(n, want_actions=want_actions)
         ptrs = getattr(out, "ptrs", None)
         if ptrs is None:
             ptrs = (_lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
@@ -304,10 +310,7 @@ class BatchedABREnv:
             raise ValueError(f"actions must have shape (n_steps, {self.n_lanes}), got {tuple(a.shape)}")
         n = int(a.shape[0])
         if out is None:
-            out = dict(
-                obs=torch.empty(n, OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device),
-                reward=torch.empty(n, self.n_lanes, dtype=torch.float32, device=self.device),
-                done=torch.empty(n, self.n_lanes, dtype=torch.uint8, device=self.device))
+            out = self._rollout_out(n, actions_key=False)
         self._call(self.lib.abr_env_step_script, self._h, n, _lib.ptr(a), _lib.ptr(out.get("obs")),
                    _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")))
         return out
@@ -330,13 +333,7 @@ class BatchedABREnv:
         br, sz = controller._tables()
         cfg = controller.config()
         if out is None:
-            out = dict(
-                obs=(torch.empty(n, OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device)
-                     if want_obs else None),
-                reward=torch.empty(n, self.n_lanes, dtype=torch.float32, device=self.device),
-                done=torch.empty(n, self.n_lanes, dtype=torch.uint8, device=self.device),
-                actions=(torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
-                         if want_actions else None))
+            out = self._rollout_out(n, want_obs, want_actions)
         if getattr(controller, "method", None) == "robust":
             # RobustMPC: the controller's per-lane state rides along; the estimates go through the workspace's scratch
             rob = controller.robust_options(self.n_lanes)
@@ -357,13 +354,7 @@ class BatchedABREnv:
         n = int(n_steps)
         cfg = controller.config()
         if out is None:
-            out = dict(
-                obs=(torch.empty(n, OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device)
-                     if want_obs else None),
-                reward=torch.empty(n, self.n_lanes, dtype=torch.float32, device=self.device),
-                done=torch.empty(n, self.n_lanes, dtype=torch.uint8, device=self.device),
-                actions=(torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
-                         if want_actions else None))
+            out = self._rollout_out(n, want_obs, want_actions)
         self._call(self.lib.abr_env_step_rule, self._h, C.byref(cfg), n, _lib.ptr(out.get("obs")),
                    _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
         return out

@@ -158,6 +158,14 @@ class BatchedMPCController:
             r.scratch_dev, r.scratch_bytes = scratch.data_ptr(), scratch.numel()
         return r
 
+    def _predictor_scratch(self, cfg, n_lanes):
+        """The predictor kernel's scratch for n_lanes lanes (abr_mpc_scratch_bytes), grown when it is too small."""
+        need = C.c_size_t()
+        _lib.check(self.lib.abr_mpc_scratch_bytes(C.byref(cfg), n_lanes, C.byref(need)))
+        if self._scratch is None or self._scratch.numel() < need.value:
+            self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        return self._scratch
+
     def next_bitrate(self, want_details=False):
         """mpc.py:181-186, batched: returns int32 [N] bitrate indices."""
         ci = self.player.get_next_chunk_info()
@@ -188,11 +196,8 @@ class BatchedMPCController:
             opt.predictor, opt.utility = self.METHODS[self.method], self.UTILITIES[self.utility]
             if self.use_scratch:
                 # scratch for the predictor pre-kernel (include/abr_env.h: abr_mpc_options.scratch_dev)
-                need = C.c_size_t()
-                _lib.check(self.lib.abr_mpc_scratch_bytes(C.byref(cfg), N, C.byref(need)))
-                if self._scratch is None or self._scratch.numel() < need.value:
-                    self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
-                opt.scratch_dev, opt.scratch_bytes = self._scratch.data_ptr(), self._scratch.numel()
+                scratch = self._predictor_scratch(cfg, N)
+                opt.scratch_dev, opt.scratch_bytes = scratch.data_ptr(), scratch.numel()
             self._bound = (key, cfg, opt)
         _, cfg, opt = self._bound
         opt.mask_is_done = mask_is_done
@@ -218,10 +223,7 @@ class BatchedMPCController:
         key = self._bind_key(N)
         if self._bound is None or self._bound[0] != key:
             cfg = self.config()
-            need = C.c_size_t()
-            _lib.check(self.lib.abr_mpc_scratch_bytes(C.byref(cfg), N, C.byref(need)))
-            if self._scratch is None or self._scratch.numel() < need.value:
-                self._scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+            self._predictor_scratch(cfg, N)
             self._bound = (key, cfg, None)
         cfg = self._bound[1]
         hist = ci.previous_bandwidths

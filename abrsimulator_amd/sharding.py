@@ -264,29 +264,25 @@ class ShardedABREnv:
         n = int(actions.shape[0])
         return self._launch(n, lambda out: self.env.step_script(actions, out=out))
 
-    def step_mpc(self, controller, n_steps):
-        """n_steps decisions taken by `controller` on this shard's own state (actions are computed where the lane lives;
-        only (obs, reward) is gathered)."""
-        n = int(n_steps)
-
+    def _launch_controlled(self, step, controller, n):
+        """_launch of env.step_mpc / env.step_rule (`step`) under `controller`: the actions are computed where the lane
+        lives, into a tensor of their own when the bound output has none."""
         def call(out):
             if out is not None and out.get("actions") is None:
                 out = dict(out)
                 out["actions"] = torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
-            return self.env.step_mpc(controller, n, out=out)
+            return step(controller, n, out=out)
         return self._launch(n, call)
+
+    def step_mpc(self, controller, n_steps):
+        """n_steps decisions taken by `controller` on this shard's own state (actions are computed where the lane lives;
+        only (obs, reward) is gathered)."""
+        return self._launch_controlled(self.env.step_mpc, controller, int(n_steps))
 
     def step_rule(self, controller, n_steps):
         """n_steps decisions taken by a bitrate rule (rules.py) on this shard's own state; as step_mpc, only (obs, reward)
         is gathered."""
-        n = int(n_steps)
-
-        def call(out):
-            if out is not None and out.get("actions") is None:
-                out = dict(out)
-                out["actions"] = torch.empty(n, self.n_lanes, dtype=torch.int32, device=self.device)
-            return self.env.step_rule(controller, n, out=out)
-        return self._launch(n, call)
+        return self._launch_controlled(self.env.step_rule, controller, int(n_steps))
 
     @property
     def n_collectives(self):

@@ -152,7 +152,8 @@ int abr_env_set_lane_id_base(abr_env *env, int64_t lane_id_base);
  * speeds they started with; the next abr_env_reset picks the new ones up, and that reset must
  * cover all lanes (lane_mask_dev == NULL, else ABR_E_INVALID).  On a handle that has seen neither
  * abr_env_reset nor abr_env_notify_restore there is no episode to protect and the call takes
- * effect at once.  NULL restores the single speed.  Event-driven kernels only. */
+ * effect at once.  NULL restores the single speed.  Event-driven kernels only: ABR_E_UNSUPPORTED on
+ * impl 1, and abr_env_set_impl(1) refuses while per-lane speeds are in force or pending. */
 int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev);   /* latched: see above */
 
 /* What a speed controller answers, call by call (Simulator.py:176-177: get_next_speed() is
@@ -191,8 +192,8 @@ typedef struct abr_speed_rule {
  * [log_rows][n_lanes] (same lifetime rules as speeds_dev above): row p receives the speed answered for
  * played chunk p of the lane's current episode, for p < log_rows; rows never reached keep what they
  * held.  A bad field (or log_rows < 0, or log_rows > 0 without a log) is ABR_E_INVALID before anything is
- * stored, and the struct is checked before the handle.  Event-driven kernels only: ABR_E_UNSUPPORTED on
- * impl 1, and abr_env_set_impl(1) refuses while a rule is set or pending. */
+ * stored, and the struct is checked before the handle.  Impl 0, 2, 3 and 5 only: ABR_E_UNSUPPORTED on 1 (tick) and
+ * on the diagnostic pipelines 4, 6 and 7, and abr_env_set_impl refuses those while a rule is set or pending. */
 int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, double *speed_log_dev, int32_t log_rows);
 
 /* Per-chunk bitrate ladders: br_table_dev float64 [video_length][n_rates], caller-owned, valid
@@ -431,7 +432,7 @@ int abr_mpc_select_opt(const abr_mpc_config *cfg, const abr_mpc_options *opt,
  *  reference would raise on (empty history at chunk 0: ZeroDivisionError, D13; horizon past
  *  the video end without clip_horizon, D12) downloads bitrate 0 and keeps its history.
  *  Outputs (all nullable): obs [n_steps][ABR_OBS_DIM][n_lanes], reward/done/actions
- *  [n_steps][n_lanes], as abr_env_step_random.  Event-driven kernels only (impl 0 or 2).
+ *  [n_steps][n_lanes], as abr_env_step_random.  Event-driven kernels only: ABR_E_UNSUPPORTED on impl 1.
  */
 int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg, const double *br_table_dev,
                      const double *sz_table_dev, int32_t n_steps, float *obs_out_dev,

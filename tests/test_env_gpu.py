@@ -726,3 +726,71 @@ def test_product_kernels_answer_the_fresh_params_selfcheck():
     assert res.cpu().tolist() == [1, 1], res.cpu().tolist()
     assert torch.equal(env.workspace, before)                    # no lane state touched
     assert env.lib.abr_debug_selfcheck(None, _lib.ptr(res), None) == -1
+
+
+# What each implementation accepts, as return codes (0 or ABR_E_UNSUPPORTED = -4): abr_env_set_impl(k); then on that
+# handle abr_env_set_lane_speeds, abr_env_set_speed_schedule and abr_env_set_speed_rule with a valid argument (each
+# withdrawn again), one decision each of abr_env_step_rule, abr_env_step_mpc and abr_env_step_mpc_robust; then
+# abr_env_set_impl(k) on a handle with a speed rule in force and on one with per-lane speeds in force.  None: not reached,
+# the library does not carry impl k.
+CAPS = ("set_impl", "lane_speeds", "schedule", "speed_rule", "step_rule", "step_mpc", "step_mpc_robust",
+        "set_impl_under_rule", "set_impl_under_speeds")
+_U = -4
+_ABSENT = (_U, None, None, None, None, None, None, _U, _U)
+CAPABILITY = {
+    ("product", 0): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+    ("product", 1): (0, _U, _U, _U, 0, _U, _U, _U, _U),
+    ("product", 2): (0, 0, 0, 0, _U, 0, 0, 0, 0),
+    ("product", 3): (0, 0, 0, 0, 0, 0, 0, 0, 0),
+    ("product", 4): _ABSENT,
+    ("product", 5): (0, 0, 0, 0, _U, 0, 0, 0, 0),
+    ("product", 6): _ABSENT,
+    ("product", 7): _ABSENT,
+    ("diag", 4): (0, 0, 0, _U, _U, 0, 0, _U, 0),
+    ("diag", 6): (0, 0, 0, _U, _U, 0, 0, _U, 0),
+    ("diag", 7): (0, 0, 0, _U, _U, 0, 0, _U, 0),
+}
+
+
+@pytest.mark.parametrize("library,impl", list(CAPABILITY), ids=[f"{l}-{k}" for l, k in CAPABILITY])
+def test_capability_matrix(library, impl):
+    import ctypes as C
+
+    import abrsimulator_amd as A
+    from abrsimulator_amd import _lib
+    from helpers import diag_lib
+    N = 64
+    meta, traces, trace_id, offset, _ = _random_case(seed=43, N=N, V=8)
+    kw = {"library": diag_lib()} if library == "diag" else {}
+    speeds = torch.full((2, N), 1.25, dtype=torch.float64, device="cuda")
+    ctl = A.LatencySpeedController((2.0, 6.0), (1.0, 8.0), ((0.9, 1.0, 1.0), (0.9, 1.1, 1.25), (0.75, 1.5, 2.0)))
+    env = make_env(meta, traces, N, **kw)
+    lib, h = env.lib, env._h
+    got = [lib.abr_env_set_impl(h, impl)]
+    if got[0] == 0:
+        got.append(lib.abr_env_set_lane_speeds(h, _lib.ptr(speeds[0])))
+        _lib.check(lib.abr_env_set_lane_speeds(h, None), lib)
+        got.append(lib.abr_env_set_speed_schedule(h, _lib.ptr(speeds), 2))
+        _lib.check(lib.abr_env_set_speed_schedule(h, None, 0), lib)
+        got.append(lib.abr_env_set_speed_rule(h, C.byref(ctl.to_struct()), None, 0))
+        _lib.check(lib.abr_env_set_speed_rule(h, None, None, 0), lib)
+        env.reset(torch.from_numpy(trace_id), torch.from_numpy(offset))
+        player, st = A.EnvPlayer(env), _lib.current_stream(env.device)
+        rule = A.BufferBasedController(player).config()
+        got.append(lib.abr_env_step_rule(h, C.byref(rule), 1, None, None, None, None, st))
+        mpc = A.BatchedMPCController(player, horizon=3)
+        br, sz = mpc._tables()
+        got.append(lib.abr_env_step_mpc(h, C.byref(mpc.config()), _lib.ptr(br), _lib.ptr(sz), 1, None, None, None,
+                                        None, st))
+        rob = A.BatchedMPCController(player, horizon=3, method="robust")
+        got.append(lib.abr_env_step_mpc_robust(h, C.byref(rob.config()), C.byref(rob.robust_options(N)), _lib.ptr(br),
+                                               _lib.ptr(sz), 1, None, None, None, None, st))
+        torch.cuda.synchronize()
+    else:
+        got += [None] * 6
+    for in_force in (lambda e: e.set_speed_controller(ctl),
+                     lambda e: _lib.check(e.lib.abr_env_set_lane_speeds(e._h, _lib.ptr(speeds[0])), e.lib)):
+        e = make_env(meta, traces, N, **kw)
+        in_force(e)
+        got.append(e.lib.abr_env_set_impl(e._h, impl))
+    assert tuple(got) == CAPABILITY[(library, impl)], dict(zip(CAPS, got))
