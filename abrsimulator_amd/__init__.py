@@ -6,6 +6,7 @@ the import fails (there is no CPU fallback).
 from . import _lib
 from .datamodel import MPD, Chunk, ChunkInfo, NetworkInfo, QOEMetric
 from .env import BatchedABREnv, obs_dict, pack_traces
+from .fastmpc import FastMPCController
 from .mpc import BatchedMPCController, EnvPlayer
 from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
@@ -17,6 +18,6 @@ from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd
 _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
-           "BatchedMPCController", "EnvPlayer", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
+           "BatchedMPCController", "EnvPlayer", "FastMPCController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

@@ -94,6 +94,14 @@ class RuleConfig(C.Structure):
 
 RULE_BUFFER, RULE_RATE, RULE_BOLA = 1, 2, 3
 
+FASTMPC_MAX_POINTS = 256
+
+
+class FastMpc(C.Structure):
+    _fields_ = [("window", C.c_int32), ("utility", C.c_int32), ("n_rows", C.c_int32), ("n_buffer", C.c_int32),
+                ("n_tput", C.c_int32), ("buffer_points", C.c_void_p), ("buffer_edges", C.c_void_p),
+                ("tput_points", C.c_void_p), ("tput_edges", C.c_void_p), ("reserved_", C.c_int32 * 2)]
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -147,6 +155,15 @@ SYMBOLS = [
                                         _P, C.c_int64, _P]),
     ("abr_env_step_mpc_robust", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(MpcRobust), _P, _P, C.c_int32, _P, _P,
                                           _P, _P, _P]),
+    ("abr_fastmpc_table_bytes", C.c_int, [C.POINTER(MpcConfig), C.POINTER(FastMpc), C.POINTER(C.c_size_t)]),
+    ("abr_fastmpc_build_scratch_bytes", C.c_int, [C.POINTER(MpcConfig), C.POINTER(FastMpc), C.POINTER(C.c_size_t)]),
+    ("abr_fastmpc_build", C.c_int, [C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, _P, _P, C.c_size_t, _P, C.c_size_t,
+                                    _P]),
+    ("abr_fastmpc_select", C.c_int, [C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, C.c_size_t, _P, _P, _P, _P,
+                                     C.c_int64, _P, C.c_int32, _P, C.c_int64, _P]),
+    ("abr_env_step_fastmpc", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, C.c_int32, _P, _P, _P, _P,
+                                       _P]),
+    ("abr_env_fastmpc_select", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

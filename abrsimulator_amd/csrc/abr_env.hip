@@ -15,6 +15,8 @@
 //         caller provides scratch) + exhaustive B^H: B^2 threads per lane; tables in LDS, depth-first enumeration with
 //         prefix sharing, LDS arg-max over the threads, first-leaf search below the winning node
 //   K3r   mpc_robust_predict_kernel      RobustMPC's estimate (abr_lane_jump.h: robust_estimate) ahead of the same search
+//   K3f   fastmpc_grid_kernel / _pack    FastMPC's table: every grid point through the same search, first actions as uint8;
+//         the lookup itself is MODE 4 (abr_lane_jump.h: fastmpc_lookup) and fastmpc_select_kernel
 //   K4    episode_qoe_kernel        Simulator.py:79-86
 //
 // Exactness contract: every quantity that feeds a decision in the
@@ -356,11 +358,12 @@ __device__ inline void write_obs(const Lane &s, const EnvParams &p, int64_t i, f
 
 // MODE 4's action: a standard bitrate rule (abr_lane_jump.h: rule_select) on the lane's call-site state -- chunk_id,
 // buffer_level, and previous_bandwidths read back from the lane's bw_hist rows (coalesced: row stride n_lanes; the rows
-// of this launch's earlier decisions are the lane's own stores)
-__device__ inline int32_t rule_action(const EnvParams &p, const abrx::RuleParams &rule, int64_t i, int32_t c, double B) {
+// of this launch's earlier decisions are the lane's own stores); FastMPC also reads previous_bitrates[-1] (pv)
+__device__ inline int32_t rule_action(const EnvParams &p, const abrx::RuleParams &rule, int64_t i, int32_t c, int32_t pv,
+                                      double B) {
     const auto br = [&](int32_t m) { return chunk_bitrate(p, c, m); };
     const auto hist = [&](int32_t j) { return p.bw_hist[(int64_t)j * p.n_lanes + i]; };
-    return abrx::rule_select(rule, br, hist, p.n_rates, c, B);
+    return abrx::rule_select_at(rule, br, hist, p.n_rates, p.video_length, c, pv, B);
 }
 
 // MODE 0: reset (fresh lanes run to their first call site)
@@ -488,7 +491,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                 int32_t a;
                 if (MODE == 1) a = actions[i];
                 else if (MODE == 3) a = actions[(int64_t)step_idx * p.n_lanes + i];
-                else if (MODE == 4) a = rule_action(p, rule, i, s.chunk_id, s.buf);
+                else if (MODE == 4) a = rule_action(p, rule, i, s.chunk_id, s.last_action, s.buf);
                 else a = (int32_t)philox_action(seed, (uint64_t)(p.lane_id_base + i),
                                                 (uint32_t)s.chunk_id, (uint32_t)episode_no,
                                                 (uint32_t)p.n_rates);
@@ -749,7 +752,7 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
             if (active) {
                 // MODE 4: the rule runs BEFORE the step's burst of loads, so that its loops do not hold the burst's
                 // registers live (it decides chunk_id's download: nothing of the step is needed)
-                const int32_t a_rule = (MODE == 4) ? rule_action(p, rule, i, s.chunk_id, s.buf) : 0;
+                const int32_t a_rule = (MODE == 4) ? rule_action(p, rule, i, s.chunk_id, s.last_action, s.buf) : 0;
                 // one burst of loads for everything the step needs (issued before the
                 // policy arithmetic so that the two overlap)
                 const abrx::StepStart st = abrx::lanej_begin_step(s.cur, tb, s.k, s.chunk_id);
@@ -1479,7 +1482,7 @@ extern "C" int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int3
 __global__ __launch_bounds__(256) void rule_select_kernel(EnvParams p, abrx::RuleParams rule, int32_t *__restrict__ action_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n_lanes) return;
-    action_out[i] = p.done[i] ? -1 : rule_action(p, rule, i, p.chunk_id[i], p.buf[i]);
+    action_out[i] = p.done[i] ? -1 : rule_action(p, rule, i, p.chunk_id[i], p.last_action[i], p.buf[i]);
 }
 
 extern "C" int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, int32_t *action_out_dev, void *stream) {
@@ -2407,6 +2410,277 @@ extern "C" int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, 
     if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
     return mpc_rollout(env, cfg, robust, br_table_dev, sz_table_dev, n_steps, obs_out_dev, reward_out_dev, done_out_dev,
                        actions_out_dev, (hipStream_t)stream);
+}
+
+// ===========================================================================
+// FastMPC (include/abr_env.h: abr_fastmpc): the search over a quantised state space, then a lookup per decision
+// ===========================================================================
+// The build: per slice of grid entries, fastmpc_grid_kernel writes each entry's chunk / previous bitrate / buffer and the
+// pre_pred / pre_he / pre_prev scratch exactly as mpc_robust_predict_kernel does, the unchanged mpc_select_kernel
+// instances search it (launch_mpc_select without a predictor), and fastmpc_pack_kernel stores the first actions as uint8.
+// The grids reach the device as kernel arguments (fastmpc_copy_kernel): no host copy, nothing synchronises.
+constexpr int64_t kFastMpcSlice = 131072;      // grid entries per slice: bounds the scratch (~9 MB at H = 5)
+constexpr int kFastMpcCopy = 128;              // doubles per fastmpc_copy_kernel launch
+
+struct FastMpcCopy {
+    int32_t n;
+    double v[kFastMpcCopy];
+};
+
+__global__ __launch_bounds__(kFastMpcCopy) void fastmpc_copy_kernel(double *__restrict__ dst, FastMpcCopy a) {
+    const int k = threadIdx.x;
+    if (k < a.n) dst[k] = a.v[k];
+}
+
+// entries [first, first + p.n_lanes) of the table; lane = entry - first
+__global__ __launch_bounds__(256) void fastmpc_grid_kernel(MpcParams p, int64_t first, int32_t uniform, int32_t nb,
+                                                           int32_t nq, const double *__restrict__ bp,
+                                                           const double *__restrict__ tp, int32_t *__restrict__ chunk_w,
+                                                           int32_t *__restrict__ prev_w, double *__restrict__ buf_w) {
+    const int64_t lane = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (lane >= p.n_lanes) return;
+    const int64_t N = p.n_lanes;
+    int64_t e = first + lane;
+    const int32_t qi = (int32_t)(e % nq); e /= nq;
+    const int32_t bi = (int32_t)(e % nb); e /= nb;
+    const int32_t pv = (int32_t)(e % p.B);
+    const int32_t row = (int32_t)(e / p.B);
+    const int32_t c = uniform ? p.V - 1 - row : row;           // 0 <= c < V: the host checked the layout
+    chunk_w[lane] = c; prev_w[lane] = pv; buf_w[lane] = bp[bi];
+    // D12 as mpc_predict_lane; the previous bitrate is a valid index and the prediction > 0 by construction
+    int he = p.H;
+    if (c + p.H > p.V) he = p.clip ? (p.V - c) : 0;
+    const double P = tp[qi];
+    for (int i = 0; i < p.H; i++) p.pre_pred_w[(int64_t)i * N + lane] = P;
+    p.pre_he_w[lane] = he; p.pre_prev_w[lane] = pv;
+}
+
+// "no decision" (-1) is stored as 0: what abr_env_step_mpc downloads for it
+__global__ __launch_bounds__(256) void fastmpc_pack_kernel(const int32_t *__restrict__ act, uint8_t *__restrict__ table,
+                                                           int64_t first, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t a = act[i];
+    table[first + i] = (uint8_t)(a < 0 ? 0 : a);
+}
+
+// the standalone lookup: one thread per player
+__global__ __launch_bounds__(256) void fastmpc_select_kernel(abrx::RuleParams r, int32_t M, int32_t V,
+                                                             const int32_t *__restrict__ chunk,
+                                                             const int32_t *__restrict__ prev,
+                                                             const double *__restrict__ buffer,
+                                                             const double *__restrict__ hist, int64_t hist_stride,
+                                                             const uint8_t *__restrict__ mask, int32_t mask_is_done,
+                                                             int32_t *__restrict__ action_out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (mask && ((mask[i] != 0) == (mask_is_done != 0))) {
+        if (mask_is_done) action_out[i] = -1;
+        return;
+    }
+    const auto hf = [&](int32_t j) { return hist[(int64_t)j * hist_stride + i]; };
+    action_out[i] = abrx::fastmpc_lookup(r, hf, M, V, chunk[i], prev[i], buffer[i]);
+}
+
+// one grid: count, finiteness, order, the points' sign, and every point in its own cell
+static int validate_fastmpc_grid(const char *what, int32_t n, const double *pt, const double *ed, bool positive) {
+    if (n < 1 || n > ABR_FASTMPC_MAX_POINTS)
+        return fail(ABR_E_INVALID, "%s grid has %d points, allowed 1..%d", what, n, ABR_FASTMPC_MAX_POINTS);
+    if (!pt) return fail(ABR_E_INVALID, "%s points are NULL", what);
+    if (n > 1 && !ed) return fail(ABR_E_INVALID, "%s edges are NULL", what);
+    for (int32_t k = 0; k < n; k++) {
+        if (!std::isfinite(pt[k])) return fail(ABR_E_INVALID, "%s point %d is not finite", what, k);
+        if (k > 0 && !(pt[k] > pt[k - 1])) return fail(ABR_E_INVALID, "%s points are not strictly ascending at %d", what, k);
+    }
+    if (positive ? !(pt[0] > 0.0) : !(pt[0] >= 0.0))
+        return fail(ABR_E_INVALID, "%s points must be %s (got %g)", what, positive ? "> 0" : ">= 0", pt[0]);
+    for (int32_t k = 0; k + 1 < n; k++) {
+        if (!std::isfinite(ed[k])) return fail(ABR_E_INVALID, "%s edge %d is not finite", what, k);
+        if (k > 0 && !(ed[k] > ed[k - 1])) return fail(ABR_E_INVALID, "%s edges are not strictly ascending at %d", what, k);
+    }
+    for (int32_t k = 0; k < n; k++) {
+        const bool lo_ok = k == 0 || ed[k - 1] <= pt[k], hi_ok = k + 1 == n || pt[k] < ed[k];
+        if (!lo_ok || !hi_ok) return fail(ABR_E_INVALID, "%s point %d (%g) lies outside its cell", what, k, pt[k]);
+    }
+    return ABR_OK;
+}
+
+// the options every entry point checks: window, utility, layout, grid counts; `grids`: the points and edges too
+static int validate_fastmpc(const abr_mpc_config *cfg, const abr_fastmpc *fm, bool grids) {
+    int rc = validate_mpc(cfg);
+    if (rc) return rc;
+    if (!fm) return fail(ABR_E_INVALID, "fastmpc options are NULL");
+    if (fm->window < 1 || fm->window > ABR_ROBUST_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "fastmpc window %d outside 1..%d", fm->window, ABR_ROBUST_MAX_WINDOW);
+    if (fm->utility != ABR_UTILITY_IDENTITY && fm->utility != ABR_UTILITY_LOG)
+        return fail(ABR_E_INVALID, "utility must be ABR_UTILITY_IDENTITY or ABR_UTILITY_LOG");
+    if (fm->n_rows != cfg->video_length && fm->n_rows != cfg->horizon)
+        return fail(ABR_E_INVALID, "fastmpc n_rows %d is neither video_length %d nor horizon %d", fm->n_rows,
+                    cfg->video_length, cfg->horizon);
+    if (fm->n_rows != cfg->video_length && cfg->horizon > cfg->video_length)
+        return fail(ABR_E_INVALID, "the uniform layout (n_rows = horizon %d) needs horizon < video_length %d",
+                    cfg->horizon, cfg->video_length);
+    for (int32_t n : {fm->n_buffer, fm->n_tput})
+        if (n < 1 || n > ABR_FASTMPC_MAX_POINTS)
+            return fail(ABR_E_INVALID, "fastmpc grid has %d points, allowed 1..%d", n, ABR_FASTMPC_MAX_POINTS);
+    if (!grids) return ABR_OK;
+    if ((rc = validate_fastmpc_grid("buffer", fm->n_buffer, fm->buffer_points, fm->buffer_edges, false))) return rc;
+    return validate_fastmpc_grid("throughput", fm->n_tput, fm->tput_points, fm->tput_edges, true);
+}
+
+static int64_t fastmpc_entries(const abr_mpc_config *cfg, const abr_fastmpc *fm) {
+    return (int64_t)fm->n_rows * cfg->n_rates * fm->n_buffer * fm->n_tput;
+}
+static size_t fastmpc_table_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm) {
+    return (size_t)abrx::fastmpc_entry_bytes(fm->n_rows, cfg->n_rates, fm->n_buffer, fm->n_tput) +
+           (size_t)(fm->n_buffer - 1 + fm->n_tput - 1) * sizeof(double);
+}
+// the grid points, then per slice: pre_pred [H][S] and buffer [S] float64, pre_he, pre_prev, chunk, prev, action [S] int32
+static int64_t fastmpc_slice(const abr_mpc_config *cfg, const abr_fastmpc *fm) {
+    const int64_t n = fastmpc_entries(cfg, fm);
+    return n < kFastMpcSlice ? n : kFastMpcSlice;
+}
+static size_t fastmpc_scratch_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm) {
+    return (size_t)(fm->n_buffer + fm->n_tput) * sizeof(double) +
+           (size_t)fastmpc_slice(cfg, fm) * ((size_t)(cfg->horizon + 1) * sizeof(double) + 5 * sizeof(int32_t));
+}
+
+extern "C" int abr_fastmpc_table_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm, size_t *bytes_out) {
+    int rc = validate_fastmpc(cfg, fm, true);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    *bytes_out = fastmpc_table_bytes(cfg, fm);
+    return ABR_OK;
+}
+
+extern "C" int abr_fastmpc_build_scratch_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm, size_t *bytes_out) {
+    int rc = validate_fastmpc(cfg, fm, true);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    *bytes_out = fastmpc_scratch_bytes(cfg, fm);
+    return ABR_OK;
+}
+
+// host array -> device, in kernel-argument slices on `st`
+static void fastmpc_copy(double *dst, const double *src, int32_t n, hipStream_t st) {
+    for (int32_t k0 = 0; k0 < n; k0 += kFastMpcCopy) {
+        FastMpcCopy a;
+        a.n = n - k0 < kFastMpcCopy ? n - k0 : kFastMpcCopy;
+        for (int32_t k = 0; k < a.n; k++) a.v[k] = src[k0 + k];
+        hipLaunchKernelGGL(fastmpc_copy_kernel, dim3(1), dim3(kFastMpcCopy), 0, st, dst + k0, a);
+    }
+}
+
+extern "C" int abr_fastmpc_build(const abr_mpc_config *cfg, const abr_fastmpc *fm, const double *br_table_dev,
+                                 const double *sz_table_dev, void *table_dev, size_t table_bytes, void *scratch_dev,
+                                 size_t scratch_bytes, void *stream) {
+    int rc = validate_fastmpc(cfg, fm, true);
+    if (rc) return rc;
+    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if (table_bytes < fastmpc_table_bytes(cfg, fm))
+        return fail(ABR_E_INVALID, "fastmpc table has %zu bytes, need %zu", table_bytes, fastmpc_table_bytes(cfg, fm));
+    if (!scratch_dev || ((uintptr_t)scratch_dev & 7))
+        return fail(ABR_E_INVALID, "fastmpc scratch must be non-NULL and 8-byte aligned");
+    if (scratch_bytes < fastmpc_scratch_bytes(cfg, fm))
+        return fail(ABR_E_INVALID, "fastmpc scratch has %zu bytes, need %zu", scratch_bytes, fastmpc_scratch_bytes(cfg, fm));
+    if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
+    hipStream_t st = (hipStream_t)stream;
+    const int32_t M = cfg->n_rates, nb = fm->n_buffer, nq = fm->n_tput, H = cfg->horizon;
+    const int32_t uniform = fm->n_rows != cfg->video_length;
+    uint8_t *table = (uint8_t *)table_dev;
+    double *be = (double *)(table + abrx::fastmpc_entry_bytes(fm->n_rows, M, nb, nq)), *te = be + (nb - 1);
+    fastmpc_copy(be, fm->buffer_edges, nb - 1, st);
+    fastmpc_copy(te, fm->tput_edges, nq - 1, st);
+    double *bp = (double *)scratch_dev, *tp = bp + nb;
+    fastmpc_copy(bp, fm->buffer_points, nb, st);
+    fastmpc_copy(tp, fm->tput_points, nq, st);
+    HIP_TRY(hipGetLastError());
+    const int64_t S = fastmpc_slice(cfg, fm), total = fastmpc_entries(cfg, fm);
+    double *pre_pred = tp + nq, *buf = pre_pred + (size_t)H * S;
+    int32_t *pre_he = (int32_t *)(buf + S), *pre_prev = pre_he + S, *chunk = pre_prev + S, *prev = chunk + S,
+            *act = prev + S;
+    for (int64_t first = 0; first < total; first += S) {
+        const int64_t n = total - first < S ? total - first : S;
+        MpcParams p = mpc_params(cfg, n, chunk, prev, buf, nullptr, nullptr, br_table_dev, sz_table_dev, nullptr, act,
+                                 nullptr, nullptr);
+        p.utility = fm->utility;
+        p.pre_pred_w = pre_pred; p.pre_he_w = pre_he; p.pre_prev_w = pre_prev;
+        const dim3 grid((unsigned)((n + 255) / 256));
+        hipLaunchKernelGGL(fastmpc_grid_kernel, grid, dim3(256), 0, st, p, first, uniform, nb, nq, bp, tp, chunk, prev,
+                           buf);
+        p.pre_pred = pre_pred; p.pre_he = pre_he; p.pre_prev = pre_prev;
+        if ((rc = launch_mpc_select(p, st, nullptr))) return rc;
+        hipLaunchKernelGGL(fastmpc_pack_kernel, grid, dim3(256), 0, st, act, table, first, n);
+        HIP_TRY(hipGetLastError());
+    }
+    return ABR_OK;
+}
+
+static abrx::RuleParams fastmpc_rule(const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev) {
+    abrx::RuleParams r{};
+    r.kind = abrx::kRuleFastMpc; r.window = fm->window;
+    r.fm_table = (const uint8_t *)table_dev;
+    r.fm_uniform = fm->n_rows != cfg->video_length;
+    r.fm_horizon = cfg->horizon; r.fm_nb = fm->n_buffer; r.fm_nq = fm->n_tput;
+    return r;
+}
+
+extern "C" int abr_fastmpc_select(const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev,
+                                  size_t table_bytes, const int32_t *chunk_dev, const int32_t *prev_bitrate_dev,
+                                  const double *buffer_dev, const double *hist_dev, int64_t hist_stride,
+                                  const uint8_t *lane_mask_dev, int32_t mask_is_done, int32_t *action_out_dev,
+                                  int64_t n_lanes, void *stream) {
+    int rc = validate_fastmpc(cfg, fm, false);
+    if (rc) return rc;
+    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if (table_bytes < fastmpc_table_bytes(cfg, fm))
+        return fail(ABR_E_INVALID, "fastmpc table has %zu bytes, need %zu", table_bytes, fastmpc_table_bytes(cfg, fm));
+    if (!hist_dev || hist_stride < 1) return fail(ABR_E_INVALID, "the lookup needs the history: hist_dev and hist_stride >= 1");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "n_lanes must be >= 1");
+    if (!chunk_dev || !prev_bitrate_dev || !buffer_dev || !action_out_dev) return fail(ABR_E_INVALID, "NULL device pointer");
+    hipLaunchKernelGGL(fastmpc_select_kernel, dim3((unsigned)((n_lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       fastmpc_rule(cfg, fm, table_dev), cfg->n_rates, cfg->video_length, chunk_dev, prev_bitrate_dev,
+                       buffer_dev, hist_dev, hist_stride, lane_mask_dev, mask_is_done, action_out_dev, n_lanes);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// the env entry points' checks after the handle: the tables' shape, the layout against a per-chunk bitrate table
+static int fastmpc_env_check(const abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm) {
+    if (cfg->n_rates != env->p.n_rates || cfg->video_length != env->p.video_length)
+        return fail(ABR_E_INVALID, "the FastMPC table is for video_length %d, n_rates %d; the environment has %d, %d",
+                    cfg->video_length, cfg->n_rates, env->p.video_length, env->p.n_rates);
+    const bool per_chunk = env->br_table_dirty ? env->pending_br_table != nullptr : env->p.br_table != nullptr;
+    if (fm->n_rows != cfg->video_length && per_chunk)
+        return fail(ABR_E_INVALID, "the uniform FastMPC layout needs one ladder, but a per-chunk bitrate table is in force");
+    return ABR_OK;
+}
+
+extern "C" int abr_env_step_fastmpc(abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev,
+                                    int32_t n_steps, float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                    int32_t *actions_out_dev, void *stream) {
+    int rc = validate_fastmpc(cfg, fm, false);
+    if (rc) return rc;
+    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if ((rc = fastmpc_env_check(env, cfg, fm))) return rc;
+    if ((rc = require(kRuleRollout, env->impl))) return rc;
+    return launch_env<4>(env, launch_impl<4>(env, n_steps), (hipStream_t)stream, nullptr, obs_out_dev, reward_out_dev,
+                         done_out_dev, actions_out_dev, n_steps, 0ull, fastmpc_rule(cfg, fm, table_dev));
+}
+
+extern "C" int abr_env_fastmpc_select(abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm,
+                                      const void *table_dev, int32_t *action_out_dev, void *stream) {
+    int rc = validate_fastmpc(cfg, fm, false);
+    if (rc) return rc;
+    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    if ((rc = fastmpc_env_check(env, cfg, fm))) return rc;
+    hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, env->p, fastmpc_rule(cfg, fm, table_dev), action_out_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
 }
 
 // Diagnostic: the exact chain (abr_exact_jump.h) on arbitrary inputs, one case per thread, so

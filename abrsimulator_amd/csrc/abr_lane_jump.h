@@ -649,14 +649,20 @@ ABR_HD StepResult lanej_step(LaneJ &s, const Tables &t, double target, int32_t a
 // float64 in a fixed operation order (the library builds with -ffp-contract=off), so a numpy twin written in the same
 // order reproduces every answer bit for bit.  `br` and `hist` are accessors, so that the kernels read the ladder and the
 // history rows straight from where they live (no copy into a local array, which would cost scratch).
-enum { kRuleBuffer = 1, kRuleRate = 2, kRuleBola = 3 };
+// kRuleFastMpc is internal: the FastMPC lookup (include/abr_env.h: abr_fastmpc), reached through abr_env_step_fastmpc only
+enum { kRuleBuffer = 1, kRuleRate = 2, kRuleBola = 3, kRuleFastMpc = 4 };
 
 struct RuleParams {
-    int32_t kind, window;                    // kRule*; RATE: W >= 1
+    int32_t kind, window;                    // kRule*; RATE, FastMPC: W >= 1
     double reservoir, cushion;               // BUFFER: r >= 0, k > 0 [s]
     double safety;                           // RATE: s > 0
     double bola_v, bola_gp;                  // BOLA: V > 0, gp
     const double *utility;                   // BOLA: [video_length][n_rates]
+    // FastMPC (appended, so that every field above keeps its offset): the blob -- uint8 entries [fm_rows][M][fm_nb][fm_nq],
+    // padded to 8 bytes, then the fm_nb - 1 buffer edges and the fm_nq - 1 throughput edges, float64
+    const uint8_t *fm_table;
+    int32_t fm_uniform;                      // 0: row = c; 1: row = min(V - c, fm_horizon) - 1
+    int32_t fm_horizon, fm_nb, fm_nq;
 };
 
 // the highest index m in 1..M-1 with br(m) <= X, else 0 (on an ascending ladder: the highest rate not above X)
@@ -711,6 +717,50 @@ ABR_HD int32_t rule_select(const RuleParams &r, const BR &br, const HIST &hist, 
     if (r.kind == kRuleBuffer) return rule_buffer(r, br, M, B);
     if (r.kind == kRuleRate) return rule_rate(r, br, hist, M, c);
     return rule_bola(r, br, M, c, B);
+}
+
+// ---- FastMPC's lookup (include/abr_env.h: abr_fastmpc) ----
+// the number of the n ascending edges e[0..n) that are <= x, by bisection (NaN: 0; +inf: n)
+ABR_HD int32_t fastmpc_cell(const double *e, int32_t n, double x) {
+    int32_t lo = 0, hi = n;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (e[mid] <= x) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// bytes of the blob's entries before the edges: n_rows * M * Nb * Nq, rounded up to 8
+ABR_HD int64_t fastmpc_entry_bytes(int32_t n_rows, int32_t M, int32_t nb, int32_t nq) {
+    return (((int64_t)n_rows * M * nb * nq) + 7) & ~(int64_t)7;
+}
+
+// The decision at a call site: chunk c, previous bitrate pv (Python's -M..-1 wrap), buffer B, history h[0..c).  -1 for a
+// chunk outside [0, V) or a previous bitrate outside [-M, M), which no environment lane presents.
+template <class HIST>
+ABR_HD int32_t fastmpc_lookup(const RuleParams &r, const HIST &hist, int32_t M, int32_t V, int32_t c, int32_t pv,
+                              double B) {
+    if (c < 0 || c >= V || pv < -M || pv >= M) return -1;
+    const int32_t n = r.window < c ? r.window : c;
+    if (n <= 0) return 0;
+    const double P = harmonic_tail(hist, c, n);
+    if (pv < 0) pv += M;
+    const int32_t row = r.fm_uniform ? ((V - c < r.fm_horizon ? V - c : r.fm_horizon) - 1) : c;
+    const int32_t rows = r.fm_uniform ? r.fm_horizon : V;
+    const double *be = (const double *)(r.fm_table + fastmpc_entry_bytes(rows, M, r.fm_nb, r.fm_nq));
+    const double *te = be + (r.fm_nb - 1);
+    const int32_t bi = fastmpc_cell(be, r.fm_nb - 1, B);
+    const int32_t qi = fastmpc_cell(te, r.fm_nq - 1, P);
+    return r.fm_table[(((int64_t)row * M + pv) * r.fm_nb + bi) * r.fm_nq + qi];
+}
+
+// rule_select with the call-site arguments only FastMPC reads (V, the previous bitrate)
+template <class BR, class HIST>
+ABR_HD int32_t rule_select_at(const RuleParams &r, const BR &br, const HIST &hist, int32_t M, int32_t V, int32_t c,
+                              int32_t pv, double B) {
+    if (r.kind == kRuleFastMpc) return fastmpc_lookup(r, hist, M, V, c, pv, B);
+    return rule_select(r, br, hist, M, c, B);
 }
 
 // ---- RobustMPC's throughput estimate (Yin et al. 2015; include/abr_env.h: abr_mpc_robust) ----

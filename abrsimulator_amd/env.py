@@ -348,10 +348,19 @@ class BatchedABREnv:
 
     def step_rule(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True):
         """n_steps decisions per lane taken by a bitrate rule (rules.py: BufferBasedController, RateBasedController,
-        BolaController) on the device, on each lane's own call-site state, with no host work between decisions.  Runs the
-        one-thread-per-lane kernel under 'auto' and 'jump', the tick kernel under 'tick'; 'split' / 'split3' are refused
-        (include/abr_env.h).  Returns dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
+        BolaController; fastmpc.py: FastMPCController, which runs abr_env_step_fastmpc on its table) on the device, on each
+        lane's own call-site state, with no host work between decisions.  Runs the one-thread-per-lane kernel under 'auto'
+        and 'jump', the tick kernel under 'tick'; 'split' / 'split3' are refused (include/abr_env.h).  Returns
+        dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
         n = int(n_steps)
+        if getattr(controller, "method", None) == "fastmpc":
+            cfg, fm, table = controller.bound()
+            if out is None:
+                out = self._rollout_out(n, want_obs, want_actions)
+            self._call(self.lib.abr_env_step_fastmpc, self._h, C.byref(cfg), C.byref(fm), _lib.ptr(table), n,
+                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
+                       _lib.ptr(out.get("actions")))
+            return out
         cfg = controller.config()
         if out is None:
             out = self._rollout_out(n, want_obs, want_actions)

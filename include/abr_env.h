@@ -535,6 +535,86 @@ int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int32_t n_steps
  * lane whose done bits are set. */
 int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, int32_t *action_out_dev, void *stream);
 
+/*
+ * FastMPC (Yin et al., SIGCOMM 2015; ABI 4, additive; BUILD-DEFINED: the reference has no FastMPC).  The MPC search is run
+ * once, on the device, over a quantised state space; a decision is then one table lookup, evaluated inside the environment
+ * kernels like the bitrate rules above.
+ *
+ * Inputs: an abr_mpc_config and br / sz tables [V][M] exactly as for abr_mpc_select, the utility, a window W in 1..16, a
+ * buffer grid of Nb points bp[] with Nb - 1 edges be[], and a throughput grid of Nq points tp[] with Nq - 1 edges te[]
+ * (host arrays of float64, Nb and Nq in 1..ABR_FASTMPC_MAX_POINTS, edges NULL allowed when there are none).  Points and
+ * edges are finite and strictly ascending, buffer points >= 0, throughput points > 0, and every point lies in its own cell:
+ * e[k-1] <= p[k] < e[k] (so that a state exactly on a grid point reads that point's entry).
+ * Layout: n_rows == V: one row per chunk (row = c); otherwise n_rows == H < V: the UNIFORM layout, valid only when every
+ * row of br / sz is the same (the caller's promise: the library does not read the tables on the host), row of chunk c =
+ * min(V - c, H) - 1, and row r is built at chunk V - 1 - r.
+ *
+ * Table: uint8 entries [n_rows][M][Nb][Nq] (q fastest).  Entry (row, p, bi, qi) = int(result[0]) of the first-minimum
+ * arg-min of objective() at chunk c_row, previous_bitrate p, buffer_level bp[bi] and C_hat[i] = tp[qi] for every
+ * i < H_eff -- D10, D11, the D12 clip, the non-finite rules and the utility as abr_mpc_select -- with "no decision" (without
+ * clip_horizon: c_row + H > V) stored as 0, which is what abr_env_step_mpc downloads for it.
+ *
+ * Lookup, for a lane at a call site with chunk c, previous bitrate prev (-M..-1 wrap as in Python), buffer B and history
+ * h[0..c):  n = min(W, c); n == 0 -> action 0 (as RATE).  P = ABR_RULE_RATE's harmonic mean of h[c-n .. c-1] (same
+ * float64 operations, same order).  bi = number of buffer edges <= B, qi = number of throughput edges <= P (NaN: 0, +inf:
+ * the last cell).  action = table[row(c)][prev][bi][qi].  Comparisons only after P: a numpy twin reproduces every answer.
+ *
+ * Blob (caller-owned device memory, 8-byte aligned, abr_fastmpc_table_bytes): the entries, padded to a multiple of 8 bytes,
+ * then be[0 .. Nb-1), then te[0 .. Nq-1), float64.  abr_fastmpc_build writes all of it on the stream (the grids travel as
+ * kernel arguments: the host arrays may go as soon as the call returns).  A blob is only meaningful for the config, tables,
+ * utility, layout and grid it was built with, and the window of the lookups is the caller's to keep with it (as the
+ * RobustMPC state and its window).
+ */
+#define ABR_FASTMPC_MAX_POINTS 256
+typedef struct abr_fastmpc {
+    int32_t window;               /* W, 1..ABR_ROBUST_MAX_WINDOW */
+    int32_t utility;              /* ABR_UTILITY_* */
+    int32_t n_rows;               /* video_length (per chunk) or horizon (uniform, horizon < video_length) */
+    int32_t n_buffer;             /* Nb, 1..ABR_FASTMPC_MAX_POINTS */
+    int32_t n_tput;               /* Nq, 1..ABR_FASTMPC_MAX_POINTS */
+    const double *buffer_points;  /* host [Nb], [s] */
+    const double *buffer_edges;   /* host [Nb - 1] */
+    const double *tput_points;    /* host [Nq], the ladder's unit */
+    const double *tput_edges;     /* host [Nq - 1] */
+    int32_t reserved_[2];         /* set to 0 */
+} abr_fastmpc;
+
+/* Bytes of the blob, and of the build's device scratch (8-byte aligned; the build runs the grid in slices, so this is
+ * bounded whatever the table's size).  Both check the config and every field of fm as the build does. */
+int abr_fastmpc_table_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm, size_t *bytes_out);
+int abr_fastmpc_build_scratch_bytes(const abr_mpc_config *cfg, const abr_fastmpc *fm, size_t *bytes_out);
+
+/* Build the table into the blob: the existing MPC search on every grid point, slice after slice, all enqueued on `stream`.
+ * br_table_dev / sz_table_dev: [video_length][n_rates] as abr_mpc_select.  Validation (ABR_E_INVALID, nothing launched):
+ * the config, fm, the blob and the scratch (non-NULL, 8-byte aligned, at least the size queries' bytes), the tables. */
+int abr_fastmpc_build(const abr_mpc_config *cfg, const abr_fastmpc *fm, const double *br_table_dev,
+                      const double *sz_table_dev, void *table_dev, size_t table_bytes, void *scratch_dev,
+                      size_t scratch_bytes, void *stream);
+
+/* The lookup for n_lanes independent players: chunk_dev / prev_bitrate_dev / buffer_dev as abr_mpc_select, the history
+ * entry j of lane i at hist_dev[j * hist_stride + i] (at least min(W, chunk) rows before the chunk).  action_out_dev int32
+ * [n_lanes]; a lane whose chunk is outside [0, V) or whose previous bitrate is outside [-M, M) reports -1.
+ * lane_mask_dev (nullable) as abr_mpc_options with mask_is_done: skipped lanes keep their action, except under
+ * mask_is_done, which reports -1.  table_bytes is checked against the size query. */
+int abr_fastmpc_select(const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev, size_t table_bytes,
+                       const int32_t *chunk_dev, const int32_t *prev_bitrate_dev, const double *buffer_dev,
+                       const double *hist_dev, int64_t hist_stride, const uint8_t *lane_mask_dev, int32_t mask_is_done,
+                       int32_t *action_out_dev, int64_t n_lanes, void *stream);
+
+/* n_steps fused decisions per lane taken by the lookup on each lane's own call-site state (chunk_id, previous_bitrates[-1],
+ * buffer_level, the environment's previous_bandwidths rows), as abr_env_step_rule: outputs (nullable) as
+ * abr_env_step_random, done lanes take no decision (action -1); kernels as abr_env_step_rule (ABR_E_UNSUPPORTED on 2 and 5).
+ * Validation (ABR_E_INVALID, nothing launched): the config, fm (its grid only by count: the lookup reads the edges from the
+ * blob) and n_steps before the handle; then M and V against the environment, and the uniform layout is refused while a
+ * per-chunk bitrate table (abr_env_set_bitrate_table) is in force or pending. */
+int abr_env_step_fastmpc(abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev,
+                         int32_t n_steps, float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                         int32_t *actions_out_dev, void *stream);
+/* The lookup's answer for each lane on the environment's current state, no step: action_out_dev int32 [n_lanes], -1 for a
+ * lane whose done bits are set.  Checks as abr_env_step_fastmpc. */
+int abr_env_fastmpc_select(abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev,
+                           int32_t *action_out_dev, void *stream);
+
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
 int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t prev_bitrate,
