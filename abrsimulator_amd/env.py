@@ -330,6 +330,11 @@ class BatchedABREnv:
         abr_env_step_mpc_robust with its own per-lane state).  Returns
         dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
         n = int(n_steps)
+        method, utility = getattr(controller, "method", "harmonic"), getattr(controller, "utility", "identity")
+        if method != "robust" and (method != "harmonic" or utility != "identity"):
+            # abr_env_step_mpc runs the harmonic predictor and the identity utility: anything else would be ignored
+            raise ValueError(f"step_mpc runs method='harmonic' with utility='identity', or method='robust'; this "
+                             f"controller has method={method!r}, utility={utility!r}")
         br, sz = controller._tables()
         cfg = controller.config()
         if out is None:
