@@ -102,6 +102,15 @@ class FastMpc(C.Structure):
                 ("n_tput", C.c_int32), ("buffer_points", C.c_void_p), ("buffer_edges", C.c_void_p),
                 ("tput_points", C.c_void_p), ("tput_edges", C.c_void_p), ("reserved_", C.c_int32 * 2)]
 
+POLICY_MAX_WINDOW, POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH = 16, 2, 64
+
+
+class Policy(C.Structure):
+    _fields_ = [("window", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * POLICY_MAX_HIDDEN),
+                ("weights_dev", C.c_void_p), ("weights_bytes", C.c_size_t), ("norm_dev", C.c_void_p),
+                ("seed", C.c_uint64), ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
+
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -164,6 +173,10 @@ SYMBOLS = [
     ("abr_env_step_fastmpc", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, C.c_int32, _P, _P, _P, _P,
                                        _P]),
     ("abr_env_fastmpc_select", C.c_int, [_P, C.POINTER(MpcConfig), C.POINTER(FastMpc), _P, _P, _P]),
+    ("abr_policy_feature_dim", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    ("abr_policy_weights_bytes", C.c_int, [C.POINTER(Policy), C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_policy_select", C.c_int, [_P, C.POINTER(Policy), _P, _P, _P, _P]),
+    ("abr_env_step_policy", C.c_int, [_P, C.POINTER(Policy), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

@@ -1135,12 +1135,13 @@ extern "C" int abr_env_has_impl(int32_t impl) {
 // lanes and take no MPC rollout; a speed rule is read where a played chunk begins, which the pipelines 4, 6 and 7 do not
 // do; a bitrate rule needs the call-site state in the thread that decides, which the role-split kernels' download wave
 // (2, 5: it runs ahead of the player) does not have -- `auto` (3) runs the one-thread-per-lane kernel for it.
-enum Feature { kLaneSpeeds, kSpeedRule, kRuleRollout, kMpcRollout };
+enum Feature { kLaneSpeeds, kSpeedRule, kRuleRollout, kMpcRollout, kPolicyRollout };
 static const struct { unsigned impls; const char *what; } kFeatures[] = {
     {0xFDu, "per-lane speeds and speed schedules need the event-driven kernels"},   // all but 1
     {0x2Du, "a speed rule needs the event-driven kernels that read it"},            // 0, 2, 3, 5
     {0x0Bu, "rule rollouts run on the one-thread-per-lane kernels"},                // 0, 1, 3
     {0xFDu, "the fused MPC rollout needs the event-driven kernels"},                // all but 1
+    {0xFDu, "the fused policy rollout needs the event-driven kernels"},             // all but 1 (as the MPC rollout)
 };
 
 // ABR_OK if `impl` can serve `f`, else ABR_E_UNSUPPORTED with a message that names the impls this build accepts for it
@@ -2680,6 +2681,177 @@ extern "C" int abr_env_fastmpc_select(abr_env *env, const abr_mpc_config *cfg, c
     hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
                        (hipStream_t)stream, env->p, fastmpc_rule(cfg, fm, table_dev), action_out_dev);
     HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// ===========================================================================
+// Learned policy (include/abr_env.h: abr_policy): an MLP forward pass per lane, then K1 MODE 1 (as mpc_rollout)
+// ===========================================================================
+// One thread per lane, 256 per workgroup.  The weights are the same for every lane: the workgroup stages them in LDS once,
+// in the padded layout of abr_lane_jump.h (policy_layout: at most 30 272 B), and every read of a weight is then a
+// wave-uniform broadcast of a fixed-length row.  The
+// arithmetic is abr_lane_jump.h's (policy_features, policy_forward, policy_explore), which tests/native compiles for the host.
+constexpr int kPolicyBlock = 256;
+
+struct PolicyArgs {
+    abrx::PolicyNet net;
+    const float *weights;
+    int32_t *action_out;              // [N]
+    float *features_out, *scores_out; // [F][N], [M][N], nullable
+};
+
+__global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p, PolicyArgs a) {
+    extern __shared__ float w_lds[];
+    const abrx::PolicyLayout lay = abrx::policy_layout(a.net);
+    for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock) w_lds[d] = abrx::policy_padded(a.net, lay, a.weights, d);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * kPolicyBlock + threadIdx.x;
+    if (i >= p.n_lanes) return;
+    const int64_t N = p.n_lanes;
+    const abrx::PolicyNet &n = a.net;
+    const int32_t c = p.chunk_id[i];
+    if (p.done[i] || c < 0 || c >= p.video_length) {
+        a.action_out[i] = -1;
+        if (a.features_out)
+            for (int32_t f = 0; f < n.F; f++) a.features_out[f * N + i] = 0.0f;
+        if (a.scores_out)
+            for (int32_t m = 0; m < n.M; m++) a.scores_out[m * N + i] = 0.0f;
+        return;
+    }
+    const double G = p.G[p.k[i]];
+    const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
+    const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
+    const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+    float x[abrx::kPolicyMaxF];
+    abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    if (a.features_out) {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) {
+            if (f < n.F) {
+                a.features_out[f * N + i] = x[f];
+            }
+        }
+    }
+    float *so = a.scores_out;
+    const auto emit = [&](int32_t m, float v) { if (so) so[m * N + i] = v; };
+    const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
+    a.action_out[i] = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+}
+
+// the struct alone (before the handle): shape, window, reserved fields, pointers, threshold
+static int validate_policy_shape(const abr_policy *pol) {
+    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
+    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
+    if (pol->n_hidden < 0 || pol->n_hidden > ABR_POLICY_MAX_HIDDEN)
+        return fail(ABR_E_INVALID, "policy n_hidden %d outside 0..%d", pol->n_hidden, ABR_POLICY_MAX_HIDDEN);
+    for (int l = 0; l < ABR_POLICY_MAX_HIDDEN; l++) {
+        const int32_t wl = pol->width[l];
+        if (l < pol->n_hidden && (wl < 1 || wl > ABR_POLICY_MAX_WIDTH))
+            return fail(ABR_E_INVALID, "policy width[%d] = %d outside 1..%d", l, wl, ABR_POLICY_MAX_WIDTH);
+        if (l >= pol->n_hidden && wl != 0) return fail(ABR_E_INVALID, "policy width[%d] must be 0 past n_hidden", l);
+    }
+    return ABR_OK;
+}
+
+static int validate_policy(const abr_policy *pol) {
+    int rc = validate_policy_shape(pol);
+    if (rc) return rc;
+    for (int32_t r : pol->reserved_)
+        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
+    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
+        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
+    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
+    if (pol->explore_threshold > (1ull << 32))
+        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
+    return ABR_OK;
+}
+
+static size_t policy_weights_bytes(const abr_policy *pol, int32_t M) {
+    size_t in = 4 + (size_t)pol->window + (size_t)M, words = 0;
+    for (int l = 0; l <= pol->n_hidden; l++) {
+        const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
+        words += out * in + out;
+        in = out;
+    }
+    return words * sizeof(float);
+}
+
+extern "C" int abr_policy_feature_dim(int32_t window, int32_t n_rates, int32_t *dim_out) {
+    if (!dim_out) return fail(ABR_E_INVALID, "dim_out is NULL");
+    if (window < 0 || window > ABR_POLICY_MAX_WINDOW) return fail(ABR_E_INVALID, "window %d outside 0..%d", window, ABR_POLICY_MAX_WINDOW);
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *dim_out = 4 + window + n_rates;
+    return ABR_OK;
+}
+
+extern "C" int abr_policy_weights_bytes(const abr_policy *pol, int32_t n_rates, size_t *bytes_out) {
+    int rc = validate_policy_shape(pol);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *bytes_out = policy_weights_bytes(pol, n_rates);
+    return ABR_OK;
+}
+
+// after the handle: the blob's size for the environment's n_rates
+static int policy_args(const abr_env *env, const abr_policy *pol, PolicyArgs *a) {
+    const int32_t M = env->p.n_rates;
+    const size_t want = policy_weights_bytes(pol, M);
+    if (pol->weights_bytes != want)
+        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
+    *a = PolicyArgs{};
+    a->net.window = pol->window; a->net.n_hidden = pol->n_hidden;
+    a->net.w0 = pol->n_hidden >= 1 ? pol->width[0] : 0; a->net.w1 = pol->n_hidden >= 2 ? pol->width[1] : 0;
+    a->net.M = M; a->net.F = 4 + pol->window + M;
+    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
+    a->weights = pol->weights_dev;
+    return ABR_OK;
+}
+
+static void launch_policy(const abr_env *env, const PolicyArgs &a, hipStream_t st) {
+    hipLaunchKernelGGL(policy_select_kernel, dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
+                       dim3(kPolicyBlock), (size_t)abrx::policy_layout(a.net).total * sizeof(float), st, env->p, a);
+}
+
+extern "C" int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_t *action_out_dev, float *features_out_dev,
+                                     float *scores_out_dev, void *stream) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyArgs a;
+    if ((rc = policy_args(env, pol, &a))) return rc;
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    launch_policy(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// per decision the policy kernel, then K1 MODE 1 on its actions, back to back on the stream (as mpc_rollout)
+extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev,
+                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                   float *features_out_dev, float *scores_out_dev, void *stream) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyArgs a;
+    if ((rc = policy_args(env, pol, &a))) return rc;
+    if ((rc = require(kPolicyRollout, env->impl))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
+        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        launch_policy(env, a, st);
+        HIP_TRY(hipGetLastError());
+        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
     return ABR_OK;
 }
 

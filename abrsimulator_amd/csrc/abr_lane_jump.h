@@ -812,5 +812,182 @@ ABR_HD double robust_estimate(int32_t W, int32_t c, const HIST &hist, int32_t &c
     return P > 0.0 ? P : 0.0;
 }
 
+
+// ---------------------------------------------------------------------------
+// Learned policy (include/abr_env.h: abr_policy): features, the MLP forward pass as k-ordered fmaf chains, the decision.
+// The widths are runtime values, so every register array is indexed by an unrolled loop with a uniform early exit: no
+// array is ever indexed by a runtime value (0 B of scratch on the device).
+// ---------------------------------------------------------------------------
+constexpr int kPolicyMaxWindow = 16, kPolicyMaxWidth = 64, kPolicyMaxRates = 16;
+constexpr int kPolicyMaxF = 4 + kPolicyMaxWindow + kPolicyMaxRates;
+
+struct PolicyNet {
+    int32_t window, n_hidden, w0, w1, M, F;   // F = 4 + window + M; w0 / w1 the hidden widths (0 when absent)
+    const double *norm;                       // [2][F] shift, scale; nullptr: 0 and 1
+    uint64_t seed, thr;                       // philox key, explore threshold (0 .. 2^32)
+};
+
+// philox4x32-10, all four output words; the same rounds as abr_env.hip: philox_action, whose action is
+// ((uint64)word0 * n_rates) >> 32
+ABR_HD void philox4(uint64_t seed, uint64_t lane, uint32_t step, uint32_t episode, uint32_t out[4]) {
+    uint32_t c0 = (uint32_t)lane, c1 = (uint32_t)(lane >> 32), c2 = step, c3 = episode;
+    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+#pragma unroll
+    for (int r = 0; r < 10; r++) {
+        uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1;
+        uint32_t n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// The features of one lane at a call site: chunk c (0 <= c < V), buffer B, previous bitrate a, latency G - P,
+// h(j) = previous_bandwidths[j], br(r, m) = chunk r's bitrate m.  x[i] = (float)((raw_i - shift_i) * scale_i).
+template <class Hist, class Br>
+ABR_HD void policy_features(const PolicyNet &n, const Hist &h, const Br &br, int32_t V, int32_t c, int32_t a, double B,
+                            double G, double P, float x[kPolicyMaxF]) {
+    const int32_t W = n.window;
+#pragma unroll
+    for (int i = 0; i < kPolicyMaxF; i++) {
+        if (i < n.F) {
+            double raw;
+            if (i == 0) raw = B;
+            else if (i == 1) raw = (a >= 0 && a < n.M && c >= 1) ? br(c - 1, a) : 0.0;
+            else if (i == 2) raw = (double)(V - c);
+            else if (i == 3) raw = G - P;
+            else if (i < 4 + W) { const int32_t j = c - W + (i - 4); raw = j >= 0 ? h(j) : 0.0; }
+            else raw = br(c, i - 4 - W);
+            const double sh = n.norm ? n.norm[i] : 0.0, sc = n.norm ? n.norm[n.F + i] : 1.0;
+            x[i] = (float)((raw - sh) * sc);
+        } else {
+            x[i] = 0.0f;
+        }
+    }
+}
+
+ABR_HD float relu_f32(float v) { return v > 0.0f ? v : 0.0f; }   // NaN and -0 -> +0
+
+// The padded layout the forward pass reads (the kernel stages it in LDS).  Every row has a fixed length -- 36 for the
+// features, 64 for a hidden layer, 16 for the outputs -- so that the inner loops are fully unrolled and branch-free (one
+// wave can issue all the loads of a row before it waits).  A padded weight is -0.0f and a padded input +0.0f:
+// fmaf(-0, +0, acc) == acc for every acc (NaN, infinities and both zeros included), so padding leaves each chain's bits
+// as the contract's.  The layer-1 and single-hidden-layer output weights are stored transposed ([k][j]), the order in which
+// hidden unit k adds its term into every accumulator j.
+constexpr int kPolicyRowF = kPolicyMaxF, kPolicyRowH = kPolicyMaxWidth, kPolicyRowM = kPolicyMaxRates;
+struct PolicyLayout { int32_t W0, b0, W1, b1, Wo, bo, total; };
+
+ABR_HD int32_t policy_align4(int32_t x) { return (x + 3) & ~3; }
+
+ABR_HD PolicyLayout policy_layout(const PolicyNet &n) {
+    PolicyLayout L{};
+    int32_t o = 0;
+    if (n.n_hidden >= 1) { L.W0 = o; o += n.w0 * kPolicyRowF; L.b0 = o; o = policy_align4(o + n.w0); }
+    if (n.n_hidden == 2) { L.W1 = o; o += n.w0 * kPolicyRowH; L.b1 = o; o += kPolicyRowH; }
+    if (n.n_hidden == 1) {
+        L.Wo = o; o += n.w0 * kPolicyRowM; L.bo = o; o += kPolicyRowM;
+    } else {
+        L.Wo = o; o += n.M * (n.n_hidden == 0 ? kPolicyRowF : kPolicyRowH); L.bo = o; o = policy_align4(o + n.M);
+    }
+    L.total = o;
+    return L;
+}
+
+// Slot d of the padded layout, read from the packed blob (per layer Wt[out][in] row-major, then b[out])
+ABR_HD float policy_padded(const PolicyNet &n, const PolicyLayout &L, const float *__restrict__ blob, int32_t d) {
+    const float pw = -0.0f, pb = 0.0f;
+    const int32_t F = n.F, H0 = n.w0, H1 = n.w1, M = n.M;
+    int32_t o = 0;                                            // packed offset of the current layer
+    if (n.n_hidden >= 1) {
+        if (d >= L.W0 && d < L.b0) { const int32_t k = (d - L.W0) / kPolicyRowF, i = (d - L.W0) % kPolicyRowF;
+                                     return i < F ? blob[o + k * F + i] : pw; }
+        if (d >= L.b0 && d < L.b0 + H0) return blob[o + H0 * F + (d - L.b0)];
+        o += H0 * F + H0;
+    }
+    if (n.n_hidden == 2) {
+        if (d >= L.W1 && d < L.b1) { const int32_t k = (d - L.W1) / kPolicyRowH, j = (d - L.W1) % kPolicyRowH;
+                                     return j < H1 ? blob[o + j * H0 + k] : pw; }
+        if (d >= L.b1 && d < L.b1 + kPolicyRowH) { const int32_t j = d - L.b1; return j < H1 ? blob[o + H1 * H0 + j] : pb; }
+        o += H1 * H0 + H1;
+    }
+    if (n.n_hidden == 1) {
+        if (d >= L.Wo && d < L.bo) { const int32_t k = (d - L.Wo) / kPolicyRowM, j = (d - L.Wo) % kPolicyRowM;
+                                     return j < M ? blob[o + j * H0 + k] : pw; }
+        if (d >= L.bo && d < L.bo + kPolicyRowM) { const int32_t j = d - L.bo; return j < M ? blob[o + M * H0 + j] : pb; }
+    } else {
+        const int32_t row = n.n_hidden == 0 ? kPolicyRowF : kPolicyRowH, in = n.n_hidden == 0 ? F : H1;
+        if (d >= L.Wo && d < L.bo) { const int32_t j = (d - L.Wo) / row, k = (d - L.Wo) % row;
+                                     return k < in ? blob[o + j * in + k] : pw; }
+        if (d >= L.bo && d < L.bo + M) return blob[o + M * in + (d - L.bo)];
+    }
+    return pb;
+}
+
+// acc = b, then fmaf(row[k], in[k], acc) for k = 0 .. CAP-1: the contract's chain over the real inputs, the padded
+// terms being exact no-ops
+template <int CAP>
+ABR_HD float dot_row(const float *__restrict__ row, float b, const float *in) {
+    float acc = b;
+#pragma unroll
+    for (int k = 0; k < CAP; k++) acc = fmaf(row[k], in[k], acc);
+    return acc;
+}
+
+// The forward pass and the first argmax over the padded layout `w` (policy_layout / policy_padded); x[i] = +0 for
+// i >= F.  emit(j, score_j) is called once per output j in order.  Returns g.
+template <class Emit>
+ABR_HD int32_t policy_forward(const PolicyNet &n, const float *__restrict__ w, const float x[kPolicyMaxF], const Emit &emit) {
+    const PolicyLayout L = policy_layout(n);
+    const int32_t M = n.M;
+    int32_t g = 0;
+    float best = 0.0f;
+    const auto take = [&](int32_t j, float s) {
+        emit(j, s);
+        if (j == 0) best = s;
+        else if (s > best) { best = s; g = j; }
+    };
+    if (n.n_hidden == 0) {
+        for (int32_t j = 0; j < M; j++) take(j, dot_row<kPolicyRowF>(w + L.Wo + j * kPolicyRowF, w[L.bo + j], x));
+    } else if (n.n_hidden == 1) {
+        // hidden unit k, then its term in every output accumulator: each output stays a k-ordered chain
+        float acc[kPolicyRowM];
+#pragma unroll
+        for (int j = 0; j < kPolicyRowM; j++) acc[j] = w[L.bo + j];
+        for (int32_t k = 0; k < n.w0; k++) {
+            const float hk = relu_f32(dot_row<kPolicyRowF>(w + L.W0 + k * kPolicyRowF, w[L.b0 + k], x));
+            const float *wk = w + L.Wo + k * kPolicyRowM;
+#pragma unroll
+            for (int j = 0; j < kPolicyRowM; j++) acc[j] = fmaf(wk[j], hk, acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kPolicyRowM; j++)
+            if (j < M) take(j, acc[j]);
+    } else {
+        // layer-0 unit k, then its term in every layer-1 accumulator; then the output layer unit by unit
+        float acc[kPolicyRowH];
+#pragma unroll
+        for (int j = 0; j < kPolicyRowH; j++) acc[j] = w[L.b1 + j];
+        for (int32_t k = 0; k < n.w0; k++) {
+            const float hk = relu_f32(dot_row<kPolicyRowF>(w + L.W0 + k * kPolicyRowF, w[L.b0 + k], x));
+            const float *wk = w + L.W1 + k * kPolicyRowH;
+#pragma unroll
+            for (int j = 0; j < kPolicyRowH; j++) acc[j] = fmaf(wk[j], hk, acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < kPolicyRowH; j++) acc[j] = relu_f32(acc[j]);
+        for (int32_t j = 0; j < M; j++) take(j, dot_row<kPolicyRowH>(w + L.Wo + j * kPolicyRowH, w[L.bo + j], acc));
+    }
+    return g;
+}
+
+// The decision: the random policy's action from the same philox block when word 1 < thr, else g.
+ABR_HD int32_t policy_explore(const PolicyNet &n, uint64_t lane, int32_t c, int32_t episode, int32_t g) {
+    if (n.thr == 0) return g;
+    uint32_t r[4];
+    philox4(n.seed, lane, (uint32_t)c, (uint32_t)episode, r);
+    return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : g;
+}
+
 }  // namespace abrx
 #endif

@@ -373,6 +373,26 @@ class BatchedABREnv:
                    _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
         return out
 
+    def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
+                    want_scores=False):
+        """n_steps decisions per lane taken by a learned policy (policy.py: PolicyController) on the device, each one the
+        policy kernel on every lane's own call-site state followed by the download of that chunk, with no host work
+        between decisions.  Every event-driven kernel; 'tick' is refused (include/abr_env.h).  Returns
+        dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N], features[n,F,N], scores[n,M,N]); an entry that is
+        not wanted is None."""
+        n = int(n_steps)
+        pol = controller.bound(self)
+        if out is None:
+            out = self._rollout_out(n, want_obs, want_actions)
+            N, dev = self.n_lanes, self.device
+            out["features"] = (torch.empty(n, controller.feature_dim, N, dtype=torch.float32, device=dev)
+                               if want_features else None)
+            out["scores"] = torch.empty(n, self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None
+        self._call(self.lib.abr_env_step_policy, self._h, C.byref(pol), n, _lib.ptr(out.get("obs")),
+                   _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")),
+                   _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")))
+        return out
+
     # -- exact state -------------------------------------------------------
     def observe_f64(self):
         """dict of float64 [N] tensors: everything the reference's run() frame holds

@@ -1,0 +1,212 @@
+"""A learned bitrate policy: a small MLP evaluated on the device on each lane's exact call-site state (Pensieve-style
+learned ABR).  The contract -- the features, the fmaf order of the forward pass, the first argmax and the exploration
+draw -- is include/abr_env.h: abr_policy; the arithmetic is csrc/abr_lane_jump.h (policy_features, policy_forward).
+
+    net = torch.nn.Sequential(nn.Linear(F, 64), nn.ReLU(), nn.Linear(64, 64), nn.ReLU(), nn.Linear(64, M))
+    ctl = PolicyController.from_module(EnvPlayer(env), net, window=8, explore=0.1)
+    out = env.step_policy(ctl, 48, want_features=True)     # features, actions, rewards, done for a trainer
+    ...train net in PyTorch...
+    ctl.load_weights(net)                                   # refresh the device copy in place, no sync
+"""
+import ctypes as C
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+
+OBS_NAMES = ["buffer_level", "last_bitrate", "chunks_left", "latency"]
+
+
+def _as_f32(t, device):
+    if not torch.is_tensor(t):
+        t = torch.as_tensor(np.asarray(t, np.float32))
+    return t.detach().to(device=device, dtype=torch.float32)
+
+
+def pack_layers(layers):
+    """The weight blob's layout on the host: per layer W [out][in] row-major, then b [out], layers in order (float32)."""
+    parts = []
+    for W, b in layers:
+        for t in (W, b):
+            t = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+            parts.append(np.asarray(t, np.float32).reshape(-1))
+    return np.concatenate(parts)
+
+
+class PolicyController:
+    """An MLP policy over `player` (an EnvPlayer: the environment is player.env).
+
+    layers: [(W [out, in], b [out]), ...], hidden layers first (0..2 of widths 1..64, ReLU after each), then the output
+    layer of width n_rates; the input width is feature_dim = 4 + window + n_rates.  norm: "default" (shift 0; scale
+    1/max_buffer for the buffer and the latency, 1/top bitrate for bitrates and throughputs, 1/video_length for the chunks
+    left), None (raw values), or (shift [F], scale [F]).  explore in [0, 1]: the probability of taking the random policy's
+    action instead of the argmax (threshold floor(explore * 2^32)), drawn with `seed` exactly as step_random draws."""
+
+    method = "policy"
+
+    def __init__(self, player, layers, window=8, norm="default", explore=0.0, seed=0, device=None):
+        self.player = player
+        env = getattr(player, "env", None)
+        self.device = torch.device(device) if device is not None else (env.device if env is not None else
+                                                                       torch.device("cuda"))
+        if isinstance(window, bool) or int(window) != window or not 0 <= int(window) <= _lib.POLICY_MAX_WINDOW:
+            raise ValueError(f"window must be an integer in 0..{_lib.POLICY_MAX_WINDOW}")
+        self.window = int(window)
+        mpd = player.get_mpd()
+        self.n_rates, self.video_length = len(mpd.chunk_list()[0].bitrates), int(mpd.video_length)
+        self.feature_dim = 4 + self.window + self.n_rates
+        shapes = [tuple(np.shape(W)) for W, _ in layers]
+        if not 1 <= len(layers) <= _lib.POLICY_MAX_HIDDEN + 1:
+            raise ValueError(f"1..{_lib.POLICY_MAX_HIDDEN + 1} layers (0..{_lib.POLICY_MAX_HIDDEN} hidden)")
+        fan_in = self.feature_dim
+        for li, ((W, b), sh) in enumerate(zip(layers, shapes)):
+            if len(sh) != 2 or sh[1] != fan_in or tuple(np.shape(b)) != (sh[0],):
+                raise ValueError(f"layer {li}: W must be [out, {fan_in}] and b [out], got {sh} / {tuple(np.shape(b))}")
+            last = li == len(layers) - 1
+            if last and sh[0] != self.n_rates:
+                raise ValueError(f"the output layer has width {sh[0]}, the MPD has {self.n_rates} bitrates")
+            if not last and not 1 <= sh[0] <= _lib.POLICY_MAX_WIDTH:
+                raise ValueError(f"hidden width {sh[0]} outside 1..{_lib.POLICY_MAX_WIDTH}")
+            fan_in = sh[0]
+        self.widths = [sh[0] for sh in shapes[:-1]]
+        self.shapes = shapes
+        nbytes = C.c_size_t()
+        _lib.check(_lib.lib().abr_policy_weights_bytes(C.byref(self._struct(0, 0, None)), self.n_rates,
+                                                       C.byref(nbytes)))
+        self.weights = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
+        self.load_weights(layers)
+        self.norm = self._norm(norm, mpd)
+        self.explore = explore
+        self.seed = int(seed)
+
+    # -- construction ----------------------------------------------------------
+    @classmethod
+    def from_module(cls, player, module, **kw):
+        """From nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers; any other shape is refused."""
+        layers = cls.module_layers(module)
+        return cls(player, layers, **kw)
+
+    @staticmethod
+    def module_layers(module):
+        """[(weight, bias)] of nn.Sequential(Linear, ReLU, Linear, ...); ValueError for any other module."""
+        nn = torch.nn
+        mods = list(module) if isinstance(module, nn.Sequential) else None
+        if not mods or len(mods) % 2 == 0 or len(mods) > 2 * _lib.POLICY_MAX_HIDDEN + 1:
+            raise ValueError("a policy module is nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers")
+        for k, m in enumerate(mods):
+            want = nn.Linear if k % 2 == 0 else nn.ReLU
+            if type(m) is not want:
+                raise ValueError(f"module {k} is {type(m).__name__}, expected {want.__name__}")
+            if want is nn.Linear and m.bias is None:
+                raise ValueError(f"module {k}: Linear without a bias")
+        return [(m.weight, m.bias) for m in mods[0::2]]
+
+    def _norm(self, norm, mpd):
+        F = self.feature_dim
+        if norm is None:
+            return None
+        if isinstance(norm, str):
+            if norm != "default":
+                raise ValueError("norm is 'default', None or (shift, scale)")
+            top = max(float(b) for c in mpd.chunk_list() for b in c.bitrates)
+            scale = np.empty(F)
+            scale[0] = scale[3] = 1.0 / float(mpd.max_buffer)
+            scale[1] = 1.0 / top
+            scale[2] = 1.0 / self.video_length
+            scale[4:] = 1.0 / top
+            shift = np.zeros(F)
+        else:
+            shift, scale = (np.asarray(x, np.float64).ravel() for x in norm)
+            if shift.size != F or scale.size != F:
+                raise ValueError(f"shift and scale need {F} entries each")
+        return torch.tensor(np.stack([shift, scale]), dtype=torch.float64, device=self.device).contiguous()
+
+    @property
+    def explore(self):
+        return self._explore
+
+    @explore.setter
+    def explore(self, eps):
+        eps = float(eps)
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError("explore must be in [0, 1]")
+        self._explore = eps
+        self.explore_threshold = 1 << 32 if eps >= 1.0 else int(math.floor(eps * 2.0 ** 32))
+
+    # -- the weights -------------------------------------------------------------
+    def load_weights(self, layers):
+        """Copy new weights (a list of (W, b) of this controller's shapes, or an nn.Sequential) into the device blob in
+        place, on the current stream, without synchronising."""
+        if isinstance(layers, torch.nn.Module):
+            layers = self.module_layers(layers)
+        if [tuple(np.shape(W)) for W, _ in layers] != self.shapes:
+            raise ValueError(f"layer shapes {[tuple(np.shape(W)) for W, _ in layers]}, this policy has {self.shapes}")
+        o = 0
+        with torch.no_grad():
+            for W, b in layers:
+                for t in (W, b):
+                    t = _as_f32(t, self.device).reshape(-1)
+                    self.weights[o:o + t.numel()].copy_(t, non_blocking=True)
+                    o += t.numel()
+        assert o == self.weights.numel()
+
+    def layers(self):
+        """[(W, b)] views of the device blob."""
+        out, o, fan_in = [], 0, self.feature_dim
+        for out_w, _ in self.shapes:
+            W = self.weights[o:o + out_w * fan_in].view(out_w, fan_in)
+            o += out_w * fan_in
+            out.append((W, self.weights[o:o + out_w]))
+            o += out_w
+            fan_in = out_w
+        return out
+
+    def _struct(self, wptr, nbytes, norm):
+        p = _lib.Policy()
+        p.window, p.n_hidden = self.window, len(self.widths)
+        for k, w in enumerate(self.widths):
+            p.width[k] = w
+        p.weights_dev, p.weights_bytes = wptr, nbytes
+        p.norm_dev = norm.data_ptr() if norm is not None else None
+        p.seed = getattr(self, "seed", 0) & (2 ** 64 - 1)
+        p.explore_threshold = getattr(self, "explore_threshold", 0)
+        return p
+
+    def bound(self, env=None):
+        """The abr_policy struct for the C ABI (it points into this controller's tensors)."""
+        env = env if env is not None else self.player.env
+        if env.n_rates != self.n_rates:
+            raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
+        return self._struct(self.weights.data_ptr(), self.weights.numel() * 4, self.norm)
+
+    # -- decisions ---------------------------------------------------------------
+    def feature_names(self):
+        return (OBS_NAMES + [f"throughput[-{self.window - k}]" for k in range(self.window)] +
+                [f"bitrate[{m}]" for m in range(self.n_rates)])
+
+    def select(self, want_features=True, want_scores=True):
+        """One decision per lane on the environment's current state (no step): dict(actions int32 [N], features float32
+        [F, N], scores float32 [M, N]); a lane whose done bits are set answers -1 with zero columns."""
+        env = self.player.env
+        N, dev = env.n_lanes, env.device
+        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
+                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
+                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None)
+        pol = self.bound(env)
+        env._call(env.lib.abr_env_policy_select, env._h, C.byref(pol), _lib.ptr(out["actions"]),
+                  _lib.ptr(out["features"]), _lib.ptr(out["scores"]))
+        return out
+
+    def next_bitrate(self):
+        """int32 [N]: the policy's action for each lane (-1 for finished lanes)."""
+        return self.select(False, False)["actions"]
+
+    def features(self):
+        """float32 [F, N]: the network's input on the current state."""
+        return self.select(True, False)["features"]
+
+    def scores(self):
+        """float32 [M, N]: the network's output on the current state."""
+        return self.select(False, True)["scores"]

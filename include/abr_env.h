@@ -615,6 +615,77 @@ int abr_env_step_fastmpc(abr_env *env, const abr_mpc_config *cfg, const abr_fast
 int abr_env_fastmpc_select(abr_env *env, const abr_mpc_config *cfg, const abr_fastmpc *fm, const void *table_dev,
                            int32_t *action_out_dev, void *stream);
 
+/*
+ * Learned policy (ABI 4, additive; BUILD-DEFINED: the reference has no learned controller).  A small MLP evaluated on the
+ * device on each lane's exact call-site state, one decision per lane, with no host round trip; the caller trains it (in
+ * PyTorch, say) and refreshes the weights in place between rollouts.
+ *
+ * Inputs of a lane that takes a decision: c = chunk_id, B = buffer_level, a = previous_bitrates[-1] (-1 if none),
+ * h[0..c) = the lane's previous_bandwidths (abr_env_state_view.bw_hist rows of the current episode), G and P =
+ * global_time and play_time exactly as abr_env_observe_f64 reports them, br(r, m) = chunk r's bitrate m (the
+ * abr_env_set_bitrate_table row, else config.ladder), V = video_length, M = n_rates, W = window (0..16).
+ *
+ * Features, F = 4 + W + M, raw values float64:
+ *   0         B
+ *   1         (a >= 0 and c >= 1) ? br(c - 1, a) : 0.0
+ *   2         (double)(V - c)
+ *   3         G - P
+ *   4 + k     h[c - W + k], or 0.0 where c - W + k < 0 (k < W, oldest first)
+ *   4 + W + m br(c, m) (m < M)
+ * x_i = (float)((raw_i - shift_i) * scale_i): both operations in float64, then one round-to-nearest conversion.  norm_dev:
+ * float64 [2][F], row 0 shift, row 1 scale (caller-owned device memory); NULL = shift 0, scale 1.
+ *
+ * Network: n_hidden (0..2) hidden layers of widths width[0..n_hidden) (1..64 each), then an output layer of width M.
+ * Weights: one float32 blob, per layer Wt [out][in] row-major (torch.nn.Linear.weight's layout) then b [out], layers in
+ * order, no padding (abr_policy_weights_bytes).  Output j of a layer: acc = b[j], then acc = fmaf(Wt[j][k], x[k], acc) for
+ * k = 0, 1, .., in - 1 in that order (one rounding per term: an f32 MFMA, a VALU and a host std::fmaf chain give the same
+ * bits).  A hidden output becomes acc > 0.0f ? acc : 0.0f (NaN and -0 become +0).  The output layer gives score[0..M).
+ * f32 subnormals are kept (the library is not built with flush-to-zero).
+ *
+ * Decision: g = the first argmax (g = 0, then g = m if score[m] > score[g]; NaN never wins, a NaN score[0] answers 0).
+ * Exploration, an exact integer contract: one philox4x32-10 block with the random policy's key and counter (key = seed,
+ * ctr = (global lane id lo, hi, c, episode number), as abr_env_step_random).  Output word 1 < explore_threshold (a uint64 in
+ * [0, 2^32]): the action is the random policy's action from the same block (what abr_env_step_random would draw at this
+ * call site); otherwise g.  0 never explores, 2^32 always does.
+ *
+ * A lane whose done bits are set takes no decision: action -1, its feature and score columns 0.0f.
+ */
+#define ABR_POLICY_MAX_WINDOW 16
+#define ABR_POLICY_MAX_HIDDEN 2
+#define ABR_POLICY_MAX_WIDTH 64
+typedef struct abr_policy {
+    int32_t window;                       /* W, 0..ABR_POLICY_MAX_WINDOW */
+    int32_t n_hidden;                     /* 0..ABR_POLICY_MAX_HIDDEN */
+    int32_t width[ABR_POLICY_MAX_HIDDEN]; /* hidden widths, 1..ABR_POLICY_MAX_WIDTH; entries past n_hidden set to 0 */
+    const float *weights_dev;             /* the blob (device, 4-byte aligned) */
+    size_t weights_bytes;                 /* == abr_policy_weights_bytes(this, n_rates) */
+    const double *norm_dev;               /* float64 [2][F] (device, 8-byte aligned) or NULL */
+    uint64_t seed;                        /* philox key of the exploration draw */
+    uint64_t explore_threshold;           /* 0 .. 2^32 */
+    int32_t reserved_[4];                 /* set to 0 */
+} abr_policy;
+
+/* F = 4 + window + n_rates (window 0..16, n_rates 1..ABR_MAX_RATES). */
+int abr_policy_feature_dim(int32_t window, int32_t n_rates, int32_t *dim_out);
+/* Bytes of the weight blob for pol's shape (window, n_hidden, width; the pointers are not looked at) and n_rates. */
+int abr_policy_weights_bytes(const abr_policy *pol, int32_t n_rates, size_t *bytes_out);
+
+/* The policy's decision for each lane on the environment's current state, no step: action_out_dev int32 [n_lanes];
+ * features_out_dev float32 [F][n_lanes] and scores_out_dev float32 [n_rates][n_lanes], both nullable.  Validation
+ * (ABR_E_INVALID, nothing launched): the struct (shape, window, reserved_ zero, weights non-NULL and aligned, norm aligned,
+ * threshold <= 2^32) before the handle; then weights_bytes against the environment's n_rates. */
+int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_t *action_out_dev, float *features_out_dev,
+                          float *scores_out_dev, void *stream);
+
+/* n_steps fused decisions: per decision the policy kernel on each lane's own state, then the download of that chunk
+ * (abr_env_step).  Outputs (all nullable): obs [n_steps][ABR_OBS_DIM][n_lanes], reward / done / actions [n_steps][n_lanes]
+ * as abr_env_step_random, features [n_steps][F][n_lanes], scores [n_steps][n_rates][n_lanes] as abr_env_policy_select.
+ * Kernels as abr_env_step_mpc (ABR_E_UNSUPPORTED on impl 1, tick).  Validation as abr_env_policy_select, with
+ * n_steps >= 1 before the handle. */
+int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                        uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                        void *stream);
+
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
 int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t prev_bitrate,
