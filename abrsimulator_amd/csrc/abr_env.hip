@@ -160,6 +160,11 @@ struct WorkspaceTag {
     uint8_t pad_[256 - 72];
 };
 static_assert(sizeof(WorkspaceTag) == 256, "the tag is one 256-byte block");
+static_assert(sizeof(abrx::EpisodeSampler) == sizeof(abr_episode_sampler) &&
+              offsetof(abrx::EpisodeSampler, pool) == offsetof(abr_episode_sampler, pool) &&
+              offsetof(abrx::EpisodeSampler, n_pool) == offsetof(abr_episode_sampler, n_pool) &&
+              offsetof(abrx::EpisodeSampler, offset_span) == offsetof(abr_episode_sampler, offset_span),
+              "abr_episode_sampler: one layout");
 
 struct abr_env {
     EnvParams p;
@@ -180,6 +185,8 @@ struct abr_env {
     const double *pending_br_table; // abr_env_set_bitrate_table: latched the same way
     bool br_table_dirty;
     bool armed;                     // abr_env_reset has run at least once: episodes may be in flight
+    bool sampler_on;                // abr_env_set_episode_sampler: launches run the SAMPLE instances with `sampler`
+    abrx::EpisodeSampler sampler;
 };
 
 // A handle on which no reset has run has no episode to protect: the setters take effect at once
@@ -366,17 +373,26 @@ __device__ inline int32_t rule_action(const EnvParams &p, const abrx::RuleParams
     return abrx::rule_select_at(rule, br, hist, p.n_rates, p.video_length, c, pv, B);
 }
 
+// The episode sampler's (trace, start offset) of episode e of lane i (include/abr_env.h: abr_episode_sampler)
+__device__ inline void sampled_episode(const EnvParams &p, const abrx::EpisodeSampler &smp, int64_t i, int32_t e,
+                                       int32_t &t, int32_t &off) {
+    abrx::episode_assign(smp, (uint64_t)(p.lane_id_base + i), (uint32_t)e, p.n_traces, p.trace_len, t, off);
+}
+
 // MODE 0: reset (fresh lanes run to their first call site)
 // MODE 1: step  (one externally supplied action per lane)
 // MODE 2: fused random-policy rollout of n_steps decisions per lane
 // MODE 3: fused rollout of n_steps scripted decisions per lane, actions[step][lane]
 // MODE 4: fused rollout of n_steps decisions per lane taken by a bitrate rule (`rule`; the other modes ignore it)
-template <int MODE>
+// SAMPLE: the instance that runs while an episode sampler is installed: a reset draws each lane's (trace, offset) from
+// `smp` (trace_id_in / offset_in unused) and a re-arm draws the new episode's; the other instances never read `smp`
+template <int MODE, bool SAMPLE = false>
 __global__ __launch_bounds__(64) void env_advance_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
+    abrx::EpisodeSampler smp) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -395,8 +411,13 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
         if (MODE == 0) {
             if (lane_mask && !lane_mask[i]) { active = false; touched = false; }
             if (active) {
-                int32_t t = trace_id_in[i];
-                offset0 = offset_in ? offset_in[i] : 0;
+                int32_t t;
+                if constexpr (SAMPLE) {
+                    sampled_episode(p, smp, i, (p.flags[i] & kFlagArmed) ? p.episode_no[i] + 1 : 0, t, offset0);
+                } else {
+                    t = trace_id_in[i];
+                    offset0 = offset_in ? offset_in[i] : 0;
+                }
                 // a trace id / start offset outside the tables: the lane is frozen with
                 // ABR_DONE_BADARG instead of reading out of bounds (it runs on trace 0, unseen)
                 if (t < 0 || t >= p.n_traces || offset0 < 0) { done |= ABR_DONE_BADARG; t = 0; offset0 = 0; }
@@ -466,6 +487,12 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                     p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
                     if (p.auto_reset && ended) {
                         // re-arm: this step's obs is the new episode's first call site
+                        if constexpr (SAMPLE) {
+                            int32_t t;
+                            sampled_episode(p, smp, i, episode_no + 1, t, offset0);
+                            p.trace_id[i] = t; p.offset0[i] = offset0;
+                            s.tlen = p.trace_len[t]; s.trace = p.traces + p.trace_off[t];
+                        }
                         lane_init(s, p, offset0);
                         episode_no++;
                         n_su_obs = 0; n_rb_obs = 0;
@@ -692,14 +719,17 @@ __device__ inline void write_obs_vals(const LaneJ &s, const EnvParams &p, int64_
 // MODE 1 (ONE decision per launch: abr_env_step, the K1 launches of abr_env_step_mpc -- what `auto` runs at every size) is
 // compiled for four waves: a single pass through a decision gains nothing from the fifth wave, and the 102-VGPR bound
 // cost it 12 B of scratch per lane (round 5).  MODE 4 (a rule rollout) too: at five waves its rule loops push the
-// register bound into 36 B of spills, at four it keeps none.
-#define ABR_JUMP_BOUNDS(MODE) __launch_bounds__(64, ((MODE) == 1 || (MODE) == 4 ? 4 : ABR_JUMP_WAVES))
-template <int MODE>
-__global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
+// register bound into 36 B of spills, at four it keeps none.  The episode sampler's instances (SAMPLE) as well: at five
+// waves the draw at a re-arm spilled 52-68 B per lane, at four they keep none.
+#define ABR_JUMP_BOUNDS(MODE, SAMPLE) __launch_bounds__(64, ((MODE) == 1 || (MODE) == 4 || (SAMPLE) ? 4 : ABR_JUMP_WAVES))
+// SAMPLE: as env_advance_kernel
+template <int MODE, bool SAMPLE = false>
+__global__ ABR_JUMP_BOUNDS(MODE, SAMPLE) void env_jump_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
+    abrx::EpisodeSampler smp) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -715,8 +745,13 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
         if (MODE == 0) {
             if (lane_mask && !lane_mask[i]) { active = false; touched = false; }
             if (active) {
-                int32_t t = trace_id_in[i];
-                offset0 = offset_in ? offset_in[i] : 0;
+                int32_t t;
+                if constexpr (SAMPLE) {
+                    sampled_episode(p, smp, i, (p.flags[i] & kFlagArmed) ? p.episode_no[i] + 1 : 0, t, offset0);
+                } else {
+                    t = trace_id_in[i];
+                    offset0 = offset_in ? offset_in[i] : 0;
+                }
                 // a trace id / start offset outside the tables: the lane is frozen with
                 // ABR_DONE_BADARG instead of reading out of bounds (it sits on trace 0, unseen)
                 const bool bad = t < 0 || t >= p.n_traces || offset0 < 0;
@@ -809,6 +844,12 @@ __global__ ABR_JUMP_BOUNDS(MODE) void env_jump_kernel(
                         p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
                         if (p.auto_reset && r.ended) {
                             // re-arm: this step's obs is the new episode's first call site
+                            if constexpr (SAMPLE) {
+                                int32_t t;
+                                sampled_episode(p, smp, i, episode_no + 1, t, offset0);
+                                p.trace_id[i] = t; p.offset0[i] = offset0;
+                                s.cur.tlen = p.trace_len[t]; s.cur.trace = p.traces + p.trace_off[t];
+                            }
                             abrx::lanej_init(s, tb, offset0);
                             episode_no++;
                             n_su_obs = 0; n_rb_obs = 0; g_su_obs = 0.0; g_rb_obs = 0.0;
@@ -1297,6 +1338,42 @@ extern "C" int abr_env_set_lane_id_base(abr_env *env, int64_t base) {
     return ABR_OK;
 }
 
+// the episode sampler (include/abr_env.h: abr_episode_sampler): the struct before the handle, then the pool against it
+extern "C" int abr_env_set_episode_sampler(abr_env *env, const abr_episode_sampler *s) {
+    if (s) {
+        if (s->pool && s->n_pool < 1) return fail(ABR_E_INVALID, "episode sampler: a pool needs n_pool >= 1, got %d", s->n_pool);
+        if (s->offset_span < 0) return fail(ABR_E_INVALID, "episode sampler: offset_span must be >= 0, got %d", s->offset_span);
+    }
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (!s) { env->sampler_on = false; env->sampler = abrx::EpisodeSampler{}; return ABR_OK; }
+    if (s->pool) {
+        // read back once: a trace id outside the tables would be read out of bounds by every kernel that draws it
+        std::vector<int32_t> pool((size_t)s->n_pool);
+        HIP_TRY(hipDeviceSynchronize());
+        HIP_TRY(hipMemcpy(pool.data(), s->pool, pool.size() * sizeof(int32_t), hipMemcpyDefault));
+        for (size_t q = 0; q < pool.size(); q++)
+            if (pool[q] < 0 || pool[q] >= env->p.n_traces)
+                return fail(ABR_E_INVALID, "episode sampler: pool[%zu] = %d outside [0, %d)", q, pool[q], env->p.n_traces);
+    }
+    abrx::EpisodeSampler v{};
+    v.seed = s->seed; v.pool = s->pool; v.n_pool = s->pool ? s->n_pool : 0; v.offset_span = s->offset_span;
+    env->sampler = v;
+    env->sampler_on = true;
+    return ABR_OK;
+}
+
+// each lane's current (trace, start offset, episode number): copies of the workspace rows, ordered on the stream
+extern "C" int abr_env_get_episode(abr_env *env, int32_t *trace_id_out_dev, int32_t *offset_out_dev,
+                                   int32_t *episode_out_dev, void *stream) {
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    const size_t bytes = (size_t)env->p.n_lanes * sizeof(int32_t);
+    hipStream_t st = (hipStream_t)stream;
+    if (trace_id_out_dev) HIP_TRY(hipMemcpyAsync(trace_id_out_dev, env->p.trace_id, bytes, hipMemcpyDeviceToDevice, st));
+    if (offset_out_dev) HIP_TRY(hipMemcpyAsync(offset_out_dev, env->p.offset0, bytes, hipMemcpyDeviceToDevice, st));
+    if (episode_out_dev) HIP_TRY(hipMemcpyAsync(episode_out_dev, env->p.episode_no, bytes, hipMemcpyDeviceToDevice, st));
+    return ABR_OK;
+}
+
 static inline unsigned grid64(int64_t n) { return (unsigned)((n + 63) / 64); }
 
 // Which kernel serves which size (same box, fused 48, round 5: profiles/r05_sweep_impl.txt -- the role-split kernels gained
@@ -1347,7 +1424,41 @@ static inline int launch_impl(const abr_env *env, int32_t n_steps) {
 // (`seed`); 3: n_steps decisions scripted in `actions` [n_steps][n_lanes]; 4: n_steps decisions of `rule`.  Outputs
 // obs / rew / dn / acts as abr_env_step_random, all nullable.  A reset and a rule rollout exist only as the tick and the
 // one-thread-per-lane kernel, the asynchronous pipeline only for MODE 2 and 3: the `if constexpr` keeps every other
-// instance out of the build.
+// instance out of the build.  While an episode sampler is installed the SAMPLE instances run (a reset with explicit trace
+// ids excepted: it draws nothing); the diagnostic pipelines have none and refuse.
+template <int MODE, bool SAMPLE>
+static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
+                               uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule,
+                               const int32_t *trace_id, const int32_t *start_offset, const uint8_t *lane_mask) {
+    const EnvParams &p = env->p;
+    const int64_t N = p.n_lanes;
+    const abrx::EpisodeSampler smp = SAMPLE ? env->sampler : abrx::EpisodeSampler{};
+    if (impl == 0 || impl == 1) {
+        auto *k = impl == 1 ? env_advance_kernel<MODE, SAMPLE> : env_jump_kernel<MODE, SAMPLE>;
+        hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
+                           acts, n_steps, seed, rule, smp);
+    } else if constexpr (MODE >= 1 && MODE <= 3) {
+        // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
+        if (impl == 5) {
+            auto *k = env_split3_kernel<MODE, SAMPLE>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp);
+        } else if (impl == 2) {
+            auto *k = env_split_kernel<MODE, SAMPLE>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp);
+        }
+#ifdef ABR_WITH_RING
+        else if constexpr (!SAMPLE) {
+            if (impl == 6)
+                hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
+                                   rew, dn, acts, n_steps, seed);
+            else if (impl == 7)
+                hipLaunchKernelGGL(env_pair3_kernel<MODE>, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts,
+                                   n_steps, seed);
+        }
+#endif
+    }
+}
+
 template <int MODE>
 static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
                       uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule = {},
@@ -1355,6 +1466,10 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
                       const uint8_t *lane_mask = nullptr) {
     const EnvParams &p = env->p;
     const int64_t N = p.n_lanes;
+    const bool sample = env->sampler_on && !(MODE == 0 && trace_id);
+    if (sample && impl != 0 && impl != 1 && impl != 2 && impl != 5)
+        return fail(ABR_E_UNSUPPORTED, "the episode sampler runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
+    (void)N;
 #ifdef ABR_WITH_ASYNC
     if constexpr (MODE == 2 || MODE == 3) {
         if (impl == 4) {
@@ -1373,26 +1488,12 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
         }
     }
 #endif
-    if (impl == 0 || impl == 1)
-        hipLaunchKernelGGL(impl == 1 ? env_advance_kernel<MODE> : env_jump_kernel<MODE>, dim3(grid64(N)), dim3(64), 0, st,
-                           p, actions, trace_id, start_offset, lane_mask, obs, rew, dn, acts, n_steps, seed, rule);
-    else if constexpr (MODE >= 1 && MODE <= 3) {
-        // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
-        if (impl == 5)
-            hipLaunchKernelGGL(env_split3_kernel<MODE>, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts,
-                               n_steps, seed);
-        else if (impl == 2)
-            hipLaunchKernelGGL(env_split_kernel<MODE>, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts,
-                               n_steps, seed);
-#ifdef ABR_WITH_RING
-        else if (impl == 6)
-            hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
-                               rew, dn, acts, n_steps, seed);
-        else if (impl == 7)
-            hipLaunchKernelGGL(env_pair3_kernel<MODE>, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts,
-                               n_steps, seed);
-#endif
-    }
+    if (sample)
+        launch_env_kernels<MODE, true>(env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset,
+                                       lane_mask);
+    else
+        launch_env_kernels<MODE, false>(env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset,
+                                        lane_mask);
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
@@ -1401,7 +1502,10 @@ extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
                              const int32_t *start_offset_dev, const uint8_t *lane_mask_dev,
                              float *obs_out_dev, void *stream) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    if (!trace_id_dev) return fail(ABR_E_INVALID, "trace_id_dev is NULL");
+    if (!trace_id_dev && !env->sampler_on)
+        return fail(ABR_E_INVALID, "trace_id_dev is NULL (allowed only while an episode sampler is installed)");
+    if (!trace_id_dev && start_offset_dev)
+        return fail(ABR_E_INVALID, "a sampled reset (trace_id_dev NULL) takes no start_offset_dev");
     if (env->br_table_dirty && lane_mask_dev)
         return fail(ABR_E_INVALID, "abr_env_set_bitrate_table takes effect at a reset of ALL lanes "
                     "(lane_mask_dev must be NULL for the first reset after it)");
@@ -2912,9 +3016,11 @@ extern "C" int abr_debug_selfcheck(abr_env *env, uint32_t *result_dev, void *str
     EnvParams p = env->p;
     p.sentinel = 0x5eed0000c0ffee00ull ^ (uint64_t)(uintptr_t)env;
     p.selfcheck_out = result_dev;
-    hipLaunchKernelGGL(env_split3_kernel<9>, dim3(1), dim3(192), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull);
+    hipLaunchKernelGGL(env_split3_kernel<9>, dim3(1), dim3(192), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
+                       abrx::EpisodeSampler{});
     p.selfcheck_out = result_dev + 1;
-    hipLaunchKernelGGL(env_split_kernel<9>, dim3(1), dim3(128), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull);
+    hipLaunchKernelGGL(env_split_kernel<9>, dim3(1), dim3(128), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
+                       abrx::EpisodeSampler{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }

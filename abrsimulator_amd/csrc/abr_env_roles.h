@@ -179,6 +179,8 @@ struct DVars {
     int32_t d_step, d_k, d_chunk, d_ep, offset0, issued_step, issued_k;
     int32_t issued_ndl, issued_avail;          // the download just issued took this many ticks; avail_tick of the chunk after it
     bool d_alive, was_alive;
+    const double *snap_trace;                  // SAMPLE instances only: the cursor's trace before the download just issued
+    int32_t snap_tlen;                         // (a speculative re-arm may have moved the cursor to another trace)
 };
 __device__ __forceinline__ void role_d_begin(DVars &v, const EnvParams &p) {
     const int l = threadIdx.x & 63;
@@ -197,11 +199,14 @@ __device__ __forceinline__ void role_d_begin(DVars &v, const EnvParams &p) {
     ABR_STAMP_INIT();
 }
 
-// before the barrier: the download of step d_step, started at its (predicted) call site
-template <int MODE, bool ACT_RING>
+// before the barrier: the download of step d_step, started at its (predicted) call site.  SAMPLE: a re-arm moves the cursor
+// to the episode sampler's (trace, offset) of the new episode (abr_env.hip: sampled_episode) -- speculatively, like
+// everything here: the workspace's trace_id / offset0 are written by the wave that owns the episode number
+template <int MODE, bool ACT_RING, bool SAMPLE = false>
 __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMail &m, ActRing *ring,
                                            const int32_t *__restrict__ actions, int32_t *__restrict__ actions_out,
-                                           int32_t n_total, uint64_t seed, int32_t t) {
+                                           int32_t n_total, uint64_t seed, int32_t t,
+                                           const abrx::EpisodeSampler &smp = abrx::EpisodeSampler{}) {
     const int l = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     const int32_t V = p.video_length;
@@ -211,6 +216,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
     ABR_STAMP(0);
     if (v.d_alive && v.d_step < n_total) {
         v.snap_j = v.cur.j; v.snap_tpos = v.cur.tpos;
+        if constexpr (SAMPLE) { v.snap_trace = v.cur.trace; v.snap_tlen = v.cur.tlen; }
         // (issuing these loads one iteration ahead, before the barrier, was measured three times and lost every time:
         // two-wave kernel -1.6 %, profiles/r02_ab_prefetch.txt; three-wave kernel -3 %, profiles/r03_ab_split3.txt (6);
         // the one-barrier form of round 4 -2 %, profiles/r04_experiments_not_kept.txt (6): 133 VGPRs, and the download
@@ -254,6 +260,11 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
             if (v.d_chunk >= V) {
                 if (p.auto_reset) {            // a fresh episode: clock, cursor and chunk ids restart
                     v.d_chunk = 0; v.d_ep++; v.d_k = tb.avail_tick[0];
+                    if constexpr (SAMPLE) {
+                        int32_t tr;
+                        sampled_episode(p, smp, i, v.d_ep, tr, v.offset0);
+                        v.cur.tlen = p.trace_len[tr]; v.cur.trace = p.traces + p.trace_off[tr];
+                    }
                     abrx::cursor_init(v.cur, v.offset0);
                 } else v.d_alive = false;
             }
@@ -268,6 +279,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
 
 // Validate the record issued in iteration t against the player's true call site, which P published before that
 // iteration's barrier (slot t & 1 stays intact until P's iteration t + 2): first thing in iteration t + 1.
+template <bool SAMPLE = false>
 __device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const abrx::Tables &tb, int32_t t) {
     const int l = threadIdx.x & 63;
     const int cb = t & 1;
@@ -286,7 +298,10 @@ __device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const ab
         v.d_alive = true;
         v.d_step = f_step; v.d_k = f_k;
         v.d_chunk = m.fb_chunk[cb][l]; v.d_ep = m.fb_episode[cb][l];
-        if (v.issued_step == v.d_step) { v.cur.j = v.snap_j; v.cur.tpos = v.snap_tpos; }
+        if (v.issued_step == v.d_step) {
+            v.cur.j = v.snap_j; v.cur.tpos = v.snap_tpos;
+            if constexpr (SAMPLE) { v.cur.trace = v.snap_trace; v.cur.tlen = v.snap_tlen; }
+        }
         v.issued_step = -1;
     } else if (v.d_alive && v.issued_ndl > 0 && v.d_chunk > 0) {
         // (Having the PLAYER flag "within chunk_length of max_buffer" in a spare bit of fb_alive, so that this wave reads
@@ -645,16 +660,28 @@ __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &, SplitMai
     ABR_STAMP(21);
 }
 
-template <int MODE>
+// SAMPLE: the episode the lane is in was re-armed in this launch -> its (trace, offset) is the sampler's
+__device__ __forceinline__ void sampled_episode_store(const EnvParams &p, const abrx::EpisodeSampler &smp, int64_t i,
+                                                      int32_t episode_no) {
+    if (episode_no != p.episode_no[i]) {
+        int32_t t, off;
+        sampled_episode(p, smp, i, episode_no, t, off);
+        p.trace_id[i] = t; p.offset0[i] = off;
+    }
+}
+
+template <int MODE, bool SAMPLE = false>
 __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMail2 &m2, float *__restrict__ obs_out,
                                            float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-                                           int32_t *__restrict__ actions_out, int32_t n_total) {
+                                           int32_t *__restrict__ actions_out, int32_t n_total,
+                                           const abrx::EpisodeSampler &smp = abrx::EpisodeSampler{}) {
     const EnvParams &p = fresh_params();
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
     if (i >= p.n_lanes) return;
     service_record(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
     if (!v.was_done) {
+        if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.episode_no);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.episode_no;
         p.last_bw[i] = v.last_bw; p.hist_n[i] = v.hist_n; p.hist_s[i] = v.hist_s; p.var_run[i] = v.var_run;
         p.done[i] = v.done;
@@ -671,11 +698,12 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMai
 
 // MODE 1: one externally supplied action per lane; MODE 2: fused random-policy rollout; MODE 3: fused rollout of
 // scripted actions [n_steps][n_lanes]
-template <int MODE>
+// SAMPLE: the instance that runs while an episode sampler is installed (`smp`; the other instances never read it)
+template <int MODE, bool SAMPLE = false>
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) void env_split3_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp) {
     __shared__ SplitMail m;
     __shared__ SplitMail2 m2;
     __shared__ ActRing ring;
@@ -698,8 +726,8 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     else { __builtin_amdgcn_s_setprio(ABR_PRIO_S); SVars v; role_s_begin(v, p, ring); s_park(park.s, v); }
     for (int32_t t = 0;; t++) {
         if (role == 0) {
-            if (t > 0) role_d_validate(dv, m, make_tables(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
-            role_d_pre<MODE, true>(dv, p, m, &ring, actions, actions_out, n_total, seed, t);
+            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
+            role_d_pre<MODE, true, SAMPLE>(dv, p, m, &ring, actions, actions_out, n_total, seed, t, smp);
         } else if (role == 1) {
             PVars v; p_unpark(park.p, v, p);
             role_p3_pre<MODE>(v, p, m, m2, n_total, t, t & 1);
@@ -715,7 +743,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     }
     if (role == 0) { role_d_end(dv, p); ABR_WG_TIME(1); }
     else if (role == 1) { PVars v; p_unpark(park.p, v, p); role_p3_end(v, p); ABR_WG_TIME(2); }
-    else { SVars v; s_unpark(park.s, v); role_s_end<MODE>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total); ABR_WG_TIME(3); }
+    else { SVars v; s_unpark(park.s, v); role_s_end<MODE, SAMPLE>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
 }
 
 // =====================================================================================================================
@@ -855,15 +883,17 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
     ABR_STAMP(17);
 }
 
-template <int MODE>
+template <int MODE, bool SAMPLE = false>
 __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, float *__restrict__ obs_out,
                                             float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-                                            int32_t *__restrict__ actions_out, int32_t n_total) {
+                                            int32_t *__restrict__ actions_out, int32_t n_total,
+                                            const abrx::EpisodeSampler &smp = abrx::EpisodeSampler{}) {
     const EnvParams &p = fresh_params();
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
     if (i >= p.n_lanes) return;
     if (!v.pv.was_done) {
+        if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.pv.episode_no);
         lanej_store_player(v.pv.s, p, i);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.pv.episode_no;
         p.last_bw[i] = v.last_bw; p.hist_n[i] = v.hist_n; p.hist_s[i] = v.hist_s; p.var_run[i] = v.var_run;
@@ -879,11 +909,11 @@ __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, 
     }
 }
 
-template <int MODE>
+template <int MODE, bool SAMPLE = false>
 __global__ __launch_bounds__(128) void env_split_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp) {
     __shared__ SplitMail m;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform by construction
@@ -898,8 +928,8 @@ __global__ __launch_bounds__(128) void env_split_kernel(
     else { P2Vars v; role_p2_begin(v, p); p2_park(park.p, v); }
     for (int32_t t = 0;; t++) {
         if (role == 0) {
-            if (t > 0) role_d_validate(dv, m, make_tables(p), t - 1);
-            role_d_pre<MODE, false>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t);
+            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables(p), t - 1);
+            role_d_pre<MODE, false, SAMPLE>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t, smp);
         } else {
             P2Vars v; p2_unpark(park.p, v, fresh_params());
             role_p2_pre<MODE>(v, p, m, obs_out, reward_out, done_out, n_total, t);
@@ -910,7 +940,7 @@ __global__ __launch_bounds__(128) void env_split_kernel(
         if (!m.any_alive[t & 1]) break;        // written by P before the barrier: identical in both waves
     }
     if (role == 0) role_d_end(dv, p);
-    else { P2Vars v; p2_unpark(park.p, v, fresh_params()); role_p2_end<MODE>(v, p, obs_out, reward_out, done_out, actions_out, n_total); }
+    else { P2Vars v; p2_unpark(park.p, v, fresh_params()); role_p2_end<MODE, SAMPLE>(v, p, obs_out, reward_out, done_out, actions_out, n_total, smp); }
 }
 
 #endif

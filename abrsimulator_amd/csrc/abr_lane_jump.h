@@ -989,5 +989,31 @@ ABR_HD int32_t policy_explore(const PolicyNet &n, uint64_t lane, int32_t c, int3
     return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : g;
 }
 
+// The episode sampler (include/abr_env.h: abr_episode_sampler, the same layout): which (trace, start offset) episode e of
+// global lane g runs when it was armed by the sampler.  A pure function of (seed, g, e), so every role of the split kernels
+// computes it where it needs it.  Step 0xFFFFFFFF is never a chunk id: the draw shares no counter with the random policy
+// or the policy's exploration, even under the same seed.
+struct EpisodeSampler {
+    uint64_t seed;
+    const int32_t *pool;           // nullptr: the whole corpus
+    int32_t n_pool;
+    int32_t offset_span;           // 0: the whole trace
+};
+constexpr uint32_t kEpisodeStep = 0xFFFFFFFFu;
+
+// trace_len: lengths of the n_traces traces (device memory in the kernels, host memory in tests/native)
+ABR_HD void episode_assign(const EpisodeSampler &s, uint64_t g, uint32_t e, int32_t n_traces,
+                           const int32_t *__restrict__ trace_len, int32_t &t_out, int32_t &off_out) {
+    uint32_t w[4];
+    philox4(s.seed, g, kEpisodeStep, e, w);
+    const uint32_t n = s.pool ? (uint32_t)s.n_pool : (uint32_t)n_traces;
+    const uint32_t u = (uint32_t)(((uint64_t)w[0] * n) >> 32);
+    const int32_t t = s.pool ? s.pool[u] : (int32_t)u;
+    const int32_t len = trace_len[t];
+    const int32_t span = (s.offset_span > 0 && s.offset_span < len) ? s.offset_span : len;
+    t_out = t;
+    off_out = (int32_t)(((uint64_t)w[1] * (uint32_t)span) >> 32);
+}
+
 }  // namespace abrx
 #endif

@@ -11,6 +11,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import _lib
+from .episodes import EpisodeSampler
 from .speed import LatencySpeedController
 from ._lib import F64_DIM, F64_ROWS, OBS_DIM, OBS_ROWS
 from .datamodel import MPD, NetworkInfo, QOEMetric
@@ -157,6 +158,40 @@ class BatchedABREnv:
         self.done = torch.zeros(self.n_lanes, dtype=torch.uint8, device=self.device)
         self.trace_id = None
         self.start_offset = None
+        self.episode_sampler = None
+
+    def set_episode_sampler(self, seed, pool=None, offset_span: int = 0):
+        """Draw each episode's (trace, start offset) on the device (include/abr_env.h: abr_episode_sampler): under
+        auto_reset a lane that ends its episode is re-armed on the pair drawn for its next episode number, and
+        reset(sample=True) draws the pairs of the lanes it resets.  seed: the philox key (uint64); pool: None (every trace)
+        or trace ids to draw from; offset_span: 0 (anywhere in the trace) or draw offsets from the first offset_span
+        positions.  set_episode_sampler(None) turns sampling off.  The pool is checked on the host here; episodes.py:
+        EpisodeSampler.draw computes the same pairs in numpy."""
+        if seed is None:
+            self._check(self.lib.abr_env_set_episode_sampler(self._h, None))
+            self.episode_sampler, self._sampler_pool = None, None
+            return
+        es = EpisodeSampler(seed, pool, offset_span)
+        es.check(self.n_traces)
+        pool_t = None
+        if es.pool is not None:
+            pool_t = torch.from_numpy(es.pool).to(self.device).contiguous()
+        st = _lib.EpisodeSampler()
+        st.seed, st.pool = es.seed, (pool_t.data_ptr() if pool_t is not None else None)
+        st.n_pool, st.offset_span = (int(pool_t.numel()) if pool_t is not None else 0), es.offset_span
+        with torch.cuda.device(self.device):
+            self._check(self.lib.abr_env_set_episode_sampler(self._h, C.byref(st)))
+        # the library holds the pool's address: keep the tensor alive while the sampler is installed
+        self.episode_sampler, self._sampler_pool = es, pool_t
+
+    def episodes(self):
+        """Each lane's current episode: dict(trace_id, start_offset, episode), int32 [N] each (fresh tensors, copied on the
+        current stream)."""
+        out = {k: torch.empty(self.n_lanes, dtype=torch.int32, device=self.device)
+               for k in ("trace_id", "start_offset", "episode")}
+        self._call(self.lib.abr_env_get_episode, self._h, _lib.ptr(out["trace_id"]), _lib.ptr(out["start_offset"]),
+                   _lib.ptr(out["episode"]))
+        return out
 
     def set_speed_controller(self, controller, log_rows: int = 0):
         """Install a LatencySpeedController (None: back to the constant config speed).  Latched like the per-lane speeds:
@@ -232,7 +267,7 @@ class BatchedABREnv:
         return out
 
     # -- the step surface --------------------------------------------------
-    def reset(self, trace_id=None, start_offset=None, mask=None, check=False):
+    def reset(self, trace_id=None, start_offset=None, mask=None, check=False, sample=False):
         """Simulator.py:95-133 + idle ticks to the first ABR call.  Default assignment: lane i -> trace
         i % n_traces, offset 0.  `mask`: only lanes with a non-zero byte are reset (a masked reset inside an RL loop).
 
@@ -241,7 +276,23 @@ class BatchedABREnv:
         IndexError at Simulator.py:159); the observation returned for it looks like a fresh lane's.  `done_after_reset()`
         reads the lanes' done bytes as they stand (a zero-copy view, no step needed) so that a caller can see such lanes
         without a step.  check=True validates on the host first and raises ValueError instead -- before this object or
-        the device state changes -- at the price of two synchronisations."""
+        the device state changes -- at the price of two synchronisations.
+
+        sample=True (with an episode sampler installed, set_episode_sampler): every reset lane runs the sampler's pair for
+        its new episode number; trace_id / start_offset must then be None.  self.trace_id / self.start_offset then hold
+        each lane's pair as episodes() reports it after the reset."""
+        if sample:
+            if trace_id is not None or start_offset is not None:
+                raise ValueError("reset(sample=True) draws the trace ids and start offsets: pass neither")
+            if self.episode_sampler is None:
+                raise ValueError("reset(sample=True) needs an episode sampler (set_episode_sampler)")
+            m = None
+            if mask is not None:
+                m = torch.as_tensor(mask, device=self.device).to(torch.uint8).contiguous()
+            self._call(self.lib.abr_env_reset, self._h, None, None, _lib.ptr(m), _lib.ptr(self.obs))
+            ep = self.episodes()
+            self.trace_id, self.start_offset = ep["trace_id"], ep["start_offset"]
+            return self.obs
         if trace_id is None:
             trace_id = torch.arange(self.n_lanes, device=self.device, dtype=torch.int32) % self.n_traces
         tid = self._i32(trace_id, "trace_id")

@@ -214,11 +214,19 @@ class ShardedABREnv:
         lens = [len(t) for t in (bw if hasattr(bw[0], "__len__") else [bw])]
         return lane_assignment(self.lane0, self.n_lanes, lens, xcd_groups=xcd_groups)
 
-    def reset(self, trace_id=None, start_offset=None, mask=None):
-        """Default: the deterministic global-lane map (lane_assignment); or this shard's own trace ids / offsets.
+    def set_episode_sampler(self, seed, pool=None, offset_span=0):
+        """BatchedABREnv.set_episode_sampler on this rank's stepper: draws are keyed by the GLOBAL lane id (lane_id_base),
+        so every rank with the same sampler reproduces its slice of the unsharded run."""
+        self.env.set_episode_sampler(seed, pool, offset_span)
+
+    def reset(self, trace_id=None, start_offset=None, mask=None, sample=False):
+        """Default: the deterministic global-lane map (lane_assignment); or this shard's own trace ids / offsets; or, with
+        sample=True, the episode sampler's pairs (set_episode_sampler).
         As BatchedABREnv.reset(): no host synchronisation; a lane with a trace id out of range or a negative offset is frozen
         on the device with ABR_DONE_BADARG (visible in self.env.done_after_reset(), or in `done` after the next launch) while
         its returned observation looks like a fresh lane's."""
+        if sample:
+            return self.env.reset(mask=mask, sample=True)
         if trace_id is None:
             trace_id, start_offset = self.lane_map()
         tid = torch.as_tensor(trace_id)

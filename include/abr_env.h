@@ -114,8 +114,9 @@ typedef struct abr_env_config {
     double  speed;              /* play_speed, constant                       */
     double  ladder[ABR_MAX_RATES];
     int32_t max_ticks;          /* per-episode bound on 0.01 s ticks; <=0: 32 * V * ceil(L/dt) */
-    int32_t auto_reset;         /* !=0: a lane that finishes is re-armed (same trace, same offset)
-                                   inside the step; the obs returned is the new episode's first */
+    int32_t auto_reset;         /* !=0: a lane that finishes is re-armed inside the step (same trace, same
+                                   offset; with an episode sampler installed, the sampler's pair for the new
+                                   episode); the obs returned is the new episode's first */
 } abr_env_config;
 
 typedef struct abr_env abr_env;   /* opaque host-side handle */
@@ -250,6 +251,8 @@ int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out);
  * frozen with ABR_DONE_BADARG (the reference would raise IndexError at Simulator.py:159).
  * Every reset of a lane after its first starts the next episode number of the built-in
  * counter-based policy (abr_env_step_random), so repeated episodes draw fresh actions.
+ * trace_id_dev == NULL (with start_offset_dev == NULL) is accepted only while an episode sampler is
+ * installed: each reset lane then runs the sampler's pair for its new episode number.
  */
 int abr_env_reset(abr_env *env, const int32_t *trace_id_dev, const int32_t *start_offset_dev,
                   const uint8_t *lane_mask_dev, float *obs_out_dev, void *stream);
@@ -265,6 +268,42 @@ int abr_env_reset(abr_env *env, const int32_t *trace_id_dev, const int32_t *star
  */
 int abr_env_step(abr_env *env, const int32_t *actions_dev, float *obs_out_dev,
                  float *reward_out_dev, uint8_t *done_out_dev, void *stream);
+
+/*
+ * Episode sampler (ABI 4, additive; BUILD-DEFINED: the reference runs one trace from one offset per run()).  Under
+ * auto_reset a lane that ends with ABR_DONE_EPISODE is re-armed inside the launch on a (trace, start offset) pair drawn on
+ * the device instead of its previous one.  The assignment of episode e of global lane g = lane_id_base + i is a pure
+ * function (abr_lane_jump.h: episode_assign):
+ *   w[0..3] = philox4x32-10(key = seed, ctr = (g lo, g hi, 0xFFFFFFFF, (uint32)e))
+ *   u       = ((uint64)w0 * n) >> 32            n = n_pool with a pool, else n_traces
+ *   t       = pool ? pool[u] : u
+ *   span    = offset_span > 0 ? min(offset_span, trace_len[t]) : trace_len[t]
+ *   offset  = ((uint64)w1 * span) >> 32
+ * The counter step 0xFFFFFFFF is never a chunk id: no draw of abr_env_step_random or of the policy's exploration shares it.
+ * e is the lane's episode number (abr_env_get_episode): 0 after the first reset of a fresh lane, +1 at every later reset and
+ * at every re-arm.  The draw is keyed by the global lane id, so shards (abr_env_set_lane_id_base) see the unsharded lanes'
+ * sequences.  Lanes that end with ABR_DONE_TIMEOUT are not re-armed, with or without a sampler.
+ *
+ * abr_env_set_episode_sampler copies the struct (s == NULL: sampling off).  Refused with ABR_E_INVALID before anything is
+ * stored: a pool with n_pool < 1, offset_span < 0, then (after the handle is checked) a pool id outside [0, n_traces) -- the
+ * pool is read back once to be checked (one device synchronisation).  pool is caller-owned device memory that must stay
+ * valid and unchanged while the sampler is installed.  The sampler takes effect at the next re-arm or sampled reset; nothing
+ * is latched.  abr_env_reset with trace_id_dev == NULL and start_offset_dev == NULL while a sampler is installed draws each
+ * reset lane's pair for its new episode number (lane_mask_dev still applies).  Every launch kind and implementation
+ * honours it (0, 1, 2, 3, 5); the diagnostic pipelines 4, 6 and 7 refuse a launch with a sampler (ABR_E_UNSUPPORTED).
+ */
+typedef struct abr_episode_sampler {
+    uint64_t seed;
+    const int32_t *pool;        /* nullable: device int32 [n_pool] trace ids; NULL = every trace */
+    int32_t n_pool;
+    int32_t offset_span;        /* >= 0; 0 = the whole trace */
+} abr_episode_sampler;          /* 24 bytes */
+int abr_env_set_episode_sampler(abr_env *env, const abr_episode_sampler *s);
+
+/* Each lane's current episode: trace id, start offset (as given to abr_env_reset, or drawn) and episode number, int32
+ * [n_lanes] device memory each, all nullable; copies enqueued on the stream. */
+int abr_env_get_episode(abr_env *env, int32_t *trace_id_out_dev, int32_t *offset_out_dev, int32_t *episode_out_dev,
+                        void *stream);
 
 /*
  * n_steps fused decisions per lane with the built-in random policy

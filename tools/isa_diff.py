@@ -5,7 +5,8 @@
 
 Bodies are compared without comments, with basic-block label numbers normalised, and with the kernel's own symbol name
 normalised (so that a template whose signature grew a trailing argument -- a different mangled name -- is still compared
-with its old self; --strip SUFFIX removes that suffix from the new names, default: the RuleParams argument's mangling).
+with its old self; --strip SUFFIX removes that suffix from the new names, default: the RuleParams argument's mangling;
+give it more than once to strip several, e.g. a defaulted template flag's `Lb0E` as well).
 Prints one line per kernel that differs, every kernarg-size change, the kernels that are new, and a summary."""
 import argparse
 import re
@@ -29,12 +30,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("old")
     ap.add_argument("new")
-    ap.add_argument("--strip", default="N4abrx10RuleParamsE")
+    ap.add_argument("--strip", action="append")
     a = ap.parse_args()
+    strips = a.strip if a.strip is not None else ["N4abrx10RuleParamsE"]
     old = kernels(a.old)
     new = {}
     for name, (body, ka) in kernels(a.new).items():
-        short = name.replace(a.strip, "") if a.strip else name
+        short = name
+        for suffix in strips:
+            if suffix:
+                short = short.replace(suffix, "")
         new[short] = (body.replace(name, short), ka)
     same = 0
     for name, (body, ka) in sorted(old.items()):
