@@ -100,16 +100,30 @@ def pack_traces(traces):
 
 
 def env_batch(cfg, traces, trace_id, offset, actions, max_ticks=1 << 40, speeds=None,
-              want_steps=True):
+              want_steps=True, threads=1):
     """Replay episodes. traces: list of arrays. actions: [N, V] int32.  speeds: optional
     per-lane constant play speeds [N] (default: cfg.speed for every lane), or per-lane speed
     SCHEDULES [N, rows]: the answers to each lane's successive get_next_speed() calls.
-    Returns (steps[N,V] STEP_DTYPE, bw[N,V], final[N] FINAL_DTYPE, total_ticks)."""
-    flat, off, lens = pack_traces(traces)
+    Returns (steps[N,V] STEP_DTYPE, bw[N,V], final[N] FINAL_DTYPE, total_ticks).  threads > 1
+    splits the lanes over a thread pool (ctypes releases the GIL)."""
     trace_id = np.ascontiguousarray(trace_id, np.int32)
     offset = np.ascontiguousarray(offset, np.int32)
     actions = np.ascontiguousarray(actions, np.int32)
     N, V = actions.shape
+    threads = min(threads, N)
+    if threads > 1:
+        from concurrent.futures import ThreadPoolExecutor
+        cuts = np.linspace(0, N, threads + 1).astype(int)
+
+        def run(i):
+            s = slice(cuts[i], cuts[i + 1])
+            return env_batch(cfg, traces, trace_id[s], offset[s], actions[s], max_ticks,
+                             None if speeds is None else speeds[s], want_steps)
+        with ThreadPoolExecutor(threads) as ex:
+            parts = list(ex.map(run, range(threads)))
+        cat = lambda k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts])
+        return cat(0), cat(1), cat(2), sum(p[3] for p in parts)
+    flat, off, lens = pack_traces(traces)
     assert V == cfg.video_length
     steps = np.zeros((N, V), STEP_DTYPE) if want_steps else None
     bw = np.zeros((N, V), np.float64)

@@ -24,14 +24,11 @@ runs at the clipped horizon V - c (D12).  Under auto_reset a lane restarts from 
 (n, S) restarts, RobustMPC's state empties itself at chunk 0 (carried across episodes here, as on the device), RATE and
 FastMPC read the current episode's history only.  A speed rule's log holds the lane's current episode only, so the
 generator pairs the speed rule with auto_reset off (tests/test_speed_rule_gpu.py covers a rule under auto_reset)."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 
 from oracle import oracle as O
 from oracle.pyloop import PyTickEnv
-from helpers import oracle_rewards
+from helpers import oracle_env_cfg, oracle_rewards, thread_map, threads
 import fastmpc_twin
 import robust_twin
 import rules_twin
@@ -48,11 +45,6 @@ OBS = ("chunk_id", "last_bitrate", "last_bandwidth", "buffer_level", "global_tim
        "start_up_time")                                         # abrsimulator_amd._lib.OBS_ROWS
 TWIN_LANES = 16
 DONE_TIMEOUT = 2                                                # include/abr_env.h: ABR_DONE_TIMEOUT
-
-
-def threads():
-    """Oracle work runs on at most 16 threads (a GPU machine lends 16 CPUs whatever os.cpu_count() says)."""
-    return max(1, min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS", "16") or 16)))
 
 
 def accepted_impls(ctl, feature):
@@ -172,9 +164,7 @@ def br_table(case):
 
 
 def env_cfg(case):
-    m = case["meta"]
-    return O.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"], m["start_up_length"],
-                     m["interval"], m["weights"], m["speed"], br_table=case["br"])
+    return oracle_env_cfg(O, case["meta"], br_table=case["br"])
 
 
 def mpc_cfg(case, horizon=None):
@@ -280,19 +270,9 @@ def lane_speeds_for(case, speed_log):
 
 
 def replay(case, actions, speeds):
-    """oracle.env_batch over lane slices on a thread pool: (steps, bw, fin)."""
-    cfg, tr, tid, off = env_cfg(case), case["traces"], case["tid"], case["off"]
-    N = len(tid)
-    k = min(threads(), N)
-    cuts = np.linspace(0, N, k + 1).astype(int)
-
-    def run(j):
-        lo, hi = cuts[j], cuts[j + 1]
-        sp = None if speeds is None else speeds[lo:hi]
-        return O.env_batch(cfg, tr, tid[lo:hi], off[lo:hi], actions[lo:hi], speeds=sp)[:3]
-    with ThreadPoolExecutor(k) as ex:
-        parts = list(ex.map(run, range(k)))
-    return tuple(np.concatenate([q[j] for q in parts]) for j in range(3))
+    """The device's actions replayed through the oracle on a thread pool: (steps, bw, fin)."""
+    return O.env_batch(env_cfg(case), case["traces"], case["tid"], case["off"], actions, speeds=speeds,
+                       threads=threads())[:3]
 
 
 class _Row:
@@ -457,8 +437,7 @@ def check(case, out, stats=None):
         fin, a = ep[0][5], ep[0][2]
         log = np.asarray(out["speed_log"])
         sub = np.sort(np.argsort(fin["ticks"], kind="stable")[:TWIN_LANES])
-        with ThreadPoolExecutor(min(threads(), len(sub))) as ex:
-            logs = list(ex.map(lambda i: twin_log(case, i, a[i]), sub))
+        logs = thread_map(lambda i: twin_log(case, i, a[i]), sub)
         for i, tl in zip(sub, logs):
             w = np.zeros(log.shape[0])
             k = min(len(tl), log.shape[0])

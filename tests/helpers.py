@@ -1,6 +1,10 @@
 """Shared helpers for the parity tests (tests may use the oracle; the product may not)."""
+import ctypes as C
+import glob
 import os
 import subprocess
+import tempfile
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
@@ -10,6 +14,72 @@ from oracle.oracle import philox_action  # noqa: E402,F401  (bit-exact numpy twi
 
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DIAG_IMPLS = ("async", "ring3", "pair3")      # pipelines that were measured slower and live in the diagnostic build only
+
+
+def threads():
+    """Oracle work runs on at most 16 threads (a GPU machine lends 16 CPUs whatever os.cpu_count() says), and on no
+    more than OMP_NUM_THREADS."""
+    return max(1, min(16, os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS", "16") or 16)))
+
+
+def thread_map(fn, items):
+    """list(map(fn, items)) on a pool of threads() workers (the oracle's ctypes calls release the GIL)."""
+    with ThreadPoolExecutor(max(1, min(threads(), len(items)))) as ex:
+        return list(ex.map(fn, items))
+
+
+_harness_cache = {}
+
+
+def native_harness(name):
+    """tests/native/<name>.cpp -- the kernels' own headers compiled for the host -- as a ctypes.CDLL, once per session.
+    tests/native/lib<name>.so is rebuilt when it is older than the harness or than any header of abrsimulator_amd/csrc;
+    the compiler writes a temporary file that then replaces it, so a concurrent test process never loads half a file."""
+    if name not in _harness_cache:
+        d, inc = os.path.join(_ROOT, "tests", "native"), os.path.join(_ROOT, "abrsimulator_amd", "csrc")
+        src, so = os.path.join(d, name + ".cpp"), os.path.join(d, "lib" + name + ".so")
+        deps = [src] + glob.glob(os.path.join(inc, "*.h"))
+        if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
+            tmp = os.path.join(d, f".lib{name}.{os.getpid()}.so")
+            try:
+                subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
+                                       "-fno-fast-math", "-I", inc, src, "-o", tmp])
+                os.replace(tmp, so)
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+        _harness_cache[name] = C.CDLL(so)
+    return _harness_cache[name]
+
+
+def c_abi_output(program):
+    """Compiles a C program against include/ (gcc -std=c11), runs it and returns its stdout as a list of lines: the C
+    compiler's view of the public header, for the ABI tests to compare with the ctypes mirrors."""
+    with tempfile.TemporaryDirectory() as td:
+        c, exe = os.path.join(td, "t.c"), os.path.join(td, "t")
+        with open(c, "w") as f:
+            f.write(program)
+        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(_ROOT, "include"), c, "-o", exe])
+        return subprocess.check_output([exe]).decode().splitlines()
+
+
+def golden_workload(N, seed=7):
+    """N lanes over the env_bench_shape golden's traces: (meta, traces, trace_id, offset), trace ids round robin and
+    seeded offsets."""
+    from conftest import load_golden
+    m, g = load_golden("env_bench_shape")
+    traces = [np.asarray(t, np.float64) for t in g["traces"]]
+    rng = np.random.default_rng(seed)
+    tid = (np.arange(N) % len(traces)).astype(np.int32)
+    off = rng.integers(0, len(traces[0]), N).astype(np.int32)
+    return m, traces, tid, off
+
+
+def oracle_env_cfg(oracle, meta, br_table=None):
+    """oracle.env_cfg from a golden's (or a generated case's) meta dict; a meta without a speed plays at 1.0."""
+    return oracle.env_cfg(meta["ladder"], meta["chunk_length"], meta["video_length"], meta["max_buffer"],
+                          meta["start_up_length"], meta["interval"], meta["weights"], meta.get("speed", 1.0),
+                          br_table=br_table)
 
 
 _diag_lib_cache = {}

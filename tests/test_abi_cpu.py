@@ -5,13 +5,12 @@ paths return before any HIP call)."""
 import ctypes as C
 import os
 import re
-import subprocess
 import sys
-import tempfile
 
 import pytest
 
 from conftest import ROOT
+from helpers import c_abi_output
 
 HDR = os.path.join(ROOT, "include", "abr_env.h")
 
@@ -56,12 +55,7 @@ int main(void) {
   printf("%d %d %d %d\n", ABR_OBS_DIM, ABR_F64_DIM, ABR_MAX_RATES, ABR_MAX_HORIZON);
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
+    out = c_abi_output(prog)
     a = list(map(int, out[0].split()))
     E = L.EnvConfig
     assert a == [C.sizeof(E), E.ladder.offset, E.max_ticks.offset, E.speed.offset, E.interval.offset]

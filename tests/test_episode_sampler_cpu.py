@@ -4,29 +4,21 @@ an independent numpy twin of the contract in include/abr_env.h, on seeded cases 
 the header, and the refusals that need no device."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import c_abi_output, native_harness
 import policy_twin as T
 
-SRC = os.path.join(ROOT, "tests", "native", "episode_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "libepisode_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 P_ = lambda a, t: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(t))
 M32 = (1 << 32) - 1
 
 
 @pytest.fixture(scope="module")
 def EH():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math",
-                               "-I", INC, SRC, "-o", SO])
-    return C.CDLL(SO)
+    return native_harness("episode_harness")
 
 
 @pytest.fixture(scope="module")
@@ -161,12 +153,7 @@ int main(void) {
          offsetof(abr_episode_sampler, offset_span));
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        got = list(map(int, subprocess.check_output([exe]).decode().split()))
+    got = list(map(int, c_abi_output(prog)[0].split()))
     S = L.EpisodeSampler
     assert got == [C.sizeof(S), S.seed.offset, S.pool.offset, S.n_pool.offset, S.offset_span.offset] == [24, 0, 8, 16, 20]
     assert EH.eh_sampler_size() == 24

@@ -3,26 +3,17 @@ on the CPU against the naive one-addition-per-tick loop: results must be
 bit-identical, including round-to-even ties, binade crossings, thresholds that
 sit exactly on reachable values, and the simulator's own constants."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from helpers import native_harness
 
-SRC = os.path.join(ROOT, "tests", "native", "exact_jump_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "libexact_jump_harness.so")
 
 
 @pytest.fixture(scope="module")
 def H():
-    inc = os.path.join(ROOT, "abrsimulator_amd", "csrc")
-    if (not os.path.exists(SO) or os.path.getmtime(SO) < max(
-            os.path.getmtime(SRC), os.path.getmtime(os.path.join(inc, "abr_exact_jump.h")))):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", inc, SRC, "-o", SO])
-    lib = C.CDLL(SO)
+    lib = native_harness("exact_jump_harness")
     for f in (lib.fuzz_ge, lib.fuzz_le, lib.fuzz_lt, lib.fuzz_biased, lib.overshoot_count):
         f.restype = C.c_int64
     return lib

@@ -2,30 +2,20 @@
 against the numpy twin on seeded cases with their knife edges, the ABI struct, the size queries, every validation refusal
 and the controller's arguments."""
 import ctypes as C
-import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
 from fastmpc_twin import lookup
+from helpers import c_abi_output, native_harness
 
-SRC = os.path.join(ROOT, "tests", "native", "fastmpc_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "libfastmpc_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 HMAX = 40
 
 
 @pytest.fixture(scope="module")
 def FH():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    return C.CDLL(SO)
+    return native_harness("fastmpc_harness")
 
 
 def _blob(entries, be, te):
@@ -160,12 +150,7 @@ int main(void) {
   printf("%d\n", ABR_FASTMPC_MAX_POINTS);
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
+    out = c_abi_output(prog)
     F = _lib.FastMpc
     assert list(map(int, out[0].split())) == [C.sizeof(F), F.window.offset, F.utility.offset, F.n_rows.offset,
                                               F.n_buffer.offset, F.n_tput.offset, F.buffer_points.offset,

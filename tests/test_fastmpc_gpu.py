@@ -2,9 +2,6 @@
 the standalone lookup against RobustMPC on a zeroed state (on grid points) and against the twin reading the built table
 (off them), fused rollouts against the oracle driven by the twin (jump, tick, auto, auto-reset, per-chunk ladders,
 per-lane speeds, frozen lanes), the fused rollout against the host loop, a full-size replay, and the refusals."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 import torch
@@ -13,7 +10,7 @@ import abrsimulator_amd as A
 from abrsimulator_amd import _lib
 from conftest import load_golden
 from fastmpc_twin import chunk_of_row, entry_oracle, lookup, lookup_lanes, row_of
-from helpers import make_env, oracle_rewards
+from helpers import golden_workload, make_env, oracle_env_cfg, oracle_rewards, thread_map, threads
 
 pytestmark = pytest.mark.gpu
 
@@ -128,8 +125,7 @@ def test_bench_size_table_sampled(oracle):
     def run(part):
         return [(k, entry_oracle(oracle, ocfg, br, sz, chunk_of_row(k[0], V, True), k[1], ctl.buffer_points[k[2]],
                                  ctl.tput_points[k[3]])) for k in part]
-    with ThreadPoolExecutor(16) as ex:
-        res = [x for part in ex.map(run, np.array_split(np.array(idx), 16)) for x in part]
+    res = [x for part in thread_map(run, np.array_split(np.array(idx), threads())) for x in part]
     bad = [(tuple(k), int(e[tuple(k)]), w) for k, w in res if e[tuple(k)] != w]
     assert not bad, bad[:10]
 
@@ -205,34 +201,6 @@ def test_standalone_select_on_and_off_grid(oracle, utility, clip):
 # ---------------------------------------------------------------------------------------------------------------------
 # 4. - 6.  rollouts
 
-def _golden(N, seed=7):
-    m, g = load_golden("env_bench_shape")
-    traces = [np.asarray(t, np.float64) for t in g["traces"]]
-    rng = np.random.default_rng(seed)
-    tid = (np.arange(N) % len(traces)).astype(np.int32)
-    off = rng.integers(0, len(traces[0]), N).astype(np.int32)
-    return m, traces, tid, off
-
-
-def _ecfg(oracle, m, br_table=None):
-    return oracle.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"], m["start_up_length"],
-                          m["interval"], m["weights"], m.get("speed", 1.0), br_table=br_table)
-
-
-def _replay(oracle, cfg, traces, tid, off, actions, speeds=None):
-    N = len(tid)
-    threads = min(16, N)
-    cuts = np.linspace(0, N, threads + 1).astype(int)
-
-    def run(i):
-        lo, hi = cuts[i], cuts[i + 1]
-        return oracle.env_batch(cfg, traces, tid[lo:hi], off[lo:hi], actions[lo:hi],
-                                speeds=None if speeds is None else speeds[lo:hi])
-    with ThreadPoolExecutor(threads) as ex:
-        parts = list(ex.map(run, range(threads)))
-    return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
-
-
 def _twin_over_replay(ctl, e, steps, bw, V):
     """The twin's action at every call site of the replayed episodes: [V, N]."""
     N = steps.shape[0]
@@ -247,7 +215,7 @@ def _twin_over_replay(ctl, e, steps, bw, V):
 @pytest.mark.parametrize("impl", ["jump", "tick", "auto"])
 def test_rollout_equals_oracle_driven_by_twin(oracle, impl):
     N = 96
-    m, traces, tid, off = _golden(N)
+    m, traces, tid, off = golden_workload(N)
     V = m["video_length"]
     env = make_env(m, traces, N, impl=impl)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -257,14 +225,14 @@ def test_rollout_equals_oracle_driven_by_twin(oracle, impl):
     acts = out["actions"].cpu().numpy()
     e = _host(ctl)
     assert (acts[V:] == -1).all()
-    cfg = _ecfg(oracle, m)
+    cfg = oracle_env_cfg(oracle, m)
     # a few lanes literally driven by the twin through the oracle
     for i in range(8):
         pol = lambda o, h: lookup(e, ctl.buffer_edges, ctl.tput_edges, 3, V, 5, True, int(o["chunk_id"]),
                                   int(o["last_bitrate"]), float(o["buffer_level"]), h)
         st, _, a, f = oracle.env_episode_policy(cfg, traces[tid[i]], off[i], pol)
         assert np.array_equal(acts[:V, i], a), i
-    steps, bw, fin = _replay(oracle, cfg, traces, tid, off, np.ascontiguousarray(acts[:V].T))
+    steps, bw, fin, _ = oracle.env_batch(cfg, traces, tid, off, np.ascontiguousarray(acts[:V].T), threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, e, steps, bw, V), acts[:V])
     assert len(np.unique(acts[:V])) >= 3
     rew = out["reward"].cpu().numpy()
@@ -279,7 +247,7 @@ def test_rollout_equals_oracle_driven_by_twin(oracle, impl):
 
 
 def test_auto_reset_repeats_the_first_episode():
-    m, traces, tid, off = _golden(128)
+    m, traces, tid, off = golden_workload(128)
     V = m["video_length"]
     env = make_env(m, traces, 128, auto_reset=True)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -292,7 +260,7 @@ def test_auto_reset_repeats_the_first_episode():
 
 def test_per_chunk_ladder_and_lane_speeds(oracle):
     N = 128
-    m, traces, tid, off = _golden(N, seed=13)
+    m, traces, tid, off = golden_workload(N, seed=13)
     V, L = m["video_length"], m["chunk_length"]
     rng = np.random.default_rng(2)
     table = np.sort(np.asarray(m["ladder"]) * rng.uniform(0.7, 1.3, (V, 1)) * rng.uniform(0.9, 1.1, (V, 6)), axis=1)
@@ -306,8 +274,8 @@ def test_per_chunk_ladder_and_lane_speeds(oracle):
     out = env.step_rule(ctl, V)
     acts = out["actions"].cpu().numpy()
     e = _host(ctl)
-    steps, bw, fin = _replay(oracle, _ecfg(oracle, m, br_table=table), traces, tid, off, np.ascontiguousarray(acts.T),
-                             speeds=speeds)
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m, br_table=table), traces, tid, off,
+                                         np.ascontiguousarray(acts.T), speeds=speeds, threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, e, steps, bw, V), acts)
     assert len(np.unique(acts)) >= 3
     assert np.array_equal(env.observe_f64()["global_time"].cpu().numpy(), fin["global_time"])
@@ -316,7 +284,7 @@ def test_per_chunk_ladder_and_lane_speeds(oracle):
 @pytest.mark.parametrize("impl", ["jump", "tick"])
 def test_fused_equals_host_loop(impl):
     N = 256
-    m, traces, tid, off = _golden(N, seed=3)
+    m, traces, tid, off = golden_workload(N, seed=3)
     V = m["video_length"]
     envs = [make_env(m, traces, N, impl=impl) for _ in range(2)]
     for env in envs:
@@ -335,7 +303,7 @@ def test_fused_equals_host_loop(impl):
 
 def test_full_size_replay(oracle):
     N = 65536
-    m, traces, tid, off = _golden(N, seed=21)
+    m, traces, tid, off = golden_workload(N, seed=21)
     V = m["video_length"]
     env = make_env(m, traces, N)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -344,8 +312,8 @@ def test_full_size_replay(oracle):
     acts = out["actions"].cpu().numpy()
     e = _host(ctl)
     lanes = np.sort(np.random.default_rng(0).choice(N, 512, replace=False))
-    steps, bw, fin = _replay(oracle, _ecfg(oracle, m), traces, tid[lanes], off[lanes],
-                             np.ascontiguousarray(acts[:, lanes].T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid[lanes], off[lanes],
+                                         np.ascontiguousarray(acts[:, lanes].T), threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, e, steps, bw, V), acts[:, lanes])
     assert np.array_equal(env.observe_f64()["global_time"].cpu().numpy()[lanes], fin["global_time"])
 
@@ -355,7 +323,7 @@ def test_full_size_replay(oracle):
 
 @pytest.mark.parametrize("impl", ["split", "split3"])
 def test_role_split_is_refused(impl):
-    m, traces, tid, off = _golden(64)
+    m, traces, tid, off = golden_workload(64)
     env = make_env(m, traces, 64, impl=impl)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     ctl = A.FastMPCController(A.EnvPlayer(env))
@@ -364,7 +332,7 @@ def test_role_split_is_refused(impl):
 
 
 def test_uniform_layout_refused_with_per_chunk_table():
-    m, traces, tid, off = _golden(64)
+    m, traces, tid, off = golden_workload(64)
     V = m["video_length"]
     table = np.tile(np.asarray(m["ladder"]), (V, 1)) * np.linspace(1.0, 1.1, V)[:, None]
     mpd = A.MPD(V, m["chunk_length"], m["max_buffer"], m["start_up_length"], [A.Chunk(list(r)) for r in table])

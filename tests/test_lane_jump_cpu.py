@@ -3,26 +3,18 @@ the reference-generated goldens and against the C oracle on large seeded sets.
 This is the same source the HIP kernels compile for gfx950; running it on the CPU
 lets the exactness claim be fuzzed over millions of lane-steps without a GPU."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ENV_GOLDENS, ROOT, load_golden
+from conftest import ENV_GOLDENS, load_golden
+from helpers import native_harness
 
-SRC = os.path.join(ROOT, "tests", "native", "lane_jump_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "liblane_jump_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 
 
 @pytest.fixture(scope="module")
 def H():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h", "abr_tick_tables.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    lib = C.CDLL(SO)
+    lib = native_harness("lane_jump_harness")
     lib.lj_create.restype = C.c_void_p
     lib.lj_batch.restype = C.c_int64
     return lib

@@ -12,17 +12,13 @@ import numpy as np
 import pytest
 
 from conftest import ENV_GOLDENS, GOLDEN, MPC_GOLDENS, load_golden
-
-
-def _env_cfg(o, m):
-    return o.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"],
-                     m["start_up_length"], m["interval"], m["weights"], m["speed"])
+from helpers import golden_workload, oracle_env_cfg
 
 
 @pytest.mark.parametrize("name", ENV_GOLDENS)
 def test_env_episode_bit_exact(oracle, name):
     m, g = load_golden(name)
-    cfg = _env_cfg(oracle, m)
+    cfg = oracle_env_cfg(oracle, m)
     steps, bw, fin, ticks = oracle.env_batch(cfg, list(g["traces"]), g["trace_id"], g["offset"],
                                              g["actions"])
     for k in ["global_time", "rebuffer_time", "start_up_time", "play_time", "average_latency",
@@ -44,7 +40,7 @@ def test_env_speed_schedule_bit_exact(oracle):
     """A scripted speed controller: get_next_speed() answers differently at every played chunk
     (Simulator.py:176-177).  The fixture is the reference itself driven by that script."""
     m, g = load_golden("env_speed_schedule")
-    cfg = _env_cfg(oracle, m)
+    cfg = oracle_env_cfg(oracle, m)
     steps, bw, fin, _ = oracle.env_batch(cfg, list(g["traces"]), g["trace_id"], g["offset"],
                                          g["actions"], speeds=g["speed_sched"])
     for k in ["global_time", "rebuffer_time", "start_up_time", "play_time", "average_latency",
@@ -60,6 +56,26 @@ def test_env_speed_schedule_bit_exact(oracle):
     # the script really was consumed past its end (the last answer repeats) and speeds differ
     assert g["final_speed_calls"].min() > g["speed_sched"].shape[1]
     assert len(np.unique(g["speed_sched"])) > 8
+
+
+def test_env_batch_threads_match_one_thread(oracle):
+    """Splitting the lanes over a thread pool changes nothing: every field, with a config speed, per-lane speeds and
+    per-lane speed schedules, and lane counts that do not divide evenly."""
+    m, traces, tid, off = golden_workload(301)
+    rng = np.random.default_rng(3)
+    N, V = len(tid), m["video_length"]
+    actions = rng.integers(0, len(m["ladder"]), (N, V)).astype(np.int32)
+    cfg = oracle_env_cfg(oracle, m)
+    for speeds in (None, rng.choice([0.75, 1.0, 1.5], N), rng.choice([0.5, 1.0, 2.0], (N, 6))):
+        want = oracle.env_batch(cfg, traces, tid, off, actions, speeds=speeds)
+        for k in (1, 3, 16):
+            got = oracle.env_batch(cfg, traces, tid, off, actions, speeds=speeds, threads=k)
+            for name in oracle.STEP_DTYPE.names:
+                assert np.array_equal(got[0][name], want[0][name]), (k, name)
+            assert np.array_equal(got[1], want[1]), k
+            for name in oracle.FINAL_DTYPE.names:
+                assert np.array_equal(got[2][name], want[2][name]), (k, name)
+            assert got[3] == want[3] > 0, k
 
 
 def test_env_golden_exercises_the_edges():

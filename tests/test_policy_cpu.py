@@ -3,31 +3,21 @@ policy_explore) compiled for the host against the numpy twin, bit for bit, on se
 twin's fmaf against exact rational arithmetic; the ABI struct, the size queries and every validation refusal; the
 controller's packing of an nn.Sequential and its refusals."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 from fractions import Fraction
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from helpers import c_abi_output, native_harness
 import policy_twin as T
 
-SRC = os.path.join(ROOT, "tests", "native", "policy_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "libpolicy_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 HMAX = 40
 P_ = lambda a, t: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(t))
 
 
 @pytest.fixture(scope="module")
 def PH():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    return C.CDLL(SO)
+    return native_harness("policy_harness")
 
 
 @pytest.fixture(scope="module")
@@ -342,12 +332,7 @@ int main(void) {
   printf("%d %d %d\n", ABR_POLICY_MAX_WINDOW, ABR_POLICY_MAX_HIDDEN, ABR_POLICY_MAX_WIDTH);
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
+    out = c_abi_output(prog)
     P = L.Policy
     got = list(map(int, out[0].split()))
     assert got == [C.sizeof(P), P.window.offset, P.n_hidden.offset, P.width.offset, P.weights_dev.offset,

@@ -2,30 +2,20 @@
 host against the numpy twin on seeded cases with their edges, the ABI struct, every validation refusal, the controller's
 arguments, and the compiled predictor kernel."""
 import ctypes as C
-import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from helpers import c_abi_output, native_harness
 from robust_twin import empty_state, estimate_scalar, estimate_vec, state_bytes, state_from_bytes, state_nbytes
 
-SRC = os.path.join(ROOT, "tests", "native", "robust_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "librobust_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 HMAX = 40
 
 
 @pytest.fixture(scope="module")
 def H():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    return C.CDLL(SO)
+    return native_harness("robust_harness")
 
 
 def _cases(rng, n):
@@ -186,12 +176,7 @@ int main(void) {
   printf("%d\n", ABR_ROBUST_MAX_WINDOW);
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
+    out = c_abi_output(prog)
     R = _lib.MpcRobust
     assert list(map(int, out[0].split())) == [C.sizeof(R), R.window.offset, R.utility.offset, R.state_dev.offset,
                                               R.state_bytes.offset, R.hist_dev.offset, R.hist_stride.offset,

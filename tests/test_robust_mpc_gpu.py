@@ -3,8 +3,6 @@
 idempotence, episodes driven through the oracle, the fused rollout against the host loop on every event-driven kernel,
 auto-reset, a robust controller after random steps, a full-size replay, and the tick refusal."""
 import ctypes as C
-import os
-from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import pytest
@@ -12,8 +10,7 @@ import torch
 
 import abrsimulator_amd as A
 from abrsimulator_amd import _lib
-from conftest import load_golden
-from helpers import make_env, oracle_rewards
+from helpers import golden_workload, make_env, oracle_env_cfg, oracle_rewards, thread_map, threads
 from robust_twin import copy_state, empty_state, select_scalar, state_bytes, state_from_bytes
 
 pytestmark = pytest.mark.gpu
@@ -38,20 +35,6 @@ class _Player:
 
     def get_next_chunk_info(self):
         return self.ci
-
-
-def _golden(N, seed=7):
-    m, g = load_golden("env_bench_shape")
-    traces = [np.asarray(t, np.float64) for t in g["traces"]]
-    rng = np.random.default_rng(seed)
-    tid = (np.arange(N) % len(traces)).astype(np.int32)
-    off = rng.integers(0, len(traces[0]), N).astype(np.int32)
-    return m, traces, tid, off
-
-
-def _ecfg(oracle, m):
-    return oracle.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"], m["start_up_length"],
-                          m["interval"], m["weights"], m.get("speed", 1.0))
 
 
 def _ocfg(oracle, m):
@@ -225,13 +208,13 @@ def test_select_twice_on_the_same_state_gives_the_same_answer(oracle):
 @pytest.mark.parametrize("window", [5, 1, 16])
 def test_episodes_match_oracle_driven_by_twin(oracle, window):
     N = 64
-    m, traces, tid, off = _golden(N)
+    m, traces, tid, off = golden_workload(N)
     V = m["video_length"]
     env, ctl = _env_ctl(m, traces, tid, off, N, window=window)
     out = env.step_mpc(ctl, V)
     acts = out["actions"].cpu().numpy()
     obs, rew, done = out["obs"].cpu().numpy(), out["reward"].cpu().numpy(), out["done"].cpu().numpy()
-    ocfg, (br, sz), cfg = _ocfg(oracle, m), _tables(m), _ecfg(oracle, m)
+    ocfg, (br, sz), cfg = _ocfg(oracle, m), _tables(m), oracle_env_cfg(oracle, m)
     steps = np.zeros((N, V), oracle.STEP_DTYPE)
     fin = np.zeros(N, oracle.FINAL_DTYPE)
     want_a = np.zeros((N, V), np.int32)
@@ -263,7 +246,7 @@ def test_episodes_match_oracle_driven_by_twin(oracle, window):
 @pytest.mark.parametrize("impl", ["jump", "split", "split3", "auto"])
 def test_fused_rollout_matches_host_loop(impl):
     N = 1000
-    m, traces, tid, off = _golden(N, seed=3)
+    m, traces, tid, off = golden_workload(N, seed=3)
     V = m["video_length"]
     env, ctl = _env_ctl(m, traces, tid, off, N, impl=impl)
     out = env.step_mpc(ctl, V)
@@ -281,7 +264,7 @@ def test_fused_rollout_matches_host_loop(impl):
 
 
 def test_auto_reset_repeats_the_first_episode():
-    m, traces, tid, off = _golden(256, seed=9)
+    m, traces, tid, off = golden_workload(256, seed=9)
     V = m["video_length"]
     env, ctl = _env_ctl(m, traces, tid, off, 256, auto_reset=True)
     out = env.step_mpc(ctl, 2 * V + 10)
@@ -293,7 +276,7 @@ def test_auto_reset_repeats_the_first_episode():
 
 def test_robust_after_random_steps_starts_with_empty_errors(oracle):
     N, k = 512, 7
-    m, traces, tid, off = _golden(N, seed=21)
+    m, traces, tid, off = golden_workload(N, seed=21)
     V = m["video_length"]
     env, ctl = _env_ctl(m, traces, tid, off, N)
     env.step_random(k, seed=99)
@@ -316,28 +299,16 @@ def test_robust_after_random_steps_starts_with_empty_errors(oracle):
 # ---------------------------------------------------------------------------------------------------------------------
 # 7.  full size
 
-def _replay(oracle, cfg, traces, tid, off, actions, threads=16):
-    N = len(tid)
-    cuts = np.linspace(0, N, threads + 1).astype(int)
-
-    def run(i):
-        lo, hi = cuts[i], cuts[i + 1]
-        return oracle.env_batch(cfg, traces, tid[lo:hi], off[lo:hi], actions[lo:hi])
-    with ThreadPoolExecutor(threads) as ex:
-        parts = list(ex.map(run, range(threads)))
-    return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]),
-            np.concatenate([p[2] for p in parts]))
-
-
 def test_full_size_replay_and_sampled_decisions(oracle):
     N = 65536
-    m, traces, tid, off = _golden(N, seed=11)
+    m, traces, tid, off = golden_workload(N, seed=11)
     V = m["video_length"]
     env, ctl = _env_ctl(m, traces, tid, off, N)
     out = env.step_mpc(ctl, V)
     acts = out["actions"].cpu().numpy()
     assert (acts >= 0).all() and len(np.unique(acts)) >= 2
-    steps, bw, fin = _replay(oracle, _ecfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+                                         threads=threads())
     obs = out["obs"].cpu().numpy()
     for s in range(V - 1):
         for r, k in ((3, "buffer_level"), (4, "global_time"), (5, "play_time"), (6, "rebuffer_time"), (2, "last_bandwidth")):
@@ -352,8 +323,7 @@ def test_full_size_replay_and_sampled_decisions(oracle):
         return np.array([max(select_scalar(oracle, ocfg, br, sz, 5, int(steps["chunk_id"][i, s]),
                                            int(steps["last_bitrate"][i, s]), float(steps["buffer_level"][i, s]),
                                            bw[i], st, 0)[0], 0) for s in range(V)])
-    with ThreadPoolExecutor(16) as ex:
-        want = np.stack(list(ex.map(lane, sample)), 1)
+    want = np.stack(thread_map(lane, sample), 1)
     assert np.array_equal(acts[:, sample], want)
 
 
@@ -361,7 +331,7 @@ def test_full_size_replay_and_sampled_decisions(oracle):
 # 8.  refusals
 
 def test_tick_kernel_is_refused():
-    m, traces, tid, off = _golden(64)
+    m, traces, tid, off = golden_workload(64)
     env, ctl = _env_ctl(m, traces, tid, off, 64, impl="tick")
     with pytest.raises(_lib.AbrError, match="-4"):
         env.step_mpc(ctl, 2)
@@ -369,7 +339,7 @@ def test_tick_kernel_is_refused():
 
 
 def test_state_follows_lane_count_and_window():
-    m, traces, tid, off = _golden(128)
+    m, traces, tid, off = golden_workload(128)
     env, ctl = _env_ctl(m, traces, tid, off, 128)
     env.step_mpc(ctl, 3)
     sd = ctl.state_dict()

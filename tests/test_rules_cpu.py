@@ -6,27 +6,20 @@ import os
 import re
 import shutil
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import c_abi_output, native_harness
 from rules_twin import BOLA, BUFFER, RATE, rule_scalar, rule_vec
 
-SRC = os.path.join(ROOT, "tests", "native", "rules_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "librules_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 HMAX = 64
 
 
 @pytest.fixture(scope="module")
 def H():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    return C.CDLL(SO)
+    return native_harness("rules_harness")
 
 
 def _cases(rng, n, kind):
@@ -168,12 +161,7 @@ int main(void) {
   printf("%d %d %d\n", ABR_RULE_BUFFER, ABR_RULE_RATE, ABR_RULE_BOLA);
   return 0;
 }'''
-    with tempfile.TemporaryDirectory() as td:
-        c = os.path.join(td, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(td, "t")
-        subprocess.check_call(["gcc", "-std=c11", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        out = subprocess.check_output([exe]).decode().split("\n")
+    out = c_abi_output(prog)
     R = _lib.RuleConfig
     assert list(map(int, out[0].split())) == [C.sizeof(R), R.kind.offset, R.window.offset, R.reservoir.offset,
                                               R.cushion.offset, R.safety.offset, R.bola_v.offset, R.bola_gp.offset,

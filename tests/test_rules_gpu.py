@@ -1,16 +1,12 @@
 """The bitrate rules on the device (abr_env_step_rule / abr_env_rule_select): episodes against the C oracle driven by the
 numpy twin (tests/rules_twin.py), full-size replays, the fused rollout against the host-driven loop and a script, the
 tick kernel as a cross-check, auto-reset, per-chunk ladders, per-lane speeds, mixed policies, frozen lanes, refusals."""
-import os
-from concurrent.futures import ThreadPoolExecutor
-
 import numpy as np
 import pytest
 import torch
 
 import abrsimulator_amd as A
-from conftest import load_golden
-from helpers import make_env, oracle_rewards
+from helpers import golden_workload, make_env, oracle_env_cfg, oracle_rewards, threads
 from rules_twin import params_of, rule_scalar, rule_vec
 
 pytestmark = pytest.mark.gpu
@@ -26,20 +22,6 @@ CLS = {"buffer": A.BufferBasedController, "rate": A.RateBasedController, "bola":
 F64_FINAL = ["global_time", "rebuffer_time", "start_up_time", "play_time", "buffer_level"]
 
 
-def _golden(N, seed=7):
-    m, g = load_golden("env_bench_shape")
-    traces = [np.asarray(t, np.float64) for t in g["traces"]]
-    rng = np.random.default_rng(seed)
-    tid = (np.arange(N) % len(traces)).astype(np.int32)
-    off = rng.integers(0, len(traces[0]), N).astype(np.int32)
-    return m, traces, tid, off
-
-
-def _cfg(oracle, m, br_table=None):
-    return oracle.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"], m["start_up_length"],
-                          m["interval"], m["weights"], m.get("speed", 1.0), br_table=br_table)
-
-
 def _ctl(env, kind, kw):
     return CLS[kind](A.EnvPlayer(env), **kw)
 
@@ -48,24 +30,6 @@ def _rows(ctl, c, table):
     """Each lane's chunk-c bitrates and utilities for the vectorised twin."""
     c = np.minimum(np.asarray(c), table.shape[0] - 1)
     return table[c], (ctl.utility[c] if hasattr(ctl, "utility") else None)
-
-
-def _replay(oracle, cfg, traces, tid, off, actions, speeds=None, threads=None):
-    """oracle.env_batch over lane slices on a thread pool (ctypes releases the GIL)."""
-    N = len(tid)
-    threads = threads or min(16, os.cpu_count() or 1)
-    cuts = np.linspace(0, N, threads + 1).astype(int)
-
-    def run(i):
-        lo, hi = cuts[i], cuts[i + 1]
-        return oracle.env_batch(cfg, traces, tid[lo:hi], off[lo:hi], actions[lo:hi],
-                                speeds=None if speeds is None else speeds[lo:hi])
-    with ThreadPoolExecutor(threads) as ex:
-        parts = list(ex.map(run, range(threads)))
-    steps = np.concatenate([p[0] for p in parts])
-    bw = np.concatenate([p[1] for p in parts])
-    fin = np.concatenate([p[2] for p in parts])
-    return steps, bw, fin
 
 
 def _twin_over_replay(ctl, steps, bw, table, s0=0):
@@ -85,7 +49,7 @@ def _table(m, V):
 
 @pytest.mark.parametrize("kind,kw", RULES)
 def test_episodes_match_oracle_driven_by_twin(oracle, kind, kw):
-    m, traces, tid, off = _golden(256)
+    m, traces, tid, off = golden_workload(256)
     N, V = 256, m["video_length"]
     env = make_env(m, traces, N)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -94,7 +58,7 @@ def test_episodes_match_oracle_driven_by_twin(oracle, kind, kw):
     acts = out["actions"].cpu().numpy()
     obs, rew, done = out["obs"].cpu().numpy(), out["reward"].cpu().numpy(), out["done"].cpu().numpy()
     p, table = params_of(ctl), _table(m, V)
-    cfg = _cfg(oracle, m)
+    cfg = oracle_env_cfg(oracle, m)
     steps = np.zeros((N, V), oracle.STEP_DTYPE)
     fin = np.zeros(N, oracle.FINAL_DTYPE)
     want_a = np.zeros((N, V), np.int32)
@@ -122,7 +86,7 @@ def test_episodes_match_oracle_driven_by_twin(oracle, kind, kw):
 @pytest.mark.parametrize("kind", ["buffer", "rate", "bola"])
 def test_full_size_replay(oracle, kind):
     N = 65536
-    m, traces, tid, off = _golden(N, seed=11)
+    m, traces, tid, off = golden_workload(N, seed=11)
     V = m["video_length"]
     env = make_env(m, traces, N)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -130,7 +94,8 @@ def test_full_size_replay(oracle, kind):
     out = env.step_rule(ctl, V)
     acts = out["actions"].cpu().numpy()
     assert (acts >= 0).all() and len(np.unique(acts)) >= 3
-    steps, bw, fin = _replay(oracle, _cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+                                         threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, steps, bw, _table(m, V)), acts)
     obs = out["obs"].cpu().numpy()
     for s in range(V - 1):
@@ -153,7 +118,7 @@ def _same_state(a, b):
 
 @pytest.mark.parametrize("kind,kw", [RULES[1], RULES[3], RULES[5]])
 def test_fused_equals_host_loop_and_script(kind, kw):
-    m, traces, tid, off = _golden(1024, seed=3)
+    m, traces, tid, off = golden_workload(1024, seed=3)
     N, n = 1024, 20
     envs = [make_env(m, traces, N) for _ in range(3)]
     for e in envs:
@@ -176,7 +141,7 @@ def test_fused_equals_host_loop_and_script(kind, kw):
 
 @pytest.mark.parametrize("kind,kw", RULES)
 def test_jump_equals_tick(kind, kw):
-    m, traces, tid, off = _golden(512, seed=5)
+    m, traces, tid, off = golden_workload(512, seed=5)
     outs = []
     for impl in ("jump", "tick"):
         env = make_env(m, traces, 512, impl=impl)
@@ -190,7 +155,7 @@ def test_jump_equals_tick(kind, kw):
 
 @pytest.mark.parametrize("kind", ["buffer", "rate", "bola"])
 def test_auto_reset_repeats_the_first_episode(kind):
-    m, traces, tid, off = _golden(256, seed=9)
+    m, traces, tid, off = golden_workload(256, seed=9)
     V = m["video_length"]
     env = make_env(m, traces, 256, auto_reset=True)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -205,7 +170,7 @@ def test_auto_reset_repeats_the_first_episode(kind):
 
 @pytest.mark.parametrize("kind", ["buffer", "rate", "bola"])
 def test_per_chunk_bitrate_table(oracle, kind):
-    m, traces, tid, off = _golden(128, seed=13)
+    m, traces, tid, off = golden_workload(128, seed=13)
     V, N = m["video_length"], 128
     rng = np.random.default_rng(2)
     table = np.sort(np.asarray(m["ladder"]) * rng.uniform(0.7, 1.3, (V, 1)) * rng.uniform(0.9, 1.1, (V, 6)), axis=1)
@@ -215,7 +180,7 @@ def test_per_chunk_bitrate_table(oracle, kind):
     ctl = _ctl(env, kind, VARIED[kind])
     out = env.step_rule(ctl, V)
     acts = out["actions"].cpu().numpy()
-    cfg = _cfg(oracle, m, br_table=table)
+    cfg = oracle_env_cfg(oracle, m, br_table=table)
     p = params_of(ctl)
     gt = env.observe_f64()["global_time"].cpu().numpy()
     for i in range(N):
@@ -228,7 +193,7 @@ def test_per_chunk_bitrate_table(oracle, kind):
 
 @pytest.mark.parametrize("kind", ["buffer", "rate", "bola"])
 def test_per_lane_speeds(oracle, kind):
-    m, traces, tid, off = _golden(512, seed=17)
+    m, traces, tid, off = golden_workload(512, seed=17)
     V, N = m["video_length"], 512
     speeds = np.random.default_rng(4).uniform(0.8, 1.3, N)
     env = make_env(dict(m, speed=torch.from_numpy(speeds)), traces, N)
@@ -236,7 +201,8 @@ def test_per_lane_speeds(oracle, kind):
     ctl = _ctl(env, kind, VARIED[kind])
     out = env.step_rule(ctl, V)
     acts = out["actions"].cpu().numpy()
-    steps, bw, fin = _replay(oracle, _cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T), speeds=speeds)
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+                                         speeds=speeds, threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, steps, bw, _table(m, V)), acts)
     obs = out["obs"].cpu().numpy()
     for s in range(V - 1):
@@ -246,7 +212,7 @@ def test_per_lane_speeds(oracle, kind):
 
 
 def test_random_then_rule_sees_the_random_history(oracle):
-    m, traces, tid, off = _golden(512, seed=19)
+    m, traces, tid, off = golden_workload(512, seed=19)
     V, N, k = m["video_length"], 512, 7
     env = make_env(m, traces, N)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
@@ -254,7 +220,8 @@ def test_random_then_rule_sees_the_random_history(oracle):
     ctl = _ctl(env, "rate", dict(window=10))
     out = env.step_rule(ctl, V - k)
     acts = np.concatenate([r["actions"].cpu().numpy(), out["actions"].cpu().numpy()])
-    steps, bw, fin = _replay(oracle, _cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+                                         threads=threads())
     assert np.array_equal(_twin_over_replay(ctl, steps, bw, _table(m, V), s0=k), acts[k:])
     want = oracle_rewards(steps, fin, acts.T, m["weights"], ladder=m["ladder"])
     assert np.array_equal(out["reward"].cpu().numpy(), want.T[k:])
@@ -262,7 +229,7 @@ def test_random_then_rule_sees_the_random_history(oracle):
 
 
 def test_frozen_lanes_and_refusals():
-    m, traces, tid, off = _golden(256, seed=23)
+    m, traces, tid, off = golden_workload(256, seed=23)
     tid = tid.copy()
     tid[::5] = 99                                       # out of range: frozen with ABR_DONE_BADARG
     env = make_env(m, traces, 256)

@@ -7,28 +7,21 @@
 - The ctypes mirror of the struct, and every refusal of abr_env_set_speed_rule that needs no handle."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import ROOT
+from helpers import native_harness
 from speed_twin import rule_np, twin_batch
 
-SRC = os.path.join(ROOT, "tests", "native", "speed_rule_harness.cpp")
-SO = os.path.join(ROOT, "tests", "native", "libspeed_rule_harness.so")
-INC = os.path.join(ROOT, "abrsimulator_amd", "csrc")
 LADDER = [0.3, 0.75, 1.2, 1.85, 2.85, 4.3]
 ABR_E_INVALID = -1           # include/abr_env.h
 
 
 @pytest.fixture(scope="module")
 def H():
-    deps = [SRC] + [os.path.join(INC, f) for f in ("abr_lane_jump.h", "abr_exact_jump.h", "abr_tick_tables.h")]
-    if not os.path.exists(SO) or os.path.getmtime(SO) < max(os.path.getmtime(d) for d in deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off",
-                               "-fno-fast-math", "-I", INC, SRC, "-o", SO])
-    lib = C.CDLL(SO)
+    lib = native_harness("speed_rule_harness")
     lib.sr_batch.restype = C.c_int64
     return lib
 

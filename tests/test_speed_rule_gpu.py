@@ -9,7 +9,7 @@ import torch
 
 import abrsimulator_amd as A
 from abrsimulator_amd import _lib
-from helpers import make_env
+from helpers import make_env, oracle_env_cfg
 from speed_twin import rule_arrays, twin_batch
 
 pytestmark = pytest.mark.gpu
@@ -27,11 +27,6 @@ def _workload(N, seed=5, V=12, max_buffer=12.0, start_up=4.0):
     tid = rng.integers(0, 8, N).astype(np.int32)
     off = rng.integers(0, 800, N).astype(np.int32)
     return meta, traces, tid, off
-
-
-def _cfg(oracle, m, br_table=None):
-    return oracle.env_cfg(m["ladder"], m["chunk_length"], m["video_length"], m["max_buffer"], m["start_up_length"],
-                          m["interval"], m["weights"], 1.0, br_table=br_table)
 
 
 def _env(m, traces, N, ctl=CTL, rows=None, **kw):
@@ -111,7 +106,7 @@ def test_rollouts_match_twin_and_oracle_replay(oracle, impl, kind):
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     acts, frames = _rollout(env, kind, V, chunk=5)
     log = env.speed_log()
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
                                          speeds=_sched(log))
     _check_frames(frames, steps, fin, V)
     assert np.allclose(env.episode_qoe().cpu().numpy(), fin["qoe"], rtol=1e-9)
@@ -144,7 +139,7 @@ def test_auto_reset_logs_the_current_episode(oracle, impl):
     a2 = env.step_random(V, 7)["actions"].cpu().numpy()
     q2 = env.episode_qoe().cpu().numpy()
     for a, q, log in ((a1, q1, log1), (a2, q2, env.speed_log())):
-        steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
+        steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
                                              speeds=_sched(log))
         assert np.allclose(q, fin["qoe"], rtol=1e-9)
     _check_twin(m, traces, tid, off, a2, env.speed_log(), n=16)
@@ -162,7 +157,7 @@ def test_per_chunk_ladders_with_a_rule(oracle):
     env.set_speed_controller(CTL, log_rows=V + 4)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     acts, frames = _rollout(env, "mpc", V, chunk=4)
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m, br_table=table), traces, tid, off,
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m, br_table=table), traces, tid, off,
                                          np.ascontiguousarray(acts.T), speeds=_sched(env.speed_log()))
     _check_frames(frames, steps, fin, V)
     assert np.allclose(env.episode_qoe().cpu().numpy(), fin["qoe"], rtol=1e-9)
@@ -183,7 +178,7 @@ def test_checkpoint_mid_episode_resumes_in_a_fresh_handle(oracle):
     env2.load_state_dict(sd)
     a2 = env2.step_random(V - 5, 4)["actions"].cpu().numpy()
     acts = np.concatenate([a1, a2])
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(acts.T),
                                          speeds=_sched(env2.speed_log()))
     f = env2.observe_f64()
     for k in FRAME:
@@ -200,14 +195,14 @@ def test_latching_and_last_setter_wins(oracle):
     # armed handle: the rule waits for the next full reset
     env.set_speed_controller(CTL, log_rows=V + 4)
     a = env.step_random(V, 5)["actions"].cpu().numpy()
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T))
     assert np.array_equal(env.observe_f64()["global_time"].cpu().numpy(), fin["global_time"])
     assert not env.speed_log().any()
     with pytest.raises(_lib.AbrError):                    # a partial reset cannot adopt it
         env.reset(torch.from_numpy(tid), torch.from_numpy(off), mask=torch.ones(N, dtype=torch.uint8))
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     a = env.step_random(V, 5)["actions"].cpu().numpy()
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
                                          speeds=_sched(env.speed_log()))
     assert np.array_equal(env.observe_f64()["global_time"].cpu().numpy(), fin["global_time"])
     assert env.speed_log().any()
@@ -216,14 +211,14 @@ def test_latching_and_last_setter_wins(oracle):
     assert env.lib.abr_env_set_speed_schedule(env._h, _lib.ptr(sched), 3) == 0
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     a = env.step_random(V, 6)["actions"].cpu().numpy()
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T),
                                          speeds=np.full((N, 3), 1.25))
     assert np.array_equal(env.observe_f64()["play_time"].cpu().numpy(), fin["play_time"])
     # rule == NULL restores the config speed
     env.set_speed_controller(None)
     env.reset(torch.from_numpy(tid), torch.from_numpy(off))
     a = env.step_random(V, 6)["actions"].cpu().numpy()
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T))
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid, off, np.ascontiguousarray(a.T))
     assert np.array_equal(env.observe_f64()["play_time"].cpu().numpy(), fin["play_time"])
 
 
@@ -257,7 +252,7 @@ def test_large_run_sampled_lanes_replayed(oracle):
     f = env.observe_f64()
     pick = np.random.default_rng(0).choice(N, 2048, replace=False)
     log = env.speed_log()[:, torch.from_numpy(pick).cuda()]
-    steps, bw, fin, _ = oracle.env_batch(_cfg(oracle, m), traces, tid[pick], off[pick],
+    steps, bw, fin, _ = oracle.env_batch(oracle_env_cfg(oracle, m), traces, tid[pick], off[pick],
                                          np.ascontiguousarray(acts.T[pick]), speeds=_sched(log))
     for k in FRAME:
         assert np.array_equal(f[k].cpu().numpy()[pick], fin[k]), k
