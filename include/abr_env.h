@@ -160,8 +160,10 @@ int abr_env_set_lane_speeds(abr_env *env, const double *speeds_dev);   /* latche
 /* What a speed controller answers, call by call (Simulator.py:176-177: get_next_speed() is
  * asked at the first playing tick of every played chunk, i.e. whenever play_length == 0).
  * speeds_dev: float64 [n_rows][n_lanes]; the p-th played chunk of lane i plays at
- * speeds_dev[min(p, n_rows - 1) * n_lanes + i] (the last row repeats).  n_rows == 1 is
- * abr_env_set_lane_speeds.  Same lifetime and latching rules.  Event-driven kernels only. */
+ * speeds_dev[min(p, n_rows - 1) * n_lanes + i] (the last row repeats).  p counts the played chunks
+ * of the lane's current episode: every reset of the lane (masked or not) and every auto_reset
+ * re-arm starts it again at row 0.  n_rows == 1 is abr_env_set_lane_speeds.  Same lifetime and
+ * latching rules.  Event-driven kernels only. */
 int abr_env_set_speed_schedule(abr_env *env, const double *speeds_dev, int32_t n_rows);
 
 /* A closed-loop speed controller (ABI 4, additive; BUILD-DEFINED: the reference ships no speed
@@ -192,7 +194,8 @@ typedef struct abr_speed_rule {
  * value: the caller's struct may go right after the call.  speed_log_dev: NULL, or caller-owned float64
  * [log_rows][n_lanes] (same lifetime rules as speeds_dev above): row p receives the speed answered for
  * played chunk p of the lane's current episode, for p < log_rows; rows never reached keep what they
- * held.  A bad field (or log_rows < 0, or log_rows > 0 without a log) is ABR_E_INVALID before anything is
+ * held.  A reset of the lane (masked or not) and an auto_reset re-arm start its log over at row 0, so
+ * the rows past the current episode's last answer hold what earlier episodes wrote there.  A bad field (or log_rows < 0, or log_rows > 0 without a log) is ABR_E_INVALID before anything is
  * stored, and the struct is checked before the handle.  Impl 0, 2, 3 and 5 only: ABR_E_UNSUPPORTED on 1 (tick) and
  * on the diagnostic pipelines 4, 6 and 7, and abr_env_set_impl refuses those while a rule is set or pending. */
 int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, double *speed_log_dev, int32_t log_rows);
@@ -329,7 +332,10 @@ int abr_env_step_script(abr_env *env, int32_t n_steps, const int32_t *actions_de
 
 /* calculate_qoe (Simulator.py:79-86) in the reference's operation order from the
  * lane's action history; meaningful for lanes whose episode is complete (with
- * auto_reset: the last completed episode).  qoe_out_dev: float64 [n_lanes]. */
+ * auto_reset: the last completed episode).  qoe_out_dev: float64 [n_lanes].
+ * An episode cut by a masked reset is never complete: with auto_reset the answer stays the last
+ * completed episode's; without it the variance term reads the action history, which the new
+ * episode overwrites as it goes, so the answer is meaningful again once that episode has ended. */
 int abr_env_episode_qoe(abr_env *env, double *qoe_out_dev, void *stream);
 
 /* Full float64 observation, [ABR_F64_DIM][n_lanes]. */

@@ -47,6 +47,21 @@ typedef struct {
     int64_t speed_stride;
 } oracle_env_cfg;
 
+/* A closed-loop speed rule (include/abr_env.h: abr_speed_rule; tests/speed_twin.py), given to the *_rule entry points
+ * beside the config, whose layout it leaves alone.  It replaces both speed modes of the config.  At each
+ * get_next_speed() call (:176-177), with lat = global_time - play_time (:179, before this tick's += speed*dt) and the
+ * buffer level after :170 and before :184:
+ *   i = #{q < n_lat: lat >= lat_thr[q]}, j = #{r < n_buf: buf >= buf_thr[r]}
+ * and the chunk plays at speed[i * (n_buf + 1) + j].  Answer p goes to log[p] for p < log_rows (log may be NULL);
+ * *calls_out (nullable) receives the number of answers of the episode. */
+typedef struct {
+    int32_t n_lat, n_buf;
+    const double *lat_thr, *buf_thr, *speed;
+    double *log;
+    int32_t log_rows;
+    int32_t *calls_out;
+} oracle_speed_rule;
+
 static inline double chunk_bitrate(const oracle_env_cfg *c, int chunk, int rate) {
     return c->br_table ? c->br_table[(size_t)chunk * c->n_rates + rate] : c->ladder[rate];
 }
@@ -83,8 +98,8 @@ static inline double pymax0(double x) { return (x > 0) ? x : 0.0; }
  * steps[video_length], bw_out[video_length] (measured throughputs) may be NULL.
  * max_ticks: safety bound (returns -2 when hit).
  */
-int oracle_env_episode(const oracle_env_cfg *c, const double *trace, int32_t trace_len,
-                       int32_t offset, const int32_t *actions, oracle_policy_fn policy,
+static int env_episode(const oracle_env_cfg *c, const oracle_speed_rule *rule, const double *trace,
+                       int32_t trace_len, int32_t offset, const int32_t *actions, oracle_policy_fn policy,
                        void *ctx, oracle_step_rec *steps, double *bw_out, int32_t *act_out,
                        oracle_final_rec *fin, int64_t max_ticks)
 {
@@ -158,7 +173,15 @@ int oracle_env_episode(const oracle_env_cfg *c, const double *trace, int32_t tra
         /* :174-187 */
         if (!play_pause) {
             if (play_length == 0) {                                                        /* :176-177 */
-                if (c->speed_sched) {
+                if (rule) {
+                    double lat = global_time - play_time;
+                    int li = 0, bi = 0;
+                    for (int q = 0; q < rule->n_lat; q++) li += lat >= rule->lat_thr[q];
+                    for (int r = 0; r < rule->n_buf; r++) bi += buffer_level >= rule->buf_thr[r];
+                    play_speed = rule->speed[li * (rule->n_buf + 1) + bi];
+                    if (rule->log && speed_calls < rule->log_rows) rule->log[speed_calls] = play_speed;
+                    speed_calls++;
+                } else if (c->speed_sched) {
                     int row = speed_calls < c->speed_rows ? speed_calls : c->speed_rows - 1;
                     play_speed = c->speed_sched[(size_t)row * c->speed_stride];
                     speed_calls++;
@@ -185,6 +208,7 @@ int oracle_env_episode(const oracle_env_cfg *c, const double *trace, int32_t tra
         if (chunk_id >= V) simulation_end = 1;
     }
 
+    if (rc == 0 && rule && rule->calls_out) *rule->calls_out = speed_calls;
     if (rc == 0 && fin) {
         /* calculate_qoe, Simulator.py:79-86 */
         double variance = 0;
@@ -205,6 +229,26 @@ int oracle_env_episode(const oracle_env_cfg *c, const double *trace, int32_t tra
     free(previous_bandwidths);
     free(previous_bitrates);
     return rc;
+}
+
+int oracle_env_episode(const oracle_env_cfg *c, const double *trace, int32_t trace_len,
+                       int32_t offset, const int32_t *actions, oracle_policy_fn policy,
+                       void *ctx, oracle_step_rec *steps, double *bw_out, int32_t *act_out,
+                       oracle_final_rec *fin, int64_t max_ticks)
+{
+    return env_episode(c, NULL, trace, trace_len, offset, actions, policy, ctx, steps, bw_out, act_out, fin,
+                       max_ticks);
+}
+
+/* One episode under a speed rule (rule != NULL): as oracle_env_episode otherwise. */
+int oracle_env_episode_rule(const oracle_env_cfg *c, const oracle_speed_rule *rule, const double *trace,
+                            int32_t trace_len, int32_t offset, const int32_t *actions, oracle_policy_fn policy,
+                            void *ctx, oracle_step_rec *steps, double *bw_out, int32_t *act_out,
+                            oracle_final_rec *fin, int64_t max_ticks)
+{
+    if (!rule) return -1;
+    return env_episode(c, rule, trace, trace_len, offset, actions, policy, ctx, steps, bw_out, act_out, fin,
+                       max_ticks);
 }
 
 /* Batch helper: n_lanes independent replay episodes (lane i uses
@@ -279,6 +323,34 @@ int64_t oracle_env_batch_sched(const oracle_env_cfg *c, const double *traces,
                                     actions + (size_t)i * V, NULL, NULL,
                                     steps ? steps + (size_t)i * V : NULL,
                                     bw_out ? bw_out + (size_t)i * V : NULL, NULL, &f, max_ticks);
+        if (rc) return rc;
+        if (fin) fin[i] = f;
+        total += f.ticks;
+    }
+    return total;
+}
+
+/* Same, with the speed rule `rule` on every lane: rule->log is NULL or [n_lanes][rule->log_rows], lane i's answers
+ * in order; rule->calls_out NULL or [n_lanes], the number of answers of each episode. */
+int64_t oracle_env_batch_rule(const oracle_env_cfg *c, const oracle_speed_rule *rule, const double *traces,
+                              const int64_t *trace_off, const int32_t *trace_len,
+                              const int32_t *trace_id, const int32_t *offset,
+                              const int32_t *actions, int32_t n_lanes, oracle_step_rec *steps,
+                              double *bw_out, oracle_final_rec *fin, int64_t max_ticks)
+{
+    const int V = c->video_length;
+    int64_t total = 0;
+    if (!rule) return -1;
+    for (int32_t i = 0; i < n_lanes; i++) {
+        oracle_speed_rule ri = *rule;
+        ri.log = rule->log ? rule->log + (size_t)i * rule->log_rows : NULL;
+        ri.calls_out = rule->calls_out ? rule->calls_out + i : NULL;
+        oracle_final_rec f;
+        int t = trace_id[i];
+        int rc = env_episode(c, &ri, traces + trace_off[t], trace_len[t], offset[i],
+                             actions + (size_t)i * V, NULL, NULL,
+                             steps ? steps + (size_t)i * V : NULL,
+                             bw_out ? bw_out + (size_t)i * V : NULL, NULL, &f, max_ticks);
         if (rc) return rc;
         if (fin) fin[i] = f;
         total += f.ticks;

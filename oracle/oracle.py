@@ -25,6 +25,12 @@ class EnvCfg(C.Structure):
                 ("speed_sched", C.c_void_p), ("speed_rows", C.c_int32), ("speed_stride", C.c_int64)]
 
 
+class SpeedRule(C.Structure):
+    """abr_oracle.c: oracle_speed_rule (given beside the config to the *_rule entry points)."""
+    _fields_ = [("n_lat", C.c_int32), ("n_buf", C.c_int32), ("lat_thr", C.c_void_p), ("buf_thr", C.c_void_p),
+                ("speed", C.c_void_p), ("log", C.c_void_p), ("log_rows", C.c_int32), ("calls_out", C.c_void_p)]
+
+
 class MpcCfg(C.Structure):
     _fields_ = [("n_rates", C.c_int32), ("horizon", C.c_int32), ("video_length", C.c_int32),
                 ("_pad", C.c_int32), ("chunk_length", C.c_double), ("max_buffer", C.c_double),
@@ -61,6 +67,7 @@ def lib():
         _LIB.oracle_env_batch_speeds.restype = C.c_int64
         _LIB.oracle_env_batch_mpc.restype = C.c_int64
         _LIB.oracle_env_batch_sched.restype = C.c_int64
+        _LIB.oracle_env_batch_rule.restype = C.c_int64
         _LIB.oracle_mpc_brute.restype = C.c_int64
         _LIB.oracle_mpc_objective.restype = C.c_double
         assert STEP_DTYPE.itemsize == 96 and FINAL_DTYPE.itemsize == 72
@@ -69,6 +76,24 @@ def lib():
 
 def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
+
+
+def speed_rule(rule, log=None, calls=None):
+    """A SpeedRule struct from (lat_thr, buf_thr, speeds [n_lat+1, n_buf+1]); log: None or float64 [..., rows] (rows
+    per episode), calls: None or int32.  The arrays are kept alive on the struct."""
+    lat, buf, tab = (np.ascontiguousarray(x, np.float64) for x in rule)
+    assert tab.shape == (len(lat) + 1, len(buf) + 1)
+    r = SpeedRule()
+    r._keep = (lat, buf, tab)
+    r.n_lat, r.n_buf = len(lat), len(buf)
+    r.lat_thr, r.buf_thr, r.speed = lat.ctypes.data, buf.ctypes.data, tab.ctypes.data
+    if log is not None:
+        assert log.dtype == np.float64 and log.flags.c_contiguous
+        r.log, r.log_rows = log.ctypes.data, log.shape[-1]
+    if calls is not None:
+        assert calls.dtype == np.int32 and calls.flags.c_contiguous
+        r.calls_out = calls.ctypes.data
+    return r
 
 
 def env_cfg(ladder, chunk_length, video_length, max_buffer, start_up_length, interval,
@@ -100,10 +125,14 @@ def pack_traces(traces):
 
 
 def env_batch(cfg, traces, trace_id, offset, actions, max_ticks=1 << 40, speeds=None,
-              want_steps=True, threads=1):
+              want_steps=True, threads=1, rule=None, speed_log_out=None, speed_calls_out=None):
     """Replay episodes. traces: list of arrays. actions: [N, V] int32.  speeds: optional
     per-lane constant play speeds [N] (default: cfg.speed for every lane), or per-lane speed
     SCHEDULES [N, rows]: the answers to each lane's successive get_next_speed() calls.
+    rule: optional (lat_thr, buf_thr, speeds [n_lat+1, n_buf+1]), a speed rule evaluated at every
+    get_next_speed() call of every lane (abr_oracle.c: oracle_speed_rule; excludes `speeds`); its answers
+    go to speed_log_out (float64 [N, rows], rows past a lane's last answer untouched) and their
+    number to speed_calls_out (int32 [N]), both optional and written in place.
     Returns (steps[N,V] STEP_DTYPE, bw[N,V], final[N] FINAL_DTYPE, total_ticks).  threads > 1
     splits the lanes over a thread pool (ctypes releases the GIL)."""
     trace_id = np.ascontiguousarray(trace_id, np.int32)
@@ -111,6 +140,10 @@ def env_batch(cfg, traces, trace_id, offset, actions, max_ticks=1 << 40, speeds=
     actions = np.ascontiguousarray(actions, np.int32)
     N, V = actions.shape
     threads = min(threads, N)
+    if rule is not None:
+        assert speeds is None, "a speed rule replaces `speeds`"
+        for a in (speed_log_out, speed_calls_out):
+            assert a is None or (a.flags.c_contiguous and a.shape[0] == N)
     if threads > 1:
         from concurrent.futures import ThreadPoolExecutor
         cuts = np.linspace(0, N, threads + 1).astype(int)
@@ -118,7 +151,9 @@ def env_batch(cfg, traces, trace_id, offset, actions, max_ticks=1 << 40, speeds=
         def run(i):
             s = slice(cuts[i], cuts[i + 1])
             return env_batch(cfg, traces, trace_id[s], offset[s], actions[s], max_ticks,
-                             None if speeds is None else speeds[s], want_steps)
+                             None if speeds is None else speeds[s], want_steps, rule=rule,
+                             speed_log_out=None if speed_log_out is None else speed_log_out[s],
+                             speed_calls_out=None if speed_calls_out is None else speed_calls_out[s])
         with ThreadPoolExecutor(threads) as ex:
             parts = list(ex.map(run, range(threads)))
         cat = lambda k: None if parts[0][k] is None else np.concatenate([p[k] for p in parts])
@@ -129,7 +164,13 @@ def env_batch(cfg, traces, trace_id, offset, actions, max_ticks=1 << 40, speeds=
     bw = np.zeros((N, V), np.float64)
     fin = np.zeros(N, FINAL_DTYPE)
     sp = steps.ctypes.data_as(C.c_void_p) if want_steps else None
-    if speeds is not None and np.ndim(speeds) == 2:
+    if rule is not None:
+        r = speed_rule(rule, speed_log_out, speed_calls_out)
+        rc = lib().oracle_env_batch_rule(
+            C.byref(cfg), C.byref(r), _p(flat, C.c_double), _p(off, C.c_int64), _p(lens, C.c_int32),
+            _p(trace_id, C.c_int32), _p(offset, C.c_int32), _p(actions, C.c_int32), C.c_int32(N), sp,
+            _p(bw, C.c_double), fin.ctypes.data_as(C.c_void_p), C.c_int64(max_ticks))
+    elif speeds is not None and np.ndim(speeds) == 2:
         speeds = np.ascontiguousarray(speeds, np.float64)
         assert speeds.shape[0] == N
         rc = lib().oracle_env_batch_sched(
@@ -198,8 +239,10 @@ def env_batch_mpc(cfg, mcfg, br, sz, traces, trace_id, offset, max_ticks=1 << 40
 POLICY_FN = C.CFUNCTYPE(C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_double), C.c_int32)
 
 
-def env_episode_policy(cfg, trace, offset, policy, max_ticks=1 << 40):
-    """One episode driven by a Python callback policy(obs_record, prev_bw_array) -> int."""
+def env_episode_policy(cfg, trace, offset, policy, max_ticks=1 << 40, rule=None, speed_log_out=None,
+                       speed_calls_out=None):
+    """One episode driven by a Python callback policy(obs_record, prev_bw_array) -> int.  rule / speed_log_out
+    (float64 [rows]) / speed_calls_out (int32 [1]): a speed rule, as env_batch."""
     trace = np.ascontiguousarray(trace, np.float64)
     V = cfg.video_length
     steps = np.zeros(V, STEP_DTYPE)
@@ -213,10 +256,14 @@ def env_episode_policy(cfg, trace, offset, policy, max_ticks=1 << 40):
         hist = np.ctypeslib.as_array(bw_ptr, shape=(n,)).copy() if n else np.zeros(0)
         return int(policy(obs, hist))
 
-    rc = lib().oracle_env_episode(
-        C.byref(cfg), _p(trace, C.c_double), C.c_int32(len(trace)), C.c_int32(int(offset)),
-        None, POLICY_FN(cb), None, steps.ctypes.data_as(C.c_void_p), _p(bw, C.c_double),
-        _p(acts, C.c_int32), fin.ctypes.data_as(C.c_void_p), C.c_int64(max_ticks))
+    if rule is None:
+        fn, head = lib().oracle_env_episode, (C.byref(cfg),)
+    else:
+        r = speed_rule(rule, speed_log_out, speed_calls_out)
+        fn, head = lib().oracle_env_episode_rule, (C.byref(cfg), C.byref(r))
+    rc = fn(*head, _p(trace, C.c_double), C.c_int32(len(trace)), C.c_int32(int(offset)),
+            None, POLICY_FN(cb), None, steps.ctypes.data_as(C.c_void_p), _p(bw, C.c_double),
+            _p(acts, C.c_int32), fin.ctypes.data_as(C.c_void_p), C.c_int64(max_ticks))
     if rc:
         raise RuntimeError(f"oracle_env_episode failed: {rc}")
     return steps, bw, acts, fin[0]

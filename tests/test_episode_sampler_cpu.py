@@ -11,6 +11,7 @@ import pytest
 from conftest import ROOT
 from helpers import c_abi_output, native_harness
 import policy_twin as T
+from sampler_twin import twin
 
 P_ = lambda a, t: np.ascontiguousarray(a).ctypes.data_as(C.POINTER(t))
 M32 = (1 << 32) - 1
@@ -26,22 +27,6 @@ def L():
     from abrsimulator_amd import _lib
     _lib.build()
     return _lib
-
-
-def twin(seed, lanes, eps, trace_len, pool=None, span=0):
-    """The contract, written out from include/abr_env.h with policy_twin.philox4 and Python integers."""
-    w0, w1, _, _ = T.philox4(seed, np.asarray(lanes, np.uint64), 0xFFFFFFFF, np.asarray(eps, np.uint64))
-    tl = np.asarray(trace_len, np.int64)
-    n = len(pool) if pool is not None else len(tl)
-    t_out, off_out = [], []
-    for a, b in zip(w0.tolist(), w1.tolist()):
-        u = (a * n) >> 32
-        t = int(pool[u]) if pool is not None else u
-        length = int(tl[t])
-        sp = min(span, length) if span > 0 else length
-        t_out.append(t)
-        off_out.append((b * sp) >> 32)
-    return np.array(t_out, np.int32), np.array(off_out, np.int32)
 
 
 def device_draw(EH, seed, lanes, eps, trace_len, pool=None, span=0):

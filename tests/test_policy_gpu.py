@@ -1,7 +1,7 @@
 """The learned policy on the device: abr_env_policy_select against the numpy twin bit for bit on states reached by random
 rollouts, the fused rollout closed against the oracle (tests/closed_loop_check.py's (a) + (b) argument with the policy's
-twin as the reference controller), the fused rollout against select + step, the exploration draw against step_random,
-finished lanes, refusals and load_weights."""
+twin as the reference controller: closed_loop_check.PolicyReference), the fused rollout against select + step, the
+exploration draw against step_random, finished lanes, refusals and load_weights."""
 import ctypes as C
 
 import numpy as np
@@ -87,58 +87,6 @@ def test_select_matches_twin_on_random_rollout_states():
 # ---------------------------------------------------------------------------------------------------------------------
 # closed loop against the oracle
 
-class PolicyReference:
-    """The policy's twin as closed_loop_check's reference controller.  check() replays each episode through the oracle
-    and then asks for the answer at every replayed call site; the answers of one episode are computed for all lanes and
-    call sites at once from the replayed frames (captured from K.replay)."""
-
-    last = {}
-
-    def __init__(self, case, entries=None):
-        self.case = case
-        self.clipped = 0
-        self.ep = np.full(case["n_lanes"], -1)
-        self.key = None
-        self.used = set()
-
-    def new_episode(self, i):
-        self.ep[i] += 1
-
-    def fold(self, i, x):
-        pass
-
-    def _episode(self):
-        steps, bw = PolicyReference.last["steps"], PolicyReference.last["bw"]
-        if self.key is not None and self.key[0] is steps:
-            return self.key[1]
-        p, m = self.case["params"], self.case["meta"]
-        V, N = m["video_length"], self.case["n_lanes"]
-        M = len(m["ladder"])
-        table = K.br_table(self.case)
-        e = int(self.ep.max())
-        c = np.tile(np.arange(V), N)                                        # [N * V], lane-major
-        lanes = np.repeat(np.arange(N), V)
-        hist = np.repeat(bw, V, axis=0).T                                   # [V, N * V]: lane's whole history
-        x = T.features(p["window"], M, V, c, steps["last_bitrate"].reshape(-1), steps["buffer_level"].reshape(-1),
-                       steps["global_time"].reshape(-1), steps["play_time"].reshape(-1), hist,
-                       lambda r: table[r], p["norm"])
-        a, _, _ = T.decide(p["layers"], x, p["seed"], p["thr"], self.case["lane_ids"][lanes], c, e, M)
-        ans = a.reshape(N, V)
-        self.key = (steps, ans)
-        return ans
-
-    def answer(self, i, c, prev, buf, h):
-        return int(self._episode()[i, c])
-
-
-def _capturing_replay(orig):
-    def replay(case, actions, speeds):
-        steps, bw, fin = orig(case, actions, speeds)
-        PolicyReference.last = dict(steps=steps, bw=bw)
-        return steps, bw, fin
-    return replay
-
-
 def _policy_case(seed, W, widths, explore, auto_reset, impl, n_lanes=None):
     rng = np.random.default_rng(900 + seed)
     for s in range(seed, seed + 10_000):                                   # a case whose speed feature the policy takes
@@ -201,9 +149,7 @@ CLOSED = [  # (seed, W, widths, explore, auto_reset, impl)
 ]
 
 
-def test_closed_loop_against_the_oracle(monkeypatch):
-    monkeypatch.setattr(K, "Reference", PolicyReference)
-    monkeypatch.setattr(K, "replay", _capturing_replay(K.replay))
+def test_closed_loop_against_the_oracle():
     answers, explored = set(), 0
     for (seed, W, widths, explore, auto_reset, impl) in CLOSED:
         case = _policy_case(seed, W, widths, explore, auto_reset, impl)
@@ -216,9 +162,7 @@ def test_closed_loop_against_the_oracle(monkeypatch):
     assert len(answers) >= 3 and explored >= 3
 
 
-def test_closed_loop_sampled_lanes_at_65536(monkeypatch):
-    monkeypatch.setattr(K, "Reference", PolicyReference)
-    monkeypatch.setattr(K, "replay", _capturing_replay(K.replay))
+def test_closed_loop_sampled_lanes_at_65536():
     case = _policy_case(10, 8, [64, 64], 0.5, False, "auto", n_lanes=65536)
     out = run_policy_case(case)
     rng = np.random.default_rng(3)

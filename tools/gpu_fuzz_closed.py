@@ -5,7 +5,10 @@ per-lane speeds, schedule, LatencySpeedController} x per-chunk ladder x lane cou
 through the public API (BatchedABREnv, step_mpc / step_rule, set_speed_controller, speed_log) in pieces, then checked
 against the C oracle and the controller twins: every action, obs row, reward, done flag, the frame after every piece,
 the history, QoE, the speed log and the FastMPC entries the decisions read.
-    usage: python tools/gpu_fuzz_closed.py [n_seeds] [lanes (default: the case's own)] [first_seed]"""
+With --episodes each seed is a case of the episode family (closed_loop_check.make_episode_case: the policy as a seventh
+controller, an episode sampler, staggered lanes through masked resets, lane_id_base up to 2^40 + 2^32), run through
+step_mpc / step_rule / step_policy and reset(mask=...), and checked after every operation (check_episodes).
+    usage: python tools/gpu_fuzz_closed.py [--episodes] [n_seeds] [lanes (default: the case's own)] [first_seed]"""
 import json
 import os
 import sys
@@ -80,6 +83,71 @@ def run_case(case):
     return out
 
 
+def _policy(case, env):
+    p = case["params"]
+    ctl = A.PolicyController(A.EnvPlayer(env), p["layers"], window=p["window"], norm=(p["norm"][0], p["norm"][1]),
+                             explore=p["explore"], seed=p["seed"])
+    assert ctl.explore_threshold == p["thr"]
+    return ctl
+
+
+def run_episode_case(case):
+    """Run one case of the episode family on the device; returns the `out` dict closed_loop_check.check_episodes
+    takes (frames, episodes() and the speed log after every operation)."""
+    m = case["meta"]
+    V, N = m["video_length"], case["n_lanes"]
+    chunks = A.Chunk(m["ladder"]) if case["br"] is None else [A.Chunk(list(r)) for r in case["br"]]
+    mpd = A.MPD(V, m["chunk_length"], m["max_buffer"], m["start_up_length"], chunks)
+    speed = m["speed"]
+    if case["feature"] == "lanes":
+        speed = torch.from_numpy(np.asarray(case["lane_speeds"], np.float64))
+    elif case["feature"] == "schedule":
+        speed = torch.from_numpy(np.ascontiguousarray(np.asarray(case["schedule"], np.float64).T))
+    env = A.BatchedABREnv(mpd, A.QOEMetric(*m["weights"]), A.NetworkInfo(m["interval"], case["traces"]), N,
+                          speed=speed, impl=case["impl"], auto_reset=case["auto_reset"], max_ticks=case["max_ticks"],
+                          lane_id_base=case["lane_id_base"])
+    if case["feature"] == "rule":
+        env.set_speed_controller(A.LatencySpeedController(*case["rule"]), log_rows=case["log_rows"])
+    s = case["sampler"]
+    if s is not None:
+        env.set_episode_sampler(s["seed"], s["pool"], s["span"])
+    ctl = None
+    kind = "mpc" if case["ctl"] in ("mpc", "robust") else ("policy" if case["ctl"] == "policy" else "rule")
+    parts, frames, episodes, logs = [], [], [], []
+    for op in case["ops"]:
+        if op[0] == "reset":
+            mask = None if op[1] is None else torch.from_numpy(op[1].astype(np.uint8))
+            if op[2] is None:
+                env.reset(mask=mask, sample=True)
+            else:
+                env.reset(torch.from_numpy(op[2]), torch.from_numpy(op[3]), mask=mask)
+            if ctl is None:
+                ctl = _policy(case, env) if kind == "policy" else _controller(case, env)
+        else:
+            n = op[1]
+            o = (env.step_mpc(ctl, n) if kind == "mpc" else env.step_policy(ctl, n) if kind == "policy"
+                 else env.step_rule(ctl, n))
+            parts.append({k: o[k].cpu().numpy() for k in ("actions", "reward", "done", "obs")})
+        frames.append({k: v.cpu().numpy().copy() for k, v in env.observe_f64().items()})
+        episodes.append({k: v.cpu().numpy().copy() for k, v in env.episodes().items()})
+        logs.append(env.speed_log().cpu().numpy().copy() if case["feature"] == "rule" else None)
+    out = {k: np.concatenate([p[k] for p in parts]) for k in ("actions", "reward", "done", "obs")}
+    out["frames"], out["episodes"], out["speed_logs"] = frames, episodes, logs if case["feature"] == "rule" else None
+    out["history"] = tuple(x.cpu().numpy().copy() for x in env.history())
+    out["qoe"] = env.episode_qoe().cpu().numpy()
+    out["entries"] = ctl.entries().cpu().numpy() if case["ctl"] == "fastmpc" else None
+    torch.cuda.synchronize()
+    env.close()
+    return out
+
+
+def run_episode_seed(seed, N=None, stats=None):
+    """One case of the episode family against the reference.  Returns (mismatches, lane-steps, cell key, case)."""
+    case = K.make_episode_case(seed, N)
+    mm = K.check_episodes(case, run_episode_case(case), stats)
+    return mm, case["n_lanes"] * case["n_steps"], f"{case['ctl']}/{case['feature']}/{case['mode']}", case
+
+
 def run_seed(seed, N=None, stats=None):
     """One case against the reference.  Returns (mismatches, lane-steps, cell key, case)."""
     case = K.make_case(seed, N)
@@ -88,22 +156,25 @@ def run_seed(seed, N=None, stats=None):
 
 
 def main():
-    n_seeds = int(sys.argv[1]) if len(sys.argv) > 1 else 240
-    N = int(sys.argv[2]) if len(sys.argv) > 2 and int(sys.argv[2]) > 0 else None
-    first = int(sys.argv[3]) if len(sys.argv) > 3 else 0
+    argv = [a for a in sys.argv[1:] if a != "--episodes"]
+    episodes = len(argv) < len(sys.argv) - 1
+    n_seeds = int(argv[0]) if len(argv) > 0 else 240
+    N = int(argv[1]) if len(argv) > 1 and int(argv[1]) > 0 else None
+    first = int(argv[2]) if len(argv) > 2 else 0
     t0 = time.time()
     bad, lane_steps, cells, impls, stats, cases = 0, 0, {}, {}, {}, []
     for seed in range(first, first + n_seeds):
-        mm, ls, key, case = run_seed(seed, N, stats)
+        mm, ls, key, case = (run_episode_seed if episodes else run_seed)(seed, N, stats)
         if mm:
-            print("MISMATCH", K.describe(case), len(mm), mm[:4], flush=True)
+            print("MISMATCH", (K.describe_ep if episodes else K.describe)(case), len(mm), mm[:4], flush=True)
         bad += len(mm)
         lane_steps += ls
         cells[key] = cells.get(key, 0) + 1
         impls[case["impl"]] = impls.get(case["impl"], 0) + 1
         cases.append(case)
-    vac = K.assert_non_vacuous(stats, cases)
-    print(json.dumps(dict(seeds=n_seeds, first_seed=first, lanes_per_seed=N or "case", lane_steps=lane_steps,
+    vac = (K.assert_non_vacuous_ep if episodes else K.assert_non_vacuous)(stats, cases)
+    print(json.dumps(dict(family="episodes" if episodes else "configs", seeds=n_seeds, first_seed=first,
+                          lanes_per_seed=N or "case", lane_steps=lane_steps,
                           mismatches=bad, non_vacuity_problems=vac, cases=cells, impls=impls,
                           clipped_mpc_decisions=stats.get("clipped", 0), seconds=round(time.time() - t0, 1))))
     sys.exit(1 if bad or vac else 0)
