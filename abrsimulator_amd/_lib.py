@@ -111,6 +111,13 @@ class Policy(C.Structure):
                 ("seed", C.c_uint64), ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
 
 
+POLICY_ARGMAX, POLICY_SOFTMAX = 0, 1
+
+
+class PolicySampling(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("inv_temperature", C.c_float), ("reserved_", C.c_int32 * 6)]
+
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -183,6 +190,9 @@ SYMBOLS = [
     ("abr_policy_weights_bytes", C.c_int, [C.POINTER(Policy), C.c_int32, C.POINTER(C.c_size_t)]),
     ("abr_env_policy_select", C.c_int, [_P, C.POINTER(Policy), _P, _P, _P, _P]),
     ("abr_env_step_policy", C.c_int, [_P, C.POINTER(Policy), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_policy_select_sampled", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), _P, _P, _P, _P, _P]),
+    ("abr_env_step_policy_sampled", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.c_int32, _P, _P, _P,
+                                              _P, _P, _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

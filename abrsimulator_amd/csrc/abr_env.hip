@@ -2802,8 +2802,14 @@ struct PolicyArgs {
     const float *weights;
     int32_t *action_out;              // [N]
     float *features_out, *scores_out; // [F][N], [M][N], nullable
+    float *probs_out;                 // [M][N], nullable (SAMPLED instance only)
+    int32_t mode;                     // abr_policy_sampling (SAMPLED instance only)
+    float inv_temperature;
 };
 
+// SAMPLED: the instance behind abr_env_policy_select_sampled.  It keeps each lane's scores in its own column of LDS past
+// the weights (M * kPolicyBlock floats; the score loops run to a runtime M), where the draw turns them into e_m.
+template <bool SAMPLED = false>
 __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p, PolicyArgs a) {
     extern __shared__ float w_lds[];
     const abrx::PolicyLayout lay = abrx::policy_layout(a.net);
@@ -2820,6 +2826,10 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p
             for (int32_t f = 0; f < n.F; f++) a.features_out[f * N + i] = 0.0f;
         if (a.scores_out)
             for (int32_t m = 0; m < n.M; m++) a.scores_out[m * N + i] = 0.0f;
+        if constexpr (SAMPLED) {
+            if (a.probs_out)
+                for (int32_t m = 0; m < n.M; m++) a.probs_out[m * N + i] = 0.0f;
+        }
         return;
     }
     const double G = p.G[p.k[i]];
@@ -2837,9 +2847,23 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p
         }
     }
     float *so = a.scores_out;
-    const auto emit = [&](int32_t m, float v) { if (so) so[m * N + i] = v; };
-    const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
-    a.action_out[i] = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+    if constexpr (!SAMPLED) {
+        const auto emit = [&](int32_t m, float v) { if (so) so[m * N + i] = v; };
+        const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
+        a.action_out[i] = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+    } else {
+        float *col = w_lds + lay.total + threadIdx.x;            // this lane's scores, stride kPolicyBlock
+        const auto emit = [&](int32_t m, float v) {
+            col[m * kPolicyBlock] = v;
+            if (so) so[m * N + i] = v;
+        };
+        const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
+        float *po = a.probs_out;
+        const auto buf = [&](int32_t m) -> float & { return col[m * kPolicyBlock]; };
+        const auto prob = [&](int32_t m, float v) { if (po) po[m * N + i] = v; };
+        a.action_out[i] = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode,
+                                              a.inv_temperature, buf, prob);
+    }
 }
 
 // the struct alone (before the handle): shape, window, reserved fields, pointers, threshold
@@ -2913,9 +2937,24 @@ static int policy_args(const abr_env *env, const abr_policy *pol, PolicyArgs *a)
     return ABR_OK;
 }
 
+template <bool SAMPLED = false>
 static void launch_policy(const abr_env *env, const PolicyArgs &a, hipStream_t st) {
-    hipLaunchKernelGGL(policy_select_kernel, dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
-                       dim3(kPolicyBlock), (size_t)abrx::policy_layout(a.net).total * sizeof(float), st, env->p, a);
+    const size_t lds = ((size_t)abrx::policy_layout(a.net).total + (SAMPLED ? (size_t)a.net.M * kPolicyBlock : 0)) *
+                       sizeof(float);
+    hipLaunchKernelGGL(policy_select_kernel<SAMPLED>, dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
+                       dim3(kPolicyBlock), lds, st, env->p, a);
+}
+
+// the sampling struct alone (before the handle)
+static int validate_sampling(const abr_policy_sampling *smp) {
+    if (!smp) return fail(ABR_E_INVALID, "sampling is NULL");
+    if (smp->mode != ABR_POLICY_ARGMAX && smp->mode != ABR_POLICY_SOFTMAX)
+        return fail(ABR_E_INVALID, "sampling mode %d is neither ABR_POLICY_ARGMAX nor ABR_POLICY_SOFTMAX", smp->mode);
+    const float t = smp->inv_temperature;
+    if (!(t > 0.0f && t <= 0x1.fffffep127f)) return fail(ABR_E_INVALID, "sampling inv_temperature must be finite and > 0");
+    for (int32_t r : smp->reserved_)
+        if (r) return fail(ABR_E_INVALID, "sampling reserved_ must be 0");
+    return ABR_OK;
 }
 
 extern "C" int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_t *action_out_dev, float *features_out_dev,
@@ -2932,15 +2971,18 @@ extern "C" int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_
 }
 
 // per decision the policy kernel, then K1 MODE 1 on its actions, back to back on the stream (as mpc_rollout)
-extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev,
-                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
-                                   float *features_out_dev, float *scores_out_dev, void *stream) {
+template <bool SAMPLED>
+static int step_policy(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp, int32_t n_steps,
+                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                       float *features_out_dev, float *scores_out_dev, float *probs_out_dev, void *stream) {
     int rc = validate_policy(pol);
     if (rc) return rc;
+    if (SAMPLED && (rc = validate_sampling(smp))) return rc;
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     PolicyArgs a;
     if ((rc = policy_args(env, pol, &a))) return rc;
+    if (SAMPLED) { a.mode = smp->mode; a.inv_temperature = smp->inv_temperature; }
     if ((rc = require(kPolicyRollout, env->impl))) return rc;
     const hipStream_t st = (hipStream_t)stream;
     const int64_t N = env->p.n_lanes;
@@ -2949,13 +2991,45 @@ extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t 
         a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
         a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
         a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        launch_policy(env, a, st);
+        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        launch_policy<SAMPLED>(env, a, st);
         HIP_TRY(hipGetLastError());
         rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
                            reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
                            done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
         if (rc) return rc;
     }
+    return ABR_OK;
+}
+
+extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev,
+                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                   float *features_out_dev, float *scores_out_dev, void *stream) {
+    return step_policy<false>(env, pol, nullptr, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
+                              features_out_dev, scores_out_dev, nullptr, stream);
+}
+
+extern "C" int abr_env_step_policy_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                           int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                                           uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
+                                           float *scores_out_dev, float *probs_out_dev, void *stream) {
+    return step_policy<true>(env, pol, smp, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
+                             features_out_dev, scores_out_dev, probs_out_dev, stream);
+}
+
+extern "C" int abr_env_policy_select_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                             int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                             float *probs_out_dev, void *stream) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if ((rc = validate_sampling(smp))) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyArgs a;
+    if ((rc = policy_args(env, pol, &a))) return rc;
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    a.probs_out = probs_out_dev; a.mode = smp->mode; a.inv_temperature = smp->inv_temperature;
+    launch_policy<true>(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
 

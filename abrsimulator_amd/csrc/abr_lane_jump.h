@@ -989,6 +989,71 @@ ABR_HD int32_t policy_explore(const PolicyNet &n, uint64_t lane, int32_t c, int3
     return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : g;
 }
 
+// The sampled decision (include/abr_env.h: abr_policy_sampling).  exp_c is the contract's float32 exp for x <= 0: a
+// Cody-Waite reduction by ln 2 (Cephes' split), a degree-6 fmaf Horner chain, an exact scaling by 2^k (k >= -116 keeps
+// the result normal).  No device expf: its bits are not numpy's.
+constexpr float kExpLog2e = 0x1.715476p+0f, kExpLn2Hi = 0x1.63p-1f, kExpLn2Lo = -0x1.bd0106p-13f;
+constexpr float kExpC3 = 0x1.55549cp-3f, kExpC4 = 0x1.555694p-5f, kExpC5 = 0x1.1234fcp-7f, kExpC6 = 0x1.6b69e0p-10f;
+
+ABR_HD float exp_c(float x) {
+    if (!(x >= -80.0f)) return 0.0f;                          // -inf and NaN too
+    const float k = rintf(x * kExpLog2e);
+    float r = fmaf(-k, kExpLn2Hi, x);
+    r = fmaf(-k, kExpLn2Lo, r);
+    float p = kExpC6;
+    p = fmaf(p, r, kExpC5);
+    p = fmaf(p, r, kExpC4);
+    p = fmaf(p, r, kExpC3);
+    p = fmaf(p, r, 0.5f);
+    p = fmaf(p, r, 1.0f);
+    p = fmaf(p, r, 1.0f);
+    return ldexpf(p, (int)k);
+}
+
+// The draw from softmax(s * iT) given the first argmax g and philox word 2 w2.  buf(m) is a float& that holds s_m on
+// entry and e_m on return; prob(m, v) receives probs[m] in order.  Two passes over m: e_m and S, then cum_m, the first
+// cum_m > t and e_m / S.  A non-finite s_g answers g with a one-hot distribution.
+template <class Buf, class Prob>
+ABR_HD int32_t policy_softmax_sample(int32_t M, int32_t g, float iT, uint32_t w2, const Buf &buf, const Prob &prob) {
+    const float sg = buf(g);
+    if (!(sg >= -0x1.fffffep127f && sg <= 0x1.fffffep127f)) {
+        for (int32_t m = 0; m < M; m++) prob(m, m == g ? 1.0f : 0.0f);
+        return g;
+    }
+    float S = 0.0f;
+    for (int32_t m = 0; m < M; m++) {
+        const float d = buf(m) - sg;
+        const float e = exp_c(d * iT);
+        buf(m) = e;
+        S += e;
+    }
+    const float t = (float)(w2 >> 8) * 0x1p-24f * S;
+    float cum = 0.0f;
+    int32_t pick = -1;
+    for (int32_t m = 0; m < M; m++) {
+        const float e = buf(m);
+        cum += e;
+        if (pick < 0 && cum > t) pick = m;
+        prob(m, e / S);
+    }
+    return pick < 0 ? g : pick;
+}
+
+// The decision of a sampling mode: argmax (0) is policy_explore with probs one-hot at g; softmax (1) draws with word 2 of
+// the exploration's philox block, and word 1 < thr still takes the random policy's action from word 0.
+template <class Buf, class Prob>
+ABR_HD int32_t policy_decide(const PolicyNet &n, uint64_t lane, int32_t c, int32_t episode, int32_t g, int32_t mode,
+                             float iT, const Buf &buf, const Prob &prob) {
+    if (mode == 0) {
+        for (int32_t m = 0; m < n.M; m++) prob(m, m == g ? 1.0f : 0.0f);
+        return policy_explore(n, lane, c, episode, g);
+    }
+    uint32_t r[4];
+    philox4(n.seed, lane, (uint32_t)c, (uint32_t)episode, r);
+    const int32_t s = policy_softmax_sample(n.M, g, iT, r[2], buf, prob);
+    return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : s;
+}
+
 // The episode sampler (include/abr_env.h: abr_episode_sampler, the same layout): which (trace, start offset) episode e of
 // global lane g runs when it was armed by the sampler.  A pure function of (seed, g, e), so every role of the split kernels
 // computes it where it needs it.  Step 0xFFFFFFFF is never a chunk id: the draw shares no counter with the random policy

@@ -425,12 +425,13 @@ class BatchedABREnv:
         return out
 
     def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
-                    want_scores=False):
+                    want_scores=False, want_probs=False):
         """n_steps decisions per lane taken by a learned policy (policy.py: PolicyController) on the device, each one the
         policy kernel on every lane's own call-site state followed by the download of that chunk, with no host work
         between decisions.  Every event-driven kernel; 'tick' is refused (include/abr_env.h).  Returns
-        dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N], features[n,F,N], scores[n,M,N]); an entry that is
-        not wanted is None."""
+        dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N], features[n,F,N], scores[n,M,N], probs[n,M,N]);
+        an entry that is not wanted is None.  A controller with sample="softmax" draws each action on the device
+        (abr_env_step_policy_sampled); probs is the policy's distribution at each decision, before exploration."""
         n = int(n_steps)
         pol = controller.bound(self)
         if out is None:
@@ -439,6 +440,14 @@ class BatchedABREnv:
             out["features"] = (torch.empty(n, controller.feature_dim, N, dtype=torch.float32, device=dev)
                                if want_features else None)
             out["scores"] = torch.empty(n, self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None
+            out["probs"] = torch.empty(n, self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None
+        if controller.uses_sampled_entries(out.get("probs") is not None):
+            smp = controller.sampling()
+            self._call(self.lib.abr_env_step_policy_sampled, self._h, C.byref(pol), C.byref(smp), n,
+                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
+                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
+                       _lib.ptr(out.get("probs")))
+            return out
         self._call(self.lib.abr_env_step_policy, self._h, C.byref(pol), n, _lib.ptr(out.get("obs")),
                    _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")),
                    _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")))

@@ -7,6 +7,10 @@ draw -- is include/abr_env.h: abr_policy; the arithmetic is csrc/abr_lane_jump.h
     out = env.step_policy(ctl, 48, want_features=True)     # features, actions, rewards, done for a trainer
     ...train net in PyTorch...
     ctl.load_weights(net)                                   # refresh the device copy in place, no sync
+
+A stochastic policy (A2C, PPO) samples on the device instead: PolicyController(..., sample="softmax", temperature=T)
+draws each action from softmax(scores / T), and want_probs=True returns that distribution (include/abr_env.h:
+abr_policy_sampling).
 """
 import ctypes as C
 import math
@@ -17,6 +21,7 @@ import torch
 from . import _lib
 
 OBS_NAMES = ["buffer_level", "last_bitrate", "chunks_left", "latency"]
+SAMPLE_MODES = {"argmax": _lib.POLICY_ARGMAX, "softmax": _lib.POLICY_SOFTMAX}
 
 
 def _as_f32(t, device):
@@ -42,11 +47,14 @@ class PolicyController:
     layer of width n_rates; the input width is feature_dim = 4 + window + n_rates.  norm: "default" (shift 0; scale
     1/max_buffer for the buffer and the latency, 1/top bitrate for bitrates and throughputs, 1/video_length for the chunks
     left), None (raw values), or (shift [F], scale [F]).  explore in [0, 1]: the probability of taking the random policy's
-    action instead of the argmax (threshold floor(explore * 2^32)), drawn with `seed` exactly as step_random draws."""
+    action instead of the argmax (threshold floor(explore * 2^32)), drawn with `seed` exactly as step_random draws.
+    sample: "argmax" (the first argmax) or "softmax" (a draw from softmax(scores / temperature) with word 2 of the same
+    philox block); temperature > 0, passed as float32(1 / temperature).  Both can be changed between launches."""
 
     method = "policy"
 
-    def __init__(self, player, layers, window=8, norm="default", explore=0.0, seed=0, device=None):
+    def __init__(self, player, layers, window=8, norm="default", explore=0.0, seed=0, device=None, sample="argmax",
+                 temperature=1.0):
         self.player = player
         env = getattr(player, "env", None)
         self.device = torch.device(device) if device is not None else (env.device if env is not None else
@@ -80,6 +88,8 @@ class PolicyController:
         self.norm = self._norm(norm, mpd)
         self.explore = explore
         self.seed = int(seed)
+        self.sample = sample
+        self.temperature = temperature
 
     # -- construction ----------------------------------------------------------
     @classmethod
@@ -135,6 +145,38 @@ class PolicyController:
         self._explore = eps
         self.explore_threshold = 1 << 32 if eps >= 1.0 else int(math.floor(eps * 2.0 ** 32))
 
+    @property
+    def sample(self):
+        return self._sample
+
+    @sample.setter
+    def sample(self, mode):
+        if mode not in SAMPLE_MODES:
+            raise ValueError(f"sample must be one of {sorted(SAMPLE_MODES)}, got {mode!r}")
+        self._sample = mode
+
+    @property
+    def temperature(self):
+        return self._temperature
+
+    @temperature.setter
+    def temperature(self, t):
+        if isinstance(t, bool):
+            raise ValueError("temperature must be a finite number > 0")
+        t = float(t)
+        with np.errstate(all="ignore"):
+            inv = np.float32(1.0 / t) if math.isfinite(t) and t > 0.0 else np.float32(0.0)
+        if not (math.isfinite(t) and t > 0.0 and np.isfinite(inv) and inv > 0.0):
+            raise ValueError(f"temperature must be finite and > 0 with a finite, nonzero float32 1/temperature; got {t}")
+        self._temperature, self.inv_temperature = t, inv
+
+    def sampling(self):
+        """The abr_policy_sampling struct of the current sample mode and temperature."""
+        smp = _lib.PolicySampling()
+        smp.mode = SAMPLE_MODES[self.sample]
+        smp.inv_temperature = float(self.inv_temperature)
+        return smp
+
     # -- the weights -------------------------------------------------------------
     def load_weights(self, layers):
         """Copy new weights (a list of (W, b) of this controller's shapes, or an nn.Sequential) into the device blob in
@@ -186,18 +228,30 @@ class PolicyController:
         return (OBS_NAMES + [f"throughput[-{self.window - k}]" for k in range(self.window)] +
                 [f"bitrate[{m}]" for m in range(self.n_rates)])
 
-    def select(self, want_features=True, want_scores=True):
+    def select(self, want_features=True, want_scores=True, want_probs=False):
         """One decision per lane on the environment's current state (no step): dict(actions int32 [N], features float32
-        [F, N], scores float32 [M, N]); a lane whose done bits are set answers -1 with zero columns."""
+        [F, N], scores float32 [M, N], probs float32 [M, N] -- the policy's distribution before exploration); a lane
+        whose done bits are set answers -1 with zero columns.  An entry that is not wanted is None."""
         env = self.player.env
         N, dev = env.n_lanes, env.device
         out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
                    features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
-                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None)
+                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
+                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
         pol = self.bound(env)
-        env._call(env.lib.abr_env_policy_select, env._h, C.byref(pol), _lib.ptr(out["actions"]),
-                  _lib.ptr(out["features"]), _lib.ptr(out["scores"]))
+        if self.uses_sampled_entries(want_probs):
+            smp = self.sampling()
+            env._call(env.lib.abr_env_policy_select_sampled, env._h, C.byref(pol), C.byref(smp),
+                      _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]),
+                      _lib.ptr(out["probs"]))
+        else:
+            env._call(env.lib.abr_env_policy_select, env._h, C.byref(pol), _lib.ptr(out["actions"]),
+                      _lib.ptr(out["features"]), _lib.ptr(out["scores"]))
         return out
+
+    def uses_sampled_entries(self, want_probs):
+        """An argmax policy without probs keeps the abr_policy entry points; anything else takes the sampled ones."""
+        return self.sample != "argmax" or bool(want_probs)
 
     def next_bitrate(self):
         """int32 [N]: the policy's action for each lane (-1 for finished lanes)."""

@@ -731,6 +731,60 @@ int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, fl
                         uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
                         void *stream);
 
+/*
+ * Sampled decisions of the learned policy (ABI 4, additive; BUILD-DEFINED).  A stochastic policy (an actor trained with
+ * A2C or PPO) takes its action from softmax(score / T) and its trainer needs the probability of that action; inside a
+ * fused rollout only the device can draw it.  Exact, so that a host build of the same header and a numpy twin reproduce
+ * every bit (the library is built with -ffp-contract=off -fno-fast-math; every operation below is float32,
+ * round-to-nearest-even, one rounding each).
+ *
+ * Inputs: the scores s[0..M) and the first argmax g of abr_policy (unchanged), iT = inv_temperature (finite, > 0).
+ *   Fallback: if s[g] is not finite (+inf; NaN at index 0 with nothing greater; all scores -inf) the decision is g and
+ *     the distribution is one-hot at g.
+ *   Scaled logits, for m = 0 .. M-1 in order: d_m = s_m - s[g], x_m = d_m * iT, e_m = exp_c(x_m).  x_m <= 0 (a NaN s_m
+ *     gives a NaN x_m, and e_m = 0), so e[g] = exp_c(0) = 1 and 1 <= S <= M.
+ *   exp_c(x): +0 when !(x >= -80) (-inf and NaN included).  Otherwise
+ *     k = rintf(x * 0x1.715476p+0f)                      (one rounded product, then round half to even; -116 <= k <= 0)
+ *     r = fmaf(-k, 0x1.63p-1f, x);  r = fmaf(-k, -0x1.bd0106p-13f, r)              (Cephes' split of ln 2)
+ *     p = 0x1.6b69e0p-10f;  then p = fmaf(p, r, c) for c = 0x1.1234fcp-7f, 0x1.555694p-5f, 0x1.55549cp-3f, 0.5f, 1.0f,
+ *       1.0f in that order                                (a minimax fit of exp on [-ln2/2, ln2/2] with c0 = c1 = 1, c2 = 1/2)
+ *     exp_c = ldexpf(p, k), exact (k >= -116 keeps p * 2^k normal).
+ *     exp_c(+-0) = 1 exactly; on [-80, 0] its relative error against exp is below 2^-23 (7.7e-8 on a dense grid).
+ *   Sum: S = e_0 + e_1 + ... + e_(M-1), added in that order from 0.0f; cum_m is the same running sum after term m.
+ *   Draw: w2 = output word 2 of the policy's philox block (key seed, counter (global lane id lo, hi, c, episode number),
+ *     the block whose words 0 and 1 the exploration reads); q = (float)(w2 >> 8) * 0x1p-24f (exact, q < 1),
+ *     t = q * S (rounded).  The sample is the first m with cum_m > t.  The comparison is strict, so an action with
+ *     e_m = 0 is never drawn; t < S = cum_(M-1) always, so one m qualifies (were none to, the answer would be g).
+ *   Exploration is unchanged: word 1 < explore_threshold takes the random policy's action from word 0; otherwise the
+ *     action is the sample (ABR_POLICY_SOFTMAX) or g (ABR_POLICY_ARGMAX, exactly abr_env_policy_select's action).
+ *   probs[m] = e_m / S, the correctly rounded float32 division: the policy's distribution pi before exploration
+ *     (ABR_POLICY_ARGMAX: one-hot at g).  With explore_threshold thr, eps = thr / 2^32, the behaviour distribution is
+ *     (1 - eps) * pi[m] + eps * rho[m], rho[m] = (ceil((m + 1) * 2^32 / M) - ceil(m * 2^32 / M)) / 2^32, the exact share
+ *     of words w0 with ((uint64)w0 * M) >> 32 == m.
+ * A lane whose done bits are set takes no decision: action -1, its feature, score and probs columns 0.0f.
+ */
+#define ABR_POLICY_ARGMAX 0
+#define ABR_POLICY_SOFTMAX 1
+typedef struct abr_policy_sampling {
+    int32_t mode;                         /* ABR_POLICY_ARGMAX or ABR_POLICY_SOFTMAX */
+    float inv_temperature;                /* 1 / T: finite, > 0 (unused by ABR_POLICY_ARGMAX but checked) */
+    int32_t reserved_[6];                 /* set to 0 */
+} abr_policy_sampling;
+
+/* abr_env_policy_select with the decision of `smp` (above) and probs_out_dev float32 [n_rates][n_lanes] (nullable).
+ * Validation (ABR_E_INVALID, nothing launched): abr_env_policy_select's checks of pol, then smp (non-NULL, mode,
+ * inv_temperature, reserved_ zero), all before the handle; then as abr_env_policy_select. */
+int abr_env_policy_select_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                  int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                  float *probs_out_dev, void *stream);
+
+/* abr_env_step_policy with the decisions of `smp`; probs_out_dev float32 [n_steps][n_rates][n_lanes] (nullable).
+ * Validation as abr_env_policy_select_sampled, with n_steps >= 1 before the handle; ABR_E_UNSUPPORTED on tick. */
+int abr_env_step_policy_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp, int32_t n_steps,
+                                float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                float *probs_out_dev, void *stream);
+
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
 int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t prev_bitrate,

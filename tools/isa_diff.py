@@ -6,7 +6,8 @@
 Bodies are compared without comments, with basic-block label numbers normalised, and with the kernel's own symbol name
 normalised (so that a template whose signature grew a trailing argument -- a different mangled name -- is still compared
 with its old self; --strip SUFFIX removes that suffix from the new names, default: the RuleParams argument's mangling;
-give it more than once to strip several, e.g. a defaulted template flag's `Lb0E` as well).
+give it more than once to strip several, e.g. a defaulted template flag's `Lb0E` as well).  A template instance's
+comdat `.section` directive compares equal to the plain `.text` of the function it replaced.
 Prints one line per kernel that differs, every kernarg-size change, the kernels that are new, and a summary."""
 import argparse
 import re
@@ -20,6 +21,8 @@ def kernels(path):
         lines = [re.sub(r"\s*;.*$", "", l) for l in body.splitlines()]
         body = "\n".join(l for l in lines if l.strip() and ".amdhsa_kernarg_size" not in l)   # reported on its own
         body = re.sub(r"\.LBB\d+_", ".LBB_", body)
+        # a template instance is emitted into a comdat section of its own: the same code
+        body = re.sub(r"^\s*\.section\s+\.text\.\S+,\"axG\",@progbits,\S+,comdat$", "\t.text", body, flags=re.M)
         desc = re.search(r"\.amdhsa_kernel\s+" + re.escape(name) + r"\n(.*?)\.end_amdhsa_kernel", text, re.S).group(1)
         kernarg = int(re.search(r"\.amdhsa_kernarg_size\s+(\d+)", desc).group(1))
         out[name] = (body, kernarg)
