@@ -134,6 +134,16 @@ int abr_env_workspace_bytes(const abr_env_config *cfg, int64_t n_lanes, size_t *
  * + trace_len_dev[t]).  The three trace arrays must outlive the handle.
  * Builds the universal tick tables on the host in float64 (the reference's
  * global_time is lane-independent) and uploads them into the workspace.
+ *
+ * What a trace may contain: every sample finite and >= 0 (0.0, -0.0 and subnormal values included), every
+ * trace at least one sample long (trace_len_dev[t] >= 1, n_traces >= 1).  A lane that plays past the end of
+ * its trace wraps to the trace's start (build-defined: the reference raises); a trace of one sample wraps
+ * at every interval.  A zero sample is an outage: the download makes no progress in that interval.  A lane
+ * on a trace without a positive sample never completes a chunk and ends with ABR_DONE_TIMEOUT at
+ * config.max_ticks, one addition per tick -- a bounded crawl, not a hang; lanes of the same wave on live
+ * traces are not affected.  The library never reads the traces on the host, so it cannot refuse a NaN, an
+ * infinite or a negative sample: those are outside the contract, and a binding checks for them itself, as
+ * abrsimulator_amd.env.pack_traces does.  Covered by tests/test_trace_edges_{cpu,gpu}.py.
  */
 int abr_env_create(const abr_env_config *cfg, const double *traces_dev,
                    const int64_t *trace_off_dev, const int32_t *trace_len_dev, int32_t n_traces,

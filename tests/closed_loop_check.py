@@ -23,6 +23,10 @@ every lane's log against the oracle's rule mode (abr_oracle.c: oracle_speed_rule
 tests/speed_twin.py), which closes the same loop for the speeds.
 (d) Without auto_reset a finished lane answers -1, reports its terminal record again and its state does not move.
 
+The controller "script" (ScriptReference) is the open loop in the same layout: the action of every decision is known
+before the launch (a scripted rollout, or the counter-based random policy's draw), so (b) pins the actions the device
+reports and (a), (d) and the frames check everything else (tests/trace_families.py: open_loop_case).
+
 Edges (build-defined, include/abr_env.h): an empty history answers bitrate 0 (D13); near the video end every MPC search
 runs at the clipped horizon V - c (D12).  Under auto_reset a lane restarts from its own trace and offset, or the
 sampler's pair for its next episode number: the harmonic (n, S) restarts, RobustMPC's state empties itself at chunk 0
@@ -973,7 +977,27 @@ class PolicyReference:
         return int(self.ans[int(i)][c])
 
 
+class ScriptReference:
+    """Open loop as a controller (the config family only): case["script"][t, i] is the action of lane i at decision t
+    of the run, known before the launch (scripted actions, or the counter-based random policy's draw)."""
+
+    def __init__(self, case, entries=None):
+        self.case, self.clipped, self.used = case, 0, set()
+        self.episode = np.full(case["n_lanes"], -1)
+
+    def new_episode(self, i):
+        self.episode[i] += 1
+
+    def fold(self, i, x):
+        pass
+
+    def answer(self, i, c, prev, buf, h):
+        return int(self.case["script"][self.episode[i] * self.case["meta"]["video_length"] + c, i])
+
+
 def make_reference(case, entries=None):
+    if case["ctl"] == "script":
+        return ScriptReference(case, entries)
     return PolicyReference(case, entries) if case["ctl"] == "policy" else Reference(case, entries)
 
 

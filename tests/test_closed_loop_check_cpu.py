@@ -38,8 +38,8 @@ def _names(mm):
     return {(x["name"], x["step"], x["lane"]) for x in mm}
 
 
-def _mutated(seed, mutate):
-    case, out = _run(seed)
+def _mutated(seed, mutate, run=None):
+    case, out = (run or _run)(seed)
     assert K.check(case, out) == []
     out = copy.deepcopy(out)
     want = mutate(case, out)
@@ -48,50 +48,71 @@ def _mutated(seed, mutate):
     return mm
 
 
+# single-element mutations of a run: each changes `out` in place and returns the (name, step, lane) the checker must report
+# (module level: tests/test_trace_edges_cpu.py applies them to cases on other trace families)
+
+def mutate_action(case, out):
+    t, i = 3, 5
+    out["actions"][t, i] = (out["actions"][t, i] + 1) % len(case["meta"]["ladder"])
+    return ("action", t, i)
+
+
+def mutate_frame_ulp(case, out):
+    t, f = out["frames"][0]
+    f["buffer_level"][4] = np.nextafter(f["buffer_level"][4], np.inf)
+    return ("frame.buffer_level", t, 4)
+
+
+def mutate_reward_ulp(case, out):
+    out["reward"][2, 7] = np.nextafter(out["reward"][2, 7], np.float32(np.inf))
+    return ("reward", 2, 7)
+
+
+def mutate_speed_log(case, out):
+    log = out["speed_log"]
+    r = int(np.flatnonzero(log[:, 3])[1])
+    log[r, 3] = 2.5 if log[r, 3] != 2.5 else 0.5
+    return ("speed_log", r, 3)
+
+
+def mutate_done_flag(case, out):
+    out["done"][1, 2] ^= 1
+    return ("done", 1, 2)
+
+
+def mutate_history(case, out):
+    out["history"][1][2, 6] = np.nextafter(out["history"][1][2, 6], 0.0)
+    return ("history.bandwidth", 2, 6)
+
+
+MUTATIONS = dict(action=(12, mutate_action),              # buffer / config
+                 frame_ulp=(4, mutate_frame_ulp), reward_ulp=(16, mutate_reward_ulp),
+                 speed_log=(19, mutate_speed_log),        # rate / rule
+                 done_flag=(20, mutate_done_flag), history=(6, mutate_history))
+
+
 def test_mutation_action():
-    def m(case, out):
-        t, i = 3, 5
-        out["actions"][t, i] = (out["actions"][t, i] + 1) % len(case["meta"]["ladder"])
-        return ("action", t, i)
-    _mutated(12, m)                                       # buffer / config
+    _mutated(*MUTATIONS["action"])
 
 
 def test_mutation_frame_ulp():
-    def m(case, out):
-        t, f = out["frames"][0]
-        f["buffer_level"][4] = np.nextafter(f["buffer_level"][4], np.inf)
-        return ("frame.buffer_level", t, 4)
-    _mutated(4, m)
+    _mutated(*MUTATIONS["frame_ulp"])
 
 
 def test_mutation_reward_ulp():
-    def m(case, out):
-        out["reward"][2, 7] = np.nextafter(out["reward"][2, 7], np.float32(np.inf))
-        return ("reward", 2, 7)
-    _mutated(16, m)
+    _mutated(*MUTATIONS["reward_ulp"])
 
 
 def test_mutation_speed_log():
-    def m(case, out):
-        log = out["speed_log"]
-        r = int(np.flatnonzero(log[:, 3])[1])
-        log[r, 3] = 2.5 if log[r, 3] != 2.5 else 0.5
-        return ("speed_log", r, 3)
-    _mutated(19, m)                                       # rate / rule
+    _mutated(*MUTATIONS["speed_log"])
 
 
 def test_mutation_done_flag():
-    def m(case, out):
-        out["done"][1, 2] ^= 1
-        return ("done", 1, 2)
-    _mutated(20, m)
+    _mutated(*MUTATIONS["done_flag"])
 
 
 def test_mutation_history():
-    def m(case, out):
-        out["history"][1][2, 6] = np.nextafter(out["history"][1][2, 6], 0.0)
-        return ("history.bandwidth", 2, 6)
-    _mutated(6, m)
+    _mutated(*MUTATIONS["history"])
 
 
 def test_mutation_fastmpc_entry():

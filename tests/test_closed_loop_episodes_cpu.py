@@ -75,12 +75,14 @@ def _find(pred, seeds):
     raise AssertionError("no seed")
 
 
-def _flag_some_lane(seed, mutant_for_lane, lanes=range(8), **kw):
-    """Build the run with the mutation on one lane at a time until it changes the run; the checker must flag that lane."""
-    case, good = _run(seed)
+def _flag_some_lane(seed, mutant_for_lane, lanes=range(8), run=None, **kw):
+    """Build the run with the mutation on one lane at a time until it changes the run; the checker must flag that lane.
+    run(seed, **kw) -> (case, out) replaces _run (tests/test_trace_edges_cpu.py: cases on other trace families)."""
+    run = run or _run
+    case, good = run(seed)
     assert K.check_episodes(case, good) == []
     for x in lanes:
-        _, bad = _run(seed, **mutant_for_lane(x))
+        _, bad = run(seed, **mutant_for_lane(x))
         if any(not np.array_equal(np.asarray(good[k]), np.asarray(bad[k])) for k in ("actions", "reward", "obs")) or \
                 any(not np.array_equal(a[k], b[k]) for a, b in zip(good["episodes"], bad["episodes"]) for k in a):
             mm = K.check_episodes(case, bad)
@@ -89,15 +91,17 @@ def _flag_some_lane(seed, mutant_for_lane, lanes=range(8), **kw):
     raise AssertionError("the mutation never changed the run")
 
 
+def next_episodes_pair_mutant(x):
+    """Lane x runs its episode 1 on the pair of its episode 2."""
+    def pair_fn(case, lanes, eps):
+        eps = np.asarray(eps, np.int64) + (np.asarray(lanes) == x) * (np.asarray(eps) == 1)
+        return K.sampled_pairs(case, lanes, eps)
+    return dict(pair_fn=pair_fn)
+
+
 def test_flags_a_segment_on_the_next_episodes_pair():
     seed = _find(lambda c: c["mode"] == "sampled" and c["sampler"]["pool"] is None, range(0, 28))
-
-    def mut(x):
-        def pair_fn(case, lanes, eps):
-            eps = np.asarray(eps, np.int64) + (np.asarray(lanes) == x) * (np.asarray(eps) == 1)
-            return K.sampled_pairs(case, lanes, eps)
-        return dict(pair_fn=pair_fn)
-    mm = _flag_some_lane(seed, mut)
+    mm = _flag_some_lane(seed, next_episodes_pair_mutant)
     assert any(m["name"].startswith("episodes.") for m in mm)
 
 
@@ -202,6 +206,11 @@ def test_flags_a_speed_log_row_left_from_the_previous_episode():
                  range(3, 112, 4))
     case, out = _run(seed)
     assert K.check_episodes(case, out) == []
+    flags_a_stale_speed_log_row(case, out)
+
+
+def flags_a_stale_speed_log_row(case, out):
+    """The first speed-log row an operation rewrote, put back to what the previous episode left: flagged by name."""
     logs = out["speed_logs"]
     for oi in range(1, len(logs)):
         diff = np.argwhere(logs[oi] != logs[oi - 1])

@@ -200,6 +200,12 @@ ENV_CONFIGS = {
         ladder=[0.5, 1.0, 2.0, 3.5], chunk_length=3, video_length=20,
         max_buffer=9, start_up_length=3, interval=0.7, weights=[2.0, 0.5, 1, 0.05],
         speed=1.0, lanes=16, n_traces=4, trace_len=2000, bw=(0.3, 5.0), policy="random"),
+    # outages: zero runs of 1..11 samples (about 12 % of positions start one) and a few 1e-3 / 1e3 samples: downloads that
+    # start in a dead interval, sit through one, or finish on their first tick
+    "env_outage": dict(
+        ladder=[0.3, 0.75, 1.2, 1.85, 2.85, 4.3], chunk_length=2, video_length=16,
+        max_buffer=8, start_up_length=4, interval=0.5, weights=[4.3, 1, 1, 0.1],
+        speed=1.0, lanes=24, n_traces=4, trace_len=1500, bw=(0.3, 6.0), policy="random", outages=True),
 }
 
 
@@ -209,6 +215,19 @@ def gen_env(name, cfg, S):
     # bandwidths rounded to float32 so text, oracle and device hold one value
     traces = np.array([[np.float32(rng.uniform(lo, hi)) for _ in range(cfg["trace_len"])]
                        for _ in range(cfg["n_traces"])], dtype=np.float64)
+    if cfg.get("outages"):
+        for t in traces:
+            i = 0
+            while i < len(t):
+                u = rng.random()
+                if u < 0.12:                       # a zero run of 1..11 samples
+                    n = rng.randrange(1, 12)
+                    t[i:i + n] = 0.0
+                    i += n
+                    continue
+                if u < 0.16:
+                    t[i] = np.float32(1e-3 if u < 0.14 else 1e3)
+                i += 1
     V, N, B = cfg["video_length"], cfg["lanes"], len(cfg["ladder"])
     trace_id = np.array([i % cfg["n_traces"] for i in range(N)], dtype=np.int32)
     offset = np.array([0 if i < cfg["n_traces"] else rng.randrange(cfg["trace_len"])

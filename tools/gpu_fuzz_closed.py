@@ -8,7 +8,10 @@ the history, QoE, the speed log and the FastMPC entries the decisions read.
 With --episodes each seed is a case of the episode family (closed_loop_check.make_episode_case: the policy as a seventh
 controller, an episode sampler, staggered lanes through masked resets, lane_id_base up to 2^40 + 2^32), run through
 step_mpc / step_rule / step_policy and reset(mask=...), and checked after every operation (check_episodes).
-    usage: python tools/gpu_fuzz_closed.py [--episodes] [n_seeds] [lanes (default: the case's own)] [first_seed]"""
+With --traces FAMILY every case runs on traces of one family of tests/trace_families.py (outages, isolated zeros, tiny and
+huge samples, traces of one to seven samples, constants) with max_ticks measured on the reference's own closed loop.
+    usage: python tools/gpu_fuzz_closed.py [--episodes] [--traces FAMILY] [n_seeds] [lanes (default: the case's own)]
+           [first_seed]"""
 import json
 import os
 import sys
@@ -141,16 +144,24 @@ def run_episode_case(case):
     return out
 
 
-def run_episode_seed(seed, N=None, stats=None):
-    """One case of the episode family against the reference.  Returns (mismatches, lane-steps, cell key, case)."""
-    case = K.make_episode_case(seed, N)
+def _swap(case, traces, seed):
+    if traces is None:
+        return case
+    import trace_families
+    return trace_families.with_traces(case, traces, seed)       # the reference side, before anything is launched
+
+
+def run_episode_seed(seed, N=None, stats=None, traces=None):
+    """One case of the episode family against the reference (traces: a family of tests/trace_families.py, or the
+    case's own).  Returns (mismatches, lane-steps, cell key, case)."""
+    case = _swap(K.make_episode_case(seed, N), traces, seed)
     mm = K.check_episodes(case, run_episode_case(case), stats)
     return mm, case["n_lanes"] * case["n_steps"], f"{case['ctl']}/{case['feature']}/{case['mode']}", case
 
 
-def run_seed(seed, N=None, stats=None):
-    """One case against the reference.  Returns (mismatches, lane-steps, cell key, case)."""
-    case = K.make_case(seed, N)
+def run_seed(seed, N=None, stats=None, traces=None):
+    """One case against the reference (traces: as run_episode_seed).  Returns (mismatches, lane-steps, cell key, case)."""
+    case = _swap(K.make_case(seed, N), traces, seed)
     mm = K.check(case, run_case(case), stats)
     return mm, case["n_lanes"] * case["n_steps"], f"{case['ctl']}/{case['feature']}", case
 
@@ -158,13 +169,18 @@ def run_seed(seed, N=None, stats=None):
 def main():
     argv = [a for a in sys.argv[1:] if a != "--episodes"]
     episodes = len(argv) < len(sys.argv) - 1
+    traces = None
+    if "--traces" in argv:
+        i = argv.index("--traces")
+        traces = argv[i + 1]
+        del argv[i:i + 2]
     n_seeds = int(argv[0]) if len(argv) > 0 else 240
     N = int(argv[1]) if len(argv) > 1 and int(argv[1]) > 0 else None
     first = int(argv[2]) if len(argv) > 2 else 0
     t0 = time.time()
     bad, lane_steps, cells, impls, stats, cases = 0, 0, {}, {}, {}, []
     for seed in range(first, first + n_seeds):
-        mm, ls, key, case = (run_episode_seed if episodes else run_seed)(seed, N, stats)
+        mm, ls, key, case = (run_episode_seed if episodes else run_seed)(seed, N, stats, traces)
         if mm:
             print("MISMATCH", (K.describe_ep if episodes else K.describe)(case), len(mm), mm[:4], flush=True)
         bad += len(mm)
@@ -173,7 +189,8 @@ def main():
         impls[case["impl"]] = impls.get(case["impl"], 0) + 1
         cases.append(case)
     vac = (K.assert_non_vacuous_ep if episodes else K.assert_non_vacuous)(stats, cases)
-    print(json.dumps(dict(family="episodes" if episodes else "configs", seeds=n_seeds, first_seed=first,
+    print(json.dumps(dict(family="episodes" if episodes else "configs", traces=traces or "case", seeds=n_seeds,
+                          first_seed=first,
                           lanes_per_seed=N or "case", lane_steps=lane_steps,
                           mismatches=bad, non_vacuity_problems=vac, cases=cells, impls=impls,
                           clipped_mpc_decisions=stats.get("clipped", 0), seconds=round(time.time() - t0, 1))))
