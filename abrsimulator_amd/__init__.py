@@ -8,6 +8,7 @@ from .datamodel import MPD, Chunk, ChunkInfo, NetworkInfo, QOEMetric
 from .env import BatchedABREnv, obs_dict, pack_traces
 from .episodes import EpisodeSampler
 from .fastmpc import FastMPCController
+from .ledger import EpisodeLedger
 from .mpc import BatchedMPCController, EnvPlayer
 from .policy import PolicyController
 from .rules import BolaController, BufferBasedController, RateBasedController
@@ -21,6 +22,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "EpisodeSampler",
+           "EpisodeSampler", "EpisodeLedger",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

@@ -131,6 +131,10 @@ class EpisodeSampler(C.Structure):
     _fields_ = [("seed", C.c_uint64), ("pool", C.c_void_p), ("n_pool", C.c_int32), ("offset_span", C.c_int32)]
 
 
+class EpisodeLedger(C.Structure):
+    _fields_ = [("base_dev", C.c_void_p), ("rows", C.c_int32), ("reserved_", C.c_int32)]
+
+
 class StateView(C.Structure):
     _fields_ = [("n_lanes", C.c_int64), ("chunk_id", C.c_void_p), ("last_bitrate", C.c_void_p),
                 ("buffer_level", C.c_void_p), ("hist_n", C.c_void_p), ("hist_sum_inv", C.c_void_p),
@@ -155,6 +159,8 @@ SYMBOLS = [
     ("abr_env_set_speed_rule", C.c_int, [_P, C.POINTER(SpeedRule), _P, C.c_int32]),
     ("abr_env_set_episode_sampler", C.c_int, [_P, C.POINTER(EpisodeSampler)]),
     ("abr_env_get_episode", C.c_int, [_P, _P, _P, _P, _P]),
+    ("abr_env_ledger_bytes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_set_episode_ledger", C.c_int, [_P, C.POINTER(EpisodeLedger)]),
     ("abr_env_reset", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step_random", C.c_int, [_P, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P]),

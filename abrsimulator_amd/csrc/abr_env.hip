@@ -36,6 +36,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "abr_env.h"
@@ -165,6 +166,10 @@ static_assert(sizeof(abrx::EpisodeSampler) == sizeof(abr_episode_sampler) &&
               offsetof(abrx::EpisodeSampler, n_pool) == offsetof(abr_episode_sampler, n_pool) &&
               offsetof(abrx::EpisodeSampler, offset_span) == offsetof(abr_episode_sampler, offset_span),
               "abr_episode_sampler: one layout");
+static_assert(sizeof(abrx::EpisodeLedger) == sizeof(abr_episode_ledger) &&
+              offsetof(abrx::EpisodeLedger, base) == offsetof(abr_episode_ledger, base_dev) &&
+              offsetof(abrx::EpisodeLedger, rows) == offsetof(abr_episode_ledger, rows),
+              "abr_episode_ledger: one layout");
 
 struct abr_env {
     EnvParams p;
@@ -187,6 +192,7 @@ struct abr_env {
     bool armed;                     // abr_env_reset has run at least once: episodes may be in flight
     bool sampler_on;                // abr_env_set_episode_sampler: launches run the SAMPLE instances with `sampler`
     abrx::EpisodeSampler sampler;
+    abrx::EpisodeLedger ledger;     // abr_env_set_episode_ledger: base == nullptr while none is installed
 };
 
 // A handle on which no reset has run has no episode to protect: the setters take effect at once
@@ -379,6 +385,16 @@ __device__ inline void sampled_episode(const EnvParams &p, const abrx::EpisodeSa
     abrx::episode_assign(smp, (uint64_t)(p.lane_id_base + i), (uint32_t)e, p.n_traces, p.trace_len, t, off);
 }
 
+// The episode ledger (include/abr_env.h: abr_episode_ledger): lane i's episode has just ended and its ep_qoe_terms are
+// written -- append the same terms, calculate_qoe's sum of them, and what the episode was.  Called only by the LEDGER
+// instances; trace_id / offset0 are the FINISHED episode's, read before a re-arm replaces them.
+__device__ inline void ledger_record(const EnvParams &p, const abrx::EpisodeLedger &led, int64_t i, double g_rb, double g_su,
+                                     double lat, double var_run, int32_t episode_no, int32_t trace_id, int32_t offset0,
+                                     int32_t chunks, uint8_t done) {
+    abrx::ledger_append(led, p.n_lanes, i, p.wr, p.wv, p.ws, p.wl, g_rb, g_su, lat, var_run, episode_no, trace_id, offset0,
+                        chunks, (int32_t)done);
+}
+
 // MODE 0: reset (fresh lanes run to their first call site)
 // MODE 1: step  (one externally supplied action per lane)
 // MODE 2: fused random-policy rollout of n_steps decisions per lane
@@ -386,13 +402,15 @@ __device__ inline void sampled_episode(const EnvParams &p, const abrx::EpisodeSa
 // MODE 4: fused rollout of n_steps decisions per lane taken by a bitrate rule (`rule`; the other modes ignore it)
 // SAMPLE: the instance that runs while an episode sampler is installed: a reset draws each lane's (trace, offset) from
 // `smp` (trace_id_in / offset_in unused) and a re-arm draws the new episode's; the other instances never read `smp`
-template <int MODE, bool SAMPLE = false>
+// LEDGER: the instance that runs while an episode ledger is installed: every episode end appends a record to `led`; the
+// other instances never read `led` and are, instruction for instruction, what they were without it
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __global__ __launch_bounds__(64) void env_advance_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
-    abrx::EpisodeSampler smp) {
+    abrx::EpisodeSampler smp, abrx::EpisodeLedger led) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -485,6 +503,9 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                     p.ep_qoe_terms[1 * p.n_lanes + i] = p.G[s.n_su];
                     p.ep_qoe_terms[2 * p.n_lanes + i] = lane_avg_latency(p, s.sumk, s.n_play);
                     p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
+                    if constexpr (LEDGER)
+                        ledger_record(p, led, i, p.G[s.n_rb], p.G[s.n_su], lane_avg_latency(p, s.sumk, s.n_play), var_run,
+                                      episode_no, p.trace_id[i], offset0, s.chunk_id, done);
                     if (p.auto_reset && ended) {
                         // re-arm: this step's obs is the new episode's first call site
                         if constexpr (SAMPLE) {
@@ -720,16 +741,17 @@ __device__ inline void write_obs_vals(const LaneJ &s, const EnvParams &p, int64_
 // compiled for four waves: a single pass through a decision gains nothing from the fifth wave, and the 102-VGPR bound
 // cost it 12 B of scratch per lane (round 5).  MODE 4 (a rule rollout) too: at five waves its rule loops push the
 // register bound into 36 B of spills, at four it keeps none.  The episode sampler's instances (SAMPLE) as well: at five
-// waves the draw at a re-arm spilled 52-68 B per lane, at four they keep none.
+// waves the draw at a re-arm spilled 52-68 B per lane, at four they keep none.  The episode ledger's (LEDGER) for the same
+// reason: the append's addresses at five waves took the fused rollout from 32 B of scratch to 100 B.
 #define ABR_JUMP_BOUNDS(MODE, SAMPLE) __launch_bounds__(64, ((MODE) == 1 || (MODE) == 4 || (SAMPLE) ? 4 : ABR_JUMP_WAVES))
-// SAMPLE: as env_advance_kernel
-template <int MODE, bool SAMPLE = false>
-__global__ ABR_JUMP_BOUNDS(MODE, SAMPLE) void env_jump_kernel(
+// SAMPLE, LEDGER: as env_advance_kernel
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+__global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
-    abrx::EpisodeSampler smp) {
+    abrx::EpisodeSampler smp, abrx::EpisodeLedger led) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -842,6 +864,9 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE) void env_jump_kernel(
                             : (p.speed_rows >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
                                                  : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
                         p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
+                        if constexpr (LEDGER)     // the latency term as stored: read back (this thread's own store)
+                            ledger_record(p, led, i, g_rb, g_su, p.ep_qoe_terms[2 * p.n_lanes + i], var_run, episode_no,
+                                          p.trace_id[i], offset0, s.chunk_id, done);
                         if (p.auto_reset && r.ended) {
                             // re-arm: this step's obs is the new episode's first call site
                             if constexpr (SAMPLE) {
@@ -1362,6 +1387,28 @@ extern "C" int abr_env_set_episode_sampler(abr_env *env, const abr_episode_sampl
     return ABR_OK;
 }
 
+// the episode ledger (include/abr_env.h: abr_episode_ledger): the layout arithmetic needs no handle and no device
+extern "C" int abr_env_ledger_bytes(int32_t n_lanes, int32_t rows, size_t *bytes_out) {
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "episode ledger: n_lanes must be >= 1, got %d", n_lanes);
+    if (rows < 1) return fail(ABR_E_INVALID, "episode ledger: rows must be >= 1, got %d", rows);
+    *bytes_out = abrx::ledger_layout(n_lanes, rows).bytes;
+    return ABR_OK;
+}
+
+extern "C" int abr_env_set_episode_ledger(abr_env *env, const abr_episode_ledger *l) {
+    if (l) {
+        if (l->rows < 1) return fail(ABR_E_INVALID, "episode ledger: rows must be >= 1, got %d", l->rows);
+        if (!l->base_dev) return fail(ABR_E_INVALID, "episode ledger: base_dev is NULL");
+        if ((uintptr_t)l->base_dev % 256) return fail(ABR_E_INVALID, "episode ledger: base_dev must be 256-byte aligned");
+    }
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    abrx::EpisodeLedger v{};
+    if (l) { v.base = l->base_dev; v.rows = l->rows; }
+    env->ledger = v;
+    return ABR_OK;
+}
+
 // each lane's current (trace, start offset, episode number): copies of the workspace rows, ordered on the stream
 extern "C" int abr_env_get_episode(abr_env *env, int32_t *trace_id_out_dev, int32_t *offset_out_dev,
                                    int32_t *episode_out_dev, void *stream) {
@@ -1426,28 +1473,29 @@ static inline int launch_impl(const abr_env *env, int32_t n_steps) {
 // one-thread-per-lane kernel, the asynchronous pipeline only for MODE 2 and 3: the `if constexpr` keeps every other
 // instance out of the build.  While an episode sampler is installed the SAMPLE instances run (a reset with explicit trace
 // ids excepted: it draws nothing); the diagnostic pipelines have none and refuse.
-template <int MODE, bool SAMPLE>
+template <int MODE, bool SAMPLE, bool LEDGER>
 static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
                                uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule,
                                const int32_t *trace_id, const int32_t *start_offset, const uint8_t *lane_mask) {
     const EnvParams &p = env->p;
     const int64_t N = p.n_lanes;
     const abrx::EpisodeSampler smp = SAMPLE ? env->sampler : abrx::EpisodeSampler{};
+    const abrx::EpisodeLedger led = LEDGER ? env->ledger : abrx::EpisodeLedger{};
     if (impl == 0 || impl == 1) {
-        auto *k = impl == 1 ? env_advance_kernel<MODE, SAMPLE> : env_jump_kernel<MODE, SAMPLE>;
+        auto *k = impl == 1 ? env_advance_kernel<MODE, SAMPLE, LEDGER> : env_jump_kernel<MODE, SAMPLE, LEDGER>;
         hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
-                           acts, n_steps, seed, rule, smp);
+                           acts, n_steps, seed, rule, smp, led);
     } else if constexpr (MODE >= 1 && MODE <= 3) {
         // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
         if (impl == 5) {
-            auto *k = env_split3_kernel<MODE, SAMPLE>;
-            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp);
+            auto *k = env_split3_kernel<MODE, SAMPLE, LEDGER>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
         } else if (impl == 2) {
-            auto *k = env_split_kernel<MODE, SAMPLE>;
-            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp);
+            auto *k = env_split_kernel<MODE, SAMPLE, LEDGER>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
         }
 #ifdef ABR_WITH_RING
-        else if constexpr (!SAMPLE) {
+        else if constexpr (!SAMPLE && !LEDGER) {
             if (impl == 6)
                 hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
                                    rew, dn, acts, n_steps, seed);
@@ -1469,6 +1517,8 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
     const bool sample = env->sampler_on && !(MODE == 0 && trace_id);
     if (sample && impl != 0 && impl != 1 && impl != 2 && impl != 5)
         return fail(ABR_E_UNSUPPORTED, "the episode sampler runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
+    if (env->ledger.base && impl != 0 && impl != 1 && impl != 2 && impl != 5)
+        return fail(ABR_E_UNSUPPORTED, "the episode ledger runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
     (void)N;
 #ifdef ABR_WITH_ASYNC
     if constexpr (MODE == 2 || MODE == 3) {
@@ -1488,12 +1538,21 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
         }
     }
 #endif
-    if (sample)
-        launch_env_kernels<MODE, true>(env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset,
-                                       lane_mask);
-    else
-        launch_env_kernels<MODE, false>(env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset,
-                                        lane_mask);
+    // a reset never ends an episode: it has no LEDGER instance
+    const bool ledger = MODE != 0 && env->ledger.base;
+    const auto go = [&](auto smp_on, auto led_on) {
+        launch_env_kernels<MODE, decltype(smp_on)::value, decltype(led_on)::value>(
+            env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
+    };
+    if constexpr (MODE == 0) {
+        if (sample) go(std::true_type{}, std::false_type{});
+        else go(std::false_type{}, std::false_type{});
+    } else {
+        if (sample && ledger) go(std::true_type{}, std::true_type{});
+        else if (sample) go(std::true_type{}, std::false_type{});
+        else if (ledger) go(std::false_type{}, std::true_type{});
+        else go(std::false_type{}, std::false_type{});
+    }
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }
@@ -3091,10 +3150,10 @@ extern "C" int abr_debug_selfcheck(abr_env *env, uint32_t *result_dev, void *str
     p.sentinel = 0x5eed0000c0ffee00ull ^ (uint64_t)(uintptr_t)env;
     p.selfcheck_out = result_dev;
     hipLaunchKernelGGL(env_split3_kernel<9>, dim3(1), dim3(192), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
-                       abrx::EpisodeSampler{});
+                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{});
     p.selfcheck_out = result_dev + 1;
     hipLaunchKernelGGL(env_split_kernel<9>, dim3(1), dim3(128), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
-                       abrx::EpisodeSampler{});
+                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }

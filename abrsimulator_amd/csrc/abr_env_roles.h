@@ -531,9 +531,48 @@ __device__ __forceinline__ void service_write_obs(const SVars &v, const EnvParam
     ABR_OUT(obs[ABR_OBS_STARTUP_TIME * n + i], (float)p.G[v.o_nsu]);
 }
 
+// The episode ledger's record of the episode that has just ended in lane i (abr_env.hip: ledger_record).  The workspace's
+// trace_id / offset0 / episode_no are written at the END of a role-split launch, so they still describe the lane's first
+// episode of this launch: an episode with another number was re-armed inside it, and then (SAMPLE) ran the sampler's pair.
+// The ledger and the sampler are read afresh from the kernarg segment, like fresh_params() and for its reason: carried as
+// references through the shared loop they are ten more live scalars, which cost the three-wave kernel 36 B of private
+// segment.  CONTRACT: SplitKernargs lists the arguments of env_split3_kernel and env_split_kernel in order (both have the
+// same signature; the kernarg segment lays by-value arguments out like a C struct).
+struct SplitKernargs {
+    EnvParams p;
+    const int32_t *actions;
+    float *obs_out, *reward_out;
+    uint8_t *done_out;
+    int32_t *actions_out;
+    int32_t n_steps;
+    uint64_t seed;
+    abrx::EpisodeSampler smp;
+    abrx::EpisodeLedger led;
+};
+static_assert(offsetof(SplitKernargs, p) == 0 && offsetof(SplitKernargs, smp) == sizeof(EnvParams) + 56 &&
+              offsetof(SplitKernargs, led) == sizeof(EnvParams) + 80 && sizeof(SplitKernargs) == sizeof(EnvParams) + 96,
+              "the role-split kernels' kernarg segment (.offset of each argument in the code object's metadata)");
+// VEC_PARAMS (the three-wave kernel's service side): the parameter block's fields as well.  The two-wave kernel's player
+// keeps them scalar: it has the scalar registers, and the vector ones would cost it its fourth wave per SIMD.
+template <bool SAMPLE, bool VEC_PARAMS>
+__device__ __forceinline__ void ledger_record_split(const EnvParams &p, int64_t i, double g_rb, double g_su, double lat,
+                                                    double var_run, int32_t episode_no, int32_t chunks, uint8_t done) {
+    // ... through a VECTOR register: the ledger's base, its row count and every region offset derived from them then live in
+    // vector registers, of which the service side has dozens to spare, for the length of this rare branch
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+v"(kp));
+    const SplitKernargs &ka = *(const SplitKernargs *)kp;
+    const EnvParams &pv = VEC_PARAMS ? ka.p : p;       // the same block either way
+    int32_t t = pv.trace_id[i], off = pv.offset0[i];
+    if constexpr (SAMPLE) {
+        if (episode_no != pv.episode_no[i]) sampled_episode(pv, ka.smp, i, episode_no, t, off);
+    }
+    ledger_record(pv, ka.led, i, g_rb, g_su, lat, var_run, episode_no, t, off, chunks, done);
+}
+
 // the record P left in slot `sl`: division, history, reward, done, observation, episode end
 // (M2: SplitMail2, or the ring kernel's RingPS -- the same fields with more slots)
-template <class M2>
+template <bool SAMPLE = false, bool LEDGER = false, class M2>
 __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 &m2, int sl,
                                                float *__restrict__ obs_out, float *__restrict__ reward_out,
                                                uint8_t *__restrict__ done_out) {
@@ -582,6 +621,8 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
         p.ep_qoe_terms[1 * p.n_lanes + i] = g_su;
         p.ep_qoe_terms[2 * p.n_lanes + i] = m2.lat[sl][l];
         p.ep_qoe_terms[3 * p.n_lanes + i] = v.var_run;
+        if constexpr (LEDGER)
+            ledger_record_split<SAMPLE, true>(p, i, g_rb, g_su, m2.lat[sl][l], v.var_run, v.episode_no, v.o_chunk, v.done);
         if (m2m & kS3Reset) {
             v.episode_no++;
             v.n_su_obs = 0; v.n_rb_obs = 0; v.g_su_obs = 0.0; v.g_rb_obs = 0.0;
@@ -620,7 +661,7 @@ __device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &, ActRin
 }
 
 // before the barrier: draw the policy's actions ahead of D, then serve what P finished in the previous iteration
-template <int MODE>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &, SplitMail &m, SplitMail2 &m2, ActRing &ring,
                                            float *__restrict__ obs_out, float *__restrict__ reward_out,
                                            uint8_t *__restrict__ done_out, int32_t n_total, uint64_t seed, int32_t t) {
@@ -655,7 +696,7 @@ __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &, SplitMai
         lds_writes_done();
         if (l == 0) lds_st(&ring.act_hi, v.a_next);
     }
-    if (t >= 1 && i < p.n_lanes) service_record(v, p, m2, pb, obs_out, reward_out, done_out);
+    if (t >= 1 && i < p.n_lanes) service_record<SAMPLE, LEDGER>(v, p, m2, pb, obs_out, reward_out, done_out);
     v.last_cb = cb;
     ABR_STAMP(21);
 }
@@ -670,7 +711,7 @@ __device__ __forceinline__ void sampled_episode_store(const EnvParams &p, const 
     }
 }
 
-template <int MODE, bool SAMPLE = false>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMail2 &m2, float *__restrict__ obs_out,
                                            float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                            int32_t *__restrict__ actions_out, int32_t n_total,
@@ -679,7 +720,7 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMai
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
     if (i >= p.n_lanes) return;
-    service_record(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
+    service_record<SAMPLE, LEDGER>(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
     if (!v.was_done) {
         if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.episode_no);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.episode_no;
@@ -699,11 +740,14 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMai
 // MODE 1: one externally supplied action per lane; MODE 2: fused random-policy rollout; MODE 3: fused rollout of
 // scripted actions [n_steps][n_lanes]
 // SAMPLE: the instance that runs while an episode sampler is installed (`smp`; the other instances never read it)
-template <int MODE, bool SAMPLE = false>
+// LEDGER: the instance that runs while an episode ledger is installed (`led`; likewise)
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) void env_split3_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp,
+    abrx::EpisodeLedger led) {
+    (void)led;                         // read from the kernarg segment where an episode ends (ledger_record_split)
     __shared__ SplitMail m;
     __shared__ SplitMail2 m2;
     __shared__ ActRing ring;
@@ -734,7 +778,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
             p_park(park.p, v);
         } else {
             SVars v; s_unpark(park.s, v);
-            role_s_pre<MODE>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
+            role_s_pre<MODE, SAMPLE, LEDGER>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
             s_park(park.s, v);
         }
         __syncthreads();                       // THE barrier: every wave, every iteration, this one site
@@ -743,7 +787,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     }
     if (role == 0) { role_d_end(dv, p); ABR_WG_TIME(1); }
     else if (role == 1) { PVars v; p_unpark(park.p, v, p); role_p3_end(v, p); ABR_WG_TIME(2); }
-    else { SVars v; s_unpark(park.s, v); role_s_end<MODE, SAMPLE>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
+    else { SVars v; s_unpark(park.s, v); role_s_end<MODE, SAMPLE, LEDGER>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
 }
 
 // =====================================================================================================================
@@ -792,7 +836,7 @@ __device__ __forceinline__ void role_p2_begin(P2Vars &v, const EnvParams &) {
     ABR_STAMP_INIT();
 }
 
-template <int MODE>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitMail &m, float *__restrict__ obs_out,
                                             float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                             int32_t n_total, int32_t t) {
@@ -859,6 +903,8 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                     p.ep_qoe_terms[1 * p.n_lanes + i] = g_su;
                     p.ep_qoe_terms[2 * p.n_lanes + i] = player_latency(p, s);
                     p.ep_qoe_terms[3 * p.n_lanes + i] = v.var_run;
+                    if constexpr (LEDGER)
+                        ledger_record_split<SAMPLE, false>(p, i, g_rb, g_su, player_latency(p, s), v.var_run, v.pv.episode_no, s.chunk_id, v.done);
                     if (p.auto_reset && sr.ended) {
                         // re-arm: this step's obs is the new episode's first call site
                         abrx::lanej_init_player(s, tb);
@@ -909,11 +955,13 @@ __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, 
     }
 }
 
-template <int MODE, bool SAMPLE = false>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false>
 __global__ __launch_bounds__(128) void env_split_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
-    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp) {
+    int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp,
+    abrx::EpisodeLedger led) {
+    (void)led;                         // read from the kernarg segment where an episode ends (ledger_record_split)
     __shared__ SplitMail m;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform by construction
@@ -932,7 +980,7 @@ __global__ __launch_bounds__(128) void env_split_kernel(
             role_d_pre<MODE, false, SAMPLE>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t, smp);
         } else {
             P2Vars v; p2_unpark(park.p, v, fresh_params());
-            role_p2_pre<MODE>(v, p, m, obs_out, reward_out, done_out, n_total, t);
+            role_p2_pre<MODE, SAMPLE, LEDGER>(v, p, m, obs_out, reward_out, done_out, n_total, t);
             p2_park(park.p, v);
         }
         __syncthreads();                       // THE barrier: both waves, every iteration, this one site

@@ -1080,5 +1080,53 @@ ABR_HD void episode_assign(const EpisodeSampler &s, uint64_t g, uint32_t e, int3
     off_out = (int32_t)(((uint64_t)w[1] * (uint32_t)span) >> 32);
 }
 
+// The episode ledger (include/abr_env.h: abr_episode_ledger, the same layout): one record per finished episode, appended
+// where the kernels write ep_qoe_terms.  The blob is struct-of-arrays with row stride n_lanes, every region 256-B aligned:
+// count[N] int32 | total[5][N] float64 | rec_f64[rows][5][N] float64 | rec_i32[rows][5][N] int32.
+struct EpisodeLedger {
+    void *base;                    // nullptr: no ledger installed, ledger_append is never called
+    int32_t rows;
+    int32_t reserved_;
+};
+constexpr int kLedgerFields = 5;   // float64: rebuffer, start-up, latency, variance, qoe; int32: episode, trace, offset, chunks, done
+struct LedgerLayout { size_t count, total, rec_f64, rec_i32, bytes; };   // byte offsets of the regions, and the blob's size
+ABR_HD size_t ledger_align(size_t b) { return (b + 255) & ~(size_t)255; }
+ABR_HD LedgerLayout ledger_layout(int64_t n_lanes, int32_t rows) {
+    const size_t n = (size_t)n_lanes, r = (size_t)rows;
+    LedgerLayout lo;
+    lo.count = 0;
+    lo.total = ledger_align(n * sizeof(int32_t));
+    lo.rec_f64 = lo.total + ledger_align(kLedgerFields * n * sizeof(double));
+    lo.rec_i32 = lo.rec_f64 + ledger_align(r * kLedgerFields * n * sizeof(double));
+    lo.bytes = lo.rec_i32 + ledger_align(r * kLedgerFields * n * sizeof(int32_t));
+    return lo;
+}
+
+// Append lane i's finished episode: the record goes to slot count % rows, the totals grow in episode order, count goes up
+// by one.  qoe is calculate_qoe's sum in episode_qoe_kernel's order, so the newest record equals abr_env_episode_qoe.
+ABR_HD void ledger_append(const EpisodeLedger &L, int64_t n_lanes, int64_t i, double wr, double wv, double ws, double wl,
+                          double rebuffer, double start_up, double latency, double variance, int32_t episode,
+                          int32_t trace_id, int32_t offset0, int32_t chunks, int32_t done) {
+    const LedgerLayout lo = ledger_layout(n_lanes, L.rows);
+    char *b = (char *)L.base;
+    int32_t *count = (int32_t *)(b + lo.count);
+    double *total = (double *)(b + lo.total), *rf = (double *)(b + lo.rec_f64);
+    int32_t *ri = (int32_t *)(b + lo.rec_i32);
+    const double qoe = wr * rebuffer + wv * variance + ws * start_up + wl * latency;
+    const int32_t c = count[i];
+    const int64_t slot = (int64_t)((uint32_t)c % (uint32_t)L.rows) * kLedgerFields;
+    count[i] = c + 1;
+    const double f[kLedgerFields] = {rebuffer, start_up, latency, variance, qoe};
+    const int32_t w[kLedgerFields] = {episode, trace_id, offset0, chunks, done};
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int q = 0; q < kLedgerFields; q++) {
+        total[q * n_lanes + i] = total[q * n_lanes + i] + f[q];
+        rf[(slot + q) * n_lanes + i] = f[q];
+        ri[(slot + q) * n_lanes + i] = w[q];
+    }
+}
+
 }  // namespace abrx
 #endif

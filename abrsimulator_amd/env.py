@@ -12,6 +12,7 @@ import torch
 
 from . import _lib
 from .episodes import EpisodeSampler
+from .ledger import EpisodeLedger
 from .speed import LatencySpeedController
 from ._lib import F64_DIM, F64_ROWS, OBS_DIM, OBS_ROWS
 from .datamodel import MPD, NetworkInfo, QOEMetric
@@ -159,6 +160,39 @@ class BatchedABREnv:
         self.trace_id = None
         self.start_offset = None
         self.episode_sampler = None
+        self.episode_ledger = None
+
+    def set_episode_ledger(self, rows):
+        """Record every finished episode on the device (include/abr_env.h: abr_episode_ledger): while a ledger is
+        installed, each lane whose episode ends with ABR_DONE_EPISODE or ABR_DONE_TIMEOUT appends one record -- the QoE
+        terms episode_qoe() reads, their weighted sum, the episode's number, trace id, start offset, chunk count and done
+        byte -- to a ring of `rows` slots per lane, and adds it to per-lane running totals.  Returns the EpisodeLedger
+        (ledger.py: count(), totals(), ring(), records(), per_trace(), clear()); env.episode_ledger holds it and keeps
+        its blob alive.  `rows` may also be an EpisodeLedger built for this env's lane count and device (to continue a
+        restored one).  set_episode_ledger(None) turns recording off.  reset() never touches the ledger."""
+        if rows is None:
+            self._check(self.lib.abr_env_set_episode_ledger(self._h, None))
+            self.episode_ledger = None
+            return None
+        if isinstance(rows, EpisodeLedger):
+            led = rows
+            if led.n_lanes != self.n_lanes or led.device != self.device:
+                raise ValueError(f"the ledger is for {led.n_lanes} lanes on {led.device}, this env has {self.n_lanes} "
+                                 f"on {self.device}")
+        else:
+            with torch.cuda.device(self.device):
+                led = EpisodeLedger(self.n_lanes, int(rows), self.device)
+        nbytes = C.c_size_t()
+        self._check(self.lib.abr_env_ledger_bytes(self.n_lanes, led.rows, C.byref(nbytes)))
+        if nbytes.value != led.blob.numel():
+            raise RuntimeError(f"ledger layout mismatch: the library wants {nbytes.value} bytes, ledger.py laid out "
+                               f"{led.blob.numel()}")
+        st = _lib.EpisodeLedger()
+        st.base_dev, st.rows, st.reserved_ = led.blob.data_ptr(), led.rows, 0
+        self._check(self.lib.abr_env_set_episode_ledger(self._h, C.byref(st)))
+        # the library holds the blob's address: the ledger must live as long as it is installed
+        self.episode_ledger = led
+        return led
 
     def set_episode_sampler(self, seed, pool=None, offset_span: int = 0):
         """Draw each episode's (trace, start offset) on the device (include/abr_env.h: abr_episode_sampler): under

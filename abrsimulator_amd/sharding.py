@@ -219,6 +219,15 @@ class ShardedABREnv:
         so every rank with the same sampler reproduces its slice of the unsharded run."""
         self.env.set_episode_sampler(seed, pool, offset_span)
 
+    def set_episode_ledger(self, rows):
+        """BatchedABREnv.set_episode_ledger on this rank's stepper.  The ledger is per shard: its lanes are this shard's,
+        in shard order (global lane = lane_id_base + i), and nothing is gathered across ranks."""
+        return self.env.set_episode_ledger(rows)
+
+    @property
+    def episode_ledger(self):
+        return self.env.episode_ledger
+
     def reset(self, trace_id=None, start_offset=None, mask=None, sample=False):
         """Default: the deterministic global-lane map (lane_assignment); or this shard's own trace ids / offsets; or, with
         sample=True, the episode sampler's pairs (set_episode_sampler).

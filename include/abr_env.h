@@ -348,6 +348,50 @@ int abr_env_step_script(abr_env *env, int32_t n_steps, const int32_t *actions_de
  * episode overwrites as it goes, so the answer is meaningful again once that episode has ended. */
 int abr_env_episode_qoe(abr_env *env, double *qoe_out_dev, void *stream);
 
+/*
+ * Episode ledger (ABI 4, additive; BUILD-DEFINED).  abr_env_episode_qoe answers for a lane's LAST finished episode only,
+ * and the per-step reward leaves the latency term out: a fused launch that finishes several episodes per lane keeps one.
+ * While a ledger is installed, every env kernel appends one record per finished episode to a caller-owned blob.
+ *
+ * THE RULE: a record is appended exactly when the kernels write the episode's QoE terms (what abr_env_episode_qoe reads):
+ * at the step at which a lane's episode ends with ABR_DONE_EPISODE or ABR_DONE_TIMEOUT, in every launch kind
+ * (abr_env_step, _step_random, _step_script, _step_rule, _step_fastmpc, _step_mpc, _step_mpc_robust, _step_policy,
+ * _step_policy_sampled) on every implementation that accepts it (0, 1, 2, 3, 5).  Hence: a lane frozen by
+ * ABR_DONE_BADACT / ABR_DONE_BADARG appends nothing; an episode abandoned by a (masked) abr_env_reset appends nothing; a
+ * timed-out lane appends one record, once (later launches leave a done lane untouched); and a lane that runs out of ticks
+ * BEFORE its new episode's first call site (a reset or a re-arm that ends in ABR_DONE_TIMEOUT without a single decision)
+ * appends nothing for that episode either, because no QoE terms are written for it.
+ *
+ * The blob, abr_env_ledger_bytes(n_lanes, rows) bytes at a 256-byte aligned address: struct-of-arrays with row stride
+ * n_lanes; every region starts at the next multiple of 256 bytes after the previous one, in this order:
+ *   count   int32   [n_lanes]            episodes recorded for the lane since the blob was zeroed (< 2^31)
+ *   total   float64 [5][n_lanes]         running sums over ALL recorded episodes of the lane, added in episode order
+ *   rec_f64 float64 [rows][5][n_lanes]   the five float fields of the record in each ring slot
+ *   rec_i32 int32   [rows][5][n_lanes]   the five int fields of the record in each ring slot
+ * float fields: 0 rebuffer_time, 1 start_up_time, 2 average_latency, 3 variance (sum of |bitrate steps|), 4 qoe, where
+ *   qoe = wr * rebuffer_time + wv * variance + ws * start_up_time + wl * average_latency
+ * in that order (abr_env_episode_qoe's), so a lane's newest record's qoe equals abr_env_episode_qoe bit for bit.
+ * int fields: 0 the lane's episode number while the episode ran (abr_env_get_episode), 1 its trace id, 2 its start offset
+ * (the FINISHED episode's pair, not the re-armed one's), 3 chunks downloaded (chunk_id at the end: video_length unless
+ * timed out), 4 the done byte (ABR_DONE_EPISODE or ABR_DONE_TIMEOUT).
+ * A record goes to slot count % rows, then count is incremented: the ring keeps the lane's last min(count, rows) episodes,
+ * the totals keep all of them.  An all-zero blob is an empty ledger; the caller clears it by zeroing it, on the stream
+ * the launches run on.  abr_env_reset does not touch it.  It is not part of the workspace (layout and checkpoints unchanged).
+ *
+ * abr_env_ledger_bytes is pure arithmetic: it needs no handle and no device.  ABR_E_INVALID: n_lanes < 1, rows < 1, NULL
+ * bytes_out.  abr_env_set_episode_ledger copies the struct (l == NULL: off; the next launch appends nothing).  Refused
+ * with ABR_E_INVALID before anything is stored: rows < 1, base_dev NULL or not 256-byte aligned.  base_dev must stay valid
+ * while installed, and must have been sized for this handle's n_lanes.  The diagnostic pipelines 4, 6 and 7 refuse a
+ * launch with a ledger (ABR_E_UNSUPPORTED), as they do a sampler.
+ */
+typedef struct abr_episode_ledger {
+    void   *base_dev;           /* caller-owned, 256-B aligned, >= abr_env_ledger_bytes(); all-zero bytes = empty ledger */
+    int32_t rows;               /* ring slots per lane, >= 1 */
+    int32_t reserved_;          /* 0 */
+} abr_episode_ledger;           /* 16 bytes */
+int abr_env_ledger_bytes(int32_t n_lanes, int32_t rows, size_t *bytes_out);
+int abr_env_set_episode_ledger(abr_env *env, const abr_episode_ledger *l);
+
 /* Full float64 observation, [ABR_F64_DIM][n_lanes]. */
 int abr_env_observe_f64(abr_env *env, double *out_dev, void *stream);
 

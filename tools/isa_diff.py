@@ -6,7 +6,8 @@
 Bodies are compared without comments, with basic-block label numbers normalised, and with the kernel's own symbol name
 normalised (so that a template whose signature grew a trailing argument -- a different mangled name -- is still compared
 with its old self; --strip SUFFIX removes that suffix from the new names, default: the RuleParams argument's mangling;
-give it more than once to strip several, e.g. a defaulted template flag's `Lb0E` as well).  A template instance's
+give it more than once to strip several, e.g. a defaulted template flag's `Lb0E` as well; --sub REGEX=REPL rewrites the
+new names where removing a substring is not enough).  A template instance's
 comdat `.section` directive compares equal to the plain `.text` of the function it replaced.
 Prints one line per kernel that differs, every kernarg-size change, the kernels that are new, and a summary."""
 import argparse
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("old")
     ap.add_argument("new")
     ap.add_argument("--strip", action="append")
+    ap.add_argument("--sub", action="append", default=[], metavar="REGEX=REPL",
+                    help="rewrite the new names with re.sub before comparing, e.g. a new defaulted template flag in the middle")
     a = ap.parse_args()
     strips = a.strip if a.strip is not None else ["N4abrx10RuleParamsE"]
     old = kernels(a.old)
@@ -43,6 +46,9 @@ def main():
         for suffix in strips:
             if suffix:
                 short = short.replace(suffix, "")
+        for rule in a.sub:
+            pat, _, repl = rule.partition("=")
+            short = re.sub(pat, repl, short)
         new[short] = (body.replace(name, short), ka)
     same = 0
     for name, (body, ka) in sorted(old.items()):
