@@ -4,6 +4,8 @@ Importing the package loads the HIP library eagerly; if it has not been built
 the import fails (there is no CPU fallback).
 """
 from . import _lib
+from . import advantage
+from .advantage import gae
 from .datamodel import MPD, Chunk, ChunkInfo, NetworkInfo, QOEMetric
 from .env import BatchedABREnv, obs_dict, pack_traces
 from .episodes import EpisodeSampler
@@ -22,6 +24,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "EpisodeSampler", "EpisodeLedger",
+           "EpisodeSampler", "EpisodeLedger", "advantage", "gae",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

@@ -118,6 +118,10 @@ class PolicySampling(C.Structure):
     _fields_ = [("mode", C.c_int32), ("inv_temperature", C.c_float), ("reserved_", C.c_int32 * 6)]
 
 
+class PolicyValue(C.Structure):
+    _fields_ = [("head_dev", C.c_void_p), ("head_bytes", C.c_size_t), ("reserved_", C.c_int32 * 4)]
+
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -199,6 +203,11 @@ SYMBOLS = [
     ("abr_env_policy_select_sampled", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), _P, _P, _P, _P, _P]),
     ("abr_env_step_policy_sampled", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.c_int32, _P, _P, _P,
                                               _P, _P, _P, _P, _P]),
+    ("abr_env_policy_select_ac", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.POINTER(PolicyValue), _P, _P,
+                                           _P, _P, _P, _P]),
+    ("abr_env_step_policy_ac", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                         C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

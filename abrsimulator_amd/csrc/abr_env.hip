@@ -2866,13 +2866,27 @@ struct PolicyArgs {
     float inv_temperature;
 };
 
+// the VALUE instances' arguments (abr_policy_value): PolicyArgs itself stays what the other instances were compiled for
+struct PolicyValueArgs : PolicyArgs {
+    const float *head;                // [in + 1]: Wv then bv
+    float *value_out;                 // [N], nullable
+};
+
 // SAMPLED: the instance behind abr_env_policy_select_sampled.  It keeps each lane's scores in its own column of LDS past
 // the weights (M * kPolicyBlock floats; the score loops run to a runtime M), where the draw turns them into e_m.
-template <bool SAMPLED = false>
-__global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p, PolicyArgs a) {
+// VALUE: the instances behind the _ac entries.  The value head is one more row of the staged layout and one more fmaf
+// chain of the forward pass; with a NULL action_out the launch stores no decision: a value evaluation only.
+template <bool SAMPLED = false, bool VALUE = false>
+__global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(
+    EnvParams p, std::conditional_t<VALUE, PolicyValueArgs, PolicyArgs> a) {
     extern __shared__ float w_lds[];
-    const abrx::PolicyLayout lay = abrx::policy_layout(a.net);
-    for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock) w_lds[d] = abrx::policy_padded(a.net, lay, a.weights, d);
+    const abrx::PolicyLayout lay = abrx::policy_layout<VALUE>(a.net);
+    if constexpr (VALUE) {
+        for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock)
+            w_lds[d] = abrx::policy_padded<true>(a.net, lay, a.weights, d, a.head);
+    } else {
+        for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock) w_lds[d] = abrx::policy_padded(a.net, lay, a.weights, d);
+    }
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kPolicyBlock + threadIdx.x;
     if (i >= p.n_lanes) return;
@@ -2880,6 +2894,10 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p
     const abrx::PolicyNet &n = a.net;
     const int32_t c = p.chunk_id[i];
     if (p.done[i] || c < 0 || c >= p.video_length) {
+        if constexpr (VALUE) {
+            if (a.value_out) a.value_out[i] = 0.0f;
+            if (!a.action_out) return;
+        }
         a.action_out[i] = -1;
         if (a.features_out)
             for (int32_t f = 0; f < n.F; f++) a.features_out[f * N + i] = 0.0f;
@@ -2906,22 +2924,34 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(EnvParams p
         }
     }
     float *so = a.scores_out;
+    [[maybe_unused]] float value = 0.0f;
+    const auto forward = [&](const auto &emit) {
+        if constexpr (VALUE) return abrx::policy_forward<true>(n, w_lds, x, emit, &value);
+        else return abrx::policy_forward(n, w_lds, x, emit);
+    };
+    int32_t action;
     if constexpr (!SAMPLED) {
         const auto emit = [&](int32_t m, float v) { if (so) so[m * N + i] = v; };
-        const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
-        a.action_out[i] = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+        const int32_t g = forward(emit);
+        action = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
     } else {
         float *col = w_lds + lay.total + threadIdx.x;            // this lane's scores, stride kPolicyBlock
         const auto emit = [&](int32_t m, float v) {
             col[m * kPolicyBlock] = v;
             if (so) so[m * N + i] = v;
         };
-        const int32_t g = abrx::policy_forward(n, w_lds, x, emit);
+        const int32_t g = forward(emit);
         float *po = a.probs_out;
         const auto buf = [&](int32_t m) -> float & { return col[m * kPolicyBlock]; };
         const auto prob = [&](int32_t m, float v) { if (po) po[m * N + i] = v; };
-        a.action_out[i] = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode,
-                                              a.inv_temperature, buf, prob);
+        action = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode, a.inv_temperature,
+                                     buf, prob);
+    }
+    if constexpr (VALUE) {
+        if (a.action_out) a.action_out[i] = action;
+        if (a.value_out) a.value_out[i] = value;
+    } else {
+        a.action_out[i] = action;
     }
 }
 
@@ -3001,6 +3031,14 @@ static void launch_policy(const abr_env *env, const PolicyArgs &a, hipStream_t s
     const size_t lds = ((size_t)abrx::policy_layout(a.net).total + (SAMPLED ? (size_t)a.net.M * kPolicyBlock : 0)) *
                        sizeof(float);
     hipLaunchKernelGGL(policy_select_kernel<SAMPLED>, dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
+                       dim3(kPolicyBlock), lds, st, env->p, a);
+}
+
+template <bool SAMPLED>
+static void launch_policy_value(const abr_env *env, const PolicyValueArgs &a, hipStream_t st) {
+    const size_t lds = ((size_t)abrx::policy_layout<true>(a.net).total + (SAMPLED ? (size_t)a.net.M * kPolicyBlock : 0)) *
+                       sizeof(float);
+    hipLaunchKernelGGL((policy_select_kernel<SAMPLED, true>), dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
                        dim3(kPolicyBlock), lds, st, env->p, a);
 }
 
@@ -3088,6 +3126,143 @@ extern "C" int abr_env_policy_select_sampled(abr_env *env, const abr_policy *pol
     a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
     a.probs_out = probs_out_dev; a.mode = smp->mode; a.inv_temperature = smp->inv_temperature;
     launch_policy<true>(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Actor-critic rollouts (include/abr_env.h: abr_policy_value, abr_gae)
+// ---------------------------------------------------------------------------
+// the value struct alone (before the handle)
+static int validate_value(const abr_policy_value *val) {
+    if (!val) return fail(ABR_E_INVALID, "value is NULL");
+    if (!val->head_dev || ((uintptr_t)val->head_dev & 3))
+        return fail(ABR_E_INVALID, "value head must be non-NULL and 4-byte aligned");
+    for (int32_t r : val->reserved_)
+        if (r) return fail(ABR_E_INVALID, "value reserved_ must be 0");
+    return ABR_OK;
+}
+
+// after the handle: the policy's arguments, then the head's size for the policy's shape
+static int policy_value_args(const abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                             const abr_policy_value *val, PolicyValueArgs *a) {
+    PolicyArgs base;
+    int rc = policy_args(env, pol, &base);
+    if (rc) return rc;
+    const size_t in = pol->n_hidden == 0 ? (size_t)base.net.F : (size_t)pol->width[pol->n_hidden - 1];
+    if (val->head_bytes != (in + 1) * sizeof(float))
+        return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
+    *a = PolicyValueArgs{};
+    static_cast<PolicyArgs &>(*a) = base;
+    a->mode = smp->mode; a->inv_temperature = smp->inv_temperature;
+    a->head = val->head_dev;
+    return ABR_OK;
+}
+
+// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
+static void launch_policy_ac(const abr_env *env, const PolicyValueArgs &a, hipStream_t st) {
+    if (a.mode == ABR_POLICY_ARGMAX && !a.probs_out) launch_policy_value<false>(env, a, st);
+    else launch_policy_value<true>(env, a, st);
+}
+
+extern "C" int abr_env_policy_select_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if ((rc = validate_sampling(smp))) return rc;
+    if ((rc = validate_value(val))) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyValueArgs a;
+    if ((rc = policy_value_args(env, pol, smp, val, &a))) return rc;
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
+    launch_policy_ac(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// step_policy with the VALUE instances, then one value evaluation of the state the launch leaves behind
+extern "C" int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if ((rc = validate_sampling(smp))) return rc;
+    if ((rc = validate_value(val))) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyValueArgs a;
+    if ((rc = policy_value_args(env, pol, smp, val, &a))) return rc;
+    if ((rc = require(kPolicyRollout, env->impl))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
+        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
+        launch_policy_ac(env, a, st);
+        HIP_TRY(hipGetLastError());
+        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
+    if (last_value_out_dev) {
+        // the bootstrap value: no decision is stored, so the workspace is left as the rollout left it
+        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
+        a.value_out = last_value_out_dev;
+        launch_policy_value<false>(env, a, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return ABR_OK;
+}
+
+// One thread per lane walks its column of the slabs from the last row to the first (abr_lane_jump.h: gae_lane): a row of
+// any slab is contiguous across the wave, so every access is coalesced, and the loads of kGaeRows rows are issued before
+// the dependent chain over them starts.  No LDS, no barrier.
+constexpr int kGaeBlock = 256, kGaeRows = 8;
+
+__global__ __launch_bounds__(kGaeBlock) void gae_kernel(const float *__restrict__ reward, const float *__restrict__ values,
+                                                        const float *__restrict__ last_value,
+                                                        const uint8_t *__restrict__ done, const int32_t *__restrict__ actions,
+                                                        int32_t T, int64_t N, float gamma, float lam,
+                                                        float *__restrict__ adv, float *__restrict__ ret) {
+    const int64_t i = (int64_t)blockIdx.x * kGaeBlock + threadIdx.x;
+    if (i >= N) return;
+    const auto rew = [&](int32_t t) { return reward[(int64_t)t * N + i]; };
+    const auto val = [&](int32_t t) { return values[(int64_t)t * N + i]; };
+    const auto term = [&](int32_t t) { return done[(int64_t)t * N + i] != 0; };
+    const auto out = [&](int32_t t, float a, float r) { adv[(int64_t)t * N + i] = a; ret[(int64_t)t * N + i] = r; };
+    if (actions) {
+        const auto dead = [&](int32_t t) { return actions[(int64_t)t * N + i] < 0; };
+        abrx::gae_lane<kGaeRows>(T, gamma, lam, last_value[i], rew, val, term, dead, out);
+    } else {
+        const auto dead = [](int32_t) { return false; };
+        abrx::gae_lane<kGaeRows>(T, gamma, lam, last_value[i], rew, val, term, dead, out);
+    }
+}
+
+extern "C" int abr_gae(const float *reward_dev, const float *values_dev, const float *last_value_dev,
+                       const uint8_t *done_dev, const int32_t *actions_dev, int32_t n_steps, int64_t n_lanes, float gamma,
+                       float lam, float *adv_out_dev, float *ret_out_dev, void *stream) {
+    if (n_steps < 1) return fail(ABR_E_INVALID, "gae n_steps must be >= 1");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "gae n_lanes must be >= 1");
+    if (!reward_dev || !values_dev || !last_value_dev || !done_dev || !adv_out_dev || !ret_out_dev)
+        return fail(ABR_E_INVALID, "gae NULL argument (reward, values, last_value, done, adv_out or ret_out)");
+    if (((uintptr_t)reward_dev | (uintptr_t)values_dev | (uintptr_t)last_value_dev | (uintptr_t)actions_dev |
+         (uintptr_t)adv_out_dev | (uintptr_t)ret_out_dev) & 3)
+        return fail(ABR_E_INVALID, "gae float32 and int32 slabs must be 4-byte aligned");
+    if (!(gamma >= 0.0f && gamma <= 1.0f)) return fail(ABR_E_INVALID, "gae gamma must be in [0, 1]");
+    if (!(lam >= 0.0f && lam <= 1.0f)) return fail(ABR_E_INVALID, "gae lam must be in [0, 1]");
+    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n_lanes + kGaeBlock - 1) / kGaeBlock)), dim3(kGaeBlock), 0,
+                       (hipStream_t)stream, reward_dev, values_dev, last_value_dev, done_dev, actions_dev, n_steps, n_lanes,
+                       gamma, lam, adv_out_dev, ret_out_dev);
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }

@@ -876,10 +876,14 @@ ABR_HD float relu_f32(float v) { return v > 0.0f ? v : 0.0f; }   // NaN and -0 -
 // as the contract's.  The layer-1 and single-hidden-layer output weights are stored transposed ([k][j]), the order in which
 // hidden unit k adds its term into every accumulator j.
 constexpr int kPolicyRowF = kPolicyMaxF, kPolicyRowH = kPolicyMaxWidth, kPolicyRowM = kPolicyMaxRates;
-struct PolicyLayout { int32_t W0, b0, W1, b1, Wo, bo, total; };
+// VALUE (include/abr_env.h: abr_policy_value): one more row after everything else, the value head's weights padded to the
+// width of its input (kPolicyRowH after a hidden layer, kPolicyRowF without one) and then its bias.  The offsets of the
+// policy's own rows do not move.
+struct PolicyLayout { int32_t W0, b0, W1, b1, Wo, bo, total, Wv, bv; };
 
 ABR_HD int32_t policy_align4(int32_t x) { return (x + 3) & ~3; }
 
+template <bool VALUE = false>
 ABR_HD PolicyLayout policy_layout(const PolicyNet &n) {
     PolicyLayout L{};
     int32_t o = 0;
@@ -890,14 +894,25 @@ ABR_HD PolicyLayout policy_layout(const PolicyNet &n) {
     } else {
         L.Wo = o; o += n.M * (n.n_hidden == 0 ? kPolicyRowF : kPolicyRowH); L.bo = o; o = policy_align4(o + n.M);
     }
+    if (VALUE) { L.Wv = o; o += n.n_hidden == 0 ? kPolicyRowF : kPolicyRowH; L.bv = o; o += 4; }
     L.total = o;
     return L;
 }
 
-// Slot d of the padded layout, read from the packed blob (per layer Wt[out][in] row-major, then b[out])
-ABR_HD float policy_padded(const PolicyNet &n, const PolicyLayout &L, const float *__restrict__ blob, int32_t d) {
+// Slot d of the padded layout, read from the packed blob (per layer Wt[out][in] row-major, then b[out]); VALUE: the last
+// row from `head` (Wv[0..in) then bv, in = the width of the last hidden layer, or F without one)
+template <bool VALUE = false>
+ABR_HD float policy_padded(const PolicyNet &n, const PolicyLayout &L, const float *__restrict__ blob, int32_t d,
+                           const float *__restrict__ head = nullptr) {
     const float pw = -0.0f, pb = 0.0f;
     const int32_t F = n.F, H0 = n.w0, H1 = n.w1, M = n.M;
+    if (VALUE) {
+        if (d >= L.Wv) {
+            const int32_t in = n.n_hidden == 0 ? F : n.n_hidden == 1 ? H0 : H1, k = d - L.Wv;
+            if (d < L.bv) return k < in ? head[k] : pw;
+            return d == L.bv ? head[in] : pb;
+        }
+    }
     int32_t o = 0;                                            // packed offset of the current layer
     if (n.n_hidden >= 1) {
         if (d >= L.W0 && d < L.b0) { const int32_t k = (d - L.W0) / kPolicyRowF, i = (d - L.W0) % kPolicyRowF;
@@ -936,9 +951,12 @@ ABR_HD float dot_row(const float *__restrict__ row, float b, const float *in) {
 
 // The forward pass and the first argmax over the padded layout `w` (policy_layout / policy_padded); x[i] = +0 for
 // i >= F.  emit(j, score_j) is called once per output j in order.  Returns g.
-template <class Emit>
-ABR_HD int32_t policy_forward(const PolicyNet &n, const float *__restrict__ w, const float x[kPolicyMaxF], const Emit &emit) {
-    const PolicyLayout L = policy_layout(n);
+// VALUE: *value = bv, then fmaf(Wv[k], y[k], v) over the last hidden layer's post-ReLU outputs y (x without a hidden layer)
+// in k order -- one more chain of the same kind, which reads what the scores read and feeds nothing back into them.
+template <bool VALUE = false, class Emit>
+ABR_HD int32_t policy_forward(const PolicyNet &n, const float *__restrict__ w, const float x[kPolicyMaxF], const Emit &emit,
+                              float *value = nullptr) {
+    const PolicyLayout L = policy_layout<VALUE>(n);
     const int32_t M = n.M;
     int32_t g = 0;
     float best = 0.0f;
@@ -949,20 +967,24 @@ ABR_HD int32_t policy_forward(const PolicyNet &n, const float *__restrict__ w, c
     };
     if (n.n_hidden == 0) {
         for (int32_t j = 0; j < M; j++) take(j, dot_row<kPolicyRowF>(w + L.Wo + j * kPolicyRowF, w[L.bo + j], x));
+        if (VALUE) *value = dot_row<kPolicyRowF>(w + L.Wv, w[L.bv], x);
     } else if (n.n_hidden == 1) {
         // hidden unit k, then its term in every output accumulator: each output stays a k-ordered chain
         float acc[kPolicyRowM];
 #pragma unroll
         for (int j = 0; j < kPolicyRowM; j++) acc[j] = w[L.bo + j];
+        float accv = VALUE ? w[L.bv] : 0.0f;
         for (int32_t k = 0; k < n.w0; k++) {
             const float hk = relu_f32(dot_row<kPolicyRowF>(w + L.W0 + k * kPolicyRowF, w[L.b0 + k], x));
             const float *wk = w + L.Wo + k * kPolicyRowM;
 #pragma unroll
             for (int j = 0; j < kPolicyRowM; j++) acc[j] = fmaf(wk[j], hk, acc[j]);
+            if (VALUE) accv = fmaf(w[L.Wv + k], hk, accv);
         }
 #pragma unroll
         for (int j = 0; j < kPolicyRowM; j++)
             if (j < M) take(j, acc[j]);
+        if (VALUE) *value = accv;
     } else {
         // layer-0 unit k, then its term in every layer-1 accumulator; then the output layer unit by unit
         float acc[kPolicyRowH];
@@ -977,6 +999,7 @@ ABR_HD int32_t policy_forward(const PolicyNet &n, const float *__restrict__ w, c
 #pragma unroll
         for (int j = 0; j < kPolicyRowH; j++) acc[j] = relu_f32(acc[j]);
         for (int32_t j = 0; j < M; j++) take(j, dot_row<kPolicyRowH>(w + L.Wo + j * kPolicyRowH, w[L.bo + j], acc));
+        if (VALUE) *value = dot_row<kPolicyRowH>(w + L.Wv, w[L.bv], acc);
     }
     return g;
 }
@@ -1052,6 +1075,55 @@ ABR_HD int32_t policy_decide(const PolicyNet &n, uint64_t lane, int32_t c, int32
     philox4(n.seed, lane, (uint32_t)c, (uint32_t)episode, r);
     const int32_t s = policy_softmax_sample(n.M, g, iT, r[2], buf, prob);
     return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : s;
+}
+
+// Generalised advantage estimation over [T][N] rollout slabs (include/abr_env.h: abr_gae), one lane.  Every operation is
+// float32 with one rounding; q and w are selects, so a non-finite value behind an episode end never reaches the sum.
+// rew(t), val(t) -> float; term(t) -> bool (any done bit); dead(t) -> bool (a step that took no decision);
+// out(t, adv, ret).  Rows are taken in blocks of U, newest block first: a block's reads are all issued before its
+// dependent chain starts (on the device U rows of loads are in flight while the previous block's arithmetic retires).
+struct GaeCarry { float A, nv; };
+
+template <int U, bool FULL, class Rew, class Val, class Term, class Dead, class Out>
+ABR_HD void gae_block(GaeCarry &s, float gamma, float gl, int32_t lo, int32_t cnt, const Rew &rew, const Val &val,
+                      const Term &term, const Dead &dead, const Out &out) {
+    float r[U], v[U];
+    bool tm[U], dd[U];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int u = 0; u < U; u++) {
+        if (FULL || u < cnt) { r[u] = rew(lo + u); v[u] = val(lo + u); tm[u] = term(lo + u); dd[u] = dead(lo + u); }
+    }
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int u = U - 1; u >= 0; u--) {
+        if (FULL || u < cnt) {
+            if (dd[u]) {
+                s.A = 0.0f; s.nv = 0.0f;
+                out(lo + u, 0.0f, 0.0f);
+            } else {
+                const float q = tm[u] ? 0.0f : gamma * s.nv;
+                const float delta = (r[u] + q) - v[u];
+                const float w = tm[u] ? 0.0f : gl * s.A;
+                s.A = delta + w;
+                out(lo + u, s.A, s.A + v[u]);
+                s.nv = v[u];
+            }
+        }
+    }
+}
+
+template <int U, class Rew, class Val, class Term, class Dead, class Out>
+ABR_HD void gae_lane(int32_t T, float gamma, float lam, float last_value, const Rew &rew, const Val &val,
+                     const Term &term, const Dead &dead, const Out &out) {
+    const float gl = gamma * lam;
+    GaeCarry s{0.0f, last_value};
+    int32_t hi = T;
+    const int32_t part = T % U;                                // the newest rows that do not fill a block
+    if (part) { hi -= part; gae_block<U, false>(s, gamma, gl, hi, part, rew, val, term, dead, out); }
+    for (; hi > 0; hi -= U) gae_block<U, true>(s, gamma, gl, hi - U, U, rew, val, term, dead, out);
 }
 
 // The episode sampler (include/abr_env.h: abr_episode_sampler, the same layout): which (trace, start offset) episode e of

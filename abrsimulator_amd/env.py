@@ -459,15 +459,19 @@ class BatchedABREnv:
         return out
 
     def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
-                    want_scores=False, want_probs=False):
+                    want_scores=False, want_probs=False, want_values=False):
         """n_steps decisions per lane taken by a learned policy (policy.py: PolicyController) on the device, each one the
         policy kernel on every lane's own call-site state followed by the download of that chunk, with no host work
         between decisions.  Every event-driven kernel; 'tick' is refused (include/abr_env.h).  Returns
         dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N], features[n,F,N], scores[n,M,N], probs[n,M,N]);
         an entry that is not wanted is None.  A controller with sample="softmax" draws each action on the device
-        (abr_env_step_policy_sampled); probs is the policy's distribution at each decision, before exploration."""
+        (abr_env_step_policy_sampled); probs is the policy's distribution at each decision, before exploration.
+        want_values=True (a controller with a value head; ValueError without one) adds values[n,N], the critic's V of the
+        state each decision was taken in, and last_value[N], V of the state the launch leaves behind -- what
+        advantage.gae needs next to reward, done and actions (abr_env_step_policy_ac)."""
         n = int(n_steps)
         pol = controller.bound(self)
+        val = controller.value() if want_values or (out is not None and out.get("values") is not None) else None
         if out is None:
             out = self._rollout_out(n, want_obs, want_actions)
             N, dev = self.n_lanes, self.device
@@ -475,6 +479,16 @@ class BatchedABREnv:
                                if want_features else None)
             out["scores"] = torch.empty(n, self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None
             out["probs"] = torch.empty(n, self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None
+            if val is not None:
+                out["values"] = torch.empty(n, N, dtype=torch.float32, device=dev)
+                out["last_value"] = torch.empty(N, dtype=torch.float32, device=dev)
+        if val is not None:
+            smp = controller.sampling()
+            self._call(self.lib.abr_env_step_policy_ac, self._h, C.byref(pol), C.byref(smp), C.byref(val), n,
+                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
+                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
+                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")))
+            return out
         if controller.uses_sampled_entries(out.get("probs") is not None):
             smp = controller.sampling()
             self._call(self.lib.abr_env_step_policy_sampled, self._h, C.byref(pol), C.byref(smp), n,

@@ -11,6 +11,12 @@ draw -- is include/abr_env.h: abr_policy; the arithmetic is csrc/abr_lane_jump.h
 A stochastic policy (A2C, PPO) samples on the device instead: PolicyController(..., sample="softmax", temperature=T)
 draws each action from softmax(scores / T), and want_probs=True returns that distribution (include/abr_env.h:
 abr_policy_sampling).
+
+An actor-critic trainer whose critic shares the actor's trunk hands the controller the critic's Linear(in, 1) head
+(value_head=...): select(want_value=True) and env.step_policy(ctl, n, want_values=True) then report V(s) of the state each
+decision was taken in, computed in the same kernel (include/abr_env.h: abr_policy_value).  A critic that is a separate
+network is the trainer's own business: one batched GEMM over the features slab, which torch does faster than any
+per-lane kernel.
 """
 import ctypes as C
 import math
@@ -49,12 +55,14 @@ class PolicyController:
     left), None (raw values), or (shift [F], scale [F]).  explore in [0, 1]: the probability of taking the random policy's
     action instead of the argmax (threshold floor(explore * 2^32)), drawn with `seed` exactly as step_random draws.
     sample: "argmax" (the first argmax) or "softmax" (a draw from softmax(scores / temperature) with word 2 of the same
-    philox block); temperature > 0, passed as float32(1 / temperature).  Both can be changed between launches."""
+    philox block); temperature > 0, passed as float32(1 / temperature).  Both can be changed between launches.
+    value_head: None, or (Wv [in] or [1, in], bv scalar or [1]) -- the critic's head over the last hidden layer's output
+    (in = the last hidden width, or feature_dim without a hidden layer)."""
 
     method = "policy"
 
     def __init__(self, player, layers, window=8, norm="default", explore=0.0, seed=0, device=None, sample="argmax",
-                 temperature=1.0):
+                 temperature=1.0, value_head=None):
         self.player = player
         env = getattr(player, "env", None)
         self.device = torch.device(device) if device is not None else (env.device if env is not None else
@@ -84,7 +92,12 @@ class PolicyController:
         _lib.check(_lib.lib().abr_policy_weights_bytes(C.byref(self._struct(0, 0, None)), self.n_rates,
                                                        C.byref(nbytes)))
         self.weights = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
-        self.load_weights(layers)
+        self.value_in = self.widths[-1] if self.widths else self.feature_dim
+        self.value_head = None
+        if value_head is not None:
+            self._head_parts(value_head)                                  # refuse a bad head before anything is allocated
+            self.value_head = torch.zeros(self.value_in + 1, dtype=torch.float32, device=self.device)
+        self.load_weights(layers, value_head=value_head)
         self.norm = self._norm(norm, mpd)
         self.explore = explore
         self.seed = int(seed)
@@ -93,10 +106,32 @@ class PolicyController:
 
     # -- construction ----------------------------------------------------------
     @classmethod
-    def from_module(cls, player, module, **kw):
-        """From nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers; any other shape is refused."""
+    def from_module(cls, player, module, value_head=None, **kw):
+        """From nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers; any other shape is refused.
+        value_head: the critic's nn.Linear(in, 1) over the last hidden layer's output (or (Wv, bv))."""
         layers = cls.module_layers(module)
-        return cls(player, layers, **kw)
+        return cls(player, layers, value_head=value_head, **kw)
+
+    def _head_parts(self, head):
+        """(Wv, bv) of a value head -- an nn.Linear(value_in, 1) with a bias, or a (Wv, bv) pair -- after checking it
+        against this policy's shape; ValueError otherwise."""
+        if isinstance(head, torch.nn.Module):
+            if type(head) is not torch.nn.Linear:
+                raise ValueError(f"a value head is nn.Linear({self.value_in}, 1), got {type(head).__name__}")
+            if head.bias is None:
+                raise ValueError("value head: Linear without a bias")
+            if head.in_features != self.value_in or head.out_features != 1:
+                raise ValueError(f"value head: Linear({head.in_features}, {head.out_features}), this policy needs "
+                                 f"Linear({self.value_in}, 1)")
+            return head.weight, head.bias
+        try:
+            Wv, bv = head
+        except (TypeError, ValueError):
+            raise ValueError("value_head is nn.Linear(in, 1) or (Wv, bv)") from None
+        if tuple(np.shape(Wv)) not in ((self.value_in,), (1, self.value_in)) or tuple(np.shape(bv)) not in ((), (1,)):
+            raise ValueError(f"value head: Wv must be [{self.value_in}] or [1, {self.value_in}] and bv a scalar or [1], "
+                             f"got {tuple(np.shape(Wv))} / {tuple(np.shape(bv))}")
+        return Wv, bv
 
     @staticmethod
     def module_layers(module):
@@ -178,13 +213,21 @@ class PolicyController:
         return smp
 
     # -- the weights -------------------------------------------------------------
-    def load_weights(self, layers):
+    def load_weights(self, layers, value_head=None):
         """Copy new weights (a list of (W, b) of this controller's shapes, or an nn.Sequential) into the device blob in
-        place, on the current stream, without synchronising."""
+        place, on the current stream, without synchronising.  value_head (nn.Linear(in, 1) or (Wv, bv)) refreshes the
+        value head the same way; a controller built without one refuses it."""
         if isinstance(layers, torch.nn.Module):
             layers = self.module_layers(layers)
         if [tuple(np.shape(W)) for W, _ in layers] != self.shapes:
             raise ValueError(f"layer shapes {[tuple(np.shape(W)) for W, _ in layers]}, this policy has {self.shapes}")
+        if value_head is not None:
+            if self.value_head is None:
+                raise ValueError("this controller was built without a value head")
+            Wv, bv = self._head_parts(value_head)
+            with torch.no_grad():
+                self.value_head[:self.value_in].copy_(_as_f32(Wv, self.device).reshape(-1), non_blocking=True)
+                self.value_head[self.value_in:].copy_(_as_f32(bv, self.device).reshape(-1), non_blocking=True)
         o = 0
         with torch.no_grad():
             for W, b in layers:
@@ -223,15 +266,24 @@ class PolicyController:
             raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
         return self._struct(self.weights.data_ptr(), self.weights.numel() * 4, self.norm)
 
+    def value(self):
+        """The abr_policy_value struct (it points into this controller's value head); ValueError without a head."""
+        if self.value_head is None:
+            raise ValueError("values need a value head: PolicyController(..., value_head=(Wv, bv))")
+        v = _lib.PolicyValue()
+        v.head_dev, v.head_bytes = self.value_head.data_ptr(), self.value_head.numel() * 4
+        return v
+
     # -- decisions ---------------------------------------------------------------
     def feature_names(self):
         return (OBS_NAMES + [f"throughput[-{self.window - k}]" for k in range(self.window)] +
                 [f"bitrate[{m}]" for m in range(self.n_rates)])
 
-    def select(self, want_features=True, want_scores=True, want_probs=False):
+    def select(self, want_features=True, want_scores=True, want_probs=False, want_value=False):
         """One decision per lane on the environment's current state (no step): dict(actions int32 [N], features float32
         [F, N], scores float32 [M, N], probs float32 [M, N] -- the policy's distribution before exploration); a lane
-        whose done bits are set answers -1 with zero columns.  An entry that is not wanted is None."""
+        whose done bits are set answers -1 with zero columns.  An entry that is not wanted is None.  want_value=True
+        (a controller with a value head) adds value float32 [N], the critic's V of the current state, 0 on a done lane."""
         env = self.player.env
         N, dev = env.n_lanes, env.device
         out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
@@ -239,6 +291,13 @@ class PolicyController:
                    scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
                    probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
         pol = self.bound(env)
+        if want_value:
+            val, smp = self.value(), self.sampling()
+            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
+            env._call(env.lib.abr_env_policy_select_ac, env._h, C.byref(pol), C.byref(smp), C.byref(val),
+                      _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]),
+                      _lib.ptr(out["probs"]), _lib.ptr(out["value"]))
+            return out
         if self.uses_sampled_entries(want_probs):
             smp = self.sampling()
             env._call(env.lib.abr_env_policy_select_sampled, env._h, C.byref(pol), C.byref(smp),

@@ -356,7 +356,7 @@ int abr_env_episode_qoe(abr_env *env, double *qoe_out_dev, void *stream);
  * THE RULE: a record is appended exactly when the kernels write the episode's QoE terms (what abr_env_episode_qoe reads):
  * at the step at which a lane's episode ends with ABR_DONE_EPISODE or ABR_DONE_TIMEOUT, in every launch kind
  * (abr_env_step, _step_random, _step_script, _step_rule, _step_fastmpc, _step_mpc, _step_mpc_robust, _step_policy,
- * _step_policy_sampled) on every implementation that accepts it (0, 1, 2, 3, 5).  Hence: a lane frozen by
+ * _step_policy_sampled, _step_policy_ac) on every implementation that accepts it (0, 1, 2, 3, 5).  Hence: a lane frozen by
  * ABR_DONE_BADACT / ABR_DONE_BADARG appends nothing; an episode abandoned by a (masked) abr_env_reset appends nothing; a
  * timed-out lane appends one record, once (later launches leave a done lane untouched); and a lane that runs out of ticks
  * BEFORE its new episode's first call site (a reset or a re-arm that ends in ABR_DONE_TIMEOUT without a single decision)
@@ -838,6 +838,70 @@ int abr_env_step_policy_sampled(abr_env *env, const abr_policy *pol, const abr_p
                                 float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
                                 int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
                                 float *probs_out_dev, void *stream);
+
+/*
+ * Actor-critic rollouts (ABI 4, additive; BUILD-DEFINED): the critic's estimate V(s_t) of the state each decision was
+ * taken in, for a critic that shares the actor's trunk -- a Linear(in, 1) head next to the Linear(in, M) output layer.
+ * Everything but one dot product is already computed by the policy's forward pass.  (A critic that is a separate network
+ * is left to the trainer: it is one batched GEMM over the features slab.)
+ *
+ * head_dev: float32 [in + 1], Wv[0..in) then bv; in = width[n_hidden - 1], or F when n_hidden == 0.
+ * Value: v = bv, then v = fmaf(Wv[k], y[k], v) for k = 0, 1, .., in - 1 in that order, y = the last hidden layer's
+ * post-ReLU output (x when n_hidden == 0): the chain rule of every other output of abr_policy.  The value takes no part
+ * in the argmax, the softmax or the exploration, and the scores are bit for bit what they are without it.
+ * A lane whose done bits are set reports value 0.0f.
+ */
+typedef struct abr_policy_value {
+    const float *head_dev;                /* device, 4-byte aligned, non-NULL */
+    size_t head_bytes;                    /* == (in + 1) * 4 */
+    int32_t reserved_[4];                 /* set to 0 */
+} abr_policy_value;
+
+/* abr_env_policy_select_sampled with value_out_dev float32 [n_lanes] (nullable).  smp with ABR_POLICY_ARGMAX gives
+ * abr_env_policy_select's actions and a one-hot probs.  Validation (ABR_E_INVALID, nothing launched): pol, smp, then val
+ * (non-NULL, head non-NULL and aligned, reserved_ zero), all before the handle; then weights_bytes and head_bytes against
+ * the shape. */
+int abr_env_policy_select_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                             const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                             float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream);
+
+/* abr_env_step_policy_sampled with values_out_dev float32 [n_steps][n_lanes] (nullable), the value of the state each
+ * decision was taken in, and last_value_out_dev float32 [n_lanes] (nullable), the value of each lane's state after the
+ * last step: one more evaluation of the forward pass at the end of the call that stores no decision.  It is 0.0f
+ * for a lane whose done bits are set; under auto_reset a lane that finished on the last step reports the re-armed episode's
+ * first state (abr_gae never reads it there: done[n_steps - 1] ends the recurrence).  Every other output and the
+ * workspace are byte for byte what abr_env_step_policy_sampled leaves.  Validation as abr_env_policy_select_ac, with
+ * n_steps >= 1 before the handle; ABR_E_UNSUPPORTED on tick. */
+int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                           const abr_policy_value *val, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                           uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
+                           float *scores_out_dev, float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                           void *stream);
+
+/*
+ * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
+ * reward, values float32 [n_steps][n_lanes]; last_value float32 [n_lanes]; done uint8 [n_steps][n_lanes]; actions int32
+ * [n_steps][n_lanes] or NULL (every step is live); outputs adv, ret float32 [n_steps][n_lanes], which may not overlap
+ * the inputs.  gamma and lam are finite and in [0, 1].
+ *
+ * Exact: float32, round-to-nearest-even, one rounding per operation.  gl = gamma * lam.  Per lane i: A = 0,
+ * nv = last_value[i]; then for t = n_steps - 1 down to 0, with r = reward[t][i], v = values[t][i]:
+ *   a dead step (actions != NULL and actions[t][i] < 0: the lane took no decision) writes adv = ret = +0.0f and sets
+ *     A = 0, nv = 0;
+ *   otherwise, term = (done[t][i] != 0):
+ *     q = term ? 0 : gamma * nv;  delta = (r + q) - v;  w = term ? 0 : gl * A;  A = delta + w;
+ *     adv[t][i] = A;  ret[t][i] = A + v;  nv = v.
+ * q and w are selects, not products with a mask: a non-finite value behind an episode end makes no NaN in front of it.
+ * done[t] is set at the step that ends an episode and row t + 1 (under auto_reset) belongs to the next one, so the
+ * recurrence restarts at every set byte.  EVERY done bit ends it: ABR_DONE_EPISODE, _TIMEOUT, _BADACT, _BADARG.  A lane
+ * that timed out is never re-armed and has no next call site whose value could stand in for the truncated tail, so a
+ * time-out is treated as a terminal state, not bootstrapped.
+ * Refused (ABR_E_INVALID, nothing launched): n_steps < 1, n_lanes < 1, a NULL pointer other than actions, a float32 or
+ * int32 pointer that is not 4-byte aligned, gamma or lam outside [0, 1] (NaN included).
+ */
+int abr_gae(const float *reward_dev, const float *values_dev, const float *last_value_dev, const uint8_t *done_dev,
+            const int32_t *actions_dev, int32_t n_steps, int64_t n_lanes, float gamma, float lam, float *adv_out_dev,
+            float *ret_out_dev, void *stream);
 
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
