@@ -111,6 +111,15 @@ class Policy(C.Structure):
                 ("seed", C.c_uint64), ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
 
 
+POLICY_MX_MAX_HIDDEN, POLICY_MX_MAX_WIDTH = 3, 128
+
+
+class PolicyMx(C.Structure):
+    _fields_ = [("window", C.c_int32), ("n_hidden", C.c_int32), ("width", C.c_int32 * (POLICY_MX_MAX_HIDDEN + 1)),
+                ("weights_dev", C.c_void_p), ("weights_bytes", C.c_size_t), ("norm_dev", C.c_void_p),
+                ("seed", C.c_uint64), ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
+
+
 POLICY_ARGMAX, POLICY_SOFTMAX = 0, 1
 
 
@@ -206,6 +215,11 @@ SYMBOLS = [
     ("abr_env_policy_select_ac", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.POINTER(PolicyValue), _P, _P,
                                            _P, _P, _P, _P]),
     ("abr_env_step_policy_ac", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                         C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_policy_mx_weights_bytes", C.c_int, [C.POINTER(PolicyMx), C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_policy_select_mx", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue), _P,
+                                           _P, _P, _P, _P, _P]),
+    ("abr_env_step_policy_mx", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
                                          C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),

@@ -3223,6 +3223,388 @@ extern "C" int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The matrix engine of the learned policy (include/abr_env.h: abr_policy_mx): the same chains on v_mfma_f32_32x32x2_f32
+// ---------------------------------------------------------------------------
+// One thread per env lane for the prologue (policy_features) and the epilogue (policy_explore / policy_decide), as
+// policy_select_kernel; in between the wave is a matrix engine: the units of a layer are the rows of the product, its 64
+// env lanes are two tiles of 32 columns, and a layer is tiles x steps MFMAs per column tile, k ascending, on an
+// accumulator that starts as the bias (abr_lane_jump.h: the index maps and why the activations stay in registers).
+// 32x32x2 rather than 16x16x4: its K of 2 wastes at most one padded k per layer (the 16x16 form pads to 4), one
+// instruction covers 32 units x 32 lanes with a single A and B register, and its 64-cycle issue interval equals its
+// dependent latency, so the k chain of one accumulator already runs at the issue rate with one wave per SIMD.
+// Weights: the workgroup stages one layer at a time in LDS in operand order ([tile][step][wave lane], at most 64 KB: a
+// read is one conflict-free ds_read_b32 per MFMA), between two barriers; biases are read from the blob when an
+// accumulator is initialised.  No thread leaves before the last MFMA: a lane past n_lanes or a finished lane carries a
+// zero column (columns are independent) and is masked at the stores.
+constexpr int kMxBlock = 256;
+typedef float mx_acc_t __attribute__((ext_vector_type(16)));
+
+struct PolicyMxArgs {
+    abrx::PolicyNet net;              // window, M, F, norm, seed, thr (n_hidden, w0, w1 unused: the shape is below)
+    int32_t n_hidden, width[abrx::kMxMaxHidden];
+    const float *weights, *head;      // head: [in + 1] (VALUE instances only)
+    int32_t *action_out;              // [N]; NULL (VALUE only): a value evaluation that stores no decision
+    float *features_out, *scores_out, *probs_out, *value_out;
+    int32_t mode;
+    float inv_temperature;
+};
+
+// One layer on one column tile: acc[T] = bias, then the k chain; b[s] is this lane's B register of step s.  The steps are
+// taken in groups of kMxGroup: a group's A registers are all read from LDS before its first MFMA (one wait per group,
+// and the next group's reads are issued while the last MFMA of this one runs); a step of the group past the layer's
+// last one is an exact no-op, -0.0f against +0.0f.
+constexpr int kMxGroup = 4;
+
+template <int MAXT, int MAXS>
+__device__ __forceinline__ void mx_run_layer(const abrx::MxLayer &y, const float *__restrict__ a_lds, int32_t lane,
+                                             const float *b, mx_acc_t *acc) {
+    const int32_t tiles = abrx::mx_tiles(y), steps = abrx::mx_steps(y.in);
+#pragma unroll
+    for (int T = 0; T < MAXT; T++) {                         // every tile's biases are in flight before the first chain
+        if (T < tiles) {
+#pragma unroll
+            for (int r = 0; r < abrx::kMxRegs; r++) acc[T][r] = abrx::mx_bias(y, abrx::kMxTile * T + abrx::mx_acc_unit(lane, r));
+        }
+    }
+#pragma unroll
+    for (int T = 0; T < MAXT; T++) {
+        if (T < tiles) {
+            const float *at = a_lds + T * steps * abrx::kMxWave + lane;
+#pragma unroll
+            for (int g = 0; g < (MAXS + kMxGroup - 1) / kMxGroup; g++) {
+                if (g * kMxGroup < steps) {
+                    float av[kMxGroup], bv[kMxGroup];
+#pragma unroll
+                    for (int j = 0; j < kMxGroup; j++) {
+                        const int s = g * kMxGroup + j;
+                        const bool on = s < steps;
+                        const float w = at[(on ? s : steps - 1) * abrx::kMxWave];
+                        av[j] = on ? w : -0.0f;
+                        bv[j] = on ? b[s] : 0.0f;
+                    }
+#pragma unroll
+                    for (int j = 0; j < kMxGroup; j++)
+                        acc[T] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], bv[j], acc[T], 0, 0, 0);
+                }
+            }
+        }
+    }
+}
+
+template <bool SAMPLED, bool VALUE>
+__global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, PolicyMxArgs a) {
+    extern __shared__ float w_lds[];
+    constexpr int kMaxSteps = abrx::kMxMaxWidth / 2, kMaxTiles = abrx::kMxMaxWidth / abrx::kMxTile;
+    constexpr int kXSteps = abrx::kPolicyMaxF / 2;
+    const int64_t N = p.n_lanes;
+    const int64_t i = (int64_t)blockIdx.x * kMxBlock + threadIdx.x;
+    const int32_t lane = threadIdx.x & (abrx::kMxWave - 1);
+    const abrx::PolicyNet &n = a.net;
+    const bool inside = i < N;
+    int32_t c = 0;
+    bool live = false;
+    if (inside) {
+        c = p.chunk_id[i];
+        live = !(p.done[i] || c < 0 || c >= p.video_length);
+    }
+    const bool decide = !VALUE || a.action_out;              // false: a value evaluation only
+    float x[abrx::kPolicyMaxF];
+    if (live) {
+        const double G = p.G[p.k[i]];
+        const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
+        const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
+        const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+        abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    } else {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) x[f] = 0.0f;
+    }
+    if (inside && decide && a.features_out) {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) {
+            if (f < n.F) {
+                a.features_out[f * N + i] = x[f];
+            }
+        }
+    }
+    // this lane's B registers of the first layer, per column tile: input 2 s + (lane >> 5) of env lane 32 t + (lane & 31)
+    float h[2][kMaxSteps] = {};                              // a group's steps past the layer's last one read these: +0
+#pragma unroll
+    for (int t = 0; t < 2; t++) {
+        const int32_t src = abrx::kMxTile * t + abrx::mx_b_col(lane);
+#pragma unroll
+        for (int s = 0; s < kXSteps; s++) {
+            const float k0 = __shfl(x[2 * s], src), k1 = __shfl(x[2 * s + 1], src);
+            h[t][s] = abrx::mx_b_k(lane) ? k1 : k0;
+        }
+    }
+    const auto stage = [&](const abrx::MxLayer &y) {
+        __syncthreads();                                     // every wave has left the layer staged before
+        const int32_t tiles = abrx::mx_tiles(y), steps = abrx::mx_steps(y.in);
+        // A wave takes kBatch consecutive steps of a tile at a time: 16 consecutive k of 32 rows, so the 64-byte lines
+        // its gathers touch are used up within the batch (rows are unaligned, `in` apart: no wider read fits), and the
+        // batch's gathers are all issued before its first store.  No division: (tile, step) are the loop counters.
+        constexpr int kBatch = 8;
+        for (int32_t T = 0; T < tiles; T++) {
+            for (int32_t s0 = kBatch * (threadIdx.x / abrx::kMxWave); s0 < steps; s0 += kBatch * (kMxBlock / abrx::kMxWave)) {
+                float v[kBatch];
+#pragma unroll
+                for (int j = 0; j < kBatch; j++) v[j] = s0 + j < steps ? abrx::mx_staged_at(y, T, s0 + j, lane) : 0.0f;
+#pragma unroll
+                for (int j = 0; j < kBatch; j++) {
+                    if (s0 + j < steps) w_lds[abrx::mx_staged_slot(y, T, s0 + j, lane)] = v[j];
+                }
+            }
+        }
+        __syncthreads();
+    };
+    const float *head = VALUE ? a.head : nullptr;
+    mx_acc_t acc[kMaxTiles];
+    const auto activate = [&](const abrx::MxLayer &y) {      // the ReLU, into the next layer's B registers
+        const int32_t tiles = abrx::mx_tiles(y);
+        return [&, tiles](int t) {
+#pragma unroll
+            for (int T = 0; T < kMaxTiles; T++) {
+                if (T < tiles) {
+#pragma unroll
+                    for (int r = 0; r < abrx::kMxRegs; r++) h[t][abrx::kMxRegs * T + r] = abrx::relu_f32(acc[T][r]);
+                }
+            }
+        };
+    };
+    if (a.n_hidden >= 1) {
+        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, 0);
+        stage(y);
+        const auto relu = activate(y);
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            mx_run_layer<kMaxTiles, kXSteps>(y, w_lds, lane, h[t], acc);
+            relu(t);
+        }
+    }
+#pragma unroll 1
+    for (int32_t li = 1; li < a.n_hidden; li++) {
+        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, li);
+        stage(y);
+        const auto relu = activate(y);
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            mx_run_layer<kMaxTiles, kMaxSteps>(y, w_lds, lane, h[t], acc);
+            relu(t);
+        }
+    }
+    // the output layer (and the value head, one more row of its tile)
+    mx_acc_t out[2];
+    {
+        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, a.n_hidden);
+        stage(y);
+#pragma unroll
+        for (int t = 0; t < 2; t++) mx_run_layer<1, kMaxSteps>(y, w_lds, lane, h[t], &out[t]);
+    }
+    // unit u of env lane 32 t + j sits in register mx_unit_reg(u) of wave lane j + 32 mx_unit_half(u) of tile t: back to
+    // the thread that owns the env lane
+    const auto unit = [&](auto U) {
+        constexpr int u = decltype(U)::value;
+        const int32_t src = abrx::mx_d_col(lane) + abrx::kMxTile * abrx::mx_unit_half(u);
+        const float t0 = __shfl(out[0][abrx::mx_unit_reg(u)], src), t1 = __shfl(out[1][abrx::mx_unit_reg(u)], src);
+        return lane >> 5 ? t1 : t0;
+    };
+    float sc[abrx::kPolicyMaxRates];
+    [[maybe_unused]] float value = 0.0f;
+#define ABR_MX_UNIT(U) sc[U] = unit(std::integral_constant<int, U>{});
+    ABR_MX_UNIT(0) ABR_MX_UNIT(1) ABR_MX_UNIT(2) ABR_MX_UNIT(3) ABR_MX_UNIT(4) ABR_MX_UNIT(5) ABR_MX_UNIT(6) ABR_MX_UNIT(7)
+    ABR_MX_UNIT(8) ABR_MX_UNIT(9) ABR_MX_UNIT(10) ABR_MX_UNIT(11) ABR_MX_UNIT(12) ABR_MX_UNIT(13) ABR_MX_UNIT(14) ABR_MX_UNIT(15)
+#undef ABR_MX_UNIT
+    if constexpr (VALUE) value = unit(std::integral_constant<int, abrx::kMxValueUnit>{});
+    if (!inside) return;
+    if (!live) {
+        if constexpr (VALUE) {
+            if (a.value_out) a.value_out[i] = 0.0f;
+        }
+        if (!decide) return;
+        a.action_out[i] = -1;
+        if (a.scores_out)
+            for (int32_t m = 0; m < n.M; m++) a.scores_out[m * N + i] = 0.0f;
+        if constexpr (SAMPLED) {
+            if (a.probs_out)
+                for (int32_t m = 0; m < n.M; m++) a.probs_out[m * N + i] = 0.0f;
+        }
+        return;
+    }
+    if constexpr (VALUE) {
+        if (a.value_out) a.value_out[i] = value;
+    }
+    if (!decide) return;
+    float *so = a.scores_out;
+    [[maybe_unused]] float *col = w_lds + abrx::mx_score_offset(n.F, a.n_hidden, a.width) + threadIdx.x;
+    int32_t g = 0;
+    float best = 0.0f;
+#pragma unroll
+    for (int m = 0; m < abrx::kPolicyMaxRates; m++) {
+        if (m < n.M) {
+            const float v = sc[m];
+            if (so) so[m * N + i] = v;
+            if constexpr (SAMPLED) col[m * kMxBlock] = v;
+            if (m == 0) best = v;
+            else if (v > best) { best = v; g = m; }
+        }
+    }
+    int32_t action;
+    if constexpr (!SAMPLED) {
+        action = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+    } else {
+        float *po = a.probs_out;
+        const auto buf = [&](int32_t m) -> float & { return col[m * kMxBlock]; };
+        const auto prob = [&](int32_t m, float v) { if (po) po[m * N + i] = v; };
+        action = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode, a.inv_temperature,
+                                     buf, prob);
+    }
+    a.action_out[i] = action;
+}
+
+static int validate_policy_mx(const abr_policy_mx *pol) {
+    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
+    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
+    if (pol->n_hidden < 0 || pol->n_hidden > ABR_POLICY_MX_MAX_HIDDEN)
+        return fail(ABR_E_INVALID, "policy n_hidden %d outside 0..%d", pol->n_hidden, ABR_POLICY_MX_MAX_HIDDEN);
+    for (int l = 0; l < ABR_POLICY_MX_MAX_HIDDEN + 1; l++) {
+        const int32_t wl = pol->width[l];
+        if (l < pol->n_hidden && (wl < 1 || wl > ABR_POLICY_MX_MAX_WIDTH))
+            return fail(ABR_E_INVALID, "policy width[%d] = %d outside 1..%d", l, wl, ABR_POLICY_MX_MAX_WIDTH);
+        if (l >= pol->n_hidden && wl != 0) return fail(ABR_E_INVALID, "policy width[%d] must be 0 past n_hidden", l);
+    }
+    return ABR_OK;
+}
+
+static size_t policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t M) {
+    size_t in = 4 + (size_t)pol->window + (size_t)M, words = 0;
+    for (int l = 0; l <= pol->n_hidden; l++) {
+        const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
+        words += out * in + out;
+        in = out;
+    }
+    return words * sizeof(float);
+}
+
+extern "C" int abr_policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t n_rates, size_t *bytes_out) {
+    int rc = validate_policy_mx(pol);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *bytes_out = policy_mx_weights_bytes(pol, n_rates);
+    return ABR_OK;
+}
+
+// everything that is checked before the handle: the structs, then the outputs that need a struct that is absent
+static int validate_policy_mx_call(const abr_policy_mx *pol, const abr_policy_sampling *smp, const abr_policy_value *val,
+                                   const float *probs_out, const float *values_out, const float *last_value_out) {
+    int rc = validate_policy_mx(pol);
+    if (rc) return rc;
+    for (int32_t r : pol->reserved_)
+        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
+    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
+        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
+    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
+    if (pol->explore_threshold > (1ull << 32))
+        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
+    if (smp && (rc = validate_sampling(smp))) return rc;
+    if (val && (rc = validate_value(val))) return rc;
+    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
+    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
+    return ABR_OK;
+}
+
+// after the handle: the blob's and the head's sizes for the environment's n_rates
+static int policy_mx_args(const abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                          const abr_policy_value *val, PolicyMxArgs *a) {
+    const int32_t M = env->p.n_rates;
+    const size_t want = policy_mx_weights_bytes(pol, M);
+    if (pol->weights_bytes != want)
+        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
+    *a = PolicyMxArgs{};
+    a->net.window = pol->window; a->net.M = M; a->net.F = 4 + pol->window + M;
+    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
+    a->n_hidden = pol->n_hidden;
+    for (int l = 0; l < ABR_POLICY_MX_MAX_HIDDEN; l++) a->width[l] = pol->width[l];
+    a->weights = pol->weights_dev;
+    if (val) {
+        const size_t in = pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1];
+        if (val->head_bytes != (in + 1) * sizeof(float))
+            return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
+        a->head = val->head_dev;
+    }
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    return ABR_OK;
+}
+
+// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
+static void launch_policy_mx(const abr_env *env, const PolicyMxArgs &a, hipStream_t st) {
+    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
+    const dim3 grid((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)), block(kMxBlock);
+    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true>), grid, block, lds, st, env->p, a);
+    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false>), grid, block, lds, st, env->p, a);
+    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true>), grid, block, lds, st, env->p, a);
+    else hipLaunchKernelGGL((policy_mx_kernel<false, false>), grid, block, lds, st, env->p, a);
+}
+
+extern "C" int abr_env_policy_select_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
+    int rc = validate_policy_mx_call(pol, smp, val, probs_out_dev, value_out_dev, nullptr);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyMxArgs a;
+    if ((rc = policy_mx_args(env, pol, smp, val, &a))) return rc;
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
+    launch_policy_mx(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// per decision the matrix kernel, then K1 MODE 1 on its actions (as abr_env_step_policy_ac, last_value included)
+extern "C" int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
+    int rc = validate_policy_mx_call(pol, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyMxArgs a;
+    if ((rc = policy_mx_args(env, pol, smp, val, &a))) return rc;
+    if ((rc = require(kPolicyRollout, env->impl))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
+        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
+        launch_policy_mx(env, a, st);
+        HIP_TRY(hipGetLastError());
+        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
+    if (last_value_out_dev) {
+        // the bootstrap value: no decision is stored, so the workspace is left as the rollout left it
+        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
+        a.mode = ABR_POLICY_ARGMAX;
+        a.value_out = last_value_out_dev;
+        launch_policy_mx(env, a, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return ABR_OK;
+}
+
 // One thread per lane walks its column of the slabs from the last row to the first (abr_lane_jump.h: gae_lane): a row of
 // any slab is contiguous across the wave, so every access is coalesced, and the loads of kGaeRows rows are issued before
 // the dependent chain over them starts.  No LDS, no barrier.

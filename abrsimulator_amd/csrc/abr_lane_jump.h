@@ -1077,6 +1077,98 @@ ABR_HD int32_t policy_decide(const PolicyNet &n, uint64_t lane, int32_t c, int32
     return (uint64_t)r[1] < n.thr ? (int32_t)(((uint64_t)r[0] * (uint32_t)n.M) >> 32) : s;
 }
 
+// ---------------------------------------------------------------------------
+// The matrix engine of the learned policy (include/abr_env.h: abr_policy_mx; abr_env.hip: policy_mx_kernel): the same
+// chains issued as v_mfma_f32_32x32x2_f32, the units of a layer as the rows of the product and 32 env lanes as its
+// columns.  Everything here is index arithmetic, compiled for the host by tests/native/policy_matrix_harness.cpp.
+//
+// The instruction, for wave lane l (0..63): its A register is A[row l & 31][k = l >> 5], its B register is
+// B[k = l >> 5][column l & 31], and register r (0..15) of its accumulator is D[row (r & 3) + 8 (r >> 2) + 4 (l >> 5)]
+// [column l & 31]; D = fma(A[.][1], B[1][.], fma(A[.][0], B[0][.], C)): k = 0 first.  Steps are issued with k
+// ascending, so input k of a layer is k-slot k & 1 of step k >> 1.
+//
+// Unit u = 2 s + h of a 32-unit tile sits in row (s & 3) + 8 (s >> 2) + 4 h: accumulator register s of lane half h then
+// holds unit 2 s + h, which after the ReLU is exactly that lane's B register of step s of the next layer -- the
+// activations never leave the registers.  Rows past the layer's width and k-slots past its input are padded with
+// -0.0f weights and biases against +0.0f inputs (the ReLU of a padded unit, whatever its chain made of -0 * x, is +0).
+// ---------------------------------------------------------------------------
+constexpr int kMxMaxWidth = 128, kMxMaxHidden = 3, kMxTile = 32, kMxWave = 64, kMxRegs = 16;
+constexpr int kMxValueUnit = kPolicyMaxRates;             // the value head's row of the output tile (scores: 0..M-1)
+
+ABR_HD int32_t mx_a_row(int32_t l) { return l & 31; }
+ABR_HD int32_t mx_a_k(int32_t l) { return l >> 5; }
+ABR_HD int32_t mx_b_k(int32_t l) { return l >> 5; }
+ABR_HD int32_t mx_b_col(int32_t l) { return l & 31; }
+ABR_HD int32_t mx_d_row(int32_t l, int32_t r) { return (r & 3) + 8 * (r >> 2) + 4 * (l >> 5); }
+ABR_HD int32_t mx_d_col(int32_t l) { return l & 31; }
+// unit (within its tile) <-> row of the product
+ABR_HD int32_t mx_unit_row(int32_t u) { const int32_t s = u >> 1, h = u & 1; return (s & 3) + 8 * (s >> 2) + 4 * h; }
+ABR_HD int32_t mx_row_unit(int32_t i) { const int32_t h = (i >> 2) & 1, s = (i & 3) + 4 * (i >> 3); return 2 * s + h; }
+// the unit (within its tile) that accumulator register r of lane l holds, and the next layer's step it feeds
+ABR_HD int32_t mx_acc_unit(int32_t l, int32_t r) { return mx_row_unit(mx_d_row(l, r)); }
+// where unit u (within its tile) of a column ends up: the accumulator register and the lane half that hold it
+constexpr int32_t mx_unit_reg(int32_t u) { return u >> 1; }
+constexpr int32_t mx_unit_half(int32_t u) { return u & 1; }
+
+// One layer as the engine sees it: Wt [out][in] and b [out] in the blob; `extra` (the value head: Wv [in] then bv) is
+// one more unit at row kMxValueUnit of the (only) tile, nullptr without one.
+struct MxLayer { const float *W, *b; int32_t in, out; const float *extra; };
+
+ABR_HD int32_t mx_steps(int32_t in) { return (in + 1) >> 1; }
+ABR_HD int32_t mx_tiles(const MxLayer &y) { return ((y.extra ? kMxValueUnit + 1 : y.out) + kMxTile - 1) / kMxTile; }
+// floats of the staged A operands: [tile][step][lane]
+ABR_HD int32_t mx_staged_floats(const MxLayer &y) { return mx_tiles(y) * mx_steps(y.in) * kMxWave; }
+
+ABR_HD float mx_weight(const MxLayer &y, int32_t unit, int32_t k) {
+    if (k >= y.in) return -0.0f;
+    if (unit < y.out) return y.W[(int64_t)unit * y.in + k];
+    if (y.extra && unit == kMxValueUnit) return y.extra[k];
+    return -0.0f;
+}
+ABR_HD float mx_bias(const MxLayer &y, int32_t unit) {
+    if (unit < y.out) return y.b[unit];
+    if (y.extra && unit == kMxValueUnit) return y.extra[y.in];
+    return -0.0f;
+}
+// the A register of lane l at (tile T, step s), and its slot in the staged operands
+ABR_HD float mx_staged_at(const MxLayer &y, int32_t T, int32_t s, int32_t l) {
+    return mx_weight(y, kMxTile * T + mx_row_unit(mx_a_row(l)), 2 * s + mx_a_k(l));
+}
+ABR_HD int32_t mx_staged_slot(const MxLayer &y, int32_t T, int32_t s, int32_t l) {
+    return (T * mx_steps(y.in) + s) * kMxWave + l;
+}
+// slot d of the staged operands: the A register of lane d & 63 at (tile, step) = divmod(d >> 6, steps)
+ABR_HD float mx_staged(const MxLayer &y, int32_t d) {
+    const int32_t l = d & (kMxWave - 1), q = d >> 6, steps = mx_steps(y.in), T = q / steps, s = q - T * steps;
+    return mx_staged_at(y, T, s, l);
+}
+
+// layer li (0 .. n_hidden; n_hidden is the output layer) of a blob of hidden widths w[0..n_hidden) over F inputs and M
+// outputs; head = the value head or nullptr
+ABR_HD MxLayer mx_layer(const float *blob, const float *head, int32_t F, int32_t M, int32_t n_hidden, const int32_t *w,
+                        int32_t li) {
+    int64_t o = 0;
+    int32_t in = F;
+    for (int32_t l = 0; l < li; l++) { o += (int64_t)w[l] * in + w[l]; in = w[l]; }
+    const int32_t out = li < n_hidden ? w[li] : M;
+    return MxLayer{blob + o, blob + o + (int64_t)out * in, in, out, li == n_hidden ? head : nullptr};
+}
+
+// LDS floats of a launch: the largest staged layer; the SAMPLED instance's score columns ([M][block] floats) lie behind
+// the output layer's operands (what lay there belonged to a layer every wave has left: a barrier precedes each staging)
+ABR_HD int32_t mx_score_offset(int32_t F, int32_t n_hidden, const int32_t *w) {
+    return mx_steps(n_hidden ? w[n_hidden - 1] : F) * kMxWave;
+}
+ABR_HD int32_t mx_lds_floats(int32_t F, int32_t M, int32_t n_hidden, const int32_t *w, bool sampled, int32_t block) {
+    int32_t cap = mx_score_offset(F, n_hidden, w) + (sampled ? M * block : 0), in = F;
+    for (int32_t l = 0; l < n_hidden; l++) {
+        const int32_t need = ((w[l] + kMxTile - 1) / kMxTile) * mx_steps(in) * kMxWave;
+        cap = need > cap ? need : cap;
+        in = w[l];
+    }
+    return cap;
+}
+
 // Generalised advantage estimation over [T][N] rollout slabs (include/abr_env.h: abr_gae), one lane.  Every operation is
 // float32 with one rounding; q and w are selects, so a non-finite value behind an episode end never reaches the sum.
 // rew(t), val(t) -> float; term(t) -> bool (any done bit); dead(t) -> bool (a step that took no decision);

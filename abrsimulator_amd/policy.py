@@ -17,6 +17,13 @@ An actor-critic trainer whose critic shares the actor's trunk hands the controll
 decision was taken in, computed in the same kernel (include/abr_env.h: abr_policy_value).  A critic that is a separate
 network is the trainer's own business: one batched GEMM over the features slab, which torch does faster than any
 per-lane kernel.
+
+engine="matrix" evaluates the same network as f32 MFMA products (include/abr_env.h: abr_policy_mx): 0..3 hidden layers of
+1..128 units (Pensieve's 128-wide actor, PPO's 3 x 128), every output bit for bit what engine="lane" gives on a shape both
+can run.
+
+    net = torch.nn.Sequential(nn.Linear(F, 128), nn.ReLU(), nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, M))
+    ctl = PolicyController.from_module(EnvPlayer(env), net, window=8, engine="matrix")
 """
 import ctypes as C
 import math
@@ -28,6 +35,9 @@ from . import _lib
 
 OBS_NAMES = ["buffer_level", "last_bitrate", "chunks_left", "latency"]
 SAMPLE_MODES = {"argmax": _lib.POLICY_ARGMAX, "softmax": _lib.POLICY_SOFTMAX}
+# engine -> (most hidden layers, widest hidden layer, the C struct)
+ENGINES = {"lane": (_lib.POLICY_MAX_HIDDEN, _lib.POLICY_MAX_WIDTH, _lib.Policy),
+           "matrix": (_lib.POLICY_MX_MAX_HIDDEN, _lib.POLICY_MX_MAX_WIDTH, _lib.PolicyMx)}
 
 
 def _as_f32(t, device):
@@ -57,12 +67,18 @@ class PolicyController:
     sample: "argmax" (the first argmax) or "softmax" (a draw from softmax(scores / temperature) with word 2 of the same
     philox block); temperature > 0, passed as float32(1 / temperature).  Both can be changed between launches.
     value_head: None, or (Wv [in] or [1, in], bv scalar or [1]) -- the critic's head over the last hidden layer's output
-    (in = the last hidden width, or feature_dim without a hidden layer)."""
+    (in = the last hidden width, or feature_dim without a hidden layer).
+    engine: "lane" (one thread per lane; 0..2 hidden layers of 1..64 units) or "matrix" (f32 MFMA; 0..3 hidden layers of
+    1..128 units).  The outputs of a shape both can run are bit-identical."""
 
     method = "policy"
 
     def __init__(self, player, layers, window=8, norm="default", explore=0.0, seed=0, device=None, sample="argmax",
-                 temperature=1.0, value_head=None):
+                 temperature=1.0, value_head=None, engine="lane"):
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {sorted(ENGINES)}, got {engine!r}")
+        self.engine = engine
+        max_hidden, max_width, _ = ENGINES[engine]
         self.player = player
         env = getattr(player, "env", None)
         self.device = torch.device(device) if device is not None else (env.device if env is not None else
@@ -74,8 +90,8 @@ class PolicyController:
         self.n_rates, self.video_length = len(mpd.chunk_list()[0].bitrates), int(mpd.video_length)
         self.feature_dim = 4 + self.window + self.n_rates
         shapes = [tuple(np.shape(W)) for W, _ in layers]
-        if not 1 <= len(layers) <= _lib.POLICY_MAX_HIDDEN + 1:
-            raise ValueError(f"1..{_lib.POLICY_MAX_HIDDEN + 1} layers (0..{_lib.POLICY_MAX_HIDDEN} hidden)")
+        if not 1 <= len(layers) <= max_hidden + 1:
+            raise ValueError(f"1..{max_hidden + 1} layers (0..{max_hidden} hidden)")
         fan_in = self.feature_dim
         for li, ((W, b), sh) in enumerate(zip(layers, shapes)):
             if len(sh) != 2 or sh[1] != fan_in or tuple(np.shape(b)) != (sh[0],):
@@ -83,14 +99,14 @@ class PolicyController:
             last = li == len(layers) - 1
             if last and sh[0] != self.n_rates:
                 raise ValueError(f"the output layer has width {sh[0]}, the MPD has {self.n_rates} bitrates")
-            if not last and not 1 <= sh[0] <= _lib.POLICY_MAX_WIDTH:
-                raise ValueError(f"hidden width {sh[0]} outside 1..{_lib.POLICY_MAX_WIDTH}")
+            if not last and not 1 <= sh[0] <= max_width:
+                raise ValueError(f"hidden width {sh[0]} outside 1..{max_width}")
             fan_in = sh[0]
         self.widths = [sh[0] for sh in shapes[:-1]]
         self.shapes = shapes
         nbytes = C.c_size_t()
-        _lib.check(_lib.lib().abr_policy_weights_bytes(C.byref(self._struct(0, 0, None)), self.n_rates,
-                                                       C.byref(nbytes)))
+        size_query = _lib.lib().abr_policy_mx_weights_bytes if engine == "matrix" else _lib.lib().abr_policy_weights_bytes
+        _lib.check(size_query(C.byref(self._struct(0, 0, None)), self.n_rates, C.byref(nbytes)))
         self.weights = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
         self.value_in = self.widths[-1] if self.widths else self.feature_dim
         self.value_head = None
@@ -106,11 +122,13 @@ class PolicyController:
 
     # -- construction ----------------------------------------------------------
     @classmethod
-    def from_module(cls, player, module, value_head=None, **kw):
-        """From nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers; any other shape is refused.
-        value_head: the critic's nn.Linear(in, 1) over the last hidden layer's output (or (Wv, bv))."""
-        layers = cls.module_layers(module)
-        return cls(player, layers, value_head=value_head, **kw)
+    def from_module(cls, player, module, value_head=None, engine="lane", **kw):
+        """From nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers (0..3 with engine="matrix"); any other
+        shape is refused.  value_head: the critic's nn.Linear(in, 1) over the last hidden layer's output (or (Wv, bv))."""
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {sorted(ENGINES)}, got {engine!r}")
+        layers = cls.module_layers(module, ENGINES[engine][0])
+        return cls(player, layers, value_head=value_head, engine=engine, **kw)
 
     def _head_parts(self, head):
         """(Wv, bv) of a value head -- an nn.Linear(value_in, 1) with a bias, or a (Wv, bv) pair -- after checking it
@@ -134,12 +152,13 @@ class PolicyController:
         return Wv, bv
 
     @staticmethod
-    def module_layers(module):
+    def module_layers(module, max_hidden=_lib.POLICY_MAX_HIDDEN):
         """[(weight, bias)] of nn.Sequential(Linear, ReLU, Linear, ...); ValueError for any other module."""
         nn = torch.nn
         mods = list(module) if isinstance(module, nn.Sequential) else None
-        if not mods or len(mods) % 2 == 0 or len(mods) > 2 * _lib.POLICY_MAX_HIDDEN + 1:
-            raise ValueError("a policy module is nn.Sequential(Linear, ReLU, ..., Linear) with 0..2 hidden layers")
+        if not mods or len(mods) % 2 == 0 or len(mods) > 2 * max_hidden + 1:
+            raise ValueError(f"a policy module is nn.Sequential(Linear, ReLU, ..., Linear) with 0..{max_hidden} hidden "
+                             "layers")
         for k, m in enumerate(mods):
             want = nn.Linear if k % 2 == 0 else nn.ReLU
             if type(m) is not want:
@@ -218,7 +237,7 @@ class PolicyController:
         place, on the current stream, without synchronising.  value_head (nn.Linear(in, 1) or (Wv, bv)) refreshes the
         value head the same way; a controller built without one refuses it."""
         if isinstance(layers, torch.nn.Module):
-            layers = self.module_layers(layers)
+            layers = self.module_layers(layers, ENGINES[self.engine][0])
         if [tuple(np.shape(W)) for W, _ in layers] != self.shapes:
             raise ValueError(f"layer shapes {[tuple(np.shape(W)) for W, _ in layers]}, this policy has {self.shapes}")
         if value_head is not None:
@@ -249,7 +268,7 @@ class PolicyController:
         return out
 
     def _struct(self, wptr, nbytes, norm):
-        p = _lib.Policy()
+        p = ENGINES[self.engine][2]()
         p.window, p.n_hidden = self.window, len(self.widths)
         for k, w in enumerate(self.widths):
             p.width[k] = w
@@ -260,7 +279,8 @@ class PolicyController:
         return p
 
     def bound(self, env=None):
-        """The abr_policy struct for the C ABI (it points into this controller's tensors)."""
+        """The struct of this controller's engine for the C ABI -- abr_policy, or abr_policy_mx for "matrix" (it points
+        into this controller's tensors)."""
         env = env if env is not None else self.player.env
         if env.n_rates != self.n_rates:
             raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
@@ -291,6 +311,14 @@ class PolicyController:
                    scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
                    probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
         pol = self.bound(env)
+        if self.engine == "matrix":                                       # one entry for every mode
+            val, smp = (self.value() if want_value else None), self.sampling()
+            if want_value:
+                out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
+            env._call(env.lib.abr_env_policy_select_mx, env._h, C.byref(pol), C.byref(smp),
+                      C.byref(val) if val is not None else None, _lib.ptr(out["actions"]), _lib.ptr(out["features"]),
+                      _lib.ptr(out["scores"]), _lib.ptr(out["probs"]), _lib.ptr(out.get("value")))
+            return out
         if want_value:
             val, smp = self.value(), self.sampling()
             out["value"] = torch.empty(N, dtype=torch.float32, device=dev)

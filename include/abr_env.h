@@ -879,6 +879,54 @@ int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const abr_policy
                            void *stream);
 
 /*
+ * The matrix engine of the learned policy (ABI 4, additive; BUILD-DEFINED): the same network evaluated as f32 MFMA
+ * products (units as rows, env lanes as columns), which lifts the shape limits to 0..3 hidden layers of 1..128 units.
+ * Everything above that abr_policy, abr_policy_sampling and abr_policy_value say holds word for word: the features and
+ * their normalisation, the blob (per layer Wt [out][in] then b [out], unpadded), the chain of every output (acc = b[j],
+ * then acc = fmaf(Wt[j][k], x[k], acc) for k ascending -- on gfx950 v_mfma_f32_32x32x2_f32 is bit for bit that chain,
+ * subnormals kept), the ReLU, the first argmax, the exploration draw, exp_c, the softmax draw, probs, the value head over
+ * the last hidden output, and a done lane's -1, zero columns and value 0.  Only the shape limits differ: for a shape inside
+ * both limits a blob and a head are interchangeable and every output is bit-identical between the two engines.
+ * One entry pair covers every mode: smp == NULL is the first argmax (abr_env_policy_select's decision) and requires
+ * probs_out_dev == NULL; val == NULL requires the value outputs to be NULL.
+ */
+#define ABR_POLICY_MX_MAX_HIDDEN 3
+#define ABR_POLICY_MX_MAX_WIDTH 128
+typedef struct abr_policy_mx {
+    int32_t window;                       /* W, 0..ABR_POLICY_MAX_WINDOW */
+    int32_t n_hidden;                     /* 0..ABR_POLICY_MX_MAX_HIDDEN */
+    int32_t width[ABR_POLICY_MX_MAX_HIDDEN + 1]; /* 1..ABR_POLICY_MX_MAX_WIDTH below n_hidden, 0 from n_hidden on */
+    const float *weights_dev;             /* the blob (device, 4-byte aligned) */
+    size_t weights_bytes;                 /* == abr_policy_mx_weights_bytes(this, n_rates) */
+    const double *norm_dev;               /* float64 [2][F] (device, 8-byte aligned) or NULL */
+    uint64_t seed;                        /* philox key of the exploration draw */
+    uint64_t explore_threshold;           /* 0 .. 2^32 */
+    int32_t reserved_[4];                 /* set to 0 */
+} abr_policy_mx;
+
+/* Bytes of the weight blob for pol's shape and n_rates (the pointers are not looked at); == abr_policy_weights_bytes on
+ * a shape both structs can hold.  The largest (3 x 128, window 16, 16 rates) is 159 296. */
+int abr_policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t n_rates, size_t *bytes_out);
+
+/* abr_env_policy_select_ac on the matrix engine; smp and val nullable as above.  Validation (ABR_E_INVALID, nothing
+ * launched): pol (shape, window, reserved_ zero, weights non-NULL and aligned, norm aligned, threshold <= 2^32), smp and
+ * val where given, probs_out_dev without smp, value_out_dev without val, all before the handle; then weights_bytes and
+ * head_bytes against the environment's n_rates. */
+int abr_env_policy_select_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                             const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                             float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream);
+
+/* abr_env_step_policy_ac on the matrix engine: per decision the matrix kernel, then the download of that chunk;
+ * last_value_out_dev is one more forward-only launch, and the workspace after the call is byte for byte what the lane
+ * engine's rollout leaves.  Validation as abr_env_policy_select_mx (values_out_dev and last_value_out_dev need val), with
+ * n_steps >= 1 before the handle; ABR_E_UNSUPPORTED on tick. */
+int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                           const abr_policy_value *val, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                           uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
+                           float *scores_out_dev, float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                           void *stream);
+
+/*
  * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
  * reward, values float32 [n_steps][n_lanes]; last_value float32 [n_lanes]; done uint8 [n_steps][n_lanes]; actions int32
  * [n_steps][n_lanes] or NULL (every step is live); outputs adv, ret float32 [n_steps][n_lanes], which may not overlap
