@@ -131,6 +131,12 @@ class PolicyValue(C.Structure):
     _fields_ = [("head_dev", C.c_void_p), ("head_bytes", C.c_size_t), ("reserved_", C.c_int32 * 4)]
 
 
+class PolicyPop(C.Structure):
+    _fields_ = [("n_members", C.c_int32), ("group", C.c_int32), ("reserved_", C.c_int32 * 6)]
+
+
+POLICY_POP_BLOCK = 256      # a population's group is a multiple of the policy kernels' workgroup
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -221,6 +227,14 @@ SYMBOLS = [
                                            _P, _P, _P, _P, _P]),
     ("abr_env_step_policy_mx", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
                                          C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_policy_select_pop", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                            C.POINTER(PolicyValue), _P, _P, _P, _P, _P, _P]),
+    ("abr_env_step_policy_pop", C.c_int, [_P, C.POINTER(Policy), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                          C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_policy_select_mx_pop", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                               C.POINTER(PolicyValue), _P, _P, _P, _P, _P, _P]),
+    ("abr_env_step_policy_mx_pop", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                             C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),

@@ -2872,20 +2872,35 @@ struct PolicyValueArgs : PolicyArgs {
     float *value_out;                 // [N], nullable
 };
 
+// the POP instances' arguments (abr_policy_pop): the member stride of the blob and of the heads, in floats
+struct PolicyPopArgs : PolicyValueArgs {
+    int32_t group, blob_words, head_words;
+};
+
 // SAMPLED: the instance behind abr_env_policy_select_sampled.  It keeps each lane's scores in its own column of LDS past
 // the weights (M * kPolicyBlock floats; the score loops run to a runtime M), where the draw turns them into e_m.
 // VALUE: the instances behind the _ac entries.  The value head is one more row of the staged layout and one more fmaf
 // chain of the forward pass; with a NULL action_out the launch stores no decision: a value evaluation only.
-template <bool SAMPLED = false, bool VALUE = false>
+// POP: the instances behind the _pop entries (abr_policy_pop).  The workgroup computes the member it serves once, from its
+// first lane, and offsets the blob and the head before anything is staged; the rest is the single-network kernel.
+template <bool SAMPLED = false, bool VALUE = false, bool POP = false>
 __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(
-    EnvParams p, std::conditional_t<VALUE, PolicyValueArgs, PolicyArgs> a) {
+    EnvParams p, std::conditional_t<POP, PolicyPopArgs, std::conditional_t<VALUE, PolicyValueArgs, PolicyArgs>> a) {
     extern __shared__ float w_lds[];
     const abrx::PolicyLayout lay = abrx::policy_layout<VALUE>(a.net);
+    const float *weights = a.weights;
+    [[maybe_unused]] const float *head = nullptr;
+    if constexpr (VALUE) head = a.head;
+    if constexpr (POP) {
+        const int64_t member = abrx::pop_member((int64_t)blockIdx.x * kPolicyBlock, a.group);
+        weights += abrx::pop_blob_offset(member, a.blob_words);
+        if constexpr (VALUE) head += abrx::pop_head_offset(member, a.head_words);
+    }
     if constexpr (VALUE) {
         for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock)
-            w_lds[d] = abrx::policy_padded<true>(a.net, lay, a.weights, d, a.head);
+            w_lds[d] = abrx::policy_padded<true>(a.net, lay, weights, d, head);
     } else {
-        for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock) w_lds[d] = abrx::policy_padded(a.net, lay, a.weights, d);
+        for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock) w_lds[d] = abrx::policy_padded(a.net, lay, weights, d);
     }
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kPolicyBlock + threadIdx.x;
@@ -3292,8 +3307,16 @@ __device__ __forceinline__ void mx_run_layer(const abrx::MxLayer &y, const float
     }
 }
 
-template <bool SAMPLED, bool VALUE>
-__global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, PolicyMxArgs a) {
+// the POP instances' arguments (abr_policy_pop), as PolicyPopArgs
+struct PolicyMxPopArgs : PolicyMxArgs {
+    int32_t group, blob_words, head_words;
+};
+
+// POP: as policy_select_kernel's -- one scalar adjustment of the blob and head pointers, made once, before the first
+// layer is staged; biases (mx_bias) and the head's row are read through the adjusted pointers as well.
+template <bool SAMPLED, bool VALUE, bool POP = false>
+__global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p,
+                                                             std::conditional_t<POP, PolicyMxPopArgs, PolicyMxArgs> a) {
     extern __shared__ float w_lds[];
     constexpr int kMaxSteps = abrx::kMxMaxWidth / 2, kMaxTiles = abrx::kMxMaxWidth / abrx::kMxTile;
     constexpr int kXSteps = abrx::kPolicyMaxF / 2;
@@ -3360,6 +3383,12 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, Policy
         __syncthreads();
     };
     const float *head = VALUE ? a.head : nullptr;
+    [[maybe_unused]] const float *member_blob = nullptr;
+    if constexpr (POP) {
+        const int64_t member = abrx::pop_member((int64_t)blockIdx.x * kMxBlock, a.group);
+        member_blob = a.weights + abrx::pop_blob_offset(member, a.blob_words);
+        if constexpr (VALUE) head += abrx::pop_head_offset(member, a.head_words);
+    }
     mx_acc_t acc[kMaxTiles];
     const auto activate = [&](const abrx::MxLayer &y) {      // the ReLU, into the next layer's B registers
         const int32_t tiles = abrx::mx_tiles(y);
@@ -3374,7 +3403,7 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, Policy
         };
     };
     if (a.n_hidden >= 1) {
-        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, 0);
+        const abrx::MxLayer y = abrx::mx_layer(POP ? member_blob : a.weights, head, n.F, n.M, a.n_hidden, a.width, 0);
         stage(y);
         const auto relu = activate(y);
 #pragma unroll
@@ -3385,7 +3414,7 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, Policy
     }
 #pragma unroll 1
     for (int32_t li = 1; li < a.n_hidden; li++) {
-        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, li);
+        const abrx::MxLayer y = abrx::mx_layer(POP ? member_blob : a.weights, head, n.F, n.M, a.n_hidden, a.width, li);
         stage(y);
         const auto relu = activate(y);
 #pragma unroll
@@ -3397,7 +3426,7 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p, Policy
     // the output layer (and the value head, one more row of its tile)
     mx_acc_t out[2];
     {
-        const abrx::MxLayer y = abrx::mx_layer(a.weights, head, n.F, n.M, a.n_hidden, a.width, a.n_hidden);
+        const abrx::MxLayer y = abrx::mx_layer(POP ? member_blob : a.weights, head, n.F, n.M, a.n_hidden, a.width, a.n_hidden);
         stage(y);
 #pragma unroll
         for (int t = 0; t < 2; t++) mx_run_layer<1, kMaxSteps>(y, w_lds, lane, h[t], &out[t]);
@@ -3603,6 +3632,214 @@ extern "C" int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, co
         HIP_TRY(hipGetLastError());
     }
     return ABR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Policy populations (include/abr_env.h: abr_policy_pop): one weight set per lane group, both engines
+// ---------------------------------------------------------------------------
+// the struct alone (before the handle)
+static int validate_pop(const abr_policy_pop *pop) {
+    if (!pop) return fail(ABR_E_INVALID, "population is NULL");
+    if (pop->n_members < 1) return fail(ABR_E_INVALID, "population n_members %d must be >= 1", pop->n_members);
+    if (pop->group < kPolicyBlock || pop->group % kPolicyBlock)
+        return fail(ABR_E_INVALID, "population group %d must be a positive multiple of %d", pop->group, kPolicyBlock);
+    for (int32_t r : pop->reserved_)
+        if (r) return fail(ABR_E_INVALID, "population reserved_ must be 0");
+    // a launch covers at most 2^32 - 1 workgroups of 256 lanes: no environment can have the lanes of a larger product
+    if ((int64_t)pop->n_members * (int64_t)pop->group > (int64_t)UINT32_MAX * kPolicyBlock)
+        return fail(ABR_E_INVALID, "population n_members %d x group %d overflows the lanes of a launch", pop->n_members,
+                    pop->group);
+    return ABR_OK;
+}
+
+// after the handle and the one-member byte counts: the members cover the environment's lanes exactly
+static int pop_covers(const abr_env *env, const abr_policy_pop *pop) {
+    const int64_t want = (env->p.n_lanes + pop->group - 1) / pop->group;
+    if ((int64_t)pop->n_members != want)
+        return fail(ABR_E_INVALID, "population n_members %d, %lld lanes in groups of %d need %lld", pop->n_members,
+                    (long long)env->p.n_lanes, pop->group, (long long)want);
+    return ABR_OK;
+}
+
+// everything the lane engine's population entries check before the handle, but n_steps
+static int validate_policy_pop_call(const abr_policy *pol, const abr_policy_pop *pop, const abr_policy_sampling *smp,
+                                    const abr_policy_value *val, const float *probs_out, const float *values_out,
+                                    const float *last_value_out) {
+    int rc = validate_policy(pol);
+    if (rc) return rc;
+    if (smp && (rc = validate_sampling(smp))) return rc;
+    if (val && (rc = validate_value(val))) return rc;
+    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
+    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
+    return validate_pop(pop);
+}
+
+static int policy_pop_args(const abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                           const abr_policy_sampling *smp, const abr_policy_value *val, PolicyPopArgs *a) {
+    PolicyArgs base;
+    int rc = policy_args(env, pol, &base);
+    if (rc) return rc;
+    *a = PolicyPopArgs{};
+    static_cast<PolicyArgs &>(*a) = base;
+    if (val) {
+        const size_t in = pol->n_hidden == 0 ? (size_t)base.net.F : (size_t)pol->width[pol->n_hidden - 1];
+        if (val->head_bytes != (in + 1) * sizeof(float))
+            return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
+        a->head = val->head_dev;
+        a->head_words = (int32_t)(in + 1);
+    }
+    if ((rc = pop_covers(env, pop))) return rc;
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    a->group = pop->group;
+    a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+    return ABR_OK;
+}
+
+// the instance by what the launch needs, as launch_policy_ac and launch_policy_mx choose theirs
+static void launch_policy_pop(const abr_env *env, const PolicyPopArgs &a, hipStream_t st) {
+    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t total = value ? abrx::policy_layout<true>(a.net).total : abrx::policy_layout(a.net).total;
+    const size_t lds = (total + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
+    const dim3 grid((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), block(kPolicyBlock);
+    if (sampled && value) hipLaunchKernelGGL((policy_select_kernel<true, true, true>), grid, block, lds, st, env->p, a);
+    else if (sampled) hipLaunchKernelGGL((policy_select_kernel<true, false, true>), grid, block, lds, st, env->p, a);
+    else if (value) hipLaunchKernelGGL((policy_select_kernel<false, true, true>), grid, block, lds, st, env->p, a);
+    else hipLaunchKernelGGL((policy_select_kernel<false, false, true>), grid, block, lds, st, env->p, a);
+}
+
+static int validate_policy_mx_pop_call(const abr_policy_mx *pol, const abr_policy_pop *pop, const abr_policy_sampling *smp,
+                                       const abr_policy_value *val, const float *probs_out, const float *values_out,
+                                       const float *last_value_out) {
+    int rc = validate_policy_mx_call(pol, smp, val, probs_out, values_out, last_value_out);
+    if (rc) return rc;
+    return validate_pop(pop);
+}
+
+static int policy_mx_pop_args(const abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                              const abr_policy_sampling *smp, const abr_policy_value *val, PolicyMxPopArgs *a) {
+    PolicyMxArgs base;
+    int rc = policy_mx_args(env, pol, smp, val, &base);
+    if (rc) return rc;
+    if ((rc = pop_covers(env, pop))) return rc;
+    *a = PolicyMxPopArgs{};
+    static_cast<PolicyMxArgs &>(*a) = base;
+    a->group = pop->group;
+    a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+    a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
+    return ABR_OK;
+}
+
+static void launch_policy_mx_pop(const abr_env *env, const PolicyMxPopArgs &a, hipStream_t st) {
+    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
+    const dim3 grid((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)), block(kMxBlock);
+    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true, true>), grid, block, lds, st, env->p, a);
+    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false, true>), grid, block, lds, st, env->p, a);
+    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true, true>), grid, block, lds, st, env->p, a);
+    else hipLaunchKernelGGL((policy_mx_kernel<false, false, true>), grid, block, lds, st, env->p, a);
+}
+
+// one decision per lane on the current state, either engine's argument struct and launcher
+template <class Args, class Launch>
+static int select_pop(abr_env *env, Args &a, const Launch &launch, int32_t *action_out_dev, float *features_out_dev,
+                      float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
+    launch(env, a, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// per decision the population's policy kernel, then K1 MODE 1 on its actions (as abr_env_step_policy_ac, last_value included)
+template <class Args, class Launch>
+static int step_pop(abr_env *env, Args &a, const Launch &launch, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                    uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                    float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, void *stream) {
+    int rc = require(kPolicyRollout, env->impl);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
+        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
+        launch(env, a, st);
+        HIP_TRY(hipGetLastError());
+        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
+    if (last_value_out_dev) {
+        // the bootstrap value, each lane's by its own member: no decision is stored, the workspace stays as it is
+        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
+        a.mode = ABR_POLICY_ARGMAX;
+        a.value_out = last_value_out_dev;
+        launch(env, a, st);
+        HIP_TRY(hipGetLastError());
+    }
+    return ABR_OK;
+}
+
+extern "C" int abr_env_policy_select_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                                         const abr_policy_sampling *smp, const abr_policy_value *val,
+                                         int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                         float *probs_out_dev, float *value_out_dev, void *stream) {
+    int rc = validate_policy_pop_call(pol, pop, smp, val, probs_out_dev, value_out_dev, nullptr);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyPopArgs a;
+    if ((rc = policy_pop_args(env, pol, pop, smp, val, &a))) return rc;
+    return select_pop(env, a, launch_policy_pop, action_out_dev, features_out_dev, scores_out_dev, probs_out_dev,
+                      value_out_dev, stream);
+}
+
+extern "C" int abr_env_step_policy_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                                       const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                       int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                       float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                       void *stream) {
+    int rc = validate_policy_pop_call(pol, pop, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyPopArgs a;
+    if ((rc = policy_pop_args(env, pol, pop, smp, val, &a))) return rc;
+    return step_pop(env, a, launch_policy_pop, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
+                    features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, last_value_out_dev, stream);
+}
+
+extern "C" int abr_env_policy_select_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                                            const abr_policy_sampling *smp, const abr_policy_value *val,
+                                            int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                            float *probs_out_dev, float *value_out_dev, void *stream) {
+    int rc = validate_policy_mx_pop_call(pol, pop, smp, val, probs_out_dev, value_out_dev, nullptr);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyMxPopArgs a;
+    if ((rc = policy_mx_pop_args(env, pol, pop, smp, val, &a))) return rc;
+    return select_pop(env, a, launch_policy_mx_pop, action_out_dev, features_out_dev, scores_out_dev, probs_out_dev,
+                      value_out_dev, stream);
+}
+
+extern "C" int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                                          const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                          float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                          int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                          float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                          void *stream) {
+    int rc = validate_policy_mx_pop_call(pol, pop, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyMxPopArgs a;
+    if ((rc = policy_mx_pop_args(env, pol, pop, smp, val, &a))) return rc;
+    return step_pop(env, a, launch_policy_mx_pop, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
+                    features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, last_value_out_dev, stream);
 }
 
 // One thread per lane walks its column of the slabs from the last row to the first (abr_lane_jump.h: gae_lane): a row of

@@ -1169,6 +1169,13 @@ ABR_HD int32_t mx_lds_floats(int32_t F, int32_t M, int32_t n_hidden, const int32
     return cap;
 }
 
+// Policy populations (include/abr_env.h: abr_policy_pop): the member a workgroup serves and where its weights lie.
+// block_first_lane is the LOCAL index of the workgroup's first lane (blockIdx.x * 256); group is a multiple of the
+// workgroup size, so every lane of the workgroup has the same member.  Offsets are in floats from member 0.
+ABR_HD int64_t pop_member(int64_t block_first_lane, int32_t group) { return block_first_lane / group; }
+ABR_HD int64_t pop_blob_offset(int64_t member, int32_t blob_words) { return member * blob_words; }
+ABR_HD int64_t pop_head_offset(int64_t member, int32_t head_words) { return member * head_words; }
+
 // Generalised advantage estimation over [T][N] rollout slabs (include/abr_env.h: abr_gae), one lane.  Every operation is
 // float32 with one rounding; q and w are selects, so a non-finite value behind an episode end never reaches the sum.
 // rew(t), val(t) -> float; term(t) -> bool (any done bit); dead(t) -> bool (a step that took no decision);

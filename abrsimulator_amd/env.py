@@ -469,7 +469,9 @@ class BatchedABREnv:
         want_values=True (a controller with a value head; ValueError without one) adds values[n,N], the critic's V of the
         state each decision was taken in, and last_value[N], V of the state the launch leaves behind -- what
         advantage.gae needs next to reward, done and actions (abr_env_step_policy_ac).  A controller built with
-        engine="matrix" runs the same rollout on the MFMA kernel (abr_env_step_policy_mx), with the same outputs."""
+        engine="matrix" runs the same rollout on the MFMA kernel (abr_env_step_policy_mx), with the same outputs.
+        A policy.PolicyPopulation rolls out P networks at once, member m on its own lane group, with the same dict and
+        flags (abr_env_step_policy_pop, abr_env_step_policy_mx_pop)."""
         n = int(n_steps)
         pol = controller.bound(self)
         val = controller.value() if want_values or (out is not None and out.get("values") is not None) else None
@@ -483,6 +485,15 @@ class BatchedABREnv:
             if val is not None:
                 out["values"] = torch.empty(n, N, dtype=torch.float32, device=dev)
                 out["last_value"] = torch.empty(N, dtype=torch.float32, device=dev)
+        if getattr(controller, "method", None) == "policy_population":    # one weight set per lane group (abr_policy_pop)
+            pop, smp = controller.population(), controller.sampling()
+            fn = (self.lib.abr_env_step_policy_mx_pop if controller.engine == "matrix" else
+                  self.lib.abr_env_step_policy_pop)
+            self._call(fn, self._h, C.byref(pol), C.byref(pop), C.byref(smp), C.byref(val) if val is not None else None,
+                       n, _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
+                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
+                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")))
+            return out
         if getattr(controller, "engine", "lane") == "matrix":             # one entry for every mode (abr_env_step_policy_mx)
             smp = controller.sampling()
             self._call(self.lib.abr_env_step_policy_mx, self._h, C.byref(pol), C.byref(smp),

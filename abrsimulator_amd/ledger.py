@@ -113,6 +113,33 @@ class EpisodeLedger:
             out[k] = s / cnt.to(torch.float64)
         return out
 
+    def per_member(self, group, n_members):
+        """Count and mean of every float field per member of a policy population (policy.PolicyPopulation: lane i
+        belongs to member i // group) over ALL recorded episodes: dict(count int64 [n_members], and one float64
+        [n_members] mean per float field).  Built from count() and totals(), not from the ring, so a lane that has
+        recorded more than `rows` episodes still counts every one of them.  The counts are exact; a mean is the sum of
+        its member's per-lane totals in an order that is not fixed, so it is reproducible up to the error of a float64
+        sum of its n episodes in any order, n * 2^-53 * sum|x| / (1 - n * 2^-53), as per_trace.  A member without an
+        episode reports count 0 and a mean of 0.0 (not per_trace's NaN: the fitness vector an evolution strategy
+        ranks stays finite; look at count to tell)."""
+        group, P = int(group), int(n_members)
+        if group < 1 or P != -(-self.n_lanes // group):
+            raise ValueError(f"{self.n_lanes} lanes in groups of {group} make {-(-self.n_lanes // max(group, 1))} "
+                             f"members, not {P}")
+        pad = P * group - self.n_lanes
+
+        def by_member(v):                                                 # [N] -> [P] sums over each member's lanes
+            if pad:
+                v = torch.cat([v, torch.zeros(pad, dtype=v.dtype, device=v.device)])
+            return v.reshape(P, group).sum(dim=1)
+
+        cnt = by_member(self.count().to(torch.int64))
+        out = {"count": cnt}
+        den = torch.clamp(cnt, min=1).to(torch.float64)
+        for k, v in self.totals().items():
+            out[k] = by_member(v) / den
+        return out
+
     # -- lifecycle ---------------------------------------------------------
     def clear(self):
         """Empty the ledger: zero the blob (on the current stream, in order with the launches)."""

@@ -24,7 +24,16 @@ can run.
 
     net = torch.nn.Sequential(nn.Linear(F, 128), nn.ReLU(), nn.Linear(128, 128), nn.ReLU(), nn.Linear(128, M))
     ctl = PolicyController.from_module(EnvPlayer(env), net, window=8, engine="matrix")
+
+PolicyPopulation runs P networks of one shape in a single launch, member m on lanes [m * group, (m + 1) * group)
+(include/abr_env.h: abr_policy_pop) -- evolution strategies, population-based training, checkpoint leagues, A/B runs:
+
+    pop = PolicyPopulation(EnvPlayer(env), [net_0, ..., net_63], group=env.n_lanes // 64, window=8)
+    out = env.step_policy(pop, 48)                          # every member on its own lanes, one launch per decision
+    pop.load_weights(next_generation)                       # in place, no sync
+    best = pop.member(3)                                    # an ordinary PolicyController over member 3's weights
 """
+import copy
 import ctypes as C
 import math
 
@@ -351,3 +360,241 @@ class PolicyController:
     def scores(self):
         """float32 [M, N]: the network's output on the current state."""
         return self.select(False, True)["scores"]
+
+
+def _is_array(t):
+    return torch.is_tensor(t) or isinstance(t, np.ndarray)
+
+
+class PolicyPopulation:
+    """P networks of ONE shape over `player`, each deciding for its own group of lanes in the same launch
+    (include/abr_env.h: abr_policy_pop): local lane i belongs to member i // group, group is a positive multiple of 256,
+    and P == ceil(n_lanes / group) -- the last member may own fewer lanes.  For every lane of member m every output is
+    bit for bit what member(m), an ordinary PolicyController over that member's weights, gives on that lane.
+
+    members: a list of P layer lists [(W, b), ...] or nn.Sequentials of one shape, or the stacked tensors
+    [(W [P, out, in], b [P, out]), ...].  value_heads: None, a list of P heads (nn.Linear(in, 1) or (Wv, bv)), or the
+    stacked pair (Wv [P, in], bv [P]).  Every other argument is PolicyController's and is shared by all members, with the
+    same limits per engine; explore, sample, temperature and seed can be changed between launches.
+    It owns weights float32 [P, words] and value_heads float32 [P, in + 1] (or None) on the device.
+
+    Not covered: ShardedABREnv (it has no step_policy); per-member exploration, temperature or norm; and common random
+    numbers across members under the episode sampler, which draws (trace, offset) per lane -- until the sampler can
+    repeat a sequence per group, tile explicit reset(trace_id, start_offset) pairs over the groups."""
+
+    method = "policy_population"
+
+    def __init__(self, player, members, group, window=8, norm="default", explore=0.0, seed=0, sample="argmax",
+                 temperature=1.0, value_heads=None, engine="lane", device=None):
+        if engine not in ENGINES:
+            raise ValueError(f"engine must be one of {sorted(ENGINES)}, got {engine!r}")
+        if isinstance(group, bool) or int(group) != group or int(group) < _lib.POLICY_POP_BLOCK or \
+                int(group) % _lib.POLICY_POP_BLOCK:
+            raise ValueError(f"group must be a positive multiple of {_lib.POLICY_POP_BLOCK}, got {group!r}")
+        self.group = int(group)
+        self.player, self.engine = player, engine
+        layer_lists = self._member_layers(members, ENGINES[engine][0])
+        self.n_members = len(layer_lists)
+        heads = self._member_heads(value_heads, self.n_members)
+        # member 0 through the controller's own checks: shape, window, norm, explore, sample, temperature, head
+        self._proto = PolicyController(player, layer_lists[0], window=window, norm=norm, explore=explore, seed=seed,
+                                       device=device, sample=sample, temperature=temperature,
+                                       value_head=heads[0] if heads is not None else None, engine=engine)
+        c = self._proto
+        self.device, self.window, self.n_rates = c.device, c.window, c.n_rates
+        self.feature_dim, self.widths, self.shapes, self.value_in = c.feature_dim, c.widths, c.shapes, c.value_in
+        env = getattr(player, "env", None)
+        if env is not None:
+            self._check_cover(env)
+        self.weights = torch.zeros(self.n_members, c.weights.numel(), dtype=torch.float32, device=self.device)
+        self.value_heads = (torch.zeros(self.n_members, self.value_in + 1, dtype=torch.float32, device=self.device)
+                            if heads is not None else None)
+        c.weights = self.weights[0]                                        # the prototype is member 0: no second copy
+        c.value_head = self.value_heads[0] if heads is not None else None
+        self.load_weights(layer_lists, value_heads=heads)
+
+    @classmethod
+    def from_modules(cls, player, nets, group, value_heads=None, **kw):
+        """From P nn.Sequential(Linear, ReLU, ..., Linear) of one shape (as PolicyController.from_module)."""
+        nets = list(nets)
+        if not nets or not all(isinstance(n, torch.nn.Module) for n in nets):
+            raise ValueError("from_modules takes a non-empty list of nn.Sequential")
+        return cls(player, nets, group, value_heads=value_heads, **kw)
+
+    # -- the members' inputs -------------------------------------------------------
+    @staticmethod
+    def _stacked(members):
+        return (len(members) > 0 and not isinstance(members[0], torch.nn.Module) and len(members[0]) == 2 and
+                _is_array(members[0][0]) and np.ndim(members[0][0]) == 3)
+
+    @classmethod
+    def _member_layers(cls, members, max_hidden):
+        """A list of P layer lists from any of the three forms; ValueError for anything else."""
+        members = list(members) if not isinstance(members, torch.nn.Sequential) else None
+        if not members:
+            raise ValueError("members is a non-empty list of layer lists or nn.Sequentials, or stacked (W, b) tensors")
+        if cls._stacked(members):
+            P = int(np.shape(members[0][0])[0])
+            for li, (W, b) in enumerate(members):
+                if np.ndim(W) != 3 or np.ndim(b) != 2 or np.shape(W)[0] != P or np.shape(b)[0] != P:
+                    raise ValueError(f"stacked layer {li}: W must be [{P}, out, in] and b [{P}, out], got "
+                                     f"{tuple(np.shape(W))} / {tuple(np.shape(b))}")
+            if P < 1:
+                raise ValueError("a population has at least one member")
+            return [[(W[m], b[m]) for W, b in members] for m in range(P)]
+        out = []
+        for m in members:
+            out.append(PolicyController.module_layers(m, max_hidden) if isinstance(m, torch.nn.Module) else list(m))
+        return out
+
+    @staticmethod
+    def _member_heads(heads, P):
+        if heads is None:
+            return None
+        if not isinstance(heads, torch.nn.Module) and len(heads) == 2 and _is_array(heads[0]) and _is_array(heads[1]) \
+                and np.ndim(heads[0]) == 2 and np.ndim(heads[1]) == 1 and np.shape(heads[1])[0] == P:
+            if np.shape(heads[0])[0] != P:
+                raise ValueError(f"stacked value heads: Wv must be [{P}, in] and bv [{P}]")
+            return [(heads[0][m], heads[1][m]) for m in range(P)]
+        heads = list(heads)
+        if len(heads) != P:
+            raise ValueError(f"{len(heads)} value heads for {P} members")
+        return heads
+
+    def _check_cover(self, env):
+        want = -(-int(env.n_lanes) // self.group)
+        if self.n_members != want:
+            raise ValueError(f"{self.n_members} members, {env.n_lanes} lanes in groups of {self.group} need {want}")
+
+    # -- what all members share (checked by the controller's own setters) ------------
+    explore = property(lambda self: self._proto.explore, lambda self, v: setattr(self._proto, "explore", v))
+    sample = property(lambda self: self._proto.sample, lambda self, v: setattr(self._proto, "sample", v))
+    temperature = property(lambda self: self._proto.temperature, lambda self, v: setattr(self._proto, "temperature", v))
+    seed = property(lambda self: self._proto.seed, lambda self, v: setattr(self._proto, "seed", int(v)))
+    norm = property(lambda self: self._proto.norm)
+    explore_threshold = property(lambda self: self._proto.explore_threshold)
+    inv_temperature = property(lambda self: self._proto.inv_temperature)
+
+    def sampling(self):
+        return self._proto.sampling()
+
+    def feature_names(self):
+        return self._proto.feature_names()
+
+    # -- the weights -----------------------------------------------------------------
+    def member(self, m):
+        """Member m as an ordinary PolicyController whose weights (and value head) are VIEWS of row m of this
+        population's tensors, with the population's current explore, sample, temperature and seed: for equivalence
+        tests, and for promoting a winner (clone its weights to keep them past the next load)."""
+        m = self._index(m)
+        c = copy.copy(self._proto)
+        c.weights = self.weights[m]
+        c.value_head = self.value_heads[m] if self.value_heads is not None else None
+        return c
+
+    def _index(self, m):
+        if isinstance(m, bool) or int(m) != m or not 0 <= int(m) < self.n_members:
+            raise IndexError(f"member {m!r} outside 0..{self.n_members - 1}")
+        return int(m)
+
+    def load_member(self, m, net, value_head=None):
+        """Copy new weights for member m alone (layers or an nn.Sequential of the population's shape; value_head as
+        PolicyController.load_weights) in place, on the current stream, without synchronising."""
+        self.member(m).load_weights(net, value_head=value_head)
+
+    def load_weights(self, members, value_heads=None):
+        """Copy new weights for EVERY member (any form the constructor takes, P unchanged) in place, on the current
+        stream, without synchronising.  Stacked tensors take one copy per tensor, whatever P is."""
+        if not isinstance(members, torch.nn.Sequential) and self._stacked(list(members)):
+            members = list(members)
+            shapes = [tuple(np.shape(W))[1:] for W, _ in members]
+            if shapes != self.shapes or any(np.shape(W)[0] != self.n_members or
+                                            tuple(np.shape(b)) != (self.n_members, sh[0])
+                                            for (W, b), sh in zip(members, shapes)):
+                raise ValueError(f"stacked layer shapes {[tuple(np.shape(W)) for W, _ in members]}, this population "
+                                 f"has {self.n_members} x {self.shapes}")
+            o = 0
+            with torch.no_grad():
+                for W, b in members:
+                    for t in (W, b):
+                        t = _as_f32(t, self.device).reshape(self.n_members, -1)
+                        self.weights[:, o:o + t.shape[1]].copy_(t, non_blocking=True)
+                        o += t.shape[1]
+            assert o == self.weights.shape[1]
+            lists = None
+        else:
+            lists = self._member_layers(members, ENGINES[self.engine][0])
+            if len(lists) != self.n_members:
+                raise ValueError(f"{len(lists)} members, this population has {self.n_members}")
+        heads = self._member_heads(value_heads, self.n_members)
+        if heads is not None and self.value_heads is None:
+            raise ValueError("this population was built without value heads")
+        for m in range(self.n_members):
+            c = self.member(m)
+            if lists is not None:
+                c.load_weights(lists[m], value_head=heads[m] if heads is not None else None)
+            elif heads is not None:
+                Wv, bv = c._head_parts(heads[m])
+                with torch.no_grad():
+                    c.value_head[:self.value_in].copy_(_as_f32(Wv, self.device).reshape(-1), non_blocking=True)
+                    c.value_head[self.value_in:].copy_(_as_f32(bv, self.device).reshape(-1), non_blocking=True)
+
+    # -- the lanes ---------------------------------------------------------------------
+    def _n_lanes(self, env=None):
+        env = env if env is not None else self.player.env
+        return int(env.n_lanes)
+
+    def member_of_lane(self):
+        """int32 [N]: the member each local lane belongs to."""
+        return (torch.arange(self._n_lanes(), dtype=torch.int64, device=self.device) // self.group).to(torch.int32)
+
+    def lanes_of(self, m):
+        """The slice of local lanes member m owns."""
+        m = self._index(m)
+        return slice(m * self.group, min((m + 1) * self.group, self._n_lanes()))
+
+    # -- the C ABI ---------------------------------------------------------------------
+    def bound(self, env=None):
+        """abr_policy / abr_policy_mx over member 0's blob with ONE member's byte count (the population entries' rule)."""
+        env = env if env is not None else self.player.env
+        if env.n_rates != self.n_rates:
+            raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
+        self._check_cover(env)
+        return self._proto._struct(self.weights.data_ptr(), self.weights.shape[1] * 4, self._proto.norm)
+
+    def population(self):
+        """The abr_policy_pop struct."""
+        p = _lib.PolicyPop()
+        p.n_members, p.group = self.n_members, self.group
+        return p
+
+    def value(self):
+        """abr_policy_value over member 0's head with ONE head's byte count; ValueError without heads."""
+        if self.value_heads is None:
+            raise ValueError("values need value heads: PolicyPopulation(..., value_heads=[...])")
+        v = _lib.PolicyValue()
+        v.head_dev, v.head_bytes = self.value_heads.data_ptr(), self.value_heads.shape[1] * 4
+        return v
+
+    def select(self, want_features=True, want_scores=True, want_probs=False, want_value=False):
+        """One decision per lane on the environment's current state, every lane by its own member: the same dict as
+        PolicyController.select."""
+        env = self.player.env
+        N, dev = env.n_lanes, env.device
+        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
+                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
+                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
+                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
+        pol, pop, smp = self.bound(env), self.population(), self.sampling()
+        val = self.value() if want_value else None
+        if want_value:
+            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
+        fn = env.lib.abr_env_policy_select_mx_pop if self.engine == "matrix" else env.lib.abr_env_policy_select_pop
+        env._call(fn, env._h, C.byref(pol), C.byref(pop), C.byref(smp), C.byref(val) if val is not None else None,
+                  _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]), _lib.ptr(out["probs"]),
+                  _lib.ptr(out.get("value")))
+        return out
+
+    def next_bitrate(self):
+        """int32 [N]: each lane's action by its member's network (-1 for finished lanes)."""
+        return self.select(False, False)["actions"]

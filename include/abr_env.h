@@ -927,6 +927,61 @@ int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, const abr_pol
                            void *stream);
 
 /*
+ * Policy populations (ABI 4, additive; BUILD-DEFINED): P networks of ONE shape in a single launch, one weight set per
+ * group of lanes (evolution strategies, population-based training, checkpoint leagues, A/B runs of two actors).
+ * A population shares everything but the weights: window, hidden widths, n_rates, normalisation, seed, exploration
+ * threshold and the sampling struct are those of the one abr_policy / abr_policy_mx handed in.
+ * Membership: LOCAL lane i of the environment (0 <= i < n_lanes) belongs to member i / group.  group is a multiple of
+ * 256 (the workgroup of both policy kernels, so a workgroup serves one member), n_members == ceil(n_lanes / group), and
+ * the last member may own fewer than `group` lanes.  Membership never looks at lane_id_base: the philox counters keep
+ * using lane_id_base + i exactly as in the single-network entries.
+ * Weights: dense float32 [n_members][weights_bytes / 4], 4-byte aligned; pol->weights_dev points at member 0 and
+ * pol->weights_bytes is ONE member's size, abr_policy_weights_bytes (abr_policy_mx_weights_bytes) of the shape.  Member
+ * m's blob is byte for byte what a single abr_policy of that shape takes.  Value heads: float32 [n_members][in + 1];
+ * val->head_dev points at member 0's head and val->head_bytes is one head's size.
+ * Numerics: for every lane of member m, every output (action, features, scores, probs, value, last_value, and obs,
+ * reward, done and the workspace, which the environment writes) is bit for bit what the single-network entry of the same
+ * engine gives on that lane with member m's blob and head.  That sentence is the whole numerical contract.
+ */
+typedef struct abr_policy_pop {
+    int32_t n_members;      /* P >= 1 */
+    int32_t group;          /* lanes per member, a multiple of 256 */
+    int32_t reserved_[6];   /* 0 */
+} abr_policy_pop;
+
+/* abr_env_policy_select_ac for a population (lane engine).  smp == NULL is the first argmax (abr_env_policy_select's
+ * decision) and requires probs_out_dev == NULL; val == NULL requires value_out_dev == NULL.  Validation (ABR_E_INVALID,
+ * nothing launched): pol as abr_env_policy_select, smp and val where given, probs_out_dev without smp, value_out_dev
+ * without val, then pop (non-NULL, n_members >= 1, group >= 256 and a multiple of 256, reserved_ zero,
+ * n_members * (int64)group representable), all before the handle; then ONE member's weights_bytes and head_bytes against
+ * the shape, then n_members == ceil(n_lanes / group). */
+int abr_env_policy_select_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                              const abr_policy_sampling *smp, const abr_policy_value *val, int32_t *action_out_dev,
+                              float *features_out_dev, float *scores_out_dev, float *probs_out_dev, float *value_out_dev,
+                              void *stream);
+
+/* abr_env_step_policy_ac for a population (lane engine): outputs as there, smp and val nullable as above
+ * (values_out_dev and last_value_out_dev need val).  The last_value launch uses the same member mapping.  Validation as
+ * abr_env_policy_select_pop, with n_steps >= 1 after pop and before the handle; ABR_E_UNSUPPORTED on tick. */
+int abr_env_step_policy_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                            const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                            float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                            float *features_out_dev, float *scores_out_dev, float *probs_out_dev, float *values_out_dev,
+                            float *last_value_out_dev, void *stream);
+
+/* The same two entries on the matrix engine (abr_policy_mx): validation as abr_env_policy_select_mx /
+ * abr_env_step_policy_mx with pop checked after val (and before n_steps), then as above after the handle. */
+int abr_env_policy_select_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                                 const abr_policy_sampling *smp, const abr_policy_value *val, int32_t *action_out_dev,
+                                 float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                 float *value_out_dev, void *stream);
+int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                               const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                               float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                               int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                               float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, void *stream);
+
+/*
  * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
  * reward, values float32 [n_steps][n_lanes]; last_value float32 [n_lanes]; done uint8 [n_steps][n_lanes]; actions int32
  * [n_steps][n_lanes] or NULL (every step is live); outputs adv, ret float32 [n_steps][n_lanes], which may not overlap
