@@ -404,7 +404,8 @@ __device__ inline void ledger_record(const EnvParams &p, const abrx::EpisodeLedg
 // `smp` (trace_id_in / offset_in unused) and a re-arm draws the new episode's; the other instances never read `smp`
 // LEDGER: the instance that runs while an episode ledger is installed: every episode end appends a record to `led`; the
 // other instances never read `led` and are, instruction for instruction, what they were without it
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+// SPEEDS: the tick kernel plays one speed for all lanes (kFeatures), so it exists only as the no-speeds instance
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = false>
 __global__ __launch_bounds__(64) void env_advance_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
@@ -413,6 +414,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
     abrx::EpisodeSampler smp, abrx::EpisodeLedger led) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
+    static_assert(!SPEEDS, "the tick kernel takes no per-lane speeds");
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
     Lane s;
     bool active = in_range;       // still has work in this launch
@@ -651,23 +653,55 @@ using abrx::LaneJ;
 // applies.  Same results either way; measured per kernel (profiles/r06_ab_cascade.txt): +3.4 % for one thread per lane at
 // 1 M lanes, +2.5 % for the two-wave role split at 131 072 -- and -2 % for the three-wave kernel at 65 536, whose player
 // wave is not what an iteration waits for (fewer vector instructions, the same iteration time, more scalar traffic).
-__device__ inline abrx::Tables make_tables(const EnvParams &p, bool cascade = true) {
-    abrx::Tables t;
+//
+// SPEEDS: the env kernels exist in two instances.  <true> serves a handle that has per-lane speeds, a speed schedule or a
+// speed rule installed; <false> every other handle, and holds none of their code: no test of lane_speeds, no speed state
+// in registers, parking words or mailboxes.  The host picks the instance per launch (launch_env), as it picks SAMPLE and
+// LEDGER: speeds are latched at a full reset, so env->p.lane_speeds is known at every launch.
+// SpeedParams is the ONE door through which the env kernels read the speed part of the parameter block: the <false> view
+// has constants for lane_speeds / speed_rows and no accessor at all for the per-lane speed state, so code that would touch
+// that state in a no-speeds instance does not compile.
+template <bool SPEEDS>
+struct SpeedParams;
+template <>
+struct SpeedParams<true> {
+    static __device__ __forceinline__ const double *lane_speeds(const EnvParams &p) { return p.lane_speeds; }
+    static __device__ __forceinline__ int32_t speed_rows(const EnvParams &p) { return p.speed_rows; }
+    static __device__ __forceinline__ double *sd_lane(const EnvParams &p) { return p.sd_lane; }
+    static __device__ __forceinline__ double *pt_lane(const EnvParams &p) { return p.pt_lane; }
+    static __device__ __forceinline__ double *pt_sum(const EnvParams &p) { return p.pt_sum; }
+    static __device__ __forceinline__ int32_t *pl_left(const EnvParams &p) { return p.pl_left; }
+    static __device__ __forceinline__ int32_t *play_id(const EnvParams &p) { return p.play_id; }
+};
+template <>
+struct SpeedParams<false> {
+    static __device__ __forceinline__ constexpr const double *lane_speeds(const EnvParams &) { return nullptr; }
+    static __device__ __forceinline__ constexpr int32_t speed_rows(const EnvParams &) { return 1; }
+};
+
+template <bool SPEEDS = true>
+__device__ inline abrx::TablesT<SPEEDS> make_tables(const EnvParams &p, bool cascade = true) {
+    abrx::TablesT<SPEEDS> t;
     t.G = p.G; t.interval_tick = p.interval_tick; t.avail_tick = p.avail_tick;
     t.L = p.chunk_length; t.sd = p.sd; t.max_buffer = p.max_buffer;
     t.start_up_length = p.start_up_length; t.V = p.video_length; t.max_ticks = p.max_ticks;
-    t.per_lane_speed = p.lane_speeds != nullptr;
-    t.speed_rows = p.lane_speeds ? p.speed_rows : 0;
-    t.speed_stride = p.n_lanes; t.speeds = p.lane_speeds;
+    using SP = SpeedParams<SPEEDS>;
+    if constexpr (SPEEDS) {
+        t.per_lane_speed = SP::lane_speeds(p) != nullptr;
+        t.speed_rows = SP::lane_speeds(p) ? SP::speed_rows(p) : 0;
+        t.speed_stride = p.n_lanes; t.speeds = SP::lane_speeds(p);
+    }
     t.drain = p.drain;
-    if (p.lane_speeds || !cascade) t.drain.n = 0;      // per-lane speeds: every lane has a subtrahend of its own
+    if (SP::lane_speeds(p) || !cascade) t.drain.n = 0;      // per-lane speeds: every lane has a subtrahend of its own
 #ifdef ABR_NO_DRAIN_CASCADE
     t.drain.n = 0;                 // A/B knob (tools/diag/csrc: make AB_FLAGS=-DABR_NO_DRAIN_CASCADE ab): round 5's drains
 #endif
     return t;
 }
 
+template <bool SPEEDS = true>
 __device__ inline void lanej_load(LaneJ &s, const EnvParams &p, int64_t i) {
+    using SP = SpeedParams<SPEEDS>;
     s.buf = p.buf[i]; s.sumk = p.sumk[i];
     s.k = p.k[i]; s.chunk_id = p.chunk_id[i]; s.n_su = p.n_su[i]; s.n_rb = p.n_rb[i];
     s.n_play = p.n_play[i]; s.cur.j = p.j[i]; s.cur.tpos = p.tpos[i];
@@ -676,19 +710,27 @@ __device__ inline void lanej_load(LaneJ &s, const EnvParams &p, int64_t i) {
     s.su = f & kFlagStartUp; s.be = f & kFlagBufEmpty; s.bf = f & kFlagBufFull;
     const int32_t c = s.chunk_id < p.video_length ? s.chunk_id : p.video_length;
     s.avail_k = p.avail_tick[c];
-    if (p.lane_speeds) { s.sd = p.sd_lane[i]; s.pt = p.pt_lane[i]; } else { s.sd = p.sd; s.pt = 0.0; }
-    s.lane = i; s.pl_left = 0; s.play_id = 0; s.pt_sum = 0.0;
-    if (p.lane_speeds && p.speed_rows >= 2) { s.pl_left = p.pl_left[i]; s.play_id = p.play_id[i]; s.pt_sum = p.pt_sum[i]; }
+    if constexpr (SPEEDS) {
+        if (SP::lane_speeds(p)) { s.sd = SP::sd_lane(p)[i]; s.pt = SP::pt_lane(p)[i]; } else { s.sd = p.sd; s.pt = 0.0; }
+        s.lane = i; s.pl_left = 0; s.play_id = 0; s.pt_sum = 0.0;
+        if (SP::lane_speeds(p) && SP::speed_rows(p) >= 2) { s.pl_left = SP::pl_left(p)[i]; s.play_id = SP::play_id(p)[i]; s.pt_sum = SP::pt_sum(p)[i]; }
+    } else {
+        s.sd = p.sd; s.lane = i;           // the one play speed; no speed state
+    }
 }
 
+template <bool SPEEDS = true>
 __device__ inline void lanej_store(const LaneJ &s, const EnvParams &p, int64_t i) {
     p.buf[i] = s.buf; p.sumk[i] = s.sumk;
     p.k[i] = s.k; p.chunk_id[i] = s.chunk_id; p.n_su[i] = s.n_su; p.n_rb[i] = s.n_rb;
     p.n_play[i] = s.n_play; p.j[i] = s.cur.j; p.tpos[i] = s.cur.tpos; p.last_action[i] = s.last_action;
     p.flags[i] = (uint8_t)((s.su ? kFlagStartUp : 0) | (s.be ? kFlagBufEmpty : 0) |
                            (s.bf ? kFlagBufFull : 0) | kFlagArmed);
-    if (p.lane_speeds) { p.sd_lane[i] = s.sd; p.pt_lane[i] = s.pt; }
-    if (p.lane_speeds && p.speed_rows >= 2) { p.pl_left[i] = s.pl_left; p.play_id[i] = s.play_id; p.pt_sum[i] = s.pt_sum; }
+    if constexpr (SPEEDS) {
+        using SP = SpeedParams<SPEEDS>;
+        if (SP::lane_speeds(p)) { SP::sd_lane(p)[i] = s.sd; SP::pt_lane(p)[i] = s.pt; }
+        if (SP::lane_speeds(p) && SP::speed_rows(p) >= 2) { SP::pl_left(p)[i] = s.pl_left; SP::play_id(p)[i] = s.play_id; SP::pt_sum(p)[i] = s.pt_sum; }
+    }
 }
 
 // Outputs (observations, rewards, done bytes, the actions and history rows) are written once and never read by the launch that
@@ -701,6 +743,7 @@ __device__ inline void lanej_store(const LaneJ &s, const EnvParams &p, int64_t i
 #define ABR_OUT(ref, val) ((ref) = (val))
 #endif
 
+template <bool SPEEDS = true>
 __device__ inline void write_obs_j(const LaneJ &s, const EnvParams &p, int64_t i, float *obs,
                                    double last_bw) {
     if (!obs) return;
@@ -710,7 +753,7 @@ __device__ inline void write_obs_j(const LaneJ &s, const EnvParams &p, int64_t i
     ABR_OUT(obs[ABR_OBS_LAST_BANDWIDTH * n + i], (float)last_bw);
     ABR_OUT(obs[ABR_OBS_BUFFER_LEVEL * n + i], (float)s.buf);
     ABR_OUT(obs[ABR_OBS_GLOBAL_TIME * n + i], (float)p.G[s.k]);
-    ABR_OUT(obs[ABR_OBS_PLAY_TIME * n + i], (float)(p.lane_speeds ? s.pt : p.GP[s.n_play]));
+    ABR_OUT(obs[ABR_OBS_PLAY_TIME * n + i], (float)(SpeedParams<SPEEDS>::lane_speeds(p) ? s.pt : p.GP[s.n_play]));
     ABR_OUT(obs[ABR_OBS_REBUFFER_TIME * n + i], (float)p.G[s.n_rb]);
     ABR_OUT(obs[ABR_OBS_STARTUP_TIME * n + i], (float)p.G[s.n_su]);
 }
@@ -743,9 +786,17 @@ __device__ inline void write_obs_vals(const LaneJ &s, const EnvParams &p, int64_
 // register bound into 36 B of spills, at four it keeps none.  The episode sampler's instances (SAMPLE) as well: at five
 // waves the draw at a re-arm spilled 52-68 B per lane, at four they keep none.  The episode ledger's (LEDGER) for the same
 // reason: the append's addresses at five waves took the fused rollout from 32 B of scratch to 100 B.
-#define ABR_JUMP_BOUNDS(MODE, SAMPLE) __launch_bounds__(64, ((MODE) == 1 || (MODE) == 4 || (SAMPLE) ? 4 : ABR_JUMP_WAVES))
-// SAMPLE, LEDGER: as env_advance_kernel
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+#ifndef ABR_JUMP_WAVES_ONE
+// MODE 1's bound as an A/B knob.  With the no-speeds instances: <1, false, false, false> needs 89 VGPRs, so it runs five
+// waves per SIMD under either bound; a bound of five only squeezes the SPEEDS forms (98 -> 96 VGPRs), and abr_env_step
+// launches measured 0.5-0.9 % slower with it.  ABR_JUMP_WAVES 4 and 6 against 5 at 1 048 576 lanes: within the run-to-run
+// spread (profiles/speed_instances_ab.json: part4_mode1_bound, part4_jump_waves).  Both stay as they were.
+#define ABR_JUMP_WAVES_ONE 4
+#endif
+#define ABR_JUMP_BOUNDS(MODE, SAMPLE) \
+    __launch_bounds__(64, ((MODE) == 1 ? ABR_JUMP_WAVES_ONE : ((MODE) == 4 || (SAMPLE)) ? 4 : ABR_JUMP_WAVES))
+// SAMPLE, LEDGER: as env_advance_kernel; SPEEDS: see make_tables
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
 __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
@@ -755,7 +806,8 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
-    const abrx::Tables tb = make_tables(p);
+    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p);
+    using SP = SpeedParams<SPEEDS>;      // (<false>: lane_speeds() is a constant nullptr, so every test of it below folds)
     LaneJ s;
     bool active = in_range, touched = in_range;
     uint8_t done = 0;
@@ -783,18 +835,18 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                 p.trace_id[i] = t; p.offset0[i] = offset0;
                 s.cur.tlen = p.trace_len[t]; s.cur.trace = p.traces + p.trace_off[t];
                 // play_speed * dt (:182); a rule sets it at the lane's first playing tick (sched_begin_chunk)
-                s.sd = (p.lane_speeds && p.speed_rows != abrx::kSpeedRowsRule) ? p.lane_speeds[i] * kDt : p.sd;
+                s.sd = (SP::lane_speeds(p) && SP::speed_rows(p) != abrx::kSpeedRowsRule) ? SP::lane_speeds(p)[i] * kDt : p.sd;
                 s.lane = i;
                 abrx::lanej_init(s, tb, offset0);
                 if (!bad && !abrx::lanej_wait_call(s, tb)) done |= ABR_DONE_TIMEOUT;
-                write_obs_j(s, p, i, obs_out, 0.0);
+                write_obs_j<SPEEDS>(s, p, i, obs_out, 0.0);
             }
         } else {
             done = p.done[i];
             const int32_t t = p.trace_id[i];
             offset0 = p.offset0[i];
             s.cur.tlen = p.trace_len[t]; s.cur.trace = p.traces + p.trace_off[t];
-            lanej_load(s, p, i);
+            lanej_load<SPEEDS>(s, p, i);
             n_su_obs = p.n_su_obs[i]; n_rb_obs = p.n_rb_obs[i]; episode_no = p.episode_no[i];
             last_bw = p.last_bw[i]; hist_n = p.hist_n[i]; hist_s = p.hist_s[i]; var_run = p.var_run[i];
             g_su_obs = p.G[n_su_obs]; g_rb_obs = p.G[n_rb_obs];
@@ -826,7 +878,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                     done |= ABR_DONE_BADACT;
                     if (reward_out) ABR_OUT(reward_out[o], 0.0f);
                     if (done_out) ABR_OUT(done_out[o], (uint8_t)done);
-                    write_obs_j(s, p, i, obs, last_bw);
+                    write_obs_j<SPEEDS>(s, p, i, obs, last_bw);
                     active = false;
                 } else {
                     const int32_t prev_action = s.last_action;
@@ -835,7 +887,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                         s, tb, st, chunk_bitrate(p, chunk, a) * p.chunk_length /* :156 */, a);
                     // the reward's two clocks and the observation's four tick-table values in ONE burst of loads
                     const double g_rb = p.G[s.n_rb], g_su = p.G[s.n_su];
-                    double o_k = p.G[s.k], o_pl = p.lane_speeds ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
+                    double o_k = p.G[s.k], o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
                     double var = 0.0;
                     if (r.hit) {
                         const int64_t h = (int64_t)chunk * p.n_lanes + i;
@@ -860,9 +912,9 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                         p.ep_qoe_terms[0 * p.n_lanes + i] = g_rb;
                         p.ep_qoe_terms[1 * p.n_lanes + i] = g_su;
                         p.ep_qoe_terms[2 * p.n_lanes + i] =
-                            !p.lane_speeds ? lane_avg_latency(p, s.sumk, s.n_play)
-                            : (p.speed_rows >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
-                                                 : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
+                            !SP::lane_speeds(p) ? lane_avg_latency(p, s.sumk, s.n_play)
+                            : (SP::speed_rows(p) >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
+                                                    : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
                         p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
                         if constexpr (LEDGER)     // the latency term as stored: read back (this thread's own store)
                             ledger_record(p, led, i, g_rb, g_su, p.ep_qoe_terms[2 * p.n_lanes + i], var_run, episode_no,
@@ -881,7 +933,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                             last_bw = 0.0; hist_n = 0.0; hist_s = 0.0; var_run = 0.0;
                             done = 0;
                             if (!abrx::lanej_wait_call(s, tb)) done |= ABR_DONE_TIMEOUT;
-                            o_k = p.G[s.k]; o_pl = p.lane_speeds ? s.pt : p.GP[s.n_play];
+                            o_k = p.G[s.k]; o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play];
                             o_rb = p.G[s.n_rb]; o_su = p.G[s.n_su];
                         }
                     }
@@ -893,13 +945,13 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                 if (reward_out) ABR_OUT(reward_out[o], 0.0f);
                 if (done_out) ABR_OUT(done_out[o], (uint8_t)done);
                 if ((MODE == 2 || MODE == 4) && actions_out) ABR_OUT(actions_out[o], (int32_t)-1);
-                write_obs_j(s, p, i, obs, last_bw);
+                write_obs_j<SPEEDS>(s, p, i, obs, last_bw);
             }
         }
     }
 
     if (touched) {
-        lanej_store(s, p, i);
+        lanej_store<SPEEDS>(s, p, i);
         p.n_su_obs[i] = n_su_obs; p.n_rb_obs[i] = n_rb_obs; p.episode_no[i] = episode_no;
         p.last_bw[i] = last_bw; p.hist_n[i] = hist_n; p.hist_s[i] = hist_s; p.var_run[i] = var_run;
         p.done[i] = done;
@@ -1472,8 +1524,11 @@ static inline int launch_impl(const abr_env *env, int32_t n_steps) {
 // obs / rew / dn / acts as abr_env_step_random, all nullable.  A reset and a rule rollout exist only as the tick and the
 // one-thread-per-lane kernel, the asynchronous pipeline only for MODE 2 and 3: the `if constexpr` keeps every other
 // instance out of the build.  While an episode sampler is installed the SAMPLE instances run (a reset with explicit trace
-// ids excepted: it draws nothing); the diagnostic pipelines have none and refuse.
-template <int MODE, bool SAMPLE, bool LEDGER>
+// ids excepted: it draws nothing); the diagnostic pipelines have none and refuse.  While per-lane speeds, a speed schedule
+// or a speed rule is latched (env->p.lane_speeds, set at a full reset) the SPEEDS instances run, else the no-speeds ones,
+// which hold none of that code; the tick kernel (no speeds: kFeatures) and the diagnostic pipelines (written against the
+// SPEEDS form of the roles) exist in one form only.
+template <int MODE, bool SAMPLE, bool LEDGER, bool SPEEDS>
 static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
                                uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule,
                                const int32_t *trace_id, const int32_t *start_offset, const uint8_t *lane_mask) {
@@ -1481,21 +1536,26 @@ static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, con
     const int64_t N = p.n_lanes;
     const abrx::EpisodeSampler smp = SAMPLE ? env->sampler : abrx::EpisodeSampler{};
     const abrx::EpisodeLedger led = LEDGER ? env->ledger : abrx::EpisodeLedger{};
-    if (impl == 0 || impl == 1) {
-        auto *k = impl == 1 ? env_advance_kernel<MODE, SAMPLE, LEDGER> : env_jump_kernel<MODE, SAMPLE, LEDGER>;
+    if (impl == 0) {
+        auto *k = env_jump_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
+        hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
+                           acts, n_steps, seed, rule, smp, led);
+    } else if (impl == 1) {
+        // one form whatever SPEEDS says: the tick kernel plays no per-lane speeds (launch_env refuses it a handle that has some)
+        auto *k = env_advance_kernel<MODE, SAMPLE, LEDGER, false>;
         hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
                            acts, n_steps, seed, rule, smp, led);
     } else if constexpr (MODE >= 1 && MODE <= 3) {
         // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
         if (impl == 5) {
-            auto *k = env_split3_kernel<MODE, SAMPLE, LEDGER>;
+            auto *k = env_split3_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
             hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
         } else if (impl == 2) {
-            auto *k = env_split_kernel<MODE, SAMPLE, LEDGER>;
+            auto *k = env_split_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
             hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
         }
 #ifdef ABR_WITH_RING
-        else if constexpr (!SAMPLE && !LEDGER) {
+        else if constexpr (!SAMPLE && !LEDGER && SPEEDS) {
             if (impl == 6)
                 hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
                                    rew, dn, acts, n_steps, seed);
@@ -1540,9 +1600,27 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
 #endif
     // a reset never ends an episode: it has no LEDGER instance
     const bool ledger = MODE != 0 && env->ledger.base;
+    // speeds are latched at a full reset (apply_pending), so the handle knows at every launch whether any lane has one
+    const bool speeds_on = env->p.lane_speeds != nullptr;
+    // (never with the tick kernel: the speed setters and abr_env_set_impl refuse that pair, kFeatures)
     const auto go = [&](auto smp_on, auto led_on) {
-        launch_env_kernels<MODE, decltype(smp_on)::value, decltype(led_on)::value>(
-            env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
+        // The no-speeds instances exist for handles WITHOUT an episode sampler.  With the sampler's draw in them, four of
+        // the ten one-thread-per-lane instances (MODE 2-4) came out with a 36 B private segment where the SPEEDS form has
+        // none (profiles/speed_instances_resources.txt), and no measured workload samples episodes at a size where the
+        // slimmer state could pay: a sampled handle keeps running the SPEEDS form, whose speed tests are never taken.
+        // The diagnostic pipelines (6, 7) are written against the SPEEDS form of the roles: they run it whatever the handle holds.
+        constexpr bool kSample = decltype(smp_on)::value;
+        constexpr bool kLedger = decltype(led_on)::value;
+        if constexpr (kSample) {
+            launch_env_kernels<MODE, true, kLedger, true>(
+                env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
+        } else if (speeds_on || impl == 6 || impl == 7) {
+            launch_env_kernels<MODE, false, kLedger, true>(
+                env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
+        } else {
+            launch_env_kernels<MODE, false, kLedger, false>(
+                env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
+        }
     };
     if constexpr (MODE == 0) {
         if (sample) go(std::true_type{}, std::false_type{});

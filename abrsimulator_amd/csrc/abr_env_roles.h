@@ -36,6 +36,12 @@
 #ifndef ABR_SPLIT3_CASCADE
 #define ABR_SPLIT3_CASCADE 0
 #endif
+// the three-wave kernel's service role: re-read the parameter block every iteration (1, fresh_params) or use the kernel's
+// by-value copy like the download and player roles (0).  A/B knob; measured again with the no-speeds instances: 0 is
+// 1.05-1.2 % slower at 65 536 lanes in three interleaved pairs (profiles/speed_instances_ab.json: part4_fresh_params)
+#ifndef ABR_S_FRESH_PARAMS
+#define ABR_S_FRESH_PARAMS 1
+#endif
 #ifndef ABR_PRIO_D
 #define ABR_PRIO_D 2
 #endif
@@ -66,11 +72,20 @@ struct ActRing {
 };
 constexpr int kRecValid = 1, kRecHit = 2, kRecBadAct = 4;
 
-struct SplitMail2 {                      // P -> S (three-wave kernel), double-buffered by iteration parity
-    double dl[2][64], buf[2][64], lat[2][64], pt[2][64];
+// P -> S (three-wave kernel), double-buffered by iteration parity.  ONE definition for both forms: a no-speeds instance
+// (SPEEDS == false) reads play_time from GP[n_play], so its mailbox has no `pt` rows; everything else is shared, in the
+// order dl, buf, lat, [pt,] meta ... of before the flag existed.
+struct SplitMail2Head { double dl[2][64], buf[2][64], lat[2][64]; };
+template <bool SPEEDS> struct SplitMail2Pt { double pt[2][64]; };
+template <> struct SplitMail2Pt<false> {};
+struct SplitMail2Tail {
     int32_t meta[2][64], step[2][64], n_dl[2][64], k[2][64], nplay_o[2][64], nrb_o[2][64], nsu_o[2][64],
         nrb_r[2][64], nsu_r[2][64];
 };
+template <bool SPEEDS> struct SplitMail2T : SplitMail2Head, SplitMail2Pt<SPEEDS>, SplitMail2Tail {};
+using SplitMail2 = SplitMail2T<true>;
+static_assert(sizeof(SplitMail2T<true>) == sizeof(SplitMail2T<false>) + sizeof(double) * 2 * 64, "the forms differ by `pt` alone");
+template <bool SPEEDS> struct SplitMail2Of { using type = SplitMail2T<SPEEDS>; };
 constexpr int kS3Valid = 0x10000, kS3Hit = 0x100, kS3Bad = 0x200, kS3Ended = 0x400, kS3Timeout = 0x800,
               kS3Reset = 0x1000, kS3Timeout2 = 0x2000;
 
@@ -125,8 +140,14 @@ __device__ __forceinline__ void selfcheck_answer(const EnvParams &p) {
 // instruction -- and only the download wave's fifteen, the critical wave's, stay in registers (parking them as well
 // puts an LDS round trip on the critical path: measured slower).  Only the owning wave ever touches its parking area,
 // and the LDS executes a wave's accesses in order.
-struct RolePark3 { uint32_t p[24][64], s[32][64]; };                  // three-wave kernel: the player's and the service wave's variables, 14 KB
-struct RolePark2 { uint32_t p[40][64]; };                        // two-wave kernel: the player carries the service state too, 10 KB
+// (SPEEDS == false: the player parks no sd / pt / pt_sum / pl_left / play_id, 16 words instead of 24, four ds_*2st64 transfers
+// per direction instead of six; the service wave's o_pt a dead 0)
+template <bool SPEEDS = true>
+struct RolePark3T { uint32_t p[SPEEDS ? 24 : 16][64], s[32][64]; };   // three-wave kernel: the player's and the service wave's variables, 14 KB
+template <bool SPEEDS = true>
+struct RolePark2T { uint32_t p[SPEEDS ? 40 : 32][64]; };         // two-wave kernel: the player carries the service state too, 10 KB
+using RolePark3 = RolePark3T<true>;
+using RolePark2 = RolePark2T<true>;
 
 struct ParkWords {
     uint32_t w[40];
@@ -160,14 +181,18 @@ __device__ __forceinline__ void park_load(uint32_t (*area)[64], ParkWords &k) {
     k.n = 0;
 }
 
+template <bool SPEEDS = true>
 __device__ inline void lanej_store_player(const LaneJ &s, const EnvParams &p, int64_t i) {
     p.buf[i] = s.buf; p.sumk[i] = s.sumk;
     p.k[i] = s.k; p.chunk_id[i] = s.chunk_id; p.n_su[i] = s.n_su; p.n_rb[i] = s.n_rb;
     p.n_play[i] = s.n_play; p.last_action[i] = s.last_action;
     p.flags[i] = (uint8_t)((s.su ? kFlagStartUp : 0) | (s.be ? kFlagBufEmpty : 0) |
                            (s.bf ? kFlagBufFull : 0) | kFlagArmed);
-    if (p.lane_speeds) { p.sd_lane[i] = s.sd; p.pt_lane[i] = s.pt; }
-    if (p.lane_speeds && p.speed_rows >= 2) { p.pl_left[i] = s.pl_left; p.play_id[i] = s.play_id; p.pt_sum[i] = s.pt_sum; }
+    if constexpr (SPEEDS) {
+        using SP = SpeedParams<SPEEDS>;
+        if (SP::lane_speeds(p)) { SP::sd_lane(p)[i] = s.sd; SP::pt_lane(p)[i] = s.pt; }
+        if (SP::lane_speeds(p) && SP::speed_rows(p) >= 2) { SP::pl_left(p)[i] = s.pl_left; SP::play_id(p)[i] = s.play_id; SP::pt_sum(p)[i] = s.pt_sum; }
+    }
 }
 
 // =====================================================================================================================
@@ -202,7 +227,7 @@ __device__ __forceinline__ void role_d_begin(DVars &v, const EnvParams &p) {
 // before the barrier: the download of step d_step, started at its (predicted) call site.  SAMPLE: a re-arm moves the cursor
 // to the episode sampler's (trace, offset) of the new episode (abr_env.hip: sampled_episode) -- speculatively, like
 // everything here: the workspace's trace_id / offset0 are written by the wave that owns the episode number
-template <int MODE, bool ACT_RING, bool SAMPLE = false>
+template <int MODE, bool ACT_RING, bool SAMPLE = false, bool SPEEDS = true>
 __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMail &m, ActRing *ring,
                                            const int32_t *__restrict__ actions, int32_t *__restrict__ actions_out,
                                            int32_t n_total, uint64_t seed, int32_t t,
@@ -211,7 +236,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     const int32_t V = p.video_length;
     const int cb = t & 1;                      // this iteration's mailbox slot
-    const abrx::Tables tb = make_tables(p);
+    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p);
     int32_t flags = 0;
     ABR_STAMP(0);
     if (v.d_alive && v.d_step < n_total) {
@@ -279,8 +304,8 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
 
 // Validate the record issued in iteration t against the player's true call site, which P published before that
 // iteration's barrier (slot t & 1 stays intact until P's iteration t + 2): first thing in iteration t + 1.
-template <bool SAMPLE = false>
-__device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const abrx::Tables &tb, int32_t t) {
+template <bool SAMPLE = false, class TB>
+__device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const TB &tb, int32_t t) {
     const int l = threadIdx.x & 63;
     const int cb = t & 1;
     // everything the common cases look at in ONE round of LDS reads: this wave is on the iteration's critical path, and a read
@@ -338,21 +363,30 @@ struct PVars {
     int32_t episode_no, b_step;
     bool b_alive, was_done;
 };
+// SPEEDS == false: 14 words + 2 of padding = 16 (no sd, pt, pt_sum, pl_left, play_id); else 22 + 2 = 24
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p_words(ParkWords &k, const PVars &v) {
     const LaneJ &s = v.s;
-    pw_f64(k, s.buf); pw_f64(k, s.sd); pw_f64(k, s.pt); pw_f64(k, s.pt_sum); pw_i64(k, s.sumk);
+    pw_f64(k, s.buf);
+    if constexpr (SPEEDS) { pw_f64(k, s.sd); pw_f64(k, s.pt); pw_f64(k, s.pt_sum); }
+    pw_i64(k, s.sumk);
     pw_i32(k, s.k); pw_i32(k, s.chunk_id); pw_i32(k, s.n_su); pw_i32(k, s.n_rb); pw_i32(k, s.n_play);
-    pw_i32(k, s.avail_k); pw_i32(k, s.last_action); pw_i32(k, s.pl_left); pw_i32(k, s.play_id);
+    pw_i32(k, s.avail_k); pw_i32(k, s.last_action);
+    if constexpr (SPEEDS) { pw_i32(k, s.pl_left); pw_i32(k, s.play_id); }
     pw_i32(k, (s.su ? 1 : 0) | (s.be ? 2 : 0) | (s.bf ? 4 : 0) | (v.b_alive ? 8 : 0) | (v.was_done ? 16 : 0));
     pw_i32(k, v.episode_no); pw_i32(k, v.b_step);
     pw_i32(k, 0); pw_i32(k, 0);
 }
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p_unwords(const ParkWords &k, int &at, PVars &v, const EnvParams &p) {
     LaneJ &s = v.s;
-    s.buf = pr_f64(k, at); s.sd = pr_f64(k, at); s.pt = pr_f64(k, at); s.pt_sum = pr_f64(k, at); s.sumk = pr_i64(k, at);
+    s.buf = pr_f64(k, at);
+    if constexpr (SPEEDS) { s.sd = pr_f64(k, at); s.pt = pr_f64(k, at); s.pt_sum = pr_f64(k, at); }
+    else s.sd = p.sd;                          // the one play speed, uniform
+    s.sumk = pr_i64(k, at);
     s.k = pr_i32(k, at); s.chunk_id = pr_i32(k, at); s.n_su = pr_i32(k, at); s.n_rb = pr_i32(k, at);
-    s.n_play = pr_i32(k, at); s.avail_k = pr_i32(k, at); s.last_action = pr_i32(k, at); s.pl_left = pr_i32(k, at);
-    s.play_id = pr_i32(k, at);
+    s.n_play = pr_i32(k, at); s.avail_k = pr_i32(k, at); s.last_action = pr_i32(k, at);
+    if constexpr (SPEEDS) { s.pl_left = pr_i32(k, at); s.play_id = pr_i32(k, at); }
     const int32_t fl = pr_i32(k, at);
     s.su = fl & 1; s.be = fl & 2; s.bf = fl & 4; v.b_alive = fl & 8; v.was_done = fl & 16;
     v.episode_no = pr_i32(k, at); v.b_step = pr_i32(k, at);
@@ -360,21 +394,25 @@ __device__ __forceinline__ void p_unwords(const ParkWords &k, int &at, PVars &v,
     s.cur.j = 0; s.cur.tpos = 0; s.cur.tlen = 1; s.cur.trace = p.traces;      // the player never walks the trace
     s.lane = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
 }
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p_park(uint32_t (*area)[64], const PVars &v) {
     ParkWords k; k.n = 0;
-    p_words(k, v);
-    park_store<6>(area, k);
+    p_words<SPEEDS>(k, v);
+    park_store<SPEEDS ? 6 : 4>(area, k);
 }
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p_unpark(uint32_t (*area)[64], PVars &v, const EnvParams &p) {
-    ParkWords k; park_load<6>(area, k);
+    ParkWords k; park_load<SPEEDS ? 6 : 4>(area, k);
     int at = 0;
-    p_unwords(k, at, v, p);
+    p_unwords<SPEEDS>(k, at, v, p);
 }
 
+template <bool SPEEDS = true>
 __device__ __forceinline__ double player_latency(const EnvParams &p, const LaneJ &s) {
-    return !p.lane_speeds ? lane_avg_latency(p, s.sumk, s.n_play)
-           : (p.speed_rows >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
-                                : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
+    using SP = SpeedParams<SPEEDS>;
+    return !SP::lane_speeds(p) ? lane_avg_latency(p, s.sumk, s.n_play)
+           : (SP::speed_rows(p) >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
+                                   : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
 }
 
 // tell the download side where this lane really is, and all waves whether anything is left to do
@@ -399,12 +437,13 @@ __device__ __forceinline__ void player_clear(PVars &v, const EnvParams &p) {
     v.episode_no = 0; v.b_step = 0; v.b_alive = false; v.was_done = true;
 }
 
+template <bool SPEEDS = true>
 __device__ __forceinline__ void role_p3_begin(PVars &v, const EnvParams &p) {
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     player_clear(v, p);
     if (i < p.n_lanes) {
         v.was_done = p.done[i] != 0;
-        lanej_load(v.s, p, i);
+        lanej_load<SPEEDS>(v.s, p, i);
         v.episode_no = p.episode_no[i];
         v.b_alive = !v.was_done;
     }
@@ -415,13 +454,14 @@ __device__ __forceinline__ void role_p3_begin(PVars &v, const EnvParams &p) {
 // finished step goes to S through m2.
 // (M2 / cb2: where the finished step goes for S -- SplitMail2 slot t & 1 under the barrier; a deeper ring in the diagnostic
 // pair kernel, tools/diag/csrc/abr_env_pair.h)
-template <int MODE, class M2>
+template <int MODE, bool SPEEDS = true, class M2>
 __device__ __forceinline__ void role_p3_pre(PVars &v, const EnvParams &p, SplitMail &m, M2 &m2,
                                             int32_t n_total, int32_t t, int cb2) {
     const int l = threadIdx.x & 63;
     const int cb = t & 1, pb = (t + 1) & 1;    // this iteration's / the previous one's slot
-    const abrx::Tables tb = make_tables(p, ABR_SPLIT3_CASCADE != 0);
-    const bool speeds = p.lane_speeds != nullptr;
+    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p, ABR_SPLIT3_CASCADE != 0);
+    const bool speeds = SpeedParams<SPEEDS>::lane_speeds(p) != nullptr;
+    (void)speeds;
     LaneJ &s = v.s;
     int32_t meta = 0;
     ABR_STAMP(8);
@@ -451,7 +491,7 @@ __device__ __forceinline__ void role_p3_pre(PVars &v, const EnvParams &p, SplitM
                 m2.dl[cb2][l] = d.dl; m2.n_dl[cb2][l] = d.n_dl;
                 m2.nrb_r[cb2][l] = s.n_rb; m2.nsu_r[cb2][l] = s.n_su;
                 if (sr.ended || sr.timeout) {
-                    m2.lat[cb2][l] = player_latency(p, s);
+                    m2.lat[cb2][l] = player_latency<SPEEDS>(p, s);
                     if (p.auto_reset && sr.ended) {
                         // re-arm: this step's observation is the new episode's first call site
                         abrx::lanej_init_player(s, tb);
@@ -462,7 +502,7 @@ __device__ __forceinline__ void role_p3_pre(PVars &v, const EnvParams &p, SplitM
                 }
                 m2.buf[cb2][l] = s.buf; m2.k[cb2][l] = s.k; m2.nplay_o[cb2][l] = s.n_play;
                 m2.nrb_o[cb2][l] = s.n_rb; m2.nsu_o[cb2][l] = s.n_su;
-                if (speeds) m2.pt[cb2][l] = s.pt;
+                if constexpr (SPEEDS) { if (speeds) m2.pt[cb2][l] = s.pt; }
             }
             v.b_step++;
         }
@@ -473,10 +513,11 @@ __device__ __forceinline__ void role_p3_pre(PVars &v, const EnvParams &p, SplitM
     ABR_STAMP(17);
 }
 
+template <bool SPEEDS = true>
 __device__ __forceinline__ void role_p3_end(const PVars &v, const EnvParams &p) {
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
-    if (i < p.n_lanes && !v.was_done) lanej_store_player(v.s, p, i);
+    if (i < p.n_lanes && !v.was_done) lanej_store_player<SPEEDS>(v.s, p, i);
 }
 
 // =====================================================================================================================
@@ -493,10 +534,12 @@ struct SVars {
     uint8_t done;
     bool was_done;
 };
+// SPEEDS == false: o_pt is not carried (its two words hold zeros: the area keeps its 32 words, eight transfers)
+template <bool SPEEDS = true>
 __device__ __forceinline__ void s_park(uint32_t (*area)[64], const SVars &v) {
     ParkWords k; k.n = 0;
     pw_f64(k, v.last_bw); pw_f64(k, v.hist_n); pw_f64(k, v.hist_s); pw_f64(k, v.g_su_obs); pw_f64(k, v.g_rb_obs);
-    pw_f64(k, v.o_buf); pw_f64(k, v.o_pt);
+    pw_f64(k, v.o_buf); pw_f64(k, SPEEDS ? v.o_pt : 0.0);
     pw_i32(k, v.o_chunk); pw_i32(k, v.o_last); pw_i32(k, v.o_k); pw_i32(k, v.o_nplay); pw_i32(k, v.o_nrb);
     pw_i32(k, v.o_nsu); pw_i32(k, v.n_su_obs); pw_i32(k, v.n_rb_obs); pw_i32(k, v.episode_no); pw_i32(k, v.s_next);
     pw_i32(k, v.a_next); pw_i32(k, v.a_chunk); pw_i32(k, v.a_ep); pw_i32(k, v.last_cb);
@@ -504,11 +547,13 @@ __device__ __forceinline__ void s_park(uint32_t (*area)[64], const SVars &v) {
     pw_f64(k, v.var_run); pw_i32(k, 0);
     park_store<8>(area, k);
 }
+template <bool SPEEDS = true>
 __device__ __forceinline__ void s_unpark(uint32_t (*area)[64], SVars &v) {
     ParkWords k; park_load<8>(area, k);
     int at = 0;
     v.last_bw = pr_f64(k, at); v.hist_n = pr_f64(k, at); v.hist_s = pr_f64(k, at); v.g_su_obs = pr_f64(k, at);
-    v.g_rb_obs = pr_f64(k, at); v.o_buf = pr_f64(k, at); v.o_pt = pr_f64(k, at);
+    v.g_rb_obs = pr_f64(k, at); v.o_buf = pr_f64(k, at);
+    if constexpr (SPEEDS) v.o_pt = pr_f64(k, at); else { v.o_pt = 0.0; at += 2; }
     v.o_chunk = pr_i32(k, at); v.o_last = pr_i32(k, at); v.o_k = pr_i32(k, at); v.o_nplay = pr_i32(k, at);
     v.o_nrb = pr_i32(k, at); v.o_nsu = pr_i32(k, at); v.n_su_obs = pr_i32(k, at); v.n_rb_obs = pr_i32(k, at);
     v.episode_no = pr_i32(k, at); v.s_next = pr_i32(k, at); v.a_next = pr_i32(k, at); v.a_chunk = pr_i32(k, at);
@@ -518,6 +563,7 @@ __device__ __forceinline__ void s_unpark(uint32_t (*area)[64], SVars &v) {
     v.var_run = pr_f64(k, at);
 }
 
+template <bool SPEEDS = true>
 __device__ __forceinline__ void service_write_obs(const SVars &v, const EnvParams &p, int64_t i, float *obs) {
     if (!obs) return;
     const int64_t n = p.n_lanes;
@@ -526,7 +572,7 @@ __device__ __forceinline__ void service_write_obs(const SVars &v, const EnvParam
     ABR_OUT(obs[ABR_OBS_LAST_BANDWIDTH * n + i], (float)v.last_bw);
     ABR_OUT(obs[ABR_OBS_BUFFER_LEVEL * n + i], (float)v.o_buf);
     ABR_OUT(obs[ABR_OBS_GLOBAL_TIME * n + i], (float)p.G[v.o_k]);
-    ABR_OUT(obs[ABR_OBS_PLAY_TIME * n + i], (float)(p.lane_speeds ? v.o_pt : p.GP[v.o_nplay]));
+    ABR_OUT(obs[ABR_OBS_PLAY_TIME * n + i], (float)(SpeedParams<SPEEDS>::lane_speeds(p) ? v.o_pt : p.GP[v.o_nplay]));
     ABR_OUT(obs[ABR_OBS_REBUFFER_TIME * n + i], (float)p.G[v.o_nrb]);
     ABR_OUT(obs[ABR_OBS_STARTUP_TIME * n + i], (float)p.G[v.o_nsu]);
 }
@@ -572,7 +618,7 @@ __device__ __forceinline__ void ledger_record_split(const EnvParams &p, int64_t 
 
 // the record P left in slot `sl`: division, history, reward, done, observation, episode end
 // (M2: SplitMail2, or the ring kernel's RingPS -- the same fields with more slots)
-template <bool SAMPLE = false, bool LEDGER = false, class M2>
+template <bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, class M2>
 __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 &m2, int sl,
                                                float *__restrict__ obs_out, float *__restrict__ reward_out,
                                                uint8_t *__restrict__ done_out) {
@@ -589,7 +635,7 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
         v.done |= ABR_DONE_BADACT;
         if (reward_out) ABR_OUT(reward_out[o], 0.0f);
         if (done_out) ABR_OUT(done_out[o], v.done);
-        service_write_obs(v, p, i, obs);
+        service_write_obs<SPEEDS>(v, p, i, obs);
         return;
     }
     const int32_t chunk = v.o_chunk, prev_action = v.o_last;
@@ -633,12 +679,13 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
     }
     v.o_buf = m2.buf[sl][l]; v.o_k = m2.k[sl][l]; v.o_nplay = m2.nplay_o[sl][l]; v.o_nrb = m2.nrb_o[sl][l];
     v.o_nsu = m2.nsu_o[sl][l];
-    if (p.lane_speeds) v.o_pt = m2.pt[sl][l];
-    service_write_obs(v, p, i, obs);
+    if constexpr (SPEEDS) { if (SpeedParams<SPEEDS>::lane_speeds(p)) v.o_pt = m2.pt[sl][l]; }
+    service_write_obs<SPEEDS>(v, p, i, obs);
 }
 
-__device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &, ActRing &ring) {
-    const EnvParams &p = fresh_params();
+template <bool SPEEDS = true>
+__device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &pk, ActRing &ring) {
+    const EnvParams &p = ABR_S_FRESH_PARAMS ? fresh_params() : pk;
     const int l = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     v.last_bw = 0.0; v.hist_n = 0.0; v.hist_s = 0.0; v.g_su_obs = 0.0; v.g_rb_obs = 0.0; v.o_buf = 0.0; v.o_pt = 0.0; v.var_run = 0.0;
@@ -653,7 +700,7 @@ __device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &, ActRin
         v.g_su_obs = p.G[v.n_su_obs]; v.g_rb_obs = p.G[v.n_rb_obs];
         v.o_chunk = p.chunk_id[i]; v.o_last = p.last_action[i]; v.o_k = p.k[i]; v.o_nplay = p.n_play[i];
         v.o_nrb = p.n_rb[i]; v.o_nsu = p.n_su[i]; v.o_buf = p.buf[i];
-        if (p.lane_speeds) v.o_pt = p.pt_lane[i];
+        if constexpr (SPEEDS) { using SP = SpeedParams<SPEEDS>; if (SP::lane_speeds(p)) v.o_pt = SP::pt_lane(p)[i]; }
     }
     v.a_next = 0; v.a_chunk = v.o_chunk; v.a_ep = v.episode_no;
     if (l == 0) lds_st(&ring.act_hi, 0);  // nothing drawn yet (D looks at the ring from its second iteration on)
@@ -661,11 +708,11 @@ __device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &, ActRin
 }
 
 // before the barrier: draw the policy's actions ahead of D, then serve what P finished in the previous iteration
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
-__device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &, SplitMail &m, SplitMail2 &m2, ActRing &ring,
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+__device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &pk, SplitMail &m, typename SplitMail2Of<SPEEDS>::type &m2, ActRing &ring,
                                            float *__restrict__ obs_out, float *__restrict__ reward_out,
                                            uint8_t *__restrict__ done_out, int32_t n_total, uint64_t seed, int32_t t) {
-    const EnvParams &p = fresh_params();
+    const EnvParams &p = ABR_S_FRESH_PARAMS ? fresh_params() : pk;
     const int l = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     const int cb = t & 1, pb = (t + 1) & 1;
@@ -696,7 +743,7 @@ __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &, SplitMai
         lds_writes_done();
         if (l == 0) lds_st(&ring.act_hi, v.a_next);
     }
-    if (t >= 1 && i < p.n_lanes) service_record<SAMPLE, LEDGER>(v, p, m2, pb, obs_out, reward_out, done_out);
+    if (t >= 1 && i < p.n_lanes) service_record<SAMPLE, LEDGER, SPEEDS>(v, p, m2, pb, obs_out, reward_out, done_out);
     v.last_cb = cb;
     ABR_STAMP(21);
 }
@@ -711,16 +758,16 @@ __device__ __forceinline__ void sampled_episode_store(const EnvParams &p, const 
     }
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
-__device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMail2 &m2, float *__restrict__ obs_out,
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+__device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &pk, typename SplitMail2Of<SPEEDS>::type &m2, float *__restrict__ obs_out,
                                            float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                            int32_t *__restrict__ actions_out, int32_t n_total,
                                            const abrx::EpisodeSampler &smp = abrx::EpisodeSampler{}) {
-    const EnvParams &p = fresh_params();
+    const EnvParams &p = ABR_S_FRESH_PARAMS ? fresh_params() : pk;
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
     if (i >= p.n_lanes) return;
-    service_record<SAMPLE, LEDGER>(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
+    service_record<SAMPLE, LEDGER, SPEEDS>(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
     if (!v.was_done) {
         if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.episode_no);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.episode_no;
@@ -733,7 +780,7 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMai
         if (reward_out) reward_out[o] = 0.0f;
         if (done_out) done_out[o] = v.done;
         if (MODE == 2 && actions_out) actions_out[o] = -1;
-        service_write_obs(v, p, i, obs_out ? obs_out + (int64_t)t2 * ABR_OBS_DIM * p.n_lanes : nullptr);
+        service_write_obs<SPEEDS>(v, p, i, obs_out ? obs_out + (int64_t)t2 * ABR_OBS_DIM * p.n_lanes : nullptr);
     }
 }
 
@@ -741,7 +788,9 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &, SplitMai
 // scripted actions [n_steps][n_lanes]
 // SAMPLE: the instance that runs while an episode sampler is installed (`smp`; the other instances never read it)
 // LEDGER: the instance that runs while an episode ledger is installed (`led`; likewise)
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+// SPEEDS: the instance that runs while per-lane speeds, a speed schedule or a speed rule is installed; the <false>
+// instances carry no speed state through the loop, the parking words or the mailboxes (abr_env.hip: make_tables)
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) void env_split3_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
@@ -749,7 +798,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     abrx::EpisodeLedger led) {
     (void)led;                         // read from the kernarg segment where an episode ends (ledger_record_split)
     __shared__ SplitMail m;
-    __shared__ SplitMail2 m2;
+    __shared__ typename SplitMail2Of<SPEEDS>::type m2;
     __shared__ ActRing ring;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform by construction
@@ -757,7 +806,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
 #ifdef ABR_SPLIT_STAMPS
     if (fresh_params().n_lanes != p.n_lanes || fresh_params().traces != p.traces) __builtin_trap();   // fresh_params' contract
 #endif
-    __shared__ RolePark3 park;
+    __shared__ RolePark3T<SPEEDS> park;
     // The download wave is the critical one; priority outranks age in the SIMD's issue arbitration, so its instructions
     // go first whenever they are ready (+2.8 %, profiles/r03_ab_lds_staging.txt (4)); the ORDER D > P > S is worth 8 %
     // (profiles/r03_ab_split3.txt)
@@ -766,28 +815,28 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     if (role == 0) ABR_WG_TIME(0);
     ABR_WG_WHERE(role);
     if (role == 0) __builtin_amdgcn_s_setprio(ABR_PRIO_D);
-    else if (role == 1) { __builtin_amdgcn_s_setprio(ABR_PRIO_P); PVars v; role_p3_begin(v, p); p_park(park.p, v); }
-    else { __builtin_amdgcn_s_setprio(ABR_PRIO_S); SVars v; role_s_begin(v, p, ring); s_park(park.s, v); }
+    else if (role == 1) { __builtin_amdgcn_s_setprio(ABR_PRIO_P); PVars v; role_p3_begin<SPEEDS>(v, p); p_park<SPEEDS>(park.p, v); }
+    else { __builtin_amdgcn_s_setprio(ABR_PRIO_S); SVars v; role_s_begin<SPEEDS>(v, p, ring); s_park<SPEEDS>(park.s, v); }
     for (int32_t t = 0;; t++) {
         if (role == 0) {
-            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
-            role_d_pre<MODE, true, SAMPLE>(dv, p, m, &ring, actions, actions_out, n_total, seed, t, smp);
+            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables<SPEEDS>(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
+            role_d_pre<MODE, true, SAMPLE, SPEEDS>(dv, p, m, &ring, actions, actions_out, n_total, seed, t, smp);
         } else if (role == 1) {
-            PVars v; p_unpark(park.p, v, p);
-            role_p3_pre<MODE>(v, p, m, m2, n_total, t, t & 1);
-            p_park(park.p, v);
+            PVars v; p_unpark<SPEEDS>(park.p, v, p);
+            role_p3_pre<MODE, SPEEDS>(v, p, m, m2, n_total, t, t & 1);
+            p_park<SPEEDS>(park.p, v);
         } else {
-            SVars v; s_unpark(park.s, v);
-            role_s_pre<MODE, SAMPLE, LEDGER>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
-            s_park(park.s, v);
+            SVars v; s_unpark<SPEEDS>(park.s, v);
+            role_s_pre<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
+            s_park<SPEEDS>(park.s, v);
         }
         __syncthreads();                       // THE barrier: every wave, every iteration, this one site
         ABR_STAMP(role == 0 ? 5 : (role == 1 ? 18 : 22));
         if (!m.any_alive[t & 1]) break;        // written by P before the barrier: identical in all waves
     }
     if (role == 0) { role_d_end(dv, p); ABR_WG_TIME(1); }
-    else if (role == 1) { PVars v; p_unpark(park.p, v, p); role_p3_end(v, p); ABR_WG_TIME(2); }
-    else { SVars v; s_unpark(park.s, v); role_s_end<MODE, SAMPLE, LEDGER>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
+    else if (role == 1) { PVars v; p_unpark<SPEEDS>(park.p, v, p); role_p3_end<SPEEDS>(v, p); ABR_WG_TIME(2); }
+    else { SVars v; s_unpark<SPEEDS>(park.s, v); role_s_end<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
 }
 
 // =====================================================================================================================
@@ -800,24 +849,27 @@ struct P2Vars {
     int32_t n_su_obs, n_rb_obs;
     uint8_t done;
 };
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p2_park(uint32_t (*area)[64], const P2Vars &v) {
     ParkWords k; k.n = 0;
-    p_words(k, v.pv);
+    p_words<SPEEDS>(k, v.pv);
     pw_f64(k, v.last_bw); pw_f64(k, v.hist_n); pw_f64(k, v.hist_s); pw_f64(k, v.g_su_obs); pw_f64(k, v.g_rb_obs);
     pw_i32(k, v.n_su_obs); pw_i32(k, v.n_rb_obs); pw_i32(k, v.done);
     pw_f64(k, v.var_run); pw_i32(k, 0);
-    park_store<10>(area, k);
+    park_store<SPEEDS ? 10 : 8>(area, k);
 }
+template <bool SPEEDS = true>
 __device__ __forceinline__ void p2_unpark(uint32_t (*area)[64], P2Vars &v, const EnvParams &p) {
-    ParkWords k; park_load<10>(area, k);
+    ParkWords k; park_load<SPEEDS ? 10 : 8>(area, k);
     int at = 0;
-    p_unwords(k, at, v.pv, p);
+    p_unwords<SPEEDS>(k, at, v.pv, p);
     v.last_bw = pr_f64(k, at); v.hist_n = pr_f64(k, at); v.hist_s = pr_f64(k, at); v.g_su_obs = pr_f64(k, at);
     v.g_rb_obs = pr_f64(k, at);
     v.n_su_obs = pr_i32(k, at); v.n_rb_obs = pr_i32(k, at); v.done = (uint8_t)pr_i32(k, at);
     v.var_run = pr_f64(k, at);
 }
 
+template <bool SPEEDS = true>
 __device__ __forceinline__ void role_p2_begin(P2Vars &v, const EnvParams &) {
     const EnvParams &p = fresh_params();
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
@@ -827,7 +879,7 @@ __device__ __forceinline__ void role_p2_begin(P2Vars &v, const EnvParams &) {
     if (i < p.n_lanes) {
         v.done = p.done[i];
         v.pv.was_done = v.done != 0;
-        lanej_load(v.pv.s, p, i);
+        lanej_load<SPEEDS>(v.pv.s, p, i);
         v.n_su_obs = p.n_su_obs[i]; v.n_rb_obs = p.n_rb_obs[i]; v.pv.episode_no = p.episode_no[i];
         v.last_bw = p.last_bw[i]; v.hist_n = p.hist_n[i]; v.hist_s = p.hist_s[i]; v.var_run = p.var_run[i];
         v.g_su_obs = p.G[v.n_su_obs]; v.g_rb_obs = p.G[v.n_rb_obs];
@@ -836,7 +888,7 @@ __device__ __forceinline__ void role_p2_begin(P2Vars &v, const EnvParams &) {
     ABR_STAMP_INIT();
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
 __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitMail &m, float *__restrict__ obs_out,
                                             float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                             int32_t n_total, int32_t t) {
@@ -844,7 +896,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
     const int l = threadIdx.x & 63;
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     const int cb = t & 1, pb = (t + 1) & 1;    // this iteration's / the previous one's slot
-    const abrx::Tables tb = make_tables(p);
+    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p);
     LaneJ &s = v.pv.s;
     ABR_STAMP(8);
     if (v.pv.b_alive && v.pv.b_step < n_total && t >= 1) {
@@ -862,7 +914,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                 v.done |= ABR_DONE_BADACT;
                 if (reward_out) ABR_OUT(reward_out[o], 0.0f);
                 if (done_out) ABR_OUT(done_out[o], (uint8_t)v.done);
-                write_obs_j(s, p, i, obs, v.last_bw);
+                write_obs_j<SPEEDS>(s, p, i, obs, v.last_bw);
                 v.pv.b_alive = false;
             } else {
                 abrx::Download d;
@@ -876,7 +928,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                 // ONE burst of loads, consumed after the divisions below (this wave is the two-wave kernel's critical one: two
                 // rounds of dependent loads were two L2 round trips per iteration)
                 const double g_rb = p.G[s.n_rb], g_su = p.G[s.n_su];
-                double o_k = p.G[s.k], o_pl = p.lane_speeds ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
+                double o_k = p.G[s.k], o_pl = SpeedParams<SPEEDS>::lane_speeds(p) ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
                 double var = 0.0;
                 if (sr.hit) {
                     const int64_t h = (int64_t)chunk * p.n_lanes + i;
@@ -901,10 +953,10 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                 if (sr.ended || sr.timeout) {
                     p.ep_qoe_terms[0 * p.n_lanes + i] = g_rb;
                     p.ep_qoe_terms[1 * p.n_lanes + i] = g_su;
-                    p.ep_qoe_terms[2 * p.n_lanes + i] = player_latency(p, s);
+                    p.ep_qoe_terms[2 * p.n_lanes + i] = player_latency<SPEEDS>(p, s);
                     p.ep_qoe_terms[3 * p.n_lanes + i] = v.var_run;
                     if constexpr (LEDGER)
-                        ledger_record_split<SAMPLE, false>(p, i, g_rb, g_su, player_latency(p, s), v.var_run, v.pv.episode_no, s.chunk_id, v.done);
+                        ledger_record_split<SAMPLE, false>(p, i, g_rb, g_su, player_latency<SPEEDS>(p, s), v.var_run, v.pv.episode_no, s.chunk_id, v.done);
                     if (p.auto_reset && sr.ended) {
                         // re-arm: this step's obs is the new episode's first call site
                         abrx::lanej_init_player(s, tb);
@@ -913,7 +965,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                         v.last_bw = 0.0; v.hist_n = 0.0; v.hist_s = 0.0; v.var_run = 0.0;
                         v.done = 0;
                         if (!abrx::lanej_wait_call(s, tb)) v.done |= ABR_DONE_TIMEOUT;
-                        o_k = p.G[s.k]; o_pl = p.lane_speeds ? s.pt : p.GP[s.n_play];
+                        o_k = p.G[s.k]; o_pl = SpeedParams<SPEEDS>::lane_speeds(p) ? s.pt : p.GP[s.n_play];
                         o_rb = p.G[s.n_rb]; o_su = p.G[s.n_su];
                     }
                 }
@@ -929,7 +981,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
     ABR_STAMP(17);
 }
 
-template <int MODE, bool SAMPLE = false>
+template <int MODE, bool SAMPLE = false, bool SPEEDS = true>
 __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, float *__restrict__ obs_out,
                                             float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                             int32_t *__restrict__ actions_out, int32_t n_total,
@@ -940,7 +992,7 @@ __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, 
     if (i >= p.n_lanes) return;
     if (!v.pv.was_done) {
         if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.pv.episode_no);
-        lanej_store_player(v.pv.s, p, i);
+        lanej_store_player<SPEEDS>(v.pv.s, p, i);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.pv.episode_no;
         p.last_bw[i] = v.last_bw; p.hist_n[i] = v.hist_n; p.hist_s[i] = v.hist_s; p.var_run[i] = v.var_run;
         p.done[i] = v.done;
@@ -951,11 +1003,11 @@ __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, 
         if (reward_out) ABR_OUT(reward_out[o], 0.0f);
         if (done_out) ABR_OUT(done_out[o], (uint8_t)v.done);
         if (MODE == 2 && actions_out) ABR_OUT(actions_out[o], (int32_t)-1);
-        write_obs_j(v.pv.s, p, i, obs_out ? obs_out + (int64_t)t2 * ABR_OBS_DIM * p.n_lanes : nullptr, v.last_bw);
+        write_obs_j<SPEEDS>(v.pv.s, p, i, obs_out ? obs_out + (int64_t)t2 * ABR_OBS_DIM * p.n_lanes : nullptr, v.last_bw);
     }
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
 __global__ __launch_bounds__(128) void env_split_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
@@ -969,26 +1021,26 @@ __global__ __launch_bounds__(128) void env_split_kernel(
 #ifdef ABR_SPLIT_STAMPS
     if (fresh_params().n_lanes != p.n_lanes || fresh_params().traces != p.traces) __builtin_trap();   // fresh_params' contract
 #endif
-    __shared__ RolePark2 park;
+    __shared__ RolePark2T<SPEEDS> park;
     DVars dv;                          // as in env_split3_kernel: D's variables in registers, the player's through LDS
     role_d_begin(dv, p);
     if (role == 0) __builtin_amdgcn_s_setprio(2);
-    else { P2Vars v; role_p2_begin(v, p); p2_park(park.p, v); }
+    else { P2Vars v; role_p2_begin<SPEEDS>(v, p); p2_park<SPEEDS>(park.p, v); }
     for (int32_t t = 0;; t++) {
         if (role == 0) {
-            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables(p), t - 1);
-            role_d_pre<MODE, false, SAMPLE>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t, smp);
+            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables<SPEEDS>(p), t - 1);
+            role_d_pre<MODE, false, SAMPLE, SPEEDS>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t, smp);
         } else {
-            P2Vars v; p2_unpark(park.p, v, fresh_params());
-            role_p2_pre<MODE, SAMPLE, LEDGER>(v, p, m, obs_out, reward_out, done_out, n_total, t);
-            p2_park(park.p, v);
+            P2Vars v; p2_unpark<SPEEDS>(park.p, v, fresh_params());
+            role_p2_pre<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m, obs_out, reward_out, done_out, n_total, t);
+            p2_park<SPEEDS>(park.p, v);
         }
         __syncthreads();                       // THE barrier: both waves, every iteration, this one site
         ABR_STAMP(role == 0 ? 5 : 18);
         if (!m.any_alive[t & 1]) break;        // written by P before the barrier: identical in both waves
     }
     if (role == 0) role_d_end(dv, p);
-    else { P2Vars v; p2_unpark(park.p, v, fresh_params()); role_p2_end<MODE, SAMPLE>(v, p, obs_out, reward_out, done_out, actions_out, n_total, smp); }
+    else { P2Vars v; p2_unpark<SPEEDS>(park.p, v, fresh_params()); role_p2_end<MODE, SAMPLE, SPEEDS>(v, p, obs_out, reward_out, done_out, actions_out, n_total, smp); }
 }
 
 #endif

@@ -80,7 +80,16 @@ struct SpeedRuleBlock {
     int32_t log_rows, reserved_;
 };
 
-struct Tables {
+// SPEEDS: whether the per-lane play-speed features (per-lane speeds, speed schedules, the speed rule) can be on at all.
+// TablesT<true> is the table every caller has always filled in (`Tables`); TablesT<false> carries the tag of a build that
+// has none of them: the speed fields are compile-time constants, and every lane function selects its one-speed path at
+// compile time (`if constexpr` on kSpeeds), so neither the tests nor the state they guard exist in the caller's code.
+template <bool SPEEDS = true>
+struct TablesT;
+
+template <>
+struct TablesT<true> {
+    static constexpr bool kSpeeds = true;
     const double *G;               // G[n] = dt added n times to 0.0 (global_time, download_time, ...)
     const int32_t *interval_tick;  // first tick k with int(G[k]/interval) >= j          (:158)
     const int32_t *avail_tick;     // first tick k with int(G[k]/chunk_length) - 1 >= c  (:143)
@@ -101,6 +110,24 @@ struct Tables {
     // per-lane speeds or when the speed / buffer range is not covered: the general chains then do the drains
     DrainTab drain;
 };
+
+template <>
+struct TablesT<false> {
+    static constexpr bool kSpeeds = false;
+    const double *G;
+    const int32_t *interval_tick;
+    const int32_t *avail_tick;
+    double L, sd, max_buffer, start_up_length;
+    int32_t V, max_ticks;
+    static constexpr bool per_lane_speed = false;
+    static constexpr int32_t speed_rows = 0;
+    static constexpr int64_t speed_stride = 0;
+    static constexpr const double *speeds = nullptr;
+    static constexpr const SpeedRuleBlock *rule = nullptr;
+    DrainTab drain;
+};
+
+using Tables = TablesT<true>;
 
 // Where a lane is in its bandwidth trace.  Only the download side (phase A) reads it.
 struct Cursor {
@@ -132,17 +159,21 @@ ABR_HD void cursor_init(Cursor &c, int32_t offset0) {
 }
 
 // Simulator.py:95-130, then T1-T3 of tick 0 (start_up_time += dt); everything but the cursor
-ABR_HD void lanej_init_player(LaneJ &s, const Tables &t) {
+template <class TB>
+ABR_HD void lanej_init_player(LaneJ &s, const TB &t) {
     s.buf = 0.0; s.sumk = 0;
     s.k = 0; s.chunk_id = 0; s.n_su = 1; s.n_rb = 0; s.n_play = 0;
     s.last_action = -1;
     s.su = true; s.be = true; s.bf = false;
     s.avail_k = t.avail_tick[0];
-    s.pt = 0.0;                    // play_time = 0 (:115); s.sd is set by the caller
-    s.pl_left = 0; s.play_id = 0; s.pt_sum = 0.0;      // play_length = 0, play_id = 0 (:113-114)
+    if constexpr (TB::kSpeeds) {
+        s.pt = 0.0;                    // play_time = 0 (:115); s.sd is set by the caller
+        s.pl_left = 0; s.play_id = 0; s.pt_sum = 0.0;      // play_length = 0, play_id = 0 (:113-114)
+    }
 }
 
-ABR_HD void lanej_init(LaneJ &s, const Tables &t, int32_t offset0) {
+template <class TB>
+ABR_HD void lanej_init(LaneJ &s, const TB &t, int32_t offset0) {
     lanej_init_player(s, t);
     cursor_init(s.cur, offset0);
 }
@@ -150,7 +181,8 @@ ABR_HD void lanej_init(LaneJ &s, const Tables &t, int32_t offset0) {
 // play_time += speed*dt for `a` playing ticks (:182).  With one speed for all lanes
 // play_time is the table value GP[n_play]; with per-lane speeds it is carried, advanced by
 // the same exact chain machinery.
-ABR_HD void lanej_play(LaneJ &s, const Tables &t, int32_t a) {
+template <class TB>
+ABR_HD void lanej_play(LaneJ &s, const TB &t, int32_t a) {
     if (!t.per_lane_speed || a <= 0) return;
     int32_t done = 0;
     double x = s.pt;
@@ -200,7 +232,8 @@ ABR_HD bool drain_to_zero(double &b_io, double sd, int32_t m, int32_t &a_out) {
 // is ~25 vector instructions against the ~58 of a chain segment plus its loop, and a buffer that runs dry is one pass over
 // the binades instead of six segments and a 16-tick tail).  Wave-uniform choice: a lane above the cascade (never seen: it
 // covers max_buffer + chunk_length) sends the whole wave through the chains.
-ABR_HD bool lanej_drain(const Tables &t, double &b_io, double sd, int32_t m, int32_t &a_out) {
+template <class TB>
+ABR_HD bool lanej_drain(const TB &t, double &b_io, double sd, int32_t m, int32_t &a_out) {
     if (t.drain.n > 0 && !wave_any(!(b_io < t.drain.top))) {
         const bool zero = drain_cascade(t.drain, sd, b_io, m, a_out);
         ABR_STAMP(24);
@@ -214,7 +247,8 @@ ABR_HD bool lanej_drain(const Tables &t, double &b_io, double sd, int32_t m, int
 // (:176-177); the chunk then lasts until play_length, `speed*dt` added per tick from 0, is
 // >= chunk_length (:183,:185-187): that many ticks, by the same exact chain.
 // k: the tick, b: buffer_level at that point of it (after :170, before :184) -- what a speed rule reads.
-ABR_HD void sched_begin_chunk(LaneJ &s, const Tables &t, int32_t k, double b) {
+template <class TB>
+ABR_HD void sched_begin_chunk(LaneJ &s, const TB &t, int32_t k, double b) {
     double v;
     if (t.speed_rows == kSpeedRowsRule) {
 #if defined(__HIP_DEVICE_COMPILE__) && defined(ABR_RULE_KERNARG_OFFSET)
@@ -241,7 +275,8 @@ ABR_HD void sched_begin_chunk(LaneJ &s, const Tables &t, int32_t k, double b) {
 
 // bookkeeping of `a` playing ticks inside one played chunk: play_time (exact chain), the sum of
 // play_time over those ticks (real arithmetic: it only feeds average_latency), chunk boundary
-ABR_HD void sched_played(LaneJ &s, const Tables &t, int32_t a) {
+template <class TB>
+ABR_HD void sched_played(LaneJ &s, const TB &t, int32_t a) {
     if (a <= 0) return;
     s.pt_sum += (double)a * s.pt + s.sd * (double)(((long long)a * (a - 1)) / 2);
     int32_t done = 0;
@@ -254,8 +289,8 @@ ABR_HD void sched_played(LaneJ &s, const Tables &t, int32_t a) {
 
 // buffer_level -= speed*dt for up to m playing ticks, stopping right after the first result that
 // is <= 0 (STOP_LE, :194) or < thr (STOP_LT, :190), one played chunk at a time
-template <int STOP>
-ABR_HD bool sched_drain(LaneJ &s, const Tables &t, double &b, double thr, int32_t m, int32_t &a_out) {
+template <int STOP, class TB>
+ABR_HD bool sched_drain(LaneJ &s, const TB &t, double &b, double thr, int32_t m, int32_t &a_out) {
     int32_t a_tot = 0;
     bool hit = false;
     while (a_tot < m && !hit) {
@@ -272,7 +307,8 @@ ABR_HD bool sched_drain(LaneJ &s, const Tables &t, double &b, double thr, int32_
 }
 
 // m full iterations: T4-T9 of a tick in which no chunk completes, then T1-T3 of the next
-ABR_HD void lanej_idle(LaneJ &s, const Tables &t, int32_t m) {
+template <class TB>
+ABR_HD void lanej_idle(LaneJ &s, const TB &t, int32_t m) {
     if (m <= 0) return;
     // :201-202 at the end of the first of these ticks.  A no-op everywhere (start_up implies
     // buffer_level < start_up_length once any tick has run) except right after init when
@@ -287,8 +323,12 @@ ABR_HD void lanej_idle(LaneJ &s, const Tables &t, int32_t m) {
         int32_t a = 0;
         double b = s.buf;
         bool zero;
-        if (t.speed_rows >= 2) zero = sched_drain<STOP_LE>(s, t, b, 0.0, m, a);
-        else { zero = lanej_drain(t, b, s.sd, m, a); lanej_play(s, t, a); }       // :184,:194
+        if constexpr (TB::kSpeeds) {
+            if (t.speed_rows >= 2) zero = sched_drain<STOP_LE>(s, t, b, 0.0, m, a);
+            else { zero = lanej_drain(t, b, s.sd, m, a); lanej_play(s, t, a); }   // :184,:194
+        } else {
+            zero = lanej_drain(t, b, t.sd, m, a);          // one speed for all lanes: play_time is GP[n_play]
+        }
         s.n_play += a;
         s.sumk += (long long)a * s.k + ((long long)a * (a - 1)) / 2;
         if (zero) { b = 0.0; s.be = true; s.n_rb += (m - a + 1); }             // :195-196, then :140
@@ -300,7 +340,8 @@ ABR_HD void lanej_idle(LaneJ &s, const Tables &t, int32_t m) {
 
 // From a post-head state that is not downloading: advance to the next call site
 // (returns true) or to max_ticks (returns false).
-ABR_HD bool lanej_wait_call(LaneJ &s, const Tables &t) {
+template <class TB>
+ABR_HD bool lanej_wait_call(LaneJ &s, const TB &t) {
     const int32_t mt = t.max_ticks;
     if (s.k >= s.avail_k && !s.bf) return true;
     int32_t w = s.avail_k - s.k;
@@ -319,8 +360,12 @@ ABR_HD bool lanej_wait_call(LaneJ &s, const Tables &t) {
         int32_t a = 0;
         double b = s.buf;
         bool cleared;
-        if (t.speed_rows >= 2) cleared = sched_drain<STOP_LT>(s, t, b, t.max_buffer, mt - s.k, a);
-        else { cleared = chain<STOP_LT>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
+        if constexpr (TB::kSpeeds) {
+            if (t.speed_rows >= 2) cleared = sched_drain<STOP_LT>(s, t, b, t.max_buffer, mt - s.k, a);
+            else { cleared = chain<STOP_LT>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
+        } else {
+            cleared = chain<STOP_LT>(b, -t.sd, t.max_buffer, mt - s.k, a);
+        }
         s.n_play += a;
         s.sumk += (long long)a * s.k + ((long long)a * (a - 1)) / 2;
         s.k += a;
@@ -369,7 +414,8 @@ struct StepLoads {
     int32_t avail_next;
 };
 
-ABR_HD StepLoads lanej_begin_load(const Cursor &s, const Tables &t, int32_t chunk_id) {
+template <class TB>
+ABR_HD StepLoads lanej_begin_load(const Cursor &s, const TB &t, int32_t chunk_id) {
     StepLoads ld;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma unroll
@@ -384,7 +430,8 @@ ABR_HD StepLoads lanej_begin_load(const Cursor &s, const Tables &t, int32_t chun
 
 // ... and the selection among them once the call-site tick k is known.  The cursor must be the
 // one the loads were issued for.
-ABR_HD StepStart lanej_begin_select(Cursor &s, const Tables &t, const StepLoads &ld, int32_t k) {
+template <class TB>
+ABR_HD StepStart lanej_begin_select(Cursor &s, const TB &t, const StepLoads &ld, int32_t k) {
     const int32_t *ke = ld.ke;
     const double *bw = ld.bw;
     StepStart st;
@@ -427,7 +474,8 @@ ABR_HD StepStart lanej_begin_select(Cursor &s, const Tables &t, const StepLoads 
     return st;
 }
 
-ABR_HD StepStart lanej_begin_step(Cursor &s, const Tables &t, int32_t k, int32_t chunk_id) {
+template <class TB>
+ABR_HD StepStart lanej_begin_step(Cursor &s, const TB &t, int32_t k, int32_t chunk_id) {
     const StepLoads ld = lanej_begin_load(s, t, chunk_id);
     return lanej_begin_select(s, t, ld, k);
 }
@@ -442,7 +490,8 @@ struct Download {
     bool hit;         // false: max_ticks reached first
 };
 
-ABR_HD Download lanej_download(Cursor &s, const Tables &t, const StepStart &st, int32_t k,
+template <class TB>
+ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int32_t k,
                                double target) {
     // One flat loop over chain SEGMENTS (abr_exact_jump.h); a lane moves on to its next
     // trace interval between two segments.  The next interval's bandwidth and end tick
@@ -531,7 +580,8 @@ ABR_HD Download lanej_download(Cursor &s, const Tables &t, const StepStart &st, 
 // The rest of the decision: the player side of the download's ticks, the completing tick,
 // then phase B up to the next call site.  `action` only labels the step (last_action);
 // avail_next = avail_tick[chunk_id + 1].
-ABR_HD StepResult lanej_after_download(LaneJ &s, const Tables &t, const Download &d,
+template <class TB>
+ABR_HD StepResult lanej_after_download(LaneJ &s, const TB &t, const Download &d,
                                        int32_t avail_next, int32_t action) {
     StepResult r;
     r.bw = 0.0; r.hit = false; r.ended = false; r.timeout = false;
@@ -548,11 +598,15 @@ ABR_HD StepResult lanej_after_download(LaneJ &s, const Tables &t, const Download
     double b = s.buf + t.L;                                                  // :170
     if (playing) {                                                            // :176-184
         s.sumk += s.k; s.n_play++;
-        if (t.speed_rows >= 2) {
-            if (s.pl_left == 0) sched_begin_chunk(s, t, s.k, b);
-            b = b - s.sd;
-            sched_played(s, t, 1);
-        } else { b = b - s.sd; lanej_play(s, t, 1); }
+        if constexpr (TB::kSpeeds) {
+            if (t.speed_rows >= 2) {
+                if (s.pl_left == 0) sched_begin_chunk(s, t, s.k, b);
+                b = b - s.sd;
+                sched_played(s, t, 1);
+            } else { b = b - s.sd; lanej_play(s, t, 1); }
+        } else {
+            b = b - t.sd;
+        }
     }
     s.bf = b >= t.max_buffer;                                                // :190
     s.be = b <= 0.0;                                                         // :194
@@ -587,12 +641,14 @@ ABR_HD StepResult lanej_after_download(LaneJ &s, const Tables &t, const Download
 // (buffer_level, buffer_full, k): the same chains on the same values, hence the same tick.  Returns false when the state is
 // not covered (start-up, empty buffer, the buffer running dry, max_ticks in reach, per-lane speeds): the caller keeps its
 // speculation, and the player's validation of the download's start tick stays the arbiter either way.
-ABR_HD bool lanej_gate_possible(double buf, bool su, bool be, int32_t n_dl, const Tables &t) {
+template <class TB>
+ABR_HD bool lanej_gate_possible(double buf, bool su, bool be, int32_t n_dl, const TB &t) {
     // buffer_full at the completing tick needs buffer_level - (n_dl - 1) * sd + L - sd >= max_buffer; real arithmetic with a
     // margin far above the chains' rounding (<= 1e-9 over an episode), far below one tick's sd
     return !su && !be && !t.per_lane_speed && (buf + t.L) - (double)n_dl * t.sd >= t.max_buffer - 1.0e-6;
 }
-ABR_HD bool lanej_predict_next_call(double buf, int32_t k, int32_t n_dl, int32_t avail_next, const Tables &t,
+template <class TB>
+ABR_HD bool lanej_predict_next_call(double buf, int32_t k, int32_t n_dl, int32_t avail_next, const TB &t,
                                     int32_t &k_next, double *buf_next = nullptr) {
     const int32_t mt = t.max_ticks;
     double b = buf;
@@ -631,14 +687,16 @@ ABR_HD bool lanej_predict_next_call(double buf, int32_t k, int32_t n_dl, int32_t
 
 // One decision in one thread, after lanej_begin_step: download a chunk of target_size, then
 // run to the next call site.
-ABR_HD StepResult lanej_download_and_wait(LaneJ &s, const Tables &t, const StepStart &st,
+template <class TB>
+ABR_HD StepResult lanej_download_and_wait(LaneJ &s, const TB &t, const StepStart &st,
                                           double target, int32_t action) {
     const Download d = lanej_download(s.cur, t, st, s.k, target);
     return lanej_after_download(s, t, d, st.avail_next, action);
 }
 
 // begin + download + wait in one call (host harness)
-ABR_HD StepResult lanej_step(LaneJ &s, const Tables &t, double target, int32_t action) {
+template <class TB>
+ABR_HD StepResult lanej_step(LaneJ &s, const TB &t, double target, int32_t action) {
     const StepStart st = lanej_begin_step(s.cur, t, s.k, s.chunk_id);
     return lanej_download_and_wait(s, t, st, target, action);
 }
