@@ -17,6 +17,7 @@ from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
 from .speed import LatencySpeedController
 from .simulator import Simulator
+from .tracesynth import TraceModel, synth_traces
 from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd_file,
                      save_trace_file)
 
@@ -24,6 +25,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "EpisodeSampler", "EpisodeLedger", "advantage", "gae",
+           "EpisodeSampler", "EpisodeLedger", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

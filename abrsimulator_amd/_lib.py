@@ -154,6 +154,15 @@ class EpisodeLedger(C.Structure):
     _fields_ = [("base_dev", C.c_void_p), ("rows", C.c_int32), ("reserved_", C.c_int32)]
 
 
+TRACE_MAX_STATES = 8
+
+
+class TraceModel(C.Structure):
+    _fields_ = [("n_states", C.c_int32), ("reserved_", C.c_int32), ("level", C.c_double * TRACE_MAX_STATES),
+                ("spread", C.c_double * TRACE_MAX_STATES), ("outage_thr", C.c_uint64 * TRACE_MAX_STATES),
+                ("init_cum", C.c_uint64 * TRACE_MAX_STATES), ("cum", (C.c_uint64 * TRACE_MAX_STATES) * TRACE_MAX_STATES)]
+
+
 class StateView(C.Structure):
     _fields_ = [("n_lanes", C.c_int64), ("chunk_id", C.c_void_p), ("last_bitrate", C.c_void_p),
                 ("buffer_level", C.c_void_p), ("hist_n", C.c_void_p), ("hist_sum_inv", C.c_void_p),
@@ -236,6 +245,7 @@ SYMBOLS = [
     ("abr_env_step_policy_mx_pop", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
                                              C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
+    ("abr_trace_synth", C.c_int, [C.POINTER(TraceModel), C.c_uint64, C.c_uint32, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),
     ("abr_debug_selfcheck", C.c_int, [_P, _P, _P]),
     ("abr_debug_drain", C.c_int, [C.c_double, C.c_double, _P, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int32), _P]),

@@ -3964,6 +3964,102 @@ extern "C" int abr_gae(const float *reward_dev, const float *values_dev, const f
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// The trace generator (include/abr_env.h: abr_trace_synth; abr_lane_jump.h: trace_map, trace_compose, trace_value)
+// ---------------------------------------------------------------------------
+// One wave per trace, the waves grid-stride over the traces; a wave walks its trace in tiles of 64 consecutive samples.  In
+// a tile every lane computes its sample's philox block and state map, the wave scans the maps by composition (inclusive
+// Hillis-Steele over distances 1..32) and lane l applies its prefix to the state the previous tile left: s_i without a
+// serial chain over the samples.  A lane past the trace's end carries the identity map and takes part in every shuffle; the
+// trip counts depend on the wave's trace alone, so no lane leaves before the last tile's scan.  A tile is one coalesced
+// 512-byte store.  No LDS, no barrier: the model is the by-value argument, read with static indices only.
+static_assert(sizeof(abr_trace_model) == sizeof(abrx::TraceModel) && sizeof(abr_trace_model) == 776 &&
+              offsetof(abr_trace_model, level) == offsetof(abrx::TraceModel, level) &&
+              offsetof(abr_trace_model, spread) == offsetof(abrx::TraceModel, spread) &&
+              offsetof(abr_trace_model, outage_thr) == offsetof(abrx::TraceModel, outage_thr) &&
+              offsetof(abr_trace_model, init_cum) == offsetof(abrx::TraceModel, init_cum) &&
+              offsetof(abr_trace_model, cum) == offsetof(abrx::TraceModel, cum) &&
+              ABR_TRACE_MAX_STATES == abrx::kTraceMaxStates, "abr_trace_model and abrx::TraceModel must agree");
+constexpr int kTraceBlock = 256, kTraceWaves = kTraceBlock / 64;
+constexpr int kTraceMaxBlocks = 2048;       // 8 192 waves, a little over the 7 168 that 256 CUs hold at this kernel's 7 waves per SIMD; more traces than that stride
+
+__global__ __launch_bounds__(kTraceBlock) void trace_synth_kernel(abrx::TraceModel m, uint64_t key, uint32_t generation,
+                                                                  int64_t id_base, double *__restrict__ traces,
+                                                                  const int64_t *__restrict__ trace_off,
+                                                                  const int32_t *__restrict__ trace_len, int32_t n_traces) {
+    const int32_t lane = (int32_t)(threadIdx.x & 63u);
+    const int64_t stride = (int64_t)gridDim.x * kTraceWaves;
+    for (int64_t t = (int64_t)blockIdx.x * kTraceWaves + (threadIdx.x >> 6); t < n_traces; t += stride) {
+        const int32_t len = trace_len[t];
+        if (len < 1) continue;                                   // the same for every lane of the wave
+        const uint64_t g = (uint64_t)(id_base + t);
+        double *__restrict__ row = traces + trace_off[t];
+        uint32_t w[4];
+        abrx::philox4(key, g, abrx::kTraceInitStep, generation, w);
+        uint32_t carry = abrx::trace_initial(m, w[0]);
+        for (uint32_t base = 0; base < (uint32_t)len; base += 64) {      // unsigned: base + 64 cannot overflow for any int32 len
+            const uint32_t i = base + (uint32_t)lane;
+            const bool live = i < (uint32_t)len;
+            abrx::philox4(key, g, i, generation, w);
+            uint32_t F = live ? abrx::trace_map(m, w[0]) : abrx::kTraceIdentity;
+#pragma unroll
+            for (int d = 1; d < 64; d <<= 1) {
+                const uint32_t up = (uint32_t)__shfl_up((int)F, d, 64);
+                F = lane >= d ? abrx::trace_compose(F, up) : F;
+            }
+            const uint32_t s = abrx::trace_apply(F, carry);
+            if (live) row[i] = abrx::trace_value(m, s, w[1], w[2]);
+            carry = (uint32_t)__shfl((int)s, 63, 64);
+        }
+    }
+}
+
+extern "C" int abr_trace_synth(const abr_trace_model *model, uint64_t seed, uint32_t generation, int64_t trace_id_base,
+                               double *traces_dev, const int64_t *trace_off_dev, const int32_t *trace_len_dev,
+                               int32_t n_traces, void *stream) {
+    constexpr uint64_t kOne = 1ull << 32;
+    if (!model) return fail(ABR_E_INVALID, "trace model is NULL");
+    const int32_t K = model->n_states;
+    if (K < 1 || K > ABR_TRACE_MAX_STATES) return fail(ABR_E_INVALID, "trace model n_states must be in 1..%d, got %d", ABR_TRACE_MAX_STATES, K);
+    if (model->reserved_ != 0) return fail(ABR_E_INVALID, "trace model reserved_ must be 0");
+    bool alive = false;
+    for (int s = 0; s < K; s++) {
+        if (!std::isfinite(model->level[s]) || model->level[s] < 0.0)
+            return fail(ABR_E_INVALID, "trace model level[%d] must be finite and >= 0", s);
+        alive = alive || (model->level[s] > 0.0 && model->outage_thr[s] < kOne);
+    }
+    if (!alive) return fail(ABR_E_INVALID, "trace model needs a state with level > 0 and outage_thr < 2^32: no sample could be positive");
+    for (int s = 0; s < K; s++)
+        if (!(model->spread[s] >= 0.0 && model->spread[s] <= 1.0))
+            return fail(ABR_E_INVALID, "trace model spread[%d] must be in [0, 1]", s);
+    // of a cumulative row only [0, K - 1) is read, here as in the kernel: the last value is 2^32 whatever the entry holds
+    for (int s = 0; s < K; s++) {
+        if (model->outage_thr[s] > kOne) return fail(ABR_E_INVALID, "trace model outage_thr[%d] is above 2^32", s);
+        if (s < K - 1 && model->init_cum[s] > kOne) return fail(ABR_E_INVALID, "trace model init_cum[%d] is above 2^32", s);
+        for (int j = 0; j < K - 1; j++)
+            if (model->cum[s][j] > kOne) return fail(ABR_E_INVALID, "trace model cum[%d][%d] is above 2^32", s, j);
+    }
+    for (int j = 1; j < K - 1; j++)
+        if (model->init_cum[j] < model->init_cum[j - 1]) return fail(ABR_E_INVALID, "trace model init_cum decreases at [%d]", j);
+    for (int s = 0; s < K; s++)
+        for (int j = 1; j < K - 1; j++)
+            if (model->cum[s][j] < model->cum[s][j - 1]) return fail(ABR_E_INVALID, "trace model cum[%d] decreases at [%d]", s, j);
+    if (!traces_dev || !trace_off_dev || !trace_len_dev)
+        return fail(ABR_E_INVALID, "trace synth NULL argument (traces, trace_off or trace_len)");
+    if ((((uintptr_t)traces_dev | (uintptr_t)trace_off_dev) & 7) || ((uintptr_t)trace_len_dev & 3))
+        return fail(ABR_E_INVALID, "trace synth: traces and trace_off must be 8-byte aligned, trace_len 4-byte aligned");
+    if (n_traces < 1) return fail(ABR_E_INVALID, "trace synth n_traces must be >= 1");
+    if (trace_id_base < 0) return fail(ABR_E_INVALID, "trace synth trace_id_base must be >= 0");
+    abrx::TraceModel m;
+    memcpy(&m, model, sizeof(m));
+    const int64_t blocks = ((int64_t)n_traces + kTraceWaves - 1) / kTraceWaves;
+    hipLaunchKernelGGL(trace_synth_kernel, dim3((unsigned)(blocks < kTraceMaxBlocks ? blocks : kTraceMaxBlocks)),
+                       dim3(kTraceBlock), 0, (hipStream_t)stream, m, seed ^ abrx::kTraceKey, generation, trace_id_base,
+                       traces_dev, trace_off_dev, trace_len_dev, n_traces);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
 // Diagnostic: the exact chain (abr_exact_jump.h) on arbitrary inputs, one case per thread, so
 // tests can compare the DEVICE build of the jump arithmetic -- v_rcp_f64 estimate, saturating
 // convert, and (with a biased estimate) the out-of-line exact search -- with the naive loop.

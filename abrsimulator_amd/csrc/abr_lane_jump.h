@@ -1357,5 +1357,73 @@ ABR_HD void ledger_append(const EpisodeLedger &L, int64_t n_lanes, int64_t i, do
     }
 }
 
+// The trace generator (include/abr_env.h: abr_trace_synth; abr_trace_model has the same layout, abr_env.hip asserts it): a
+// Markov chain over K <= 8 bandwidth regimes.  A sample's philox word w0 fixes where EVERY state would go next, so the
+// sample is a map of the 8 states onto themselves, packed 3 bits per source state, and the chain over a trace is the
+// composition of its samples' maps: an associative operation, which a wave scans (abr_env.hip: trace_synth_kernel).  The
+// model reaches the kernel by value, so nothing here indexes one of its arrays by a runtime value outside a fully unrolled
+// loop: every access is a static one (kernel-argument loads, no scratch copy).
+constexpr int kTraceMaxStates = 8;
+constexpr uint64_t kTraceKey = 0x5452414345535953ull;      // xor-ed into the seed: no counter shared with another philox user
+constexpr uint32_t kTraceInitStep = 0xFFFFFFFFu;           // the step word of the initial-state block: never a sample index
+constexpr uint32_t kTraceIdentity = 0xFAC688u;             // the map s -> s: sum of s << 3 s
+struct TraceModel {
+    int32_t n_states, reserved_;
+    double level[kTraceMaxStates], spread[kTraceMaxStates];
+    uint64_t outage_thr[kTraceMaxStates], init_cum[kTraceMaxStates], cum[kTraceMaxStates][kTraceMaxStates];
+};
+
+// #{ j < K - 1 : w0 >= row[j] }: the state a cumulative row sends w0 to
+ABR_HD uint32_t trace_pick(const uint64_t (&row)[kTraceMaxStates], int32_t K, uint32_t w0) {
+    uint32_t n = 0;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int j = 0; j < kTraceMaxStates - 1; j++) n += (j < K - 1 && (uint64_t)w0 >= row[j]) ? 1u : 0u;
+    return n;
+}
+
+// the sample's state map; a source state >= K (never reached) maps to itself
+ABR_HD uint32_t trace_map(const TraceModel &m, uint32_t w0) {
+    uint32_t F = 0;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int s = 0; s < kTraceMaxStates; s++) F |= (s < m.n_states ? trace_pick(m.cum[s], m.n_states, w0) : (uint32_t)s) << (3 * s);
+    return F;
+}
+
+ABR_HD uint32_t trace_apply(uint32_t F, uint32_t s) { return (F >> (3 * s)) & 7u; }
+
+// g after f
+ABR_HD uint32_t trace_compose(uint32_t g, uint32_t f) {
+    uint32_t r = 0;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int s = 0; s < kTraceMaxStates; s++) r |= trace_apply(g, trace_apply(f, (uint32_t)s)) << (3 * s);
+    return r;
+}
+
+ABR_HD uint32_t trace_initial(const TraceModel &m, uint32_t w0) { return trace_pick(m.init_cum, m.n_states, w0); }
+
+// the sample of state s: a select chain over the states, so that s never indexes the model
+ABR_HD double trace_value(const TraceModel &m, uint32_t s, uint32_t w1, uint32_t w2) {
+    double level = m.level[0], spread = m.spread[0];
+    uint64_t thr = m.outage_thr[0];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int j = 1; j < kTraceMaxStates; j++) {
+        level = s == (uint32_t)j ? m.level[j] : level;
+        spread = s == (uint32_t)j ? m.spread[j] : spread;
+        thr = s == (uint32_t)j ? m.outage_thr[j] : thr;
+    }
+    const double u = (double)(w1 >> 8) * 0x1p-24;
+    const double r = 2.0 * u - 1.0;
+    const double x = level * (1.0 + spread * r);
+    return (uint64_t)w2 < thr ? 0.0 : x;
+}
+
 }  // namespace abrx
 #endif

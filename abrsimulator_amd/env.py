@@ -14,6 +14,7 @@ from . import _lib
 from .episodes import EpisodeSampler
 from .ledger import EpisodeLedger
 from .speed import LatencySpeedController
+from .tracesynth import TraceModel
 from ._lib import F64_DIM, F64_ROWS, OBS_DIM, OBS_ROWS
 from .datamodel import MPD, NetworkInfo, QOEMetric
 
@@ -217,6 +218,19 @@ class BatchedABREnv:
             self._check(self.lib.abr_env_set_episode_sampler(self._h, C.byref(st)))
         # the library holds the pool's address: keep the tensor alive while the sampler is installed
         self.episode_sampler, self._sampler_pool = es, pool_t
+
+    def synth_traces(self, model, seed, generation: int = 0):
+        """Regenerate this environment's own corpus in place on the device (tracesynth.py: TraceModel; include/abr_env.h:
+        abr_trace_synth): self.traces is overwritten through self.trace_off / self.trace_len, trace ids from 0, on the
+        current stream, without synchronising, reading back or resetting.  Lanes reset (or re-armed) afterwards run on the
+        new samples; a lane that is mid-episode is outside the contract, so follow with reset().  TraceModel.draw(seed,
+        generation, range(n_traces), length) computes the same samples on the host."""
+        if not isinstance(model, TraceModel):
+            raise TypeError("synth_traces takes a TraceModel")
+        st = model.struct()
+        self._call(self.lib.abr_trace_synth, C.byref(st), C.c_uint64(int(seed) & (2 ** 64 - 1)),
+                   C.c_uint32(int(generation) & 0xFFFFFFFF), 0, _lib.ptr(self.traces), _lib.ptr(self.trace_off),
+                   _lib.ptr(self.trace_len), self.n_traces)
 
     def episodes(self):
         """Each lane's current episode: dict(trace_id, start_offset, episode), int32 [N] each (fresh tensors, copied on the

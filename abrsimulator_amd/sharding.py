@@ -219,6 +219,11 @@ class ShardedABREnv:
         so every rank with the same sampler reproduces its slice of the unsharded run."""
         self.env.set_episode_sampler(seed, pool, offset_span)
 
+    def synth_traces(self, model, seed, generation=0):
+        """Regenerate this rank's copy of the corpus on the device (BatchedABREnv.synth_traces).  The corpus is a pure
+        function of (model, seed, generation, trace id), so every rank generates the same one with no collective."""
+        self.env.synth_traces(model, seed, generation)
+
     def set_episode_ledger(self, rows):
         """BatchedABREnv.set_episode_ledger on this rank's stepper.  The ledger is per shard: its lanes are this shard's,
         in shard order (global lane = lane_id_base + i), and nothing is gathered across ranks."""

@@ -1006,6 +1006,49 @@ int abr_gae(const float *reward_dev, const float *values_dev, const float *last_
             const int32_t *actions_dev, int32_t n_steps, int64_t n_lanes, float gamma, float lam, float *adv_out_dev,
             float *ret_out_dev, void *stream);
 
+/*
+ * Synthesise a bandwidth corpus on the device (no handle): a Markov chain over K bandwidth regimes with uniform noise
+ * around each regime's level and per-regime outages, written over caller-owned trace arrays of abr_env_create's layout.
+ * Build-defined: the reference has no generator.  Only entries [0, K) of each array are read; of a cumulative row only
+ * [0, K - 1): the last cumulative value is implicitly 2^32.
+ *
+ * Exact: integers and float64 only, round-to-nearest-even, one rounding per operation, in this order.  For trace t
+ * (global id g = trace_id_base + t) and sample i in [0, trace_len_dev[t]), with philox4 the philox4x32-10 block of
+ * csrc/abr_lane_jump.h (key, lane, step, episode) and key = seed ^ 0x5452414345535953:
+ *   s_-1 = #{ j < K - 1 : v0 >= init_cum[j] },          (v0, ..) = philox4(key, g, 0xFFFFFFFF, generation)
+ *   s_i  = #{ j < K - 1 : w0 >= cum[s_(i-1)][j] },      (w0, w1, w2, w3) = philox4(key, g, i, generation)
+ *   u = (double)(w1 >> 8) * 2^-24;  r = 2.0 * u - 1.0   (exact, in [-1, 1))
+ *   x = level[s_i] * (1.0 + spread[s_i] * r);  x = +0.0 when w2 < outage_thr[s_i]
+ *   traces_dev[trace_off_dev[t] + i] = x
+ * With level >= 0 and spread <= 1 every sample is finite and >= 0: what abr_env_create requires of a trace.  generation
+ * selects a fresh corpus from the same seed; a sub-range generated with trace_id_base = a equals rows [a, a + n_traces)
+ * of the whole corpus.  A trace whose length on the device is < 1 is skipped; nothing outside the rows is written, and the
+ * rows need no alignment beyond 8 bytes and need not be adjacent.  Runs on `stream` without synchronising.
+ *
+ * Regenerating the corpus a handle uses is legal at any point in stream order and takes effect for lanes that are reset
+ * (or re-armed) afterwards: the library keeps nothing derived from the samples.  A lane that is mid-episode when its
+ * corpus is regenerated is outside the contract: it stays bounded, because every sample is valid, but matches no replay.
+ *
+ * Refused (ABR_E_INVALID, nothing launched), the struct before the pointers: a NULL model; n_states outside 1..8;
+ * reserved_ != 0; a level that is not finite or is negative; no state with level > 0 and outage_thr < 2^32 (no sample could
+ * ever be positive); a spread that is NaN or outside [0, 1]; an outage_thr, init_cum or cum entry above 2^32; a cumulative
+ * row that decreases (of the entries that are read); traces_dev, trace_off_dev or trace_len_dev NULL or not aligned to its element (8, 8 and 4 bytes);
+ * n_traces < 1; trace_id_base < 0.
+ */
+#define ABR_TRACE_MAX_STATES 8
+typedef struct abr_trace_model {
+    int32_t  n_states;                                             /* K, 1..8 */
+    int32_t  reserved_;                                            /* 0 */
+    double   level[ABR_TRACE_MAX_STATES];                          /* regime bandwidth, finite, >= 0, same unit as the ladder */
+    double   spread[ABR_TRACE_MAX_STATES];                         /* 0..1: relative half-width of the uniform noise */
+    uint64_t outage_thr[ABR_TRACE_MAX_STATES];                     /* 0..2^32: a sample in regime s is 0.0 when word2 < outage_thr[s] */
+    uint64_t init_cum[ABR_TRACE_MAX_STATES];                       /* 0..2^32, non-decreasing: cumulative initial distribution */
+    uint64_t cum[ABR_TRACE_MAX_STATES][ABR_TRACE_MAX_STATES];      /* cum[s][j], 0..2^32, non-decreasing in j: cumulative row s of the transition matrix */
+} abr_trace_model;              /* 776 bytes */
+int abr_trace_synth(const abr_trace_model *model, uint64_t seed, uint32_t generation, int64_t trace_id_base,
+                    double *traces_dev, const int64_t *trace_off_dev, const int32_t *trace_len_dev, int32_t n_traces,
+                    void *stream);
+
 /* Diagnostic: the full objective grid of ONE lane, J_out_dev float64
  * [n_rates^horizon], given explicit predictions pred_dev[horizon]. */
 int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t prev_bitrate,
