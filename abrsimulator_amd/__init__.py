@@ -12,7 +12,7 @@ from .episodes import EpisodeSampler
 from .fastmpc import FastMPCController
 from .ledger import EpisodeLedger
 from .mpc import BatchedMPCController, EnvPlayer
-from .policy import PolicyController, PolicyPopulation
+from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController
 from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
 from .speed import LatencySpeedController
@@ -24,7 +24,7 @@ from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd
 _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
-           "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
+           "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
            "EpisodeSampler", "EpisodeLedger", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

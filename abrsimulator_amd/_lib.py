@@ -137,6 +137,15 @@ class PolicyPop(C.Structure):
 
 POLICY_POP_BLOCK = 256      # a population's group is a multiple of the policy kernels' workgroup
 
+POLICY_GRU_MAX_HIDDEN = 64
+
+
+class PolicyGru(C.Structure):
+    _fields_ = [("window", C.c_int32), ("hidden", C.c_int32), ("weights_dev", C.c_void_p), ("weights_bytes", C.c_size_t),
+                ("norm_dev", C.c_void_p), ("state_dev", C.c_void_p), ("state_bytes", C.c_size_t), ("seed", C.c_uint64),
+                ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
+
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -244,6 +253,11 @@ SYMBOLS = [
                                                C.POINTER(PolicyValue), _P, _P, _P, _P, _P, _P]),
     ("abr_env_step_policy_mx_pop", C.c_int, [_P, C.POINTER(PolicyMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
                                              C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_policy_gru_weights_bytes", C.c_int, [C.POINTER(PolicyGru), C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_policy_select_gru", C.c_int, [_P, C.POINTER(PolicyGru), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                            C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_step_policy_gru", C.c_int, [_P, C.POINTER(PolicyGru), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                          C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_trace_synth", C.c_int, [C.POINTER(TraceModel), C.c_uint64, C.c_uint32, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),

@@ -3920,6 +3920,282 @@ extern "C" int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol
                     features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, last_value_out_dev, stream);
 }
 
+// ---------------------------------------------------------------------------
+// The recurrent policy (include/abr_env.h: abr_policy_gru): a GRU cell per lane whose state lives in the caller's slab
+// ---------------------------------------------------------------------------
+// One thread per lane, 256 per workgroup; the prologue and the epilogue are policy_select_kernel's.  The workgroup stages
+// the padded blob (abr_lane_jump.h: policy_gru_layout -- H x 324 + 16 floats, + 68 with a value head: 83 280 B at H = 64) in
+// dynamic LDS once, so every weight read is a wave-uniform broadcast of a fixed-length row.  A thread owns its column of
+// the state: it reads all of h_in into registers (coalesced [H][N] column reads) before unit 0's h' is stored, so a
+// commit in place is safe.  Unit j's six chains advance side by side in a software pipeline over the row's quads
+// (policy_gru_forward), which bounds the reads in flight: two waves per SIMD fit the register file (__launch_bounds__).
+struct PolicyGruArgs {
+    abrx::PolicyNet net;              // n_hidden = 1, w0 = H
+    const float *weights, *head;      // the blob; [H + 1] Wv then bv (VALUE instances)
+    float *state;                     // [H][N]
+    int32_t *action_out;              // [N]; NULL (VALUE instances): a value evaluation only
+    float *features_out, *scores_out, *probs_out, *value_out, *hidden_out;   // nullable
+    int32_t mode;                     // abr_policy_sampling (SAMPLED instances)
+    float inv_temperature;
+    int32_t commit;
+};
+
+template <bool SAMPLED, bool VALUE>
+__global__ __launch_bounds__(kPolicyBlock, 2) void policy_gru_kernel(EnvParams p, PolicyGruArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float gru_lds[];   // rows are read as 128-bit quads
+    float *w_lds = gru_lds;
+    const abrx::PolicyGruLayout lay = abrx::policy_gru_layout<VALUE>(a.net);
+    for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock)
+        w_lds[d] = abrx::policy_gru_padded<VALUE>(a.net, lay, a.weights, d, a.head);
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * kPolicyBlock + threadIdx.x;
+    if (i >= p.n_lanes) return;
+    const int64_t N = p.n_lanes;
+    const abrx::PolicyNet &n = a.net;
+    const int32_t H = n.w0;
+    const int32_t c = p.chunk_id[i];
+    if (p.done[i] || c < 0 || c >= p.video_length) {
+        if constexpr (VALUE) {
+            if (a.value_out) a.value_out[i] = 0.0f;
+            if (!a.action_out) return;
+        }
+        a.action_out[i] = -1;
+        if (a.features_out)
+            for (int32_t f = 0; f < n.F; f++) a.features_out[f * N + i] = 0.0f;
+        if (a.scores_out)
+            for (int32_t m = 0; m < n.M; m++) a.scores_out[m * N + i] = 0.0f;
+        if constexpr (SAMPLED) {
+            if (a.probs_out)
+                for (int32_t m = 0; m < n.M; m++) a.probs_out[m * N + i] = 0.0f;
+        }
+        if (a.hidden_out)
+            for (int32_t j = 0; j < H; j++) a.hidden_out[j * N + i] = 0.0f;
+        return;
+    }
+    // h_in: the lane's column, or +0 at the first chunk of an episode
+    float *st = a.state + i;
+    float h[abrx::kPolicyRowH];
+    {
+        const float *row = st;                                   // a running pointer: no 64-bit scalar product per unit
+#pragma unroll
+        for (int k = 0; k < abrx::kPolicyRowH; k++) {
+            float v = 0.0f;
+            if (k < H) {
+                v = *row;
+                if (c == 0) v = 0.0f;
+            }
+            h[k] = v;
+            row += N;
+        }
+    }
+    if (a.hidden_out) {
+        float *row = a.hidden_out + i;
+#pragma unroll
+        for (int k = 0; k < abrx::kPolicyRowH; k++) {
+            if (k < H) {
+                *row = h[k];
+            }
+            row += N;
+        }
+    }
+    const double G = p.G[p.k[i]];
+    const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
+    const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
+    const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+    float x[abrx::kPolicyMaxF];
+    abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    if (a.features_out) {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) {
+            if (f < n.F) {
+                a.features_out[f * N + i] = x[f];
+            }
+        }
+    }
+    const bool commit = a.commit != 0;
+    const auto hin = [&](int32_t j) { return c == 0 ? 0.0f : st[j * N]; };   // read before store(j) overwrites it
+    const auto store = [&](int32_t j, float v) { if (commit) st[j * N] = v; };
+    float *so = a.scores_out;
+    [[maybe_unused]] float value = 0.0f;
+    int32_t action;
+    if constexpr (!SAMPLED) {
+        const auto emit = [&](int32_t m, float v) { if (so) so[m * N + i] = v; };
+        const int32_t g = abrx::policy_gru_forward<VALUE>(n, w_lds, x, h, hin, store, emit, &value);
+        action = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+    } else {
+        float *col = w_lds + lay.total + threadIdx.x;            // this lane's scores, stride kPolicyBlock
+        const auto emit = [&](int32_t m, float v) {
+            col[m * kPolicyBlock] = v;
+            if (so) so[m * N + i] = v;
+        };
+        const int32_t g = abrx::policy_gru_forward<VALUE>(n, w_lds, x, h, hin, store, emit, &value);
+        float *po = a.probs_out;
+        const auto buf = [&](int32_t m) -> float & { return col[m * kPolicyBlock]; };
+        const auto prob = [&](int32_t m, float v) { if (po) po[m * N + i] = v; };
+        action = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode, a.inv_temperature,
+                                     buf, prob);
+    }
+    if (a.action_out) a.action_out[i] = action;
+    if constexpr (VALUE) {
+        if (a.value_out) a.value_out[i] = value;
+    }
+}
+
+static size_t policy_gru_weights_bytes(int32_t W, int32_t H, int32_t M) {
+    const size_t F = 4 + (size_t)W + (size_t)M, h = (size_t)H;
+    return (3 * h * (F + h + 2) + (size_t)M * (h + 1)) * sizeof(float);
+}
+
+static int validate_policy_gru_shape(const abr_policy_gru *pol) {
+    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
+    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
+    if (pol->hidden < 1 || pol->hidden > ABR_POLICY_GRU_MAX_HIDDEN)
+        return fail(ABR_E_INVALID, "policy hidden %d outside 1..%d", pol->hidden, ABR_POLICY_GRU_MAX_HIDDEN);
+    return ABR_OK;
+}
+
+extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n_rates, size_t *bytes_out) {
+    int rc = validate_policy_gru_shape(pol);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *bytes_out = policy_gru_weights_bytes(pol->window, pol->hidden, n_rates);
+    return ABR_OK;
+}
+
+// everything that is checked before the handle: the structs, then the outputs that need a struct that is absent
+static int validate_policy_gru_call(const abr_policy_gru *pol, const abr_policy_sampling *smp, const abr_policy_value *val,
+                                    const float *probs_out, const float *values_out, const float *last_value_out) {
+    int rc = validate_policy_gru_shape(pol);
+    if (rc) return rc;
+    for (int32_t r : pol->reserved_)
+        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
+    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
+        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
+    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
+    if (!pol->state_dev || ((uintptr_t)pol->state_dev & 3))
+        return fail(ABR_E_INVALID, "policy state must be non-NULL and 4-byte aligned");
+    if (pol->explore_threshold > (1ull << 32))
+        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
+    if (smp && (rc = validate_sampling(smp))) return rc;
+    if (val && (rc = validate_value(val))) return rc;
+    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
+    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
+    return ABR_OK;
+}
+
+// after the handle: the blob's, the state's and the head's sizes for the environment
+static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
+                           const abr_policy_value *val, PolicyGruArgs *a) {
+    const int32_t M = env->p.n_rates, H = pol->hidden;
+    const size_t want = policy_gru_weights_bytes(pol->window, H, M);
+    if (pol->weights_bytes != want)
+        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
+    const size_t state = (size_t)H * (size_t)env->p.n_lanes * sizeof(float);
+    if (pol->state_bytes != state)
+        return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
+                    (long long)env->p.n_lanes, state);
+    if (val && val->head_bytes != ((size_t)H + 1) * sizeof(float))
+        return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, ((size_t)H + 1) * sizeof(float));
+    *a = PolicyGruArgs{};
+    a->net.window = pol->window; a->net.n_hidden = 1; a->net.w0 = H; a->net.M = M; a->net.F = 4 + pol->window + M;
+    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
+    a->weights = pol->weights_dev; a->state = pol->state_dev;
+    if (val) a->head = val->head_dev;
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    return ABR_OK;
+}
+
+// The staged blob passes the 64 KiB a kernel may take by default, so each instance's dynamic-LDS limit is raised once,
+// to the largest launch the contract allows (H = 64, 16 rates, a value head, the score columns: 99 664 B).
+template <bool SAMPLED, bool VALUE>
+static hipError_t launch_policy_gru_instance(const abr_env *env, const PolicyGruArgs &a, size_t lds, hipStream_t st) {
+    static bool raised = false;
+    if (!raised) {
+        abrx::PolicyNet top{};
+        top.w0 = ABR_POLICY_GRU_MAX_HIDDEN;
+        const int most = (int)(((size_t)abrx::policy_gru_layout<true>(top).total + (size_t)ABR_MAX_RATES * kPolicyBlock) *
+                               sizeof(float));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_kernel<SAMPLED, VALUE>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e != hipSuccess) return e;
+        raised = true;
+    }
+    hipLaunchKernelGGL((policy_gru_kernel<SAMPLED, VALUE>), dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
+                       dim3(kPolicyBlock), lds, st, env->p, a);
+    return hipGetLastError();
+}
+
+// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
+static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruArgs &a, hipStream_t st) {
+    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t words = value ? abrx::policy_gru_layout<true>(a.net).total : abrx::policy_gru_layout(a.net).total;
+    const size_t lds = (words + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
+    if (sampled && value) return launch_policy_gru_instance<true, true>(env, a, lds, st);
+    if (sampled) return launch_policy_gru_instance<true, false>(env, a, lds, st);
+    if (value) return launch_policy_gru_instance<false, true>(env, a, lds, st);
+    return launch_policy_gru_instance<false, false>(env, a, lds, st);
+}
+
+extern "C" int abr_env_policy_select_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
+                                         const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
+                                         float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                         float *value_out_dev, float *hidden_out_dev, void *stream) {
+    int rc = validate_policy_gru_call(pol, smp, val, probs_out_dev, value_out_dev, nullptr);
+    if (rc) return rc;
+    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    PolicyGruArgs a;
+    if ((rc = policy_gru_args(env, pol, smp, val, &a))) return rc;
+    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
+    a.probs_out = probs_out_dev; a.value_out = value_out_dev; a.hidden_out = hidden_out_dev;
+    a.commit = commit != 0;
+    HIP_TRY(launch_policy_gru(env, a, (hipStream_t)stream));
+    return ABR_OK;
+}
+
+// per decision the recurrent kernel (commit), then K1 MODE 1 on its actions (as abr_env_step_policy_mx, last_value included)
+extern "C" int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
+                                       const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                       float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                       float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                       float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
+                                       void *stream) {
+    int rc = validate_policy_gru_call(pol, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
+    if (rc) return rc;
+    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    PolicyGruArgs a;
+    if ((rc = policy_gru_args(env, pol, smp, val, &a))) return rc;
+    if ((rc = require(kPolicyRollout, env->impl))) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    a.commit = 1;
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
+        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
+        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
+        a.hidden_out = hidden_out_dev ? hidden_out_dev + (int64_t)s * a.net.w0 * N : nullptr;
+        HIP_TRY(launch_policy_gru(env, a, st));
+        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
+                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
+                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
+        if (rc) return rc;
+    }
+    if (last_value_out_dev) {
+        // the bootstrap value: no decision is stored and nothing is committed, so the workspace and the state slab are
+        // left as the rollout left them
+        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = a.hidden_out = nullptr;
+        a.mode = ABR_POLICY_ARGMAX; a.commit = 0;
+        a.value_out = last_value_out_dev;
+        HIP_TRY(launch_policy_gru(env, a, st));
+    }
+    return ABR_OK;
+}
+
 // One thread per lane walks its column of the slabs from the last row to the first (abr_lane_jump.h: gae_lane): a row of
 // any slab is contiguous across the wave, so every access is coalesced, and the loads of kGaeRows rows are issued before
 // the dependent chain over them starts.  No LDS, no barrier.

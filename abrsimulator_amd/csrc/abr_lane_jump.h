@@ -1136,6 +1136,181 @@ ABR_HD int32_t policy_decide(const PolicyNet &n, uint64_t lane, int32_t c, int32
 }
 
 // ---------------------------------------------------------------------------
+// The recurrent policy (include/abr_env.h: abr_policy_gru; abr_env.hip: policy_gru_kernel): one GRU cell of H units over
+// the features and the lane's hidden state, then Linear(H, M) over the new state.  The net is a PolicyNet with n_hidden = 1
+// and w0 = H (window, M, F, norm, seed and thr mean what they mean above).
+// ---------------------------------------------------------------------------
+// The gate activations on exp_c (whose argument is never positive here).  Both are exact in the order written: one
+// rounding per operation, a correctly rounded division.
+ABR_HD float sig_c(float v) {
+    if (v != v) return v;
+    const float e = exp_c(-fabsf(v));
+    const float q = 1.0f + e;
+    return (v >= 0.0f ? 1.0f : e) / q;
+}
+
+ABR_HD float tanh_c(float v) {
+    if (v != v) return v;
+    const float e = exp_c(-2.0f * fabsf(v));
+    const float t = (1.0f - e) / (1.0f + e);
+    return copysignf(t, v);
+}
+
+// The padded layout the forward pass reads (the kernel stages it in LDS), by the conventions of policy_layout: rows of fixed
+// length, padded weights -0.0f against padded inputs +0.0f.
+//   G   H x 3 gate rows (unit j's r, z, n rows are adjacent), each kPolicyRowF input weights then kPolicyRowH recurrent ones
+//   B   H x 8: b_ih[r, z, n][j], b_hh[r, z, n][j], two pads -- the six chains' first terms in one 32-byte read
+//   Wo  H x kPolicyRowM, transposed ([k][m]): the order in which unit k adds its term into every output accumulator
+//   bo  kPolicyRowM
+//   VALUE: Wv kPolicyRowH, then bv (4 floats)
+constexpr int kGruRow = kPolicyRowF + kPolicyRowH, kGruBias = 8;
+struct PolicyGruLayout { int32_t G, B, Wo, bo, total, Wv, bv; };
+
+template <bool VALUE = false>
+ABR_HD PolicyGruLayout policy_gru_layout(const PolicyNet &n) {
+    PolicyGruLayout L{};
+    const int32_t H = n.w0;
+    int32_t o = 0;
+    L.G = o; o += H * 3 * kGruRow;
+    L.B = o; o += H * kGruBias;
+    L.Wo = o; o += H * kPolicyRowM;
+    L.bo = o; o += kPolicyRowM;
+    if (VALUE) { L.Wv = o; o += kPolicyRowH; L.bv = o; o += 4; }
+    L.total = o;
+    return L;
+}
+
+// Slot d of the padded layout, read from the packed blob in torch.nn.GRUCell's layout (W_ih [3H][F], W_hh [3H][H], b_ih [3H],
+// b_hh [3H], gates r, z, n; then W_out [M][H], b_out [M]); VALUE: the last row from `head` (Wv[0..H) then bv)
+template <bool VALUE = false>
+ABR_HD float policy_gru_padded(const PolicyNet &n, const PolicyGruLayout &L, const float *__restrict__ blob, int32_t d,
+                               const float *__restrict__ head = nullptr) {
+    const float pw = -0.0f, pb = 0.0f;
+    const int32_t F = n.F, H = n.w0, M = n.M;
+    const int32_t Wih = 0, Whh = Wih + 3 * H * F, bih = Whh + 3 * H * H, bhh = bih + 3 * H, Wout = bhh + 3 * H,
+                  bout = Wout + M * H;
+    if (VALUE) {
+        if (d >= L.Wv) {
+            const int32_t k = d - L.Wv;
+            if (d < L.bv) return k < H ? head[k] : pw;
+            return d == L.bv ? head[H] : pb;
+        }
+    }
+    if (d < L.B) {
+        const int32_t row = (d - L.G) / kGruRow, i = (d - L.G) % kGruRow, j = row / 3, g = row % 3;
+        if (i < kPolicyRowF) return i < F ? blob[Wih + (g * H + j) * F + i] : pw;
+        const int32_t k = i - kPolicyRowF;
+        return k < H ? blob[Whh + (g * H + j) * H + k] : pw;
+    }
+    if (d < L.Wo) {
+        const int32_t j = (d - L.B) / kGruBias, s = (d - L.B) % kGruBias;
+        return s < 3 ? blob[bih + s * H + j] : s < 6 ? blob[bhh + (s - 3) * H + j] : pb;
+    }
+    if (d < L.bo) {
+        const int32_t k = (d - L.Wo) / kPolicyRowM, m = (d - L.Wo) % kPolicyRowM;
+        return m < M ? blob[Wout + m * H + k] : pw;
+    }
+    if (d < L.bo + kPolicyRowM) { const int32_t m = d - L.bo; return m < M ? blob[bout + m] : pb; }
+    return pb;
+}
+
+// Four adjacent weights of a padded row (rows start on 16-byte boundaries: one 128-bit LDS read on the device).
+struct alignas(16) PolicyGruQuad { float v[4]; };
+ABR_HD PolicyGruQuad policy_gru_quad(const float *__restrict__ p) {
+    PolicyGruQuad q;
+    __builtin_memcpy(&q, __builtin_assume_aligned(p, 16), sizeof q);
+    return q;
+}
+// Pins the six accumulators in the device's instruction stream: the fmafs written before it are issued before it and the
+// ones written after it after it (an empty statement the compiler may not move values across, then a scheduling fence).
+// No effect on any value; nothing on the host.
+ABR_HD void policy_gru_pin(float (&gi)[3], float (&gh)[3]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(gi[0]), "+v"(gi[1]), "+v"(gi[2]), "+v"(gh[0]), "+v"(gh[1]), "+v"(gh[2]));
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+}
+
+// The cell, the output layer and the first argmax over the padded layout `w` (16-byte aligned).  x[i] = +0 for i >= F and
+// h[k] = +0 for k >= H; hin(j) is h[j] again for a runtime j (the register array is only ever indexed by an unrolled loop,
+// so the caller answers it from where h came from).
+// A unit is 300 weight reads and 300 fmafs, and no read depends on anything: left alone, the device compiler issues the reads
+// far ahead of the fmafs and needs a register for each (346 registers, or scratch under a tighter budget).  So the unit is
+// written as a software pipeline over its 25 groups of four k: the three gate rows' quads of group q + kGruAhead are read,
+// a pin (policy_gru_pin), then group q's twelve fmafs -- the six chains (gi and gh of r, z, n) advance side by side, and the reads in
+// flight are bounded at (kGruAhead + 1) x 12 weights.
+// h'[j] is handed to store(j, v) the moment it exists and folded at once into every output accumulator (and the value's),
+// each of which therefore stays a k-ordered chain; no second array of H registers is held.  emit(m, score_m) once per
+// output m in order.  Returns g.
+constexpr int kGruGroups = kGruRow / 4, kGruGroupsX = kPolicyRowF / 4, kGruAhead = 4;
+static_assert(kGruRow % 4 == 0 && kPolicyRowF % 4 == 0 && kPolicyRowM == 16, "quads");
+
+template <bool VALUE = false, class Hin, class Store, class Emit>
+ABR_HD int32_t policy_gru_forward(const PolicyNet &n, const float *__restrict__ w, const float x[kPolicyMaxF],
+                                  const float h[kPolicyRowH], const Hin &hin, const Store &store, const Emit &emit,
+                                  float *value = nullptr) {
+    const PolicyGruLayout L = policy_gru_layout<VALUE>(n);
+    const int32_t M = n.M, H = n.w0;
+    float acc[kPolicyRowM];
+#pragma unroll
+    for (int m = 0; m < kPolicyRowM; m++) acc[m] = w[L.bo + m];
+    float accv = VALUE ? w[L.bv] : 0.0f;
+    for (int32_t j = 0; j < H; j++) {
+        const float *__restrict__ row = w + L.G + j * (3 * kGruRow);
+        const float *__restrict__ wk = w + L.Wo + j * kPolicyRowM;
+        PolicyGruQuad q[kGruGroups][3], o[4];
+        const PolicyGruQuad b0 = policy_gru_quad(w + L.B + j * kGruBias), b1 = policy_gru_quad(w + L.B + j * kGruBias + 4);
+#pragma unroll
+        for (int t = 0; t < kGruAhead; t++) {
+#pragma unroll
+            for (int g = 0; g < 3; g++) q[t][g] = policy_gru_quad(row + g * kGruRow + 4 * t);
+        }
+        const float hj = hin(j);
+        float gi[3] = {b0.v[0], b0.v[1], b0.v[2]}, gh[3] = {b0.v[3], b1.v[0], b1.v[1]};
+#pragma unroll
+        for (int t = 0; t < kGruGroups; t++) {
+            if (t + kGruAhead < kGruGroups) {
+#pragma unroll
+                for (int g = 0; g < 3; g++) q[t + kGruAhead][g] = policy_gru_quad(row + g * kGruRow + 4 * (t + kGruAhead));
+            } else if (t + kGruAhead < kGruGroups + 4) {
+                o[t + kGruAhead - kGruGroups] = policy_gru_quad(wk + 4 * (t + kGruAhead - kGruGroups));
+            }
+            policy_gru_pin(gi, gh);
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+#pragma unroll
+                for (int g = 0; g < 3; g++) {
+                    if (t < kGruGroupsX) gi[g] = fmaf(q[t][g].v[e], x[4 * t + e], gi[g]);
+                    else gh[g] = fmaf(q[t][g].v[e], h[4 * (t - kGruGroupsX) + e], gh[g]);
+                }
+            }
+        }
+        policy_gru_pin(gi, gh);
+        const float r = sig_c(gi[0] + gh[0]);
+        const float z = sig_c(gi[1] + gh[1]);
+        const float c = tanh_c(fmaf(r, gh[2], gi[2]));
+        const float d = hj - c;
+        const float hp = fmaf(z, d, c);
+        store(j, hp);
+#pragma unroll
+        for (int m = 0; m < kPolicyRowM; m++) acc[m] = fmaf(o[m / 4].v[m % 4], hp, acc[m]);
+        if (VALUE) accv = fmaf(w[L.Wv + j], hp, accv);
+    }
+    int32_t g = 0;
+    float best = 0.0f;
+#pragma unroll
+    for (int m = 0; m < kPolicyRowM; m++) {
+        if (m < M) {
+            emit(m, acc[m]);
+            if (m == 0) best = acc[m];
+            else if (acc[m] > best) { best = acc[m]; g = m; }
+        }
+    }
+    if (VALUE) *value = accv;
+    return g;
+}
+
+// ---------------------------------------------------------------------------
 // The matrix engine of the learned policy (include/abr_env.h: abr_policy_mx; abr_env.hip: policy_mx_kernel): the same
 // chains issued as v_mfma_f32_32x32x2_f32, the units of a layer as the rows of the product and 32 env lanes as its
 // columns.  Everything here is index arithmetic, compiled for the host by tests/native/policy_matrix_harness.cpp.

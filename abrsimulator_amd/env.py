@@ -473,7 +473,7 @@ class BatchedABREnv:
         return out
 
     def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
-                    want_scores=False, want_probs=False, want_values=False):
+                    want_scores=False, want_probs=False, want_values=False, want_hidden=False):
         """n_steps decisions per lane taken by a learned policy (policy.py: PolicyController) on the device, each one the
         policy kernel on every lane's own call-site state followed by the download of that chunk, with no host work
         between decisions.  Every event-driven kernel; 'tick' is refused (include/abr_env.h).  Returns
@@ -485,8 +485,14 @@ class BatchedABREnv:
         advantage.gae needs next to reward, done and actions (abr_env_step_policy_ac).  A controller built with
         engine="matrix" runs the same rollout on the MFMA kernel (abr_env_step_policy_mx), with the same outputs.
         A policy.PolicyPopulation rolls out P networks at once, member m on its own lane group, with the same dict and
-        flags (abr_env_step_policy_pop, abr_env_step_policy_mx_pop)."""
+        flags (abr_env_step_policy_pop, abr_env_step_policy_mx_pop).
+        A policy.RecurrentPolicyController rolls out its GRU cell (abr_env_step_policy_gru): every decision advances
+        controller.hidden, and want_hidden=True adds hidden[n,H,N], the state each decision was taken from (zeros at a
+        lane's first chunk) -- with features, what a trainer needs to recompute each step in torch."""
         n = int(n_steps)
+        recurrent = getattr(controller, "method", None) == "policy_gru"
+        if want_hidden and not recurrent:
+            raise ValueError("want_hidden needs a RecurrentPolicyController")
         pol = controller.bound(self)
         val = controller.value() if want_values or (out is not None and out.get("values") is not None) else None
         if out is None:
@@ -499,6 +505,17 @@ class BatchedABREnv:
             if val is not None:
                 out["values"] = torch.empty(n, N, dtype=torch.float32, device=dev)
                 out["last_value"] = torch.empty(N, dtype=torch.float32, device=dev)
+            if want_hidden:
+                out["hidden"] = torch.empty(n, controller.hidden_size, N, dtype=torch.float32, device=dev)
+        if recurrent:                                                     # one entry for every mode (abr_policy_gru)
+            smp = controller.sampling()
+            self._call(self.lib.abr_env_step_policy_gru, self._h, C.byref(pol), C.byref(smp),
+                       C.byref(val) if val is not None else None, n,
+                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
+                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
+                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")),
+                       _lib.ptr(out.get("hidden")))
+            return out
         if getattr(controller, "method", None) == "policy_population":    # one weight set per lane group (abr_policy_pop)
             pop, smp = controller.population(), controller.sampling()
             fn = (self.lib.abr_env_step_policy_mx_pop if controller.engine == "matrix" else

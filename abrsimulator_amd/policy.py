@@ -32,6 +32,12 @@ PolicyPopulation runs P networks of one shape in a single launch, member m on la
     out = env.step_policy(pop, 48)                          # every member on its own lanes, one launch per decision
     pop.load_weights(next_generation)                       # in place, no sync
     best = pop.member(3)                                    # an ordinary PolicyController over member 3's weights
+
+RecurrentPolicyController is a GRU-cell actor whose hidden state lives on the device, one column per lane, persists
+across decisions and launches and restarts with the lane's episode (include/abr_env.h: abr_policy_gru):
+
+    ctl = RecurrentPolicyController(EnvPlayer(env), nn.GRUCell(F, 32), nn.Linear(32, M), window=8, sample="softmax")
+    out = env.step_policy(ctl, 48, want_features=True, want_hidden=True)   # hidden[t]: the state decision t started from
 """
 import copy
 import ctypes as C
@@ -63,6 +69,12 @@ def pack_layers(layers):
             t = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
             parts.append(np.asarray(t, np.float32).reshape(-1))
     return np.concatenate(parts)
+
+
+def pack_gru(cell, head):
+    """The recurrent policy's weight blob on the host: W_ih [3H, F], W_hh [3H, H], b_ih [3H], b_hh [3H] (torch.nn.GRUCell's
+    own tensors, gates r, z, n), then the head's W [M, H] and b [M], concatenated (float32)."""
+    return pack_layers([cell[:2], cell[2:], head])
 
 
 class PolicyController:
@@ -430,6 +442,11 @@ class PolicyPopulation:
     @classmethod
     def _member_layers(cls, members, max_hidden):
         """A list of P layer lists from any of the three forms; ValueError for anything else."""
+        if getattr(members, "method", None) == "policy_gru" or isinstance(members, torch.nn.GRUCell) or (
+                isinstance(members, (list, tuple)) and any(getattr(m, "method", None) == "policy_gru" or
+                                                           isinstance(m, torch.nn.GRUCell) for m in members)):
+            raise ValueError("a population's members are MLPs: a recurrent policy (RecurrentPolicyController, GRUCell) "
+                             "has per-lane state and is not supported in a PolicyPopulation")
         members = list(members) if not isinstance(members, torch.nn.Sequential) else None
         if not members:
             raise ValueError("members is a non-empty list of layer lists or nn.Sequentials, or stacked (W, b) tensors")
@@ -598,3 +615,201 @@ class PolicyPopulation:
     def next_bitrate(self):
         """int32 [N]: each lane's action by its member's network (-1 for finished lanes)."""
         return self.select(False, False)["actions"]
+
+
+class RecurrentPolicyController:
+    """A recurrent policy over `player`: one GRU cell per lane, then Linear(H, M) over the new hidden state
+    (include/abr_env.h: abr_policy_gru).  The hidden state is per-lane device state that persists across decisions and
+    across launches and restarts with the lane's episode: a decision at a lane's first chunk (chunk_id == 0) starts from
+    zeros whatever `hidden` holds, so reset, a masked reset, an auto_reset re-arm and the episode sampler all restart the
+    recurrence.
+
+        cell, head = nn.GRUCell(F, 32), nn.Linear(32, M)
+        ctl = RecurrentPolicyController(EnvPlayer(env), cell, head, window=8, sample="softmax")
+        out = env.step_policy(ctl, 48, want_features=True, want_hidden=True)
+        h1 = cell(out["features"][t].T, out["hidden"][t].T)      # the step again in torch, for the loss
+        ctl.load_weights(cell, head)                              # in place, no sync
+
+    cell: an nn.GRUCell(feature_dim, H) with bias, or (W_ih [3H, F], W_hh [3H, H], b_ih [3H], b_hh [3H]) in GRUCell's
+    layout and gate order (r, z, n); 1 <= H <= 64.  head: nn.Linear(H, n_rates) or (W [M, H], b [M]).  value_head: None,
+    nn.Linear(H, 1) or (Wv, bv), the critic's head over the new hidden state.  window, norm, explore, seed, sample and
+    temperature are PolicyController's.  It owns `weights` (the blob: the cell's four parameters, then the head's two,
+    concatenated) and `hidden`, float32 [H, N], which starts at zero.
+
+    Not covered: the matrix engine, PolicyPopulation, ShardedABREnv, LSTM cells and stacked cells.  A checkpoint taken
+    mid-episode (env.state_dict()) does not contain the policy's state: save ctl.hidden next to it."""
+
+    method = "policy_gru"
+    engine = "lane"
+
+    explore = PolicyController.explore
+    sample = PolicyController.sample
+    temperature = PolicyController.temperature
+    sampling = PolicyController.sampling
+    feature_names = PolicyController.feature_names
+    _norm = PolicyController._norm
+    _head_parts = PolicyController._head_parts
+
+    def __init__(self, player, cell, head, window=8, norm="default", explore=0.0, seed=0, sample="argmax",
+                 temperature=1.0, value_head=None, device=None):
+        self.player = player
+        env = getattr(player, "env", None)
+        if type(env).__name__ == "ShardedABREnv":
+            raise ValueError("RecurrentPolicyController does not run on a ShardedABREnv: the hidden state is one slab "
+                             "of one environment's lanes")
+        self.device = torch.device(device) if device is not None else (env.device if env is not None else
+                                                                       torch.device("cuda"))
+        if isinstance(window, bool) or int(window) != window or not 0 <= int(window) <= _lib.POLICY_MAX_WINDOW:
+            raise ValueError(f"window must be an integer in 0..{_lib.POLICY_MAX_WINDOW}")
+        self.window = int(window)
+        mpd = player.get_mpd()
+        self.n_rates, self.video_length = len(mpd.chunk_list()[0].bitrates), int(mpd.video_length)
+        self.feature_dim = 4 + self.window + self.n_rates
+        self.hidden_size = None
+        parts = self._parts(cell, head)                                   # refuse bad shapes before anything is allocated
+        self.hidden_size = self.value_in = int(np.shape(parts[1])[1])
+        self.value_head = None
+        if value_head is not None:
+            self._head_parts(value_head)
+        self.explore, self.seed, self.sample, self.temperature = explore, int(seed), sample, temperature
+        norm = self._norm(norm, mpd)
+        nbytes = C.c_size_t()
+        _lib.check(_lib.lib().abr_policy_gru_weights_bytes(C.byref(self._struct(None, 0, None, None, 0)), self.n_rates,
+                                                          C.byref(nbytes)))
+        self.n_lanes = int(env.n_lanes) if env is not None else None
+        if self.n_lanes is None:
+            raise ValueError("RecurrentPolicyController needs player.env: the hidden state is [H, env.n_lanes]")
+        self.weights = torch.zeros(nbytes.value // 4, dtype=torch.float32, device=self.device)
+        self.hidden = torch.zeros(self.hidden_size, self.n_lanes, dtype=torch.float32, device=self.device)
+        if value_head is not None:
+            self.value_head = torch.zeros(self.value_in + 1, dtype=torch.float32, device=self.device)
+        self.norm = norm
+        self.load_weights(cell, head, value_head=value_head)
+
+    def value(self):
+        """The abr_policy_value struct (it points into this controller's value head); ValueError without a head."""
+        if self.value_head is None:
+            raise ValueError("values need a value head: RecurrentPolicyController(..., value_head=(Wv, bv))")
+        v = _lib.PolicyValue()
+        v.head_dev, v.head_bytes = self.value_head.data_ptr(), self.value_head.numel() * 4
+        return v
+
+    # -- the weights -------------------------------------------------------------
+    def _parts(self, cell, head):
+        """(W_ih, W_hh, b_ih, b_hh, W_out, b_out) after checking every shape; ValueError otherwise."""
+        F, M = self.feature_dim, self.n_rates
+        if isinstance(cell, torch.nn.Module):
+            if type(cell) is not torch.nn.GRUCell:
+                raise ValueError(f"a recurrent policy's cell is nn.GRUCell({F}, H), got {type(cell).__name__}")
+            if not cell.bias:
+                raise ValueError("cell: GRUCell without a bias")
+            cell = (cell.weight_ih, cell.weight_hh, cell.bias_ih, cell.bias_hh)
+        try:
+            W_ih, W_hh, b_ih, b_hh = cell
+        except (TypeError, ValueError):
+            raise ValueError("cell is nn.GRUCell(F, H) or (W_ih, W_hh, b_ih, b_hh)") from None
+        sh = tuple(np.shape(W_hh))
+        H = sh[1] if len(sh) == 2 else -1
+        if not 1 <= H <= _lib.POLICY_GRU_MAX_HIDDEN:
+            raise ValueError(f"cell: W_hh must be [3H, H] with H in 1..{_lib.POLICY_GRU_MAX_HIDDEN}, got {sh}")
+        if self.hidden_size is not None and H != self.hidden_size:
+            raise ValueError(f"cell: {H} units, this policy has {self.hidden_size}")
+        got = tuple(tuple(np.shape(t)) for t in (W_ih, W_hh, b_ih, b_hh))
+        want = ((3 * H, F), (3 * H, H), (3 * H,), (3 * H,))
+        if got != want:
+            raise ValueError(f"cell: W_ih, W_hh, b_ih, b_hh must be {want}, got {got}")
+        if isinstance(head, torch.nn.Module):
+            if type(head) is not torch.nn.Linear:
+                raise ValueError(f"a recurrent policy's head is nn.Linear({H}, {M}), got {type(head).__name__}")
+            if head.bias is None:
+                raise ValueError("head: Linear without a bias")
+            head = (head.weight, head.bias)
+        try:
+            W, b = head
+        except (TypeError, ValueError):
+            raise ValueError("head is nn.Linear(H, n_rates) or (W, b)") from None
+        if tuple(np.shape(W)) != (M, H) or tuple(np.shape(b)) != (M,):
+            raise ValueError(f"head: W must be [{M}, {H}] and b [{M}], got {tuple(np.shape(W))} / {tuple(np.shape(b))}")
+        return W_ih, W_hh, b_ih, b_hh, W, b
+
+    def load_weights(self, cell, head, value_head=None):
+        """Copy new weights (an nn.GRUCell and an nn.Linear of this controller's shapes, or the tuples) into the device
+        blob in place, on the current stream, without synchronising; value_head refreshes the critic's head the same way.
+        The hidden state is not touched."""
+        parts = self._parts(cell, head)
+        if value_head is not None:
+            if self.value_head is None:
+                raise ValueError("this controller was built without a value head")
+            Wv, bv = self._head_parts(value_head)
+            with torch.no_grad():
+                self.value_head[:self.value_in].copy_(_as_f32(Wv, self.device).reshape(-1), non_blocking=True)
+                self.value_head[self.value_in:].copy_(_as_f32(bv, self.device).reshape(-1), non_blocking=True)
+        o = 0
+        with torch.no_grad():
+            for t in parts:
+                t = _as_f32(t, self.device).reshape(-1)
+                self.weights[o:o + t.numel()].copy_(t, non_blocking=True)
+                o += t.numel()
+        assert o == self.weights.numel()
+
+    def reset_hidden(self, mask=None):
+        """Zero the hidden state of every lane, or of the lanes where mask (bool [N]) is set.  A new episode needs no call:
+        a lane's first decision starts from zeros by the contract."""
+        if mask is None:
+            self.hidden.zero_()
+        else:
+            mask = torch.as_tensor(mask, device=self.device).to(torch.bool)
+            if tuple(mask.shape) != (self.n_lanes,):
+                raise ValueError(f"mask must be bool [{self.n_lanes}]")
+            self.hidden.masked_fill_(mask[None, :], 0.0)
+
+    # -- the C ABI ---------------------------------------------------------------
+    def _struct(self, wptr, nbytes, norm, sptr, sbytes):
+        p = _lib.PolicyGru()
+        p.window, p.hidden = self.window, self.hidden_size
+        p.weights_dev, p.weights_bytes = wptr, nbytes
+        p.norm_dev = norm.data_ptr() if norm is not None else None
+        p.state_dev, p.state_bytes = sptr, sbytes
+        p.seed = self.seed & (2 ** 64 - 1)
+        p.explore_threshold = self.explore_threshold
+        return p
+
+    def bound(self, env=None):
+        """The abr_policy_gru struct (it points into this controller's tensors)."""
+        env = env if env is not None else self.player.env
+        if env.n_rates != self.n_rates:
+            raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
+        if int(env.n_lanes) != self.n_lanes:
+            raise ValueError(f"the hidden state is for {self.n_lanes} lanes, the environment has {env.n_lanes}")
+        return self._struct(self.weights.data_ptr(), self.weights.numel() * 4, self.norm, self.hidden.data_ptr(),
+                            self.hidden.numel() * 4)
+
+    # -- decisions ---------------------------------------------------------------
+    def select(self, want_features=True, want_scores=True, want_probs=False, want_value=False, want_hidden=False,
+               commit=False):
+        """One decision per lane on the environment's current state (no step): the dict of PolicyController.select, and
+        with want_hidden=True hidden float32 [H, N], the state each decision was taken from (zeros at a lane's first
+        chunk).  commit=False leaves `hidden` as it is, so that select can be called any number of times; commit=True
+        advances it, which is right exactly when a step of the returned actions follows."""
+        env = self.player.env
+        N, dev = env.n_lanes, env.device
+        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
+                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
+                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
+                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
+        pol, smp = self.bound(env), self.sampling()
+        val = self.value() if want_value else None
+        if want_value:
+            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
+        if want_hidden:
+            out["hidden"] = torch.empty(self.hidden_size, N, dtype=torch.float32, device=dev)
+        env._call(env.lib.abr_env_policy_select_gru, env._h, C.byref(pol), C.byref(smp),
+                  C.byref(val) if val is not None else None, int(bool(commit)), _lib.ptr(out["actions"]),
+                  _lib.ptr(out["features"]), _lib.ptr(out["scores"]), _lib.ptr(out["probs"]), _lib.ptr(out.get("value")),
+                  _lib.ptr(out.get("hidden")))
+        return out
+
+    def next_bitrate(self):
+        """int32 [N]: the policy's action for each lane (-1 for finished lanes).  It commits the new hidden state: the
+        player's loop steps these actions next."""
+        return self.select(False, False, commit=True)["actions"]

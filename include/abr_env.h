@@ -982,6 +982,97 @@ int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr
                                float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, void *stream);
 
 /*
+ * Recurrent learned policy (ABI 4, additive; BUILD-DEFINED): one GRU cell per lane, evaluated on the device, whose hidden
+ * state persists across decisions and across launches and restarts with the lane's episode.  An actor that has to infer a
+ * hidden network condition (a bandwidth regime) from what it has seen carries that belief in the state.
+ *
+ * Network: the features x[0..F) exactly as abr_policy defines them (the same norm_dev); one GRU cell of H units,
+ * 1 <= H <= ABR_POLICY_GRU_MAX_HIDDEN; the output layer Linear(H, M) over the NEW hidden state h'; optionally an
+ * abr_policy_value head over h' (in = H, head_bytes == (H + 1) * 4).
+ * Blob: one float32 blob in torch.nn.GRUCell's own layout and gate order (r, z, n), so that a trained module copies over
+ * with no permutation: W_ih [3H][F], W_hh [3H][H], b_ih [3H], b_hh [3H], then W_out [M][H], b_out [M]; unpadded
+ * (abr_policy_gru_weights_bytes).
+ * State: state_dev float32 [H][n_lanes], caller-owned device memory, 4-byte aligned, state_bytes == H * n_lanes * 4.  The
+ * library keeps nothing else; the workspace is untouched (so a checkpoint of the workspace does not hold the state: the
+ * caller saves the slab next to it).
+ * h_in, the hidden state entering a decision, for a lane that takes one: +0.0f in every unit when c == 0 (c = chunk_id),
+ * otherwise the lane's column of state_dev.  That is the whole episode-boundary rule: every path that starts an episode
+ * (abr_env_reset, a masked reset, an auto_reset re-arm, the episode sampler) restarts the recurrence, and no environment
+ * kernel knows of it.
+ * Cell: every operation float32, round-to-nearest-even, one rounding each, in this order.  For unit j and gate g in
+ * (r, z, n), six k-ordered chains, each from its bias:
+ *   gi_g = b_ih[gH + j], then gi_g = fmaf(W_ih[gH + j][k], x[k], gi_g), k = 0 .. F-1
+ *   gh_g = b_hh[gH + j], then gh_g = fmaf(W_hh[gH + j][k], h_in[k], gh_g), k = 0 .. H-1
+ *   r = sig_c(gi_r + gh_r);  z = sig_c(gi_z + gh_z);  n = tanh_c(fmaf(r, gh_n, gi_n))
+ *   d = h_in[j] - n;  h'[j] = fmaf(z, d, n)                      (GRUCell's n + z * (h - n))
+ * Activations, on exp_c (abr_policy_sampling; its text is unchanged and its argument here is never positive):
+ *   sig_c(v): a NaN v returns v.  Otherwise e = exp_c(-fabsf(v)), q = 1.0f + e, result (v >= 0 ? 1.0f : e) / q, the
+ *     correctly rounded division.
+ *   tanh_c(v): a NaN v returns v.  Otherwise e = exp_c(-2.0f * fabsf(v)) (the product is exact),
+ *     t = (1.0f - e) / (1.0f + e), result copysignf(t, v).  tanh_c(+-0) = +-0; +-1 for |v| > 40.
+ *   Both are accurate in ABSOLUTE terms only (sig_c(-90) = 0, not 8e-40; near 0 tanh_c's error does not shrink with v).
+ *   Derivation, with u = 2^-24 (one rounding), exp_c = E (1 + d1), |d1| < 2u (its stated bound), E = exp(-|v|) or
+ *   exp(-2|v|) in (0, 1], first order in u:
+ *     sig_c, v >= 0: 1 / (1 + E): d1 enters through the denominator with weight E / (1 + E), then the sum and the
+ *       quotient round: relative (2E / (1 + E) + 2) u, absolute ((4E + 2) / (1 + E)^2) u, which falls in E: <= 2u.
+ *     sig_c, v < 0: E / (1 + E): d1's weight is 1 / (1 + E): absolute (E (4 + 2E) / (1 + E)^2) u, which rises in E: <= 1.5u.
+ *       Below -80, exp_c is 0 and the true value is under 2e-35.
+ *     tanh_c: T = (1 - E) / (1 + E), dT/dE = -2 / (1 + E)^2: d1 gives (4E / (1 + E)^2) u, the three roundings 3 T u:
+ *       ((3 + 4E - 3E^2) / (1 + E)^2) u, which falls in E: <= 3u.
+ *   |sig_c - sigmoid| <= 2^-23 and |tanh_c - tanh| <= 3 * 2^-24 (both times 1 + 2^-20 for the second-order terms).
+ *   Measured against float64 on 1 310 203 points of [-90, 90]: 8.915e-8 (0.748 * 2^-23) and 8.895e-8 (0.497 * 3 * 2^-24).
+ * Outputs: score[m] = b_out[m], then fmaf(W_out[m][k], h'[k], .), k ascending; the value head is the same chain over h'.
+ * Then abr_policy's first argmax, exploration and abr_policy_sampling's decision, unchanged: the same philox block, the
+ * same words, the same probs.
+ * Commit: with commit != 0 a lane that takes a decision has h' written over its column of state_dev.  A lane whose done
+ * bits are set takes no decision: action -1, its feature, score, probs and hidden-out columns 0.0f, value 0.0f, and its
+ * column of state_dev is NOT touched.
+ * Not covered: the matrix engine, populations, sharded environments, LSTM cells and stacked cells.
+ */
+#define ABR_POLICY_GRU_MAX_HIDDEN 64
+typedef struct abr_policy_gru {           /* 80 bytes, no padding */
+    int32_t window;                       /* W, 0..ABR_POLICY_MAX_WINDOW */
+    int32_t hidden;                       /* H, 1..ABR_POLICY_GRU_MAX_HIDDEN */
+    const float *weights_dev;             /* the blob (device, 4-byte aligned) */
+    size_t weights_bytes;                 /* == abr_policy_gru_weights_bytes(this, n_rates) */
+    const double *norm_dev;               /* float64 [2][F] (device, 8-byte aligned) or NULL */
+    float *state_dev;                     /* float32 [H][n_lanes] (device, 4-byte aligned, non-NULL) */
+    size_t state_bytes;                   /* == H * n_lanes * 4 */
+    uint64_t seed;                        /* philox key of the exploration draw */
+    uint64_t explore_threshold;           /* 0 .. 2^32 */
+    int32_t reserved_[4];                 /* set to 0 */
+} abr_policy_gru;
+
+/* Bytes of the weight blob for pol's shape (window, hidden; the pointers are not looked at) and n_rates:
+ * 4 * (3H (F + H + 2) + M (H + 1)). */
+int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n_rates, size_t *bytes_out);
+
+/* The recurrent policy's decision for each lane on the environment's current state, no step.  One form for every mode, as
+ * the matrix engine's: smp == NULL is the first argmax and requires probs_out_dev == NULL; val == NULL requires
+ * value_out_dev == NULL.  Outputs as abr_env_policy_select_ac, and hidden_out_dev float32 [H][n_lanes] (nullable): h_in,
+ * the state the decision was taken from AFTER the c == 0 rule -- what a trainer needs to recompute the step.  commit != 0
+ * writes h' to state_dev (above); commit == 0 leaves state_dev byte for byte.
+ * Validation (ABR_E_INVALID, nothing launched): the struct (window, hidden, reserved_ zero, weights and state non-NULL and
+ * 4-byte aligned, norm 8-byte aligned, threshold <= 2^32), smp and val where given, probs_out_dev without smp,
+ * value_out_dev without val, all before the handle; then weights_bytes, state_bytes and head_bytes against the
+ * environment. */
+int abr_env_policy_select_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
+                              const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
+                              float *features_out_dev, float *scores_out_dev, float *probs_out_dev, float *value_out_dev,
+                              float *hidden_out_dev, void *stream);
+
+/* n_steps fused decisions: outputs as abr_env_step_policy_ac, and hidden_out_dev float32 [n_steps][H][n_lanes] (nullable),
+ * the h_in of every decision.  Every decision commits.  last_value_out_dev is one more forward-only launch with
+ * commit = 0: it leaves state_dev byte for byte as the last decision left it.  Apart from the state slab the call is byte
+ * for byte a loop of abr_env_policy_select_gru(commit = 1) then abr_env_step.  Validation as abr_env_policy_select_gru
+ * (values_out_dev and last_value_out_dev need val), with n_steps >= 1 before the handle; ABR_E_UNSUPPORTED on tick. */
+int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
+                            const abr_policy_value *val, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                            uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
+                            float *scores_out_dev, float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                            float *hidden_out_dev, void *stream);
+
+/*
  * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
  * reward, values float32 [n_steps][n_lanes]; last_value float32 [n_lanes]; done uint8 [n_steps][n_lanes]; actions int32
  * [n_steps][n_lanes] or NULL (every step is live); outputs adv, ret float32 [n_steps][n_lanes], which may not overlap
