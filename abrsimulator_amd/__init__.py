@@ -11,6 +11,7 @@ from .env import BatchedABREnv, obs_dict, pack_traces
 from .episodes import EpisodeSampler
 from .fastmpc import FastMPCController
 from .ledger import EpisodeLedger
+from .quality import EpisodeQuality
 from .mpc import BatchedMPCController, EnvPlayer
 from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController
 from .rules import BolaController, BufferBasedController, RateBasedController
@@ -25,6 +26,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "EpisodeSampler", "EpisodeLedger", "advantage", "gae", "TraceModel", "synth_traces",
+           "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

@@ -163,6 +163,11 @@ class EpisodeLedger(C.Structure):
     _fields_ = [("base_dev", C.c_void_p), ("rows", C.c_int32), ("reserved_", C.c_int32)]
 
 
+class EpisodeQuality(C.Structure):
+    _fields_ = [("wq", C.c_double), ("u_dev", C.c_void_p), ("base_dev", C.c_void_p), ("rows", C.c_int32),
+                ("reserved_", C.c_int32)]
+
+
 TRACE_MAX_STATES = 8
 
 
@@ -198,6 +203,9 @@ SYMBOLS = [
     ("abr_env_get_episode", C.c_int, [_P, _P, _P, _P, _P]),
     ("abr_env_ledger_bytes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
     ("abr_env_set_episode_ledger", C.c_int, [_P, C.POINTER(EpisodeLedger)]),
+    ("abr_env_quality_bytes", C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_set_episode_quality", C.c_int, [_P, C.POINTER(EpisodeQuality)]),
+    ("abr_env_episode_quality", C.c_int, [_P, _P, _P]),
     ("abr_env_reset", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step", C.c_int, [_P, _P, _P, _P, _P, _P]),
     ("abr_env_step_random", C.c_int, [_P, C.c_int32, C.c_uint64, _P, _P, _P, _P, _P]),

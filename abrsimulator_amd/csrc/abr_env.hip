@@ -170,6 +170,12 @@ static_assert(sizeof(abrx::EpisodeLedger) == sizeof(abr_episode_ledger) &&
               offsetof(abrx::EpisodeLedger, base) == offsetof(abr_episode_ledger, base_dev) &&
               offsetof(abrx::EpisodeLedger, rows) == offsetof(abr_episode_ledger, rows),
               "abr_episode_ledger: one layout");
+static_assert(sizeof(abrx::EpisodeQuality) == sizeof(abr_episode_quality) &&
+              offsetof(abrx::EpisodeQuality, wq) == offsetof(abr_episode_quality, wq) &&
+              offsetof(abrx::EpisodeQuality, u) == offsetof(abr_episode_quality, u_dev) &&
+              offsetof(abrx::EpisodeQuality, base) == offsetof(abr_episode_quality, base_dev) &&
+              offsetof(abrx::EpisodeQuality, rows) == offsetof(abr_episode_quality, rows),
+              "abr_episode_quality: one layout");
 
 struct abr_env {
     EnvParams p;
@@ -193,6 +199,7 @@ struct abr_env {
     bool sampler_on;                // abr_env_set_episode_sampler: launches run the SAMPLE instances with `sampler`
     abrx::EpisodeSampler sampler;
     abrx::EpisodeLedger ledger;     // abr_env_set_episode_ledger: base == nullptr while none is installed
+    abrx::EpisodeQuality quality;   // abr_env_set_episode_quality: likewise
 };
 
 // A handle on which no reset has run has no episode to protect: the setters take effect at once
@@ -395,6 +402,50 @@ __device__ inline void ledger_record(const EnvParams &p, const abrx::EpisodeLedg
                         chunks, (int32_t)done);
 }
 
+// The quality model (include/abr_env.h: abr_episode_quality).  Called only by the QUALITY instances.  quality_term: lane
+// i's step has completed the download of `chunk` at rate `a` -- the weighted table entry that comes off the step's reward;
+// quality_record: the lane's episode has just ended (where ledger_record is called).
+// (the term's variable in the kernels: a double in the QUALITY instances, an empty object in the others, which then hold no
+// dead initialisation of it)
+struct NoQualityTerm {};
+template <bool QUALITY> using QualityTerm = std::conditional_t<QUALITY, double, NoQualityTerm>;
+__device__ inline double quality_term(const EnvParams &p, const abrx::EpisodeQuality &ql, int64_t i, int32_t chunk, int32_t a) {
+    return abrx::quality_step(ql, p.n_lanes, p.n_rates, i, chunk, a);
+}
+__device__ inline void quality_record(const EnvParams &p, const abrx::EpisodeQuality &ql, int64_t i, bool rearm) {
+    abrx::quality_close(ql, p.n_lanes, i, rearm);
+}
+
+// The kernarg segment of env_jump_kernel (by-value arguments lie in it like a C struct; the code object's metadata gives each
+// argument's .offset).  The QUALITY instances read the ledger and the quality model from it afresh where an episode ends,
+// through a vector register, as the role-split kernels do (abr_env_roles.h: ledger_record_split, and for its reason): held as
+// kernel arguments across the decision loop, the two are ten more live scalars next to the model's per-step three, and
+// the instances with both came out with 12-72 B of private segment per lane.
+struct JumpKernargs {
+    EnvParams p;
+    const int32_t *actions, *trace_id_in, *offset_in;
+    const uint8_t *lane_mask;
+    float *obs_out, *reward_out;
+    uint8_t *done_out;
+    int32_t *actions_out;
+    int32_t n_steps;
+    uint64_t seed;
+    abrx::RuleParams rule;
+    abrx::EpisodeSampler smp;
+    abrx::EpisodeLedger led;
+    abrx::EpisodeQuality ql;
+};
+static_assert(offsetof(JumpKernargs, n_steps) == sizeof(EnvParams) + 64 && offsetof(JumpKernargs, seed) == sizeof(EnvParams) + 72 &&
+              offsetof(JumpKernargs, rule) == sizeof(EnvParams) + 80 &&
+              offsetof(JumpKernargs, smp) == sizeof(EnvParams) + 80 + sizeof(abrx::RuleParams) &&
+              offsetof(JumpKernargs, ql) == offsetof(JumpKernargs, led) + 16 &&
+              sizeof(JumpKernargs) == offsetof(JumpKernargs, ql) + 32, "env_jump_kernel's kernarg segment");
+__device__ __forceinline__ const JumpKernargs &fresh_jump_args() {
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+v"(kp));
+    return *(const JumpKernargs *)kp;
+}
+
 // MODE 0: reset (fresh lanes run to their first call site)
 // MODE 1: step  (one externally supplied action per lane)
 // MODE 2: fused random-policy rollout of n_steps decisions per lane
@@ -405,13 +456,15 @@ __device__ inline void ledger_record(const EnvParams &p, const abrx::EpisodeLedg
 // LEDGER: the instance that runs while an episode ledger is installed: every episode end appends a record to `led`; the
 // other instances never read `led` and are, instruction for instruction, what they were without it
 // SPEEDS: the tick kernel plays one speed for all lanes (kFeatures), so it exists only as the no-speeds instance
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = false>
+// QUALITY: the instance that runs while a quality model is installed (`ql`): a completed download takes its weighted table
+// entry off the reward, every episode end records the episode's sum; the other instances never read `ql`
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = false, bool QUALITY = false>
 __global__ __launch_bounds__(64) void env_advance_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
-    abrx::EpisodeSampler smp, abrx::EpisodeLedger led) {
+    abrx::EpisodeSampler smp, abrx::EpisodeLedger led, abrx::EpisodeQuality ql) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     static_assert(!SPEEDS, "the tick kernel takes no per-lane speeds");
@@ -476,6 +529,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
             if (!need_action && !fresh) {
                 const int64_t o = (int64_t)step_idx * p.n_lanes + i;
                 double var = 0.0;
+                QualityTerm<QUALITY> qw{};
                 if (s.done_dl && s.cur_action >= 0) {
                     // the chunk this step downloaded (:164-165)
                     const double bw = s.dl / p.G[s.n_dl];
@@ -490,10 +544,12 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                         var = fabs(chunk_bitrate(p, s.chunk_id - 1, s.cur_action) -
                                    chunk_bitrate(p, s.chunk_id - 2, prev_action));
                     var_run = var_run + var;
+                    if constexpr (QUALITY) qw = quality_term(p, ql, i, s.chunk_id - 1, s.cur_action);
                 }
                 // per-step split of calculate_qoe (Simulator.py:83-85)
-                const double r = p.wr * (p.G[s.n_rb] - p.G[n_rb_obs]) +
-                                 p.ws * (p.G[s.n_su] - p.G[n_su_obs]) + p.wv * var;
+                double r = p.wr * (p.G[s.n_rb] - p.G[n_rb_obs]) +
+                           p.ws * (p.G[s.n_su] - p.G[n_su_obs]) + p.wv * var;
+                if constexpr (QUALITY) r = r - qw;          // 0.0 without a completed download: no bit of r moves
                 if (ended) done |= ABR_DONE_EPISODE;
                 if (timeout) done |= ABR_DONE_TIMEOUT;
                 if (reward_out) reward_out[o] = (float)r;
@@ -508,6 +564,9 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                     if constexpr (LEDGER)
                         ledger_record(p, led, i, p.G[s.n_rb], p.G[s.n_su], lane_avg_latency(p, s.sumk, s.n_play), var_run,
                                       episode_no, p.trace_id[i], offset0, s.chunk_id, done);
+                    // (straight from the arguments: this kernel has no register bound to meet, and with the kernarg read of
+                    // env_jump_kernel its sampled rule rollouts picked up 36 B of private segment)
+                    if constexpr (QUALITY) quality_record(p, ql, i, p.auto_reset && ended);
                     if (p.auto_reset && ended) {
                         // re-arm: this step's obs is the new episode's first call site
                         if constexpr (SAMPLE) {
@@ -795,14 +854,14 @@ __device__ inline void write_obs_vals(const LaneJ &s, const EnvParams &p, int64_
 #endif
 #define ABR_JUMP_BOUNDS(MODE, SAMPLE) \
     __launch_bounds__(64, ((MODE) == 1 ? ABR_JUMP_WAVES_ONE : ((MODE) == 4 || (SAMPLE)) ? 4 : ABR_JUMP_WAVES))
-// SAMPLE, LEDGER: as env_advance_kernel; SPEEDS: see make_tables
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
-__global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
+// SAMPLE, LEDGER, QUALITY: as env_advance_kernel; SPEEDS: see make_tables
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
+__global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kernel(
     EnvParams p, const int32_t *__restrict__ actions, const int32_t *__restrict__ trace_id_in,
     const int32_t *__restrict__ offset_in, const uint8_t *__restrict__ lane_mask,
     float *__restrict__ obs_out, float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::RuleParams rule,
-    abrx::EpisodeSampler smp, abrx::EpisodeLedger led) {
+    abrx::EpisodeSampler smp, abrx::EpisodeLedger led, abrx::EpisodeQuality ql) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     const bool in_range = i < p.n_lanes;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
@@ -889,6 +948,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                     const double g_rb = p.G[s.n_rb], g_su = p.G[s.n_su];
                     double o_k = p.G[s.k], o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
                     double var = 0.0;
+                    QualityTerm<QUALITY> qw{};
                     if (r.hit) {
                         const int64_t h = (int64_t)chunk * p.n_lanes + i;
                         ABR_OUT(p.bw_hist[h], r.bw);                            // :164
@@ -899,9 +959,11 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                         if (prev_action >= 0)
                             var = fabs(chunk_bitrate(p, chunk, a) - chunk_bitrate(p, chunk - 1, prev_action));
                         var_run = var_run + var;
+                        if constexpr (QUALITY) qw = quality_term(p, ql, i, chunk, a);
                     }
                     // ---- step boundary: per-step split of calculate_qoe (:83-85) ----
-                    const double rew = p.wr * (g_rb - g_rb_obs) + p.ws * (g_su - g_su_obs) + p.wv * var;
+                    double rew = p.wr * (g_rb - g_rb_obs) + p.ws * (g_su - g_su_obs) + p.wv * var;
+                    if constexpr (QUALITY) rew = rew - qw;      // 0.0 without a completed download: no bit of rew moves
                     if (r.ended) done |= ABR_DONE_EPISODE;
                     if (r.timeout) done |= ABR_DONE_TIMEOUT;
                     if (reward_out) ABR_OUT(reward_out[o], (float)rew);
@@ -916,7 +978,13 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER) void env_jump_kernel(
                             : (SP::speed_rows(p) >= 2 ? avg_latency_sched(s.pt, s.sumk, s.pt_sum, s.n_play)
                                                     : avg_latency_from(s.sd, s.pt, s.sumk, s.n_play));
                         p.ep_qoe_terms[3 * p.n_lanes + i] = var_run;
-                        if constexpr (LEDGER)     // the latency term as stored: read back (this thread's own store)
+                        if constexpr (QUALITY) {  // (the ledger and the model from the kernarg segment: JumpKernargs)
+                            const JumpKernargs &ka = fresh_jump_args();
+                            if constexpr (LEDGER)
+                                ledger_record(p, ka.led, i, g_rb, g_su, p.ep_qoe_terms[2 * p.n_lanes + i], var_run, episode_no,
+                                              p.trace_id[i], offset0, s.chunk_id, done);
+                            quality_record(p, ka.ql, i, p.auto_reset && r.ended);
+                        } else if constexpr (LEDGER)     // the latency term as stored: read back (this thread's own store)
                             ledger_record(p, led, i, g_rb, g_su, p.ep_qoe_terms[2 * p.n_lanes + i], var_run, episode_no,
                                           p.trace_id[i], offset0, s.chunk_id, done);
                         if (p.auto_reset && r.ended) {
@@ -1461,6 +1529,47 @@ extern "C" int abr_env_set_episode_ledger(abr_env *env, const abr_episode_ledger
     return ABR_OK;
 }
 
+// the quality model (include/abr_env.h: abr_episode_quality): the layout arithmetic needs no handle and no device
+extern "C" int abr_env_quality_bytes(int32_t n_lanes, int32_t rows, size_t *bytes_out) {
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_lanes < 1) return fail(ABR_E_INVALID, "quality model: n_lanes must be >= 1, got %d", n_lanes);
+    if (rows < 1) return fail(ABR_E_INVALID, "quality model: rows must be >= 1, got %d", rows);
+    *bytes_out = abrx::quality_layout(n_lanes, rows).bytes;
+    return ABR_OK;
+}
+
+extern "C" int abr_env_set_episode_quality(abr_env *env, const abr_episode_quality *q) {
+    if (q) {
+        if (!std::isfinite(q->wq)) return fail(ABR_E_INVALID, "quality model: wq must be finite");
+        if (!q->u_dev) return fail(ABR_E_INVALID, "quality model: u_dev is NULL");
+        if ((uintptr_t)q->u_dev % 8) return fail(ABR_E_INVALID, "quality model: u_dev must be 8-byte aligned");
+        if (q->rows < 1) return fail(ABR_E_INVALID, "quality model: rows must be >= 1, got %d", q->rows);
+        if (!q->base_dev) return fail(ABR_E_INVALID, "quality model: base_dev is NULL");
+        if ((uintptr_t)q->base_dev % 256) return fail(ABR_E_INVALID, "quality model: base_dev must be 256-byte aligned");
+    }
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    abrx::EpisodeQuality v{};
+    if (q) { v.wq = q->wq; v.u = q->u_dev; v.base = q->base_dev; v.rows = q->rows; }
+    env->quality = v;
+    return ABR_OK;
+}
+
+// each lane's last finished episode's quality sum: a copy of the blob's q_last, ordered on the stream
+extern "C" int abr_env_episode_quality(abr_env *env, double *q_out_dev, void *stream) {
+    if (!env || !q_out_dev) return fail(ABR_E_INVALID, "NULL argument");
+    if (!env->quality.base) return fail(ABR_E_INVALID, "no quality model is installed (abr_env_set_episode_quality)");
+    const char *b = (const char *)env->quality.base + abrx::quality_layout(env->p.n_lanes, env->quality.rows).q_last;
+    HIP_TRY(hipMemcpyAsync(q_out_dev, b, (size_t)env->p.n_lanes * sizeof(double), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return ABR_OK;
+}
+
+// abr_env_reset with a quality model: the running sums of the lanes it resets start again at zero
+__global__ __launch_bounds__(256) void quality_reset_kernel(abrx::EpisodeQuality ql, int64_t n_lanes,
+                                                            const uint8_t *__restrict__ lane_mask) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_lanes && (!lane_mask || lane_mask[i])) abrx::quality_reset(ql, n_lanes, i);
+}
+
 // each lane's current (trace, start offset, episode number): copies of the workspace rows, ordered on the stream
 extern "C" int abr_env_get_episode(abr_env *env, int32_t *trace_id_out_dev, int32_t *offset_out_dev,
                                    int32_t *episode_out_dev, void *stream) {
@@ -1528,7 +1637,7 @@ static inline int launch_impl(const abr_env *env, int32_t n_steps) {
 // or a speed rule is latched (env->p.lane_speeds, set at a full reset) the SPEEDS instances run, else the no-speeds ones,
 // which hold none of that code; the tick kernel (no speeds: kFeatures) and the diagnostic pipelines (written against the
 // SPEEDS form of the roles) exist in one form only.
-template <int MODE, bool SAMPLE, bool LEDGER, bool SPEEDS>
+template <int MODE, bool SAMPLE, bool LEDGER, bool SPEEDS, bool QUALITY>
 static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, const int32_t *actions, float *obs, float *rew,
                                uint8_t *dn, int32_t *acts, int32_t n_steps, uint64_t seed, const abrx::RuleParams &rule,
                                const int32_t *trace_id, const int32_t *start_offset, const uint8_t *lane_mask) {
@@ -1536,26 +1645,27 @@ static void launch_env_kernels(const abr_env *env, int impl, hipStream_t st, con
     const int64_t N = p.n_lanes;
     const abrx::EpisodeSampler smp = SAMPLE ? env->sampler : abrx::EpisodeSampler{};
     const abrx::EpisodeLedger led = LEDGER ? env->ledger : abrx::EpisodeLedger{};
+    const abrx::EpisodeQuality ql = QUALITY ? env->quality : abrx::EpisodeQuality{};
     if (impl == 0) {
-        auto *k = env_jump_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
+        auto *k = env_jump_kernel<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>;
         hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
-                           acts, n_steps, seed, rule, smp, led);
+                           acts, n_steps, seed, rule, smp, led, ql);
     } else if (impl == 1) {
         // one form whatever SPEEDS says: the tick kernel plays no per-lane speeds (launch_env refuses it a handle that has some)
-        auto *k = env_advance_kernel<MODE, SAMPLE, LEDGER, false>;
+        auto *k = env_advance_kernel<MODE, SAMPLE, LEDGER, false, QUALITY>;
         hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(64), 0, st, p, actions, trace_id, start_offset, lane_mask, obs, rew, dn,
-                           acts, n_steps, seed, rule, smp, led);
+                           acts, n_steps, seed, rule, smp, led, ql);
     } else if constexpr (MODE >= 1 && MODE <= 3) {
         // the role-split kernels: two waves per 64 lanes (impl 2) or three (impl 5); 6 and 7 in the diagnostic build
         if (impl == 5) {
-            auto *k = env_split3_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
-            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
+            auto *k = env_split3_kernel<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(192), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led, ql);
         } else if (impl == 2) {
-            auto *k = env_split_kernel<MODE, SAMPLE, LEDGER, SPEEDS>;
-            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led);
+            auto *k = env_split_kernel<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>;
+            hipLaunchKernelGGL(k, dim3(grid64(N)), dim3(128), 0, st, p, actions, obs, rew, dn, acts, n_steps, seed, smp, led, ql);
         }
 #ifdef ABR_WITH_RING
-        else if constexpr (!SAMPLE && !LEDGER && SPEEDS) {
+        else if constexpr (!SAMPLE && !LEDGER && SPEEDS && !QUALITY) {
             if (impl == 6)
                 hipLaunchKernelGGL(env_ring3_kernel<MODE>, dim3(grid64(N)), dim3(64 * ABR_RING_WAVES), 0, st, p, actions, obs,
                                    rew, dn, acts, n_steps, seed);
@@ -1579,6 +1689,8 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
         return fail(ABR_E_UNSUPPORTED, "the episode sampler runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
     if (env->ledger.base && impl != 0 && impl != 1 && impl != 2 && impl != 5)
         return fail(ABR_E_UNSUPPORTED, "the episode ledger runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
+    if (env->quality.base && impl != 0 && impl != 1 && impl != 2 && impl != 5)
+        return fail(ABR_E_UNSUPPORTED, "the quality model runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
     (void)N;
 #ifdef ABR_WITH_ASYNC
     if constexpr (MODE == 2 || MODE == 3) {
@@ -1600,10 +1712,12 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
 #endif
     // a reset never ends an episode: it has no LEDGER instance
     const bool ledger = MODE != 0 && env->ledger.base;
+    // nor a quality model's download: a reset has no QUALITY instance (abr_env_reset clears the running sums behind it)
+    const bool quality = MODE != 0 && env->quality.base;
     // speeds are latched at a full reset (apply_pending), so the handle knows at every launch whether any lane has one
     const bool speeds_on = env->p.lane_speeds != nullptr;
     // (never with the tick kernel: the speed setters and abr_env_set_impl refuse that pair, kFeatures)
-    const auto go = [&](auto smp_on, auto led_on) {
+    const auto go = [&](auto smp_on, auto led_on, auto ql_on) {
         // The no-speeds instances exist for handles WITHOUT an episode sampler.  With the sampler's draw in them, four of
         // the ten one-thread-per-lane instances (MODE 2-4) came out with a 36 B private segment where the SPEEDS form has
         // none (profiles/speed_instances_resources.txt), and no measured workload samples episodes at a size where the
@@ -1611,25 +1725,34 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
         // The diagnostic pipelines (6, 7) are written against the SPEEDS form of the roles: they run it whatever the handle holds.
         constexpr bool kSample = decltype(smp_on)::value;
         constexpr bool kLedger = decltype(led_on)::value;
-        if constexpr (kSample) {
-            launch_env_kernels<MODE, true, kLedger, true>(
+        constexpr bool kQuality = decltype(ql_on)::value;
+        // a quality model's instances exist in the SPEEDS form only, for the sampler's reason: one more flag times two forms
+        // is compile time and code size that no measured workload pays back
+        if constexpr (kSample || kQuality) {
+            launch_env_kernels<MODE, kSample, kLedger, true, kQuality>(
                 env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
         } else if (speeds_on || impl == 6 || impl == 7) {
-            launch_env_kernels<MODE, false, kLedger, true>(
+            launch_env_kernels<MODE, false, kLedger, true, false>(
                 env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
         } else {
-            launch_env_kernels<MODE, false, kLedger, false>(
+            launch_env_kernels<MODE, false, kLedger, false, false>(
                 env, impl, st, actions, obs, rew, dn, acts, n_steps, seed, rule, trace_id, start_offset, lane_mask);
         }
     };
+    constexpr std::true_type on{};
+    constexpr std::false_type off{};
     if constexpr (MODE == 0) {
-        if (sample) go(std::true_type{}, std::false_type{});
-        else go(std::false_type{}, std::false_type{});
+        if (sample) go(on, off, off);
+        else go(off, off, off);
     } else {
-        if (sample && ledger) go(std::true_type{}, std::true_type{});
-        else if (sample) go(std::true_type{}, std::false_type{});
-        else if (ledger) go(std::false_type{}, std::true_type{});
-        else go(std::false_type{}, std::false_type{});
+        const auto with_quality = [&](auto smp_on, auto led_on) {
+            if (quality) go(smp_on, led_on, on);
+            else go(smp_on, led_on, off);
+        };
+        if (sample && ledger) with_quality(on, on);
+        else if (sample) with_quality(on, off);
+        else if (ledger) with_quality(off, on);
+        else with_quality(off, off);
     }
     HIP_TRY(hipGetLastError());
     return ABR_OK;
@@ -1651,8 +1774,14 @@ extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
                     "(lane_mask_dev must be NULL for the first reset after it)");
     apply_pending(env);
     env->armed = true;
-    return launch_env<0>(env, launch_impl<0>(env, 0), (hipStream_t)stream, nullptr, obs_out_dev, nullptr, nullptr,
-                         nullptr, 0, 0ull, {}, trace_id_dev, start_offset_dev, lane_mask_dev);
+    const int rc = launch_env<0>(env, launch_impl<0>(env, 0), (hipStream_t)stream, nullptr, obs_out_dev, nullptr, nullptr,
+                                 nullptr, 0, 0ull, {}, trace_id_dev, start_offset_dev, lane_mask_dev);
+    if (rc || !env->quality.base) return rc;
+    // a quality model's running sums belong to the episodes the reset abandons: the reset lanes' start again at zero
+    hipLaunchKernelGGL(quality_reset_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                       env->quality, env->p.n_lanes, lane_mask_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
 }
 
 extern "C" int abr_env_step(abr_env *env, const int32_t *actions_dev, float *obs_out_dev,
@@ -4394,10 +4523,10 @@ extern "C" int abr_debug_selfcheck(abr_env *env, uint32_t *result_dev, void *str
     p.sentinel = 0x5eed0000c0ffee00ull ^ (uint64_t)(uintptr_t)env;
     p.selfcheck_out = result_dev;
     hipLaunchKernelGGL(env_split3_kernel<9>, dim3(1), dim3(192), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
-                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{});
+                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{}, abrx::EpisodeQuality{});
     p.selfcheck_out = result_dev + 1;
     hipLaunchKernelGGL(env_split_kernel<9>, dim3(1), dim3(128), 0, st, p, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 0ull,
-                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{});
+                       abrx::EpisodeSampler{}, abrx::EpisodeLedger{}, abrx::EpisodeQuality{});
     HIP_TRY(hipGetLastError());
     return ABR_OK;
 }

@@ -594,9 +594,11 @@ struct SplitKernargs {
     uint64_t seed;
     abrx::EpisodeSampler smp;
     abrx::EpisodeLedger led;
+    abrx::EpisodeQuality ql;
 };
 static_assert(offsetof(SplitKernargs, p) == 0 && offsetof(SplitKernargs, smp) == sizeof(EnvParams) + 56 &&
-              offsetof(SplitKernargs, led) == sizeof(EnvParams) + 80 && sizeof(SplitKernargs) == sizeof(EnvParams) + 96,
+              offsetof(SplitKernargs, led) == sizeof(EnvParams) + 80 && offsetof(SplitKernargs, ql) == sizeof(EnvParams) + 96 &&
+              sizeof(SplitKernargs) == sizeof(EnvParams) + 128,
               "the role-split kernels' kernarg segment (.offset of each argument in the code object's metadata)");
 // VEC_PARAMS (the three-wave kernel's service side): the parameter block's fields as well.  The two-wave kernel's player
 // keeps them scalar: it has the scalar registers, and the vector ones would cost it its fourth wave per SIMD.
@@ -616,9 +618,28 @@ __device__ __forceinline__ void ledger_record_split(const EnvParams &p, int64_t 
     ledger_record(pv, ka.led, i, g_rb, g_su, lat, var_run, episode_no, t, off, chunks, done);
 }
 
+// The quality model in the role-split kernels (abr_env.hip: quality_term, quality_record), read the way
+// ledger_record_split reads the ledger: afresh from the kernarg segment through a vector register, so that its weight and
+// its two addresses are no live scalars of the shared loop.  The running sum stays in global memory: the same thread
+// serves the same lane throughout, and neither role has a parking word to spare for it.
+template <bool VEC_PARAMS>
+__device__ __forceinline__ double quality_term_split(const EnvParams &p, int64_t i, int32_t chunk, int32_t a) {
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+v"(kp));
+    const SplitKernargs &ka = *(const SplitKernargs *)kp;
+    return quality_term(VEC_PARAMS ? ka.p : p, ka.ql, i, chunk, a);
+}
+template <bool VEC_PARAMS>
+__device__ __forceinline__ void quality_record_split(const EnvParams &p, int64_t i, bool rearm) {
+    auto kp = __builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+v"(kp));
+    const SplitKernargs &ka = *(const SplitKernargs *)kp;
+    quality_record(VEC_PARAMS ? ka.p : p, ka.ql, i, rearm);
+}
+
 // the record P left in slot `sl`: division, history, reward, done, observation, episode end
 // (M2: SplitMail2, or the ring kernel's RingPS -- the same fields with more slots)
-template <bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, class M2>
+template <bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false, class M2>
 __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 &m2, int sl,
                                                float *__restrict__ obs_out, float *__restrict__ reward_out,
                                                uint8_t *__restrict__ done_out) {
@@ -641,6 +662,7 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
     const int32_t chunk = v.o_chunk, prev_action = v.o_last;
     const int32_t nrb_r = m2.nrb_r[sl][l], nsu_r = m2.nsu_r[sl][l];
     double var = 0.0;
+    QualityTerm<QUALITY> qw{};
     if (m2m & kS3Hit) {
         const double bw = m2.dl[sl][l] / p.G[m2.n_dl[sl][l]];                  // :164
         const int64_t h = (int64_t)chunk * p.n_lanes + i;
@@ -653,10 +675,12 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
             var = fabs(chunk_bitrate(p, chunk, a) - chunk_bitrate(p, chunk - 1, prev_action));
         v.var_run = v.var_run + var;
         v.o_last = a; v.o_chunk = chunk + 1;
+        if constexpr (QUALITY) qw = quality_term_split<true>(p, i, chunk, a);
     }
     // ---- step boundary: per-step split of calculate_qoe (:83-85) ----
     const double g_rb = p.G[nrb_r], g_su = p.G[nsu_r];
-    const double rew = p.wr * (g_rb - v.g_rb_obs) + p.ws * (g_su - v.g_su_obs) + p.wv * var;
+    double rew = p.wr * (g_rb - v.g_rb_obs) + p.ws * (g_su - v.g_su_obs) + p.wv * var;
+    if constexpr (QUALITY) rew = rew - qw;          // 0.0 without a completed download: no bit of rew moves
     if (m2m & kS3Ended) v.done |= ABR_DONE_EPISODE;
     if (m2m & kS3Timeout) v.done |= ABR_DONE_TIMEOUT;
     if (reward_out) ABR_OUT(reward_out[o], (float)rew);
@@ -669,6 +693,7 @@ __device__ __forceinline__ void service_record(SVars &v, const EnvParams &p, M2 
         p.ep_qoe_terms[3 * p.n_lanes + i] = v.var_run;
         if constexpr (LEDGER)
             ledger_record_split<SAMPLE, true>(p, i, g_rb, g_su, m2.lat[sl][l], v.var_run, v.episode_no, v.o_chunk, v.done);
+        if constexpr (QUALITY) quality_record_split<true>(p, i, (m2m & kS3Reset) != 0);
         if (m2m & kS3Reset) {
             v.episode_no++;
             v.n_su_obs = 0; v.n_rb_obs = 0; v.g_su_obs = 0.0; v.g_rb_obs = 0.0;
@@ -708,7 +733,7 @@ __device__ __forceinline__ void role_s_begin(SVars &v, const EnvParams &pk, ActR
 }
 
 // before the barrier: draw the policy's actions ahead of D, then serve what P finished in the previous iteration
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
 __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &pk, SplitMail &m, typename SplitMail2Of<SPEEDS>::type &m2, ActRing &ring,
                                            float *__restrict__ obs_out, float *__restrict__ reward_out,
                                            uint8_t *__restrict__ done_out, int32_t n_total, uint64_t seed, int32_t t) {
@@ -743,7 +768,7 @@ __device__ __forceinline__ void role_s_pre(SVars &v, const EnvParams &pk, SplitM
         lds_writes_done();
         if (l == 0) lds_st(&ring.act_hi, v.a_next);
     }
-    if (t >= 1 && i < p.n_lanes) service_record<SAMPLE, LEDGER, SPEEDS>(v, p, m2, pb, obs_out, reward_out, done_out);
+    if (t >= 1 && i < p.n_lanes) service_record<SAMPLE, LEDGER, SPEEDS, QUALITY>(v, p, m2, pb, obs_out, reward_out, done_out);
     v.last_cb = cb;
     ABR_STAMP(21);
 }
@@ -758,7 +783,7 @@ __device__ __forceinline__ void sampled_episode_store(const EnvParams &p, const 
     }
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
 __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &pk, typename SplitMail2Of<SPEEDS>::type &m2, float *__restrict__ obs_out,
                                            float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                            int32_t *__restrict__ actions_out, int32_t n_total,
@@ -767,7 +792,7 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &pk, typena
     const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
     ABR_STAMP_FLUSH();
     if (i >= p.n_lanes) return;
-    service_record<SAMPLE, LEDGER, SPEEDS>(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
+    service_record<SAMPLE, LEDGER, SPEEDS, QUALITY>(v, p, m2, v.last_cb, obs_out, reward_out, done_out);       // P's last records
     if (!v.was_done) {
         if constexpr (SAMPLE) sampled_episode_store(p, smp, i, v.episode_no);
         p.n_su_obs[i] = v.n_su_obs; p.n_rb_obs[i] = v.n_rb_obs; p.episode_no[i] = v.episode_no;
@@ -790,13 +815,15 @@ __device__ __forceinline__ void role_s_end(SVars &v, const EnvParams &pk, typena
 // LEDGER: the instance that runs while an episode ledger is installed (`led`; likewise)
 // SPEEDS: the instance that runs while per-lane speeds, a speed schedule or a speed rule is installed; the <false>
 // instances carry no speed state through the loop, the parking words or the mailboxes (abr_env.hip: make_tables)
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+// QUALITY: the instance that runs while a quality model is installed (`ql`; as `led`)
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
 __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) void env_split3_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp,
-    abrx::EpisodeLedger led) {
+    abrx::EpisodeLedger led, abrx::EpisodeQuality ql) {
     (void)led;                         // read from the kernarg segment where an episode ends (ledger_record_split)
+    (void)ql;                          // ... and where a download completes (quality_term_split)
     __shared__ SplitMail m;
     __shared__ typename SplitMail2Of<SPEEDS>::type m2;
     __shared__ ActRing ring;
@@ -827,7 +854,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
             p_park<SPEEDS>(park.p, v);
         } else {
             SVars v; s_unpark<SPEEDS>(park.s, v);
-            role_s_pre<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
+            role_s_pre<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>(v, p, m, m2, ring, obs_out, reward_out, done_out, n_total, seed, t);
             s_park<SPEEDS>(park.s, v);
         }
         __syncthreads();                       // THE barrier: every wave, every iteration, this one site
@@ -836,7 +863,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     }
     if (role == 0) { role_d_end(dv, p); ABR_WG_TIME(1); }
     else if (role == 1) { PVars v; p_unpark<SPEEDS>(park.p, v, p); role_p3_end<SPEEDS>(v, p); ABR_WG_TIME(2); }
-    else { SVars v; s_unpark<SPEEDS>(park.s, v); role_s_end<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
+    else { SVars v; s_unpark<SPEEDS>(park.s, v); role_s_end<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>(v, p, m2, obs_out, reward_out, done_out, actions_out, n_total, smp); ABR_WG_TIME(3); }
 }
 
 // =====================================================================================================================
@@ -888,7 +915,7 @@ __device__ __forceinline__ void role_p2_begin(P2Vars &v, const EnvParams &) {
     ABR_STAMP_INIT();
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
 __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitMail &m, float *__restrict__ obs_out,
                                             float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
                                             int32_t n_total, int32_t t) {
@@ -942,7 +969,10 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                     v.var_run = v.var_run + var;
                 }
                 // ---- step boundary: per-step split of calculate_qoe (:83-85) ----
-                const double rew = p.wr * (g_rb - v.g_rb_obs) + p.ws * (g_su - v.g_su_obs) + p.wv * var;
+                double rew = p.wr * (g_rb - v.g_rb_obs) + p.ws * (g_su - v.g_su_obs) + p.wv * var;
+                // (a branch of its own here, not a term carried out of the one above as in the other three kernels: with the
+                // term's variable in this function its existing instances came out with two register copies in another order)
+                if constexpr (QUALITY) { if (sr.hit) rew = rew - quality_term_split<false>(p, i, chunk, a); }
                 if (sr.ended) v.done |= ABR_DONE_EPISODE;
                 if (sr.timeout) v.done |= ABR_DONE_TIMEOUT;
                 if (reward_out) ABR_OUT(reward_out[o], (float)rew);
@@ -957,6 +987,7 @@ __device__ __forceinline__ void role_p2_pre(P2Vars &v, const EnvParams &, SplitM
                     p.ep_qoe_terms[3 * p.n_lanes + i] = v.var_run;
                     if constexpr (LEDGER)
                         ledger_record_split<SAMPLE, false>(p, i, g_rb, g_su, player_latency<SPEEDS>(p, s), v.var_run, v.pv.episode_no, s.chunk_id, v.done);
+                    if constexpr (QUALITY) quality_record_split<false>(p, i, p.auto_reset && sr.ended);
                     if (p.auto_reset && sr.ended) {
                         // re-arm: this step's obs is the new episode's first call site
                         abrx::lanej_init_player(s, tb);
@@ -1007,13 +1038,14 @@ __device__ __forceinline__ void role_p2_end(const P2Vars &v, const EnvParams &, 
     }
 }
 
-template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true>
+template <int MODE, bool SAMPLE = false, bool LEDGER = false, bool SPEEDS = true, bool QUALITY = false>
 __global__ __launch_bounds__(128) void env_split_kernel(
     EnvParams p, const int32_t *__restrict__ actions, float *__restrict__ obs_out,
     float *__restrict__ reward_out, uint8_t *__restrict__ done_out,
     int32_t *__restrict__ actions_out, int32_t n_steps, uint64_t seed, abrx::EpisodeSampler smp,
-    abrx::EpisodeLedger led) {
+    abrx::EpisodeLedger led, abrx::EpisodeQuality ql) {
     (void)led;                         // read from the kernarg segment where an episode ends (ledger_record_split)
+    (void)ql;                          // ... and where a download completes (quality_term_split)
     __shared__ SplitMail m;
     const int32_t n_total = (MODE >= 2) ? n_steps : 1;
     const int role = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // wave-uniform by construction
@@ -1032,7 +1064,7 @@ __global__ __launch_bounds__(128) void env_split_kernel(
             role_d_pre<MODE, false, SAMPLE, SPEEDS>(dv, p, m, nullptr, actions, actions_out, n_total, seed, t, smp);
         } else {
             P2Vars v; p2_unpark<SPEEDS>(park.p, v, fresh_params());
-            role_p2_pre<MODE, SAMPLE, LEDGER, SPEEDS>(v, p, m, obs_out, reward_out, done_out, n_total, t);
+            role_p2_pre<MODE, SAMPLE, LEDGER, SPEEDS, QUALITY>(v, p, m, obs_out, reward_out, done_out, n_total, t);
             p2_park<SPEEDS>(park.p, v);
         }
         __syncthreads();                       // THE barrier: both waves, every iteration, this one site

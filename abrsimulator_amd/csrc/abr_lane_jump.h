@@ -1532,6 +1532,67 @@ ABR_HD void ledger_append(const EpisodeLedger &L, int64_t n_lanes, int64_t i, do
     }
 }
 
+// The quality model (include/abr_env.h: abr_episode_quality, the same layout): a video-quality term of the QoE.  A step
+// whose download completed takes u[chunk][action] off the reward, weighted, and adds it to the lane's running sum; the sum
+// is recorded where the kernels write ep_qoe_terms.  The blob is struct-of-arrays with row stride n_lanes, every region
+// 256-B aligned: count[N] int32 | q_run[N] | q_last[N] | total_q[N] | rec_q[rows][N], float64.
+struct EpisodeQuality {
+    double wq;
+    const double *u;               // [video_length][n_rates], the caller's table
+    void *base;                    // nullptr: no quality model installed, quality_step / quality_close are never called
+    int32_t rows;
+    int32_t reserved_;
+};
+struct QualityLayout { size_t count, q_run, q_last, total_q, rec_q, bytes; };   // byte offsets of the regions, and the blob's size
+ABR_HD QualityLayout quality_layout(int64_t n_lanes, int32_t rows) {
+    const size_t n = (size_t)n_lanes, r = (size_t)rows;
+    QualityLayout lo;
+    lo.count = 0;
+    lo.q_run = ledger_align(n * sizeof(int32_t));
+    lo.q_last = lo.q_run + ledger_align(n * sizeof(double));
+    lo.total_q = lo.q_last + ledger_align(n * sizeof(double));
+    lo.rec_q = lo.total_q + ledger_align(n * sizeof(double));
+    lo.bytes = lo.rec_q + ledger_align(r * n * sizeof(double));
+    return lo;
+}
+
+// Lane i has completed the download of `chunk` at rate `action`: its running sum grows by the table's entry (a read-modify-
+// write of the lane's own element: the same thread serves the lane throughout).  Returns the weighted entry wq * q, which
+// the caller takes off the step's float64 reward: one multiply here, one subtract there.  The kernels call this inside the
+// branch that records the download and subtract outside it (a step without a download subtracts 0.0, which changes no
+// bit of any reward), so that the QUALITY instances have no divergent branch the others lack.
+ABR_HD double quality_step(const EpisodeQuality &Q, int64_t n_lanes, int32_t n_rates, int64_t i, int32_t chunk,
+                           int32_t action) {
+    double *q_run = (double *)((char *)Q.base + quality_layout(n_lanes, 1).q_run);      // in front of the ring: no rows in it
+    const double q = Q.u[(int64_t)chunk * n_rates + action];
+    q_run[i] = q_run[i] + q;
+    return Q.wq * q;
+}
+
+// Lane i's episode has ended (called where ledger_append is): the running sum becomes the lane's last one, goes to slot
+// count % rows and into the total, count goes up by one.  rearm: the lane starts its next episode in this same step.
+ABR_HD void quality_close(const EpisodeQuality &Q, int64_t n_lanes, int64_t i, bool rearm) {
+    const QualityLayout lo = quality_layout(n_lanes, Q.rows);
+    char *b = (char *)Q.base;
+    int32_t *count = (int32_t *)(b + lo.count);
+    double *q_run = (double *)(b + lo.q_run), *q_last = (double *)(b + lo.q_last), *total_q = (double *)(b + lo.total_q),
+           *rec_q = (double *)(b + lo.rec_q);
+    const double q = q_run[i];
+    const int32_t c = count[i];
+    const int64_t slot = (int64_t)((uint32_t)c % (uint32_t)Q.rows);
+    count[i] = c + 1;
+    q_last[i] = q;
+    rec_q[slot * n_lanes + i] = q;
+    total_q[i] = total_q[i] + q;
+    if (rearm) q_run[i] = 0.0;
+}
+
+// abr_env_reset abandons lane i's episode: its running sum starts again at zero; nothing else of the blob moves
+ABR_HD void quality_reset(const EpisodeQuality &Q, int64_t n_lanes, int64_t i) {
+    double *q_run = (double *)((char *)Q.base + quality_layout(n_lanes, 1).q_run);
+    q_run[i] = 0.0;
+}
+
 // The trace generator (include/abr_env.h: abr_trace_synth; abr_trace_model has the same layout, abr_env.hip asserts it): a
 // Markov chain over K <= 8 bandwidth regimes.  A sample's philox word w0 fixes where EVERY state would go next, so the
 // sample is a map of the 8 states onto themselves, packed 3 bits per source state, and the chain over a trace is the

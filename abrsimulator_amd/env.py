@@ -13,6 +13,7 @@ import torch
 from . import _lib
 from .episodes import EpisodeSampler
 from .ledger import EpisodeLedger
+from .quality import EpisodeQuality, utility_table
 from .speed import LatencySpeedController
 from .tracesynth import TraceModel
 from ._lib import F64_DIM, F64_ROWS, OBS_DIM, OBS_ROWS
@@ -162,6 +163,50 @@ class BatchedABREnv:
         self.start_offset = None
         self.episode_sampler = None
         self.episode_ledger = None
+        self.quality = None
+
+    def set_quality(self, weight=1.0, utility="identity", rows=None):
+        """Add a video-quality term to the QoE (include/abr_env.h: abr_episode_quality).  The reward and episode_qoe() are
+        pure costs, which the lowest bitrate minimises; while a quality model is installed, every step that completes a
+        download reports reward - weight * u[chunk][action], and every finished episode's sum of u is recorded next to
+        the episode ledger's record (quality.py: EpisodeQuality -- last(), totals(), ring(), records(ledger),
+        per_trace(), per_member()), so that qoe_q = qoe - weight * quality is the episode's score.  utility: "identity"
+        (u = the bitrate: with weight 1 the term BatchedMPCController's objective maximises), "log" (ln(br / lowest),
+        BOLA's), "log_top" (ln(br / highest), the MPC's utility="log"), or a [video_length][n_rates] array; the tables are
+        built on the host in float64 from the per-chunk bitrate table when the MPD has one.  rows: ring slots per lane,
+        default the installed ledger's, else 1.  `weight` may also be an EpisodeQuality built for this env (to continue
+        a restored one).  Returns the EpisodeQuality; env.quality holds it and keeps its tensors alive.
+        set_quality(None) turns the term off: rewards are then what they were.  reset() zeroes the running sums of the
+        lanes it resets and nothing else."""
+        if weight is None:
+            self._check(self.lib.abr_env_set_episode_quality(self._h, None))
+            self.quality = None
+            return None
+        if isinstance(weight, EpisodeQuality):
+            q = weight
+            if q.n_lanes != self.n_lanes or q.device != self.device:
+                raise ValueError(f"the quality model is for {q.n_lanes} lanes on {q.device}, this env has {self.n_lanes} "
+                                 f"on {self.device}")
+            if tuple(q.table.shape) != (self.video_length, self.n_rates):
+                raise ValueError(f"the utility table must be [{self.video_length}][{self.n_rates}]")
+        else:
+            if rows is None:
+                rows = self.episode_ledger.rows if self.episode_ledger is not None else 1
+            br = self.br_table.cpu().numpy() if self.br_table is not None else [self.cfg.ladder[m] for m in range(self.n_rates)]
+            table = utility_table(utility, br, self.video_length)
+            with torch.cuda.device(self.device):
+                q = EpisodeQuality(self.n_lanes, int(rows), weight, table, self.device)
+        nbytes = C.c_size_t()
+        self._check(self.lib.abr_env_quality_bytes(self.n_lanes, q.rows, C.byref(nbytes)))
+        if nbytes.value != q.blob.numel():
+            raise RuntimeError(f"quality layout mismatch: the library wants {nbytes.value} bytes, quality.py laid out "
+                               f"{q.blob.numel()}")
+        st = _lib.EpisodeQuality()
+        st.wq, st.u_dev, st.base_dev, st.rows, st.reserved_ = q.weight, q.table.data_ptr(), q.blob.data_ptr(), q.rows, 0
+        self._check(self.lib.abr_env_set_episode_quality(self._h, C.byref(st)))
+        # the library holds the table's and the blob's addresses: the model must live as long as it is installed
+        self.quality = q
+        return q
 
     def set_episode_ledger(self, rows):
         """Record every finished episode on the device (include/abr_env.h: abr_episode_ledger): while a ledger is
@@ -560,10 +605,17 @@ class BatchedABREnv:
         self._call(self.lib.abr_env_observe_f64, self._h, _lib.ptr(out))
         return {k: out[i] for i, k in enumerate(F64_ROWS)}
 
-    def episode_qoe(self):
-        """calculate_qoe (Simulator.py:79-86) of each lane's (last) finished episode, float64 [N]."""
+    def episode_qoe(self, quality=False):
+        """calculate_qoe (Simulator.py:79-86) of each lane's (last) finished episode, float64 [N].  quality=True (with a
+        quality model installed, set_quality): qoe - weight * the episode's quality sum, the joined record's qoe_q."""
         out = torch.empty(self.n_lanes, dtype=torch.float64, device=self.device)
         self._call(self.lib.abr_env_episode_qoe, self._h, _lib.ptr(out))
+        if quality:
+            if self.quality is None:
+                raise ValueError("episode_qoe(quality=True) needs a quality model (set_quality)")
+            q = torch.empty(self.n_lanes, dtype=torch.float64, device=self.device)
+            self._call(self.lib.abr_env_episode_quality, self._h, _lib.ptr(q))
+            return out - self.quality.weight * q
         return out
 
     def state_view(self):
@@ -602,8 +654,11 @@ class BatchedABREnv:
         """All simulator state is the workspace tensor (the reference keeps it in
         run() locals and cannot checkpoint).  The dict is stamped with the ABI version and the
         workspace size it was taken under; the workspace itself ends in the library's layout tag."""
-        return dict(workspace=self.workspace.clone(), trace_id=self.trace_id, start_offset=self.start_offset,
-                    abi_version=_lib.ABI_VERSION, workspace_bytes=int(self.workspace.numel()))
+        sd = dict(workspace=self.workspace.clone(), trace_id=self.trace_id, start_offset=self.start_offset,
+                  abi_version=_lib.ABI_VERSION, workspace_bytes=int(self.workspace.numel()))
+        if self.quality is not None:           # the running sums are mid-episode state; the key exists only with a model
+            sd["quality"] = self.quality.state_dict()
+        return sd
 
     def load_state_dict(self, sd):
         """Refuses -- before anything is copied -- a state that was taken under another ABI version (the lane-state layout
@@ -618,6 +673,8 @@ class BatchedABREnv:
         if not torch.equal(w[-self.TAG_BYTES:].cpu(), self._tag.cpu()):
             raise ValueError("workspace layout tag mismatch: the checkpoint belongs to another lane count, configuration "
                              "or library version")
+        if sd.get("quality") is not None and self.quality is not None:
+            self.quality.load_state_dict(sd["quality"])        # refuses another shape, weight or table before anything is copied
         self.workspace.copy_(w)
         self.trace_id, self.start_offset = sd["trace_id"], sd["start_offset"]
         # the handle now carries episodes in flight (a freshly built one had none): the speeds /

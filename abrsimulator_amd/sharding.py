@@ -233,6 +233,15 @@ class ShardedABREnv:
     def episode_ledger(self):
         return self.env.episode_ledger
 
+    def set_quality(self, weight=1.0, utility="identity", rows=None):
+        """BatchedABREnv.set_quality on this rank's stepper.  The quality model is per shard, like the ledger: its lanes
+        are this shard's, and nothing is gathered across ranks."""
+        return self.env.set_quality(weight, utility, rows)
+
+    @property
+    def quality(self):
+        return self.env.quality
+
     def reset(self, trace_id=None, start_offset=None, mask=None, sample=False):
         """Default: the deterministic global-lane map (lane_assignment); or this shard's own trace ids / offsets; or, with
         sample=True, the episode sampler's pairs (set_episode_sampler).

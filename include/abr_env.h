@@ -392,6 +392,54 @@ typedef struct abr_episode_ledger {
 int abr_env_ledger_bytes(int32_t n_lanes, int32_t rows, size_t *bytes_out);
 int abr_env_set_episode_ledger(abr_env *env, const abr_episode_ledger *l);
 
+/*
+ * Quality model (ABI 4, additive; BUILD-DEFINED: the reference's calculate_qoe has no such term, its MPC's objective has --
+ * mpc.py:146).  The reward and the episode QoE above are pure costs, which "lowest bitrate, always" minimises.  While a
+ * quality model is installed the env kernels also score what was watched: a weight wq, a caller-owned device table u,
+ * float64 [video_length][n_rates], computed by the caller (no device log, as abr_rule_config.utility_dev), and a
+ * caller-owned blob.
+ *
+ * PER STEP.  At a step whose download completed -- the step that appends to previous_bandwidths / previous_bitrates --
+ * with c the downloaded chunk and a the action:  q = u[c][a];  q_run[i] = q_run[i] + q;  and the step's reward is
+ * (float)(rew - wq * q), where rew is the float64 reward expression without a model, in its order: then one multiply, one
+ * subtract, one rounding to float32, never fused.  The reward stays a cost: quality lowers it.  A step without a completed
+ * download (ABR_DONE_BADACT; a time-out in mid-download) adds nothing and reports the reward it reports without a model.
+ *
+ * PER EPISODE.  The blob follows the episode ledger's RULE: it is written exactly when the kernels write the episode's QoE
+ * terms (ABR_DONE_EPISODE or ABR_DONE_TIMEOUT, every launch kind, implementations 0, 1, 2, 3, 5).  With Q = q_run[i]:
+ *   q_last[i] = Q;  rec_q[count[i] % rows][i] = Q;  total_q[i] = total_q[i] + Q;  count[i] = count[i] + 1;
+ * and, if the lane is re-armed at that step (auto_reset, ABR_DONE_EPISODE), q_run[i] = 0.0.  abr_env_reset sets q_run of
+ * the lanes it resets (all, or the masked ones) to 0.0 and touches nothing else of the blob.
+ *
+ * The blob, abr_env_quality_bytes(n_lanes, rows) bytes at a 256-byte aligned address: struct-of-arrays with row stride
+ * n_lanes; every region starts at the next multiple of 256 bytes after the previous one, in this order:
+ *   count   int32   [n_lanes]         episodes recorded for the lane since the blob was zeroed
+ *   q_run   float64 [n_lanes]         the running sum of the episode in flight (mid-episode state)
+ *   q_last  float64 [n_lanes]         the sum of the lane's last finished episode
+ *   total_q float64 [n_lanes]         running sum over ALL recorded episodes of the lane, added in episode order
+ *   rec_q   float64 [rows][n_lanes]   the sum of the record in each ring slot
+ * An all-zero blob is empty.  It keeps its own count, so it needs no ledger; cleared together with a ledger of the same
+ * rows, the slots of the two coincide.  The ledger's layout, its qoe field and abr_env_episode_qoe are what they are without
+ * a model, bit for bit: the combined figure is qoe - wq * Q, formed by whoever reads both.
+ *
+ * abr_env_quality_bytes is pure arithmetic (ABR_E_INVALID: n_lanes < 1, rows < 1, NULL bytes_out).
+ * abr_env_set_episode_quality copies the struct (q == NULL: off).  Refused with ABR_E_INVALID before anything is stored: wq
+ * not finite, u_dev NULL or not 8-byte aligned, base_dev NULL or not 256-byte aligned, rows < 1.  The table's values are
+ * the caller's: a NaN in u propagates.  u_dev and base_dev must stay valid while installed.  abr_env_episode_quality copies
+ * q_last to q_out_dev, float64 [n_lanes], on the stream (ABR_E_INVALID without a model).  The diagnostic pipelines 4, 6
+ * and 7 refuse a launch with a quality model (ABR_E_UNSUPPORTED), as they do a ledger.
+ */
+typedef struct abr_episode_quality {
+    double        wq;           /* finite */
+    const double *u_dev;        /* caller-owned device float64 [video_length][n_rates] */
+    void         *base_dev;     /* caller-owned, 256-B aligned, >= abr_env_quality_bytes(); all-zero bytes = empty */
+    int32_t       rows;         /* ring slots per lane, >= 1 */
+    int32_t       reserved_;    /* 0 */
+} abr_episode_quality;          /* 32 bytes */
+int abr_env_quality_bytes(int32_t n_lanes, int32_t rows, size_t *bytes_out);
+int abr_env_set_episode_quality(abr_env *env, const abr_episode_quality *q);
+int abr_env_episode_quality(abr_env *env, double *q_out_dev, void *stream);
+
 /* Full float64 observation, [ABR_F64_DIM][n_lanes]. */
 int abr_env_observe_f64(abr_env *env, double *out_dev, void *stream);
 
