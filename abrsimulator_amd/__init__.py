@@ -14,6 +14,7 @@ from .ledger import EpisodeLedger
 from .quality import EpisodeQuality
 from .mpc import BatchedMPCController, EnvPlayer
 from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController
+from .search import HindsightSearch
 from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
 from .speed import LatencySpeedController
@@ -26,6 +27,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
+           "HindsightSearch", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

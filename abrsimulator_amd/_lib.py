@@ -215,6 +215,9 @@ SYMBOLS = [
     ("abr_env_episode_qoe", C.c_int, [_P, _P, _P]),
     ("abr_env_observe_f64", C.c_int, [_P, _P, _P]),
     ("abr_env_get_state", C.c_int, [_P, C.POINTER(StateView)]),
+    ("abr_env_fork_scratch_bytes", C.c_int, [_P, C.c_int64, C.POINTER(C.c_size_t)]),
+    ("abr_env_fork", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P, _P]),
+    ("abr_beam_select", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_mpc_select", C.c_int, [C.POINTER(MpcConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.c_int64, _P]),
     ("abr_mpc_scratch_bytes", C.c_int, [C.POINTER(MpcConfig), C.c_int64, C.POINTER(C.c_size_t)]),

@@ -1889,6 +1889,143 @@ extern "C" int abr_env_observe_f64(abr_env *env, double *out_dev, void *stream) 
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// lane fork (include/abr_env.h: abr_env_fork): gather every source column into the scratch, then scatter
+// ---------------------------------------------------------------------------
+// One thread per (pair, row chunk): x runs over the pairs, so a wave reads 64 gathered columns and writes 64 adjacent
+// scratch elements per row (the scatter the other way round); y is the row chunk, uniform per workgroup.
+template <bool SCATTER>
+__global__ __launch_bounds__(256) void fork_kernel(abrx::ForkTable T, const int32_t *__restrict__ src,
+                                                   const int32_t *__restrict__ dst, char *__restrict__ scratch) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    abrx::fork_move(T, (int32_t)blockIdx.y, i, src, dst, scratch, SCATTER);
+}
+
+static int fork_check_args(const int32_t *src_dev, int64_t count, const void *scratch_dev) {
+    if (!src_dev) return fail(ABR_E_INVALID, "fork: src_dev is NULL");
+    if (count < 0) return fail(ABR_E_INVALID, "fork: count must be >= 0, got %lld", (long long)count);
+    if (count > INT32_MAX) return fail(ABR_E_INVALID, "fork: count %lld is more than 2^31 - 1 pairs", (long long)count);
+    if (count > 0 && (!scratch_dev || (uintptr_t)scratch_dev % 256))
+        return fail(ABR_E_INVALID, "fork: scratch_dev must be non-NULL and 256-byte aligned");
+    return ABR_OK;
+}
+
+extern "C" int abr_env_fork_scratch_bytes(abr_env *env, int64_t count, size_t *bytes_out) {
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (count < 0) return fail(ABR_E_INVALID, "fork: count must be >= 0, got %lld", (long long)count);
+    if (count > INT32_MAX) return fail(ABR_E_INVALID, "fork: count %lld is more than 2^31 - 1 pairs", (long long)count);
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    abrx::ForkTable T;
+    *bytes_out = abrx::fork_table_init(T, env->p.video_length, env->p.n_lanes, count);
+    return ABR_OK;
+}
+
+extern "C" int abr_env_fork(abr_env *env, const int32_t *src_dev, const int32_t *dst_dev, int64_t count, void *scratch_dev,
+                            size_t scratch_bytes, float *obs_dev, void *stream) {
+    // the arguments before the handle: a CPU test drives these refusals with env == NULL
+    int rc = fork_check_args(src_dev, count, scratch_dev);
+    if (rc) return rc;
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (env->impl == 4 || env->impl == 6 || env->impl == 7)
+        return fail(ABR_E_UNSUPPORTED, "fork: the diagnostic pipelines (impl 4, 6, 7) keep lane state outside the workspace");
+    // per-lane speeds and schedules are caller-owned columns that belong to the slot, not to the lane's state; a constant
+    // speed and a speed rule (whose per-lane state is in the workspace) are fine
+    const bool lane_speeds = (env->p.lane_speeds && env->p.speed_rows != abrx::kSpeedRowsRule) ||
+                             (env->speeds_dirty && env->pending_speeds && !env->pending_rule_on);
+    if (lane_speeds)
+        return fail(ABR_E_UNSUPPORTED, "fork: per-lane speeds or a speed schedule are in force or pending: their columns "
+                    "belong to the slot and are not copied");
+    abrx::ForkTable T;
+    const EnvParams &p = env->p;
+    const size_t need = abrx::fork_table_init(T, p.video_length, p.n_lanes, count);
+    if (scratch_bytes < need) return fail(ABR_E_INVALID, "fork: scratch has %zu bytes, %lld pairs need %zu", scratch_bytes,
+                                          (long long)count, need);
+    if (count == 0) return ABR_OK;
+    T.r[abrx::kForkF64].base = (char *)p.buf;             // the 8 float64 rows, buf first (abr_env_create)
+    T.r[abrx::kForkI64].base = (char *)p.sumk;
+    T.r[abrx::kForkI32].base = (char *)p.k;               // the 15 int32 rows, k first
+    T.r[abrx::kForkU8].base = (char *)p.flags;            // flags, done
+    T.r[abrx::kForkActionHist].base = (char *)p.action_hist;
+    T.r[abrx::kForkBwHist].base = (char *)p.bw_hist;
+    T.r[abrx::kForkEpTerms].base = (char *)p.ep_qoe_terms;
+    T.r[abrx::kForkMpcAction].base = (char *)env->mpc_action;
+    if (env->quality.base)
+        T.r[abrx::kForkQRun].base = (char *)env->quality.base + abrx::quality_layout(p.n_lanes, 1).q_run;
+    T.r[abrx::kForkObs].base = (char *)obs_dev;
+    const dim3 grid((unsigned)((count + 255) / 256), (unsigned)T.chunks), block(256);
+    hipLaunchKernelGGL(fork_kernel<false>, grid, block, 0, (hipStream_t)stream, T, src_dev, dst_dev, (char *)scratch_dev);
+    hipLaunchKernelGGL(fork_kernel<true>, grid, block, 0, (hipStream_t)stream, T, src_dev, dst_dev, (char *)scratch_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// ---------------------------------------------------------------------------
+// beam selection (include/abr_env.h: abr_beam_select): per-group top-B by counting rank in LDS
+// ---------------------------------------------------------------------------
+constexpr int kBeamMaxSlots = 1024;
+// One workgroup per group of S = beam * n_rates consecutive lanes, one thread per slot (blockDim = S rounded up to a wave).
+// Every thread reads every key: S broadcast LDS reads per thread, S^2 compares per group, no sort network and no atomics, so
+// the ranks are a pure function of the keys.
+__global__ __launch_bounds__(kBeamMaxSlots) void beam_select_kernel(
+    int32_t S, int32_t n_rates, double wl, const double *__restrict__ R_in, const float *__restrict__ reward,
+    const double *__restrict__ lat, const uint8_t *__restrict__ done, const uint8_t *__restrict__ valid_in,
+    const double *__restrict__ key_override, int32_t *__restrict__ src_out, double *__restrict__ R_out,
+    uint8_t *__restrict__ valid_out) {
+    __shared__ double s_key[kBeamMaxSlots], s_R[kBeamMaxSlots];
+    __shared__ int32_t s_slot[kBeamMaxSlots];       // slot of the candidate with rank r, or -1
+    __shared__ uint8_t s_valid[kBeamMaxSlots];
+    const int32_t s = (int32_t)threadIdx.x;
+    const int64_t base = (int64_t)blockIdx.x * S;
+    double key = 0.0;
+    bool valid = false;
+    if (s < S) {
+        const int64_t i = base + s;
+        const double Rn = abrx::beam_r_new(R_in[i], reward[i]);
+        key = key_override ? key_override[i] : abrx::beam_key(Rn, wl, lat[i]);
+        valid = abrx::beam_valid(valid_in[i], done[i], key);
+        s_key[s] = key; s_R[s] = Rn; s_valid[s] = valid ? 1 : 0; s_slot[s] = -1;
+    }
+    __syncthreads();
+    if (valid) {
+        int32_t rank = 0;
+        for (int32_t t = 0; t < S; t++)
+            rank += (s_valid[t] && abrx::beam_before(s_key[t], t, key, s)) ? 1 : 0;
+        s_slot[rank] = s;                           // ranks of valid candidates are distinct and < S
+    }
+    __syncthreads();
+    if (s < S) {
+        const int32_t c = s_slot[s / n_rates];      // s / n_rates < beam <= S
+        src_out[base + s] = c >= 0 ? (int32_t)(base + c) : -1;
+        R_out[base + s] = c >= 0 ? s_R[c] : 0.0;
+        valid_out[base + s] = c >= 0 ? 1 : 0;
+    }
+}
+
+extern "C" int abr_beam_select(int32_t n_groups, int32_t beam, int32_t n_rates, double wl, const double *R_in_dev,
+                               const float *reward_dev, const double *lat_dev, const uint8_t *done_dev,
+                               const uint8_t *valid_in_dev, const double *key_override_dev, int32_t *src_out_dev,
+                               double *R_out_dev, uint8_t *valid_out_dev, void *stream) {
+    if (n_groups < 0) return fail(ABR_E_INVALID, "beam select: n_groups must be >= 0, got %d", n_groups);
+    if (beam < 1) return fail(ABR_E_INVALID, "beam select: beam must be >= 1, got %d", beam);
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES)
+        return fail(ABR_E_INVALID, "beam select: n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    if ((int64_t)beam * n_rates > kBeamMaxSlots)
+        return fail(ABR_E_UNSUPPORTED, "beam select: beam %d x n_rates %d is more than %d slots per group", beam, n_rates,
+                    kBeamMaxSlots);
+    if ((int64_t)n_groups * beam * n_rates > INT32_MAX)
+        return fail(ABR_E_INVALID, "beam select: n_groups x beam x n_rates is more than 2^31 - 1 lanes");
+    if (!R_in_dev || !reward_dev || !done_dev || !valid_in_dev || !src_out_dev || !R_out_dev || !valid_out_dev)
+        return fail(ABR_E_INVALID, "beam select: NULL device pointer");
+    if (!lat_dev && !key_override_dev) return fail(ABR_E_INVALID, "beam select: lat_dev is NULL and there is no key_override");
+    if (n_groups == 0) return ABR_OK;
+    const int32_t S = beam * n_rates;
+    hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)n_groups), dim3((unsigned)((S + 63) / 64 * 64)), 0,
+                       (hipStream_t)stream, S, n_rates, wl, R_in_dev, reward_dev, lat_dev, done_dev, valid_in_dev,
+                       key_override_dev, src_out_dev, R_out_dev, valid_out_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
 #ifdef ABR_SPLIT_STAMPS
 extern "C" int abr_debug_read_stamps(unsigned long long *out32, int reset) {
     (void)hipDeviceSynchronize();

@@ -1661,5 +1661,129 @@ ABR_HD double trace_value(const TraceModel &m, uint32_t s, uint32_t w1, uint32_t
     return (uint64_t)w2 < thr ? 0.0 : x;
 }
 
+// Lane fork (include/abr_env.h: abr_env_fork): lane dst[i] becomes a copy of lane src[i] as it was before the call.  All
+// lane state is struct-of-arrays with row stride n_lanes, so a lane is one COLUMN of every region below, and the fork is a
+// column gather into the caller's scratch ([row][pair]: adjacent pairs write adjacent elements) followed by a column scatter
+// -- two launches, so that src and dst may overlap in any way.  The row table is this one definition: abr_env.hip fills it
+// from the handle, tests/native/fork_harness.cpp from a host byte array, and both run fork_move below.
+constexpr int kForkRegions = 10;
+enum ForkRegionId { kForkF64 = 0, kForkI64, kForkI32, kForkU8, kForkActionHist, kForkBwHist, kForkEpTerms, kForkMpcAction,
+                    kForkQRun, kForkObs };
+constexpr int kForkRowsPerThread = 8;      // a thread moves up to this many rows of one region for one pair
+struct ForkRegion {
+    char *base;                    // element (row, lane) at base + (row * stride + lane) * elem; nullptr: region absent
+    int32_t elem;                  // 8, 4 or 1 bytes: the region's own element, the widest access its alignment allows (a u8
+                                   // row starts at a multiple of n_lanes, which is odd for an odd lane count)
+    int32_t rows;
+    int64_t stride;                // elements between two rows: n_lanes for every region
+    int64_t scratch;               // byte offset of the region's [rows][count] image in the scratch
+};
+struct ForkTable {
+    ForkRegion r[kForkRegions];
+    int64_t n_lanes, count;
+    int32_t chunks;                // row chunks over all regions: the y extent of the launch
+    int32_t reserved_;
+};
+// elem and rows of every region for episodes of V chunks; q_run and obs are reserved in the scratch whether present or not
+ABR_HD void fork_region_shape(int id, int32_t V, int32_t &elem, int32_t &rows) {
+    switch (id) {
+    case kForkF64: elem = 8; rows = 8; break;
+    case kForkI64: elem = 8; rows = 1; break;
+    case kForkI32: elem = 4; rows = 15; break;
+    case kForkU8: elem = 1; rows = 2; break;
+    case kForkActionHist: elem = 1; rows = V; break;
+    case kForkBwHist: elem = 8; rows = V; break;
+    case kForkEpTerms: elem = 8; rows = 4; break;
+    case kForkMpcAction: elem = 4; rows = 1; break;
+    case kForkQRun: elem = 8; rows = 1; break;
+    default: elem = 4; rows = 8; break;          // kForkObs: float32 [ABR_OBS_DIM][n_lanes]
+    }
+}
+// Shapes, scratch offsets (each region at the next multiple of 256 bytes) and the chunk count; bases are the caller's to
+// set.  Returns the scratch bytes `count` pairs need.
+ABR_HD size_t fork_table_init(ForkTable &T, int32_t V, int64_t n_lanes, int64_t count) {
+    size_t o = 0;
+    int32_t chunks = 0;
+    for (int id = 0; id < kForkRegions; id++) {
+        ForkRegion &g = T.r[id];
+        fork_region_shape(id, V, g.elem, g.rows);
+        g.base = nullptr; g.stride = n_lanes; g.scratch = (int64_t)o;
+        o = ledger_align(o + (size_t)g.rows * (size_t)count * (size_t)g.elem);
+        chunks += (g.rows + kForkRowsPerThread - 1) / kForkRowsPerThread;
+    }
+    T.n_lanes = n_lanes; T.count = count; T.chunks = chunks; T.reserved_ = 0;
+    return o;
+}
+// the index guard: a pair moves only when both of its lanes exist (src -1 is the documented "leave dst alone")
+ABR_HD bool fork_pair_ok(int64_t s, int64_t d, int64_t n_lanes) { return s >= 0 && s < n_lanes && d >= 0 && d < n_lanes; }
+
+// E: the element in memory; R: what a thread holds it in (a byte rides in a 32-bit register, so that the loads of a chunk
+// need no packing between them and stay in flight together)
+template <typename E, typename R>
+ABR_HD void fork_rows(const ForkRegion &g, int32_t r0, int32_t r1, int64_t lane, int64_t i, int64_t count, char *scratch,
+                      bool scatter) {
+    E *col = (E *)g.base + lane;
+    E *img = (E *)(scratch + g.scratch) + i;
+    R v[kForkRowsPerThread];
+    // all loads of the chunk first, then all stores: up to kForkRowsPerThread independent accesses in flight per thread
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int q = 0; q < kForkRowsPerThread; q++)
+        if (r0 + q < r1) v[q] = scatter ? img[(int64_t)(r0 + q) * count] : col[(int64_t)(r0 + q) * g.stride];
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int q = 0; q < kForkRowsPerThread; q++)
+        if (r0 + q < r1) {
+            if (scatter) col[(int64_t)(r0 + q) * g.stride] = (E)v[q]; else img[(int64_t)(r0 + q) * count] = (E)v[q];
+        }
+}
+// One thread's work: pair i, row chunk `chunk` (the same for a whole workgroup, so the region search is wave-uniform).
+// scatter == false: the source lane's elements go to the scratch; true: the scratch's go to the destination lane.
+ABR_HD void fork_move(const ForkTable &T, int32_t chunk, int64_t i, const int32_t *__restrict__ src,
+                      const int32_t *__restrict__ dst, char *scratch, bool scatter) {
+    if (i < 0 || i >= T.count || chunk < 0 || chunk >= T.chunks) return;
+    const int64_t s = src[i], d = dst ? (int64_t)dst[i] : i;
+    if (!fork_pair_ok(s, d, T.n_lanes)) return;
+    // the region of this chunk, by a select chain over a fully unrolled loop: the table arrives by value (kernel
+    // arguments), and indexing it with a run-time value would copy it to scratch memory first
+    ForkRegion g = T.r[0];
+    int32_t c = chunk;
+    bool found = false;
+#if defined(__clang__)
+#pragma unroll
+#endif
+    for (int id = 0; id < kForkRegions; id++) {
+        const int32_t n = (T.r[id].rows + kForkRowsPerThread - 1) / kForkRowsPerThread;
+        const bool here = !found && c < n;
+        g.base = here ? T.r[id].base : g.base; g.elem = here ? T.r[id].elem : g.elem; g.rows = here ? T.r[id].rows : g.rows;
+        g.stride = here ? T.r[id].stride : g.stride; g.scratch = here ? T.r[id].scratch : g.scratch;
+        c = (found || here) ? c : c - n;
+        found = found || here;
+    }
+    if (!found || !g.base) return;
+    const int32_t r0 = c * kForkRowsPerThread;
+    const int32_t r1 = r0 + kForkRowsPerThread < g.rows ? r0 + kForkRowsPerThread : g.rows;
+    const int64_t lane = scatter ? d : s;
+    if (g.elem == 8) fork_rows<uint64_t, uint64_t>(g, r0, r1, lane, i, T.count, scratch, scatter);
+    else if (g.elem == 4) fork_rows<uint32_t, uint32_t>(g, r0, r1, lane, i, T.count, scratch, scatter);
+    else fork_rows<uint8_t, uint32_t>(g, r0, r1, lane, i, T.count, scratch, scatter);
+}
+
+// Beam selection (include/abr_env.h: abr_beam_select): the score of one candidate slot and the order of two of them.  All
+// float64, unfused.  R_new is the running sum of the float32 step rewards in step order; the key adds the latency term the
+// step reward leaves out, or is the caller's.
+constexpr uint8_t kBeamDoneEpisode = 0x1;  // ABR_DONE_EPISODE: the one done bit a live candidate may carry
+ABR_HD double beam_r_new(double R_in, float reward) { return R_in + (double)reward; }
+ABR_HD double beam_key(double R_new, double wl, double lat) { return R_new + wl * lat; }
+ABR_HD bool beam_valid(uint8_t valid_in, uint8_t done, double key) {
+    return valid_in != 0 && !(done & (uint8_t)~kBeamDoneEpisode) && key == key;
+}
+// candidate t ranks before candidate s: the smaller key, ties (-0.0 and +0.0 among them) by the smaller slot
+ABR_HD bool beam_before(double key_t, int32_t t, double key_s, int32_t s) {
+    return key_t < key_s || (key_t == key_s && t < s);
+}
+
 }  // namespace abrx
 #endif

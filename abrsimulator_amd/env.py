@@ -647,8 +647,59 @@ class BatchedABREnv:
                 self._view(v.buffer_level, torch.float64, (N,)), self._view(v.hist_n, torch.float64, (N,)),
                 self._view(v.hist_sum_inv, torch.float64, (N,)), self._view(v.done, torch.uint8, (N,)))
 
+    # -- fork ---------------------------------------------------------------
+    def fork(self, src, dst=None, update_pairs=True):
+        """Copy lanes on the device (include/abr_env.h: abr_env_fork): lane dst[i] becomes a byte-for-byte copy of lane
+        src[i] as it was before the call -- state rows, action and bandwidth history, the quality model's running sum and
+        this env's obs columns -- and continues exactly as src[i] would have.  src, dst: int32 tensors of equal length;
+        src[i] = -1 (or any index outside the lanes, on either side) skips the pair; dst=None means dst[i] = i.  src may
+        repeat a lane and the two may overlap in any way (a permutation included); dst values must be distinct.  The
+        ledger's and the quality model's records stay with the slot.  self.trace_id / self.start_offset follow by tensor
+        indexing; controller-side state (a RobustMPC state, a GRU's hidden rows) is the caller's: t[:, dst] = t[:, src].
+        update_pairs=False leaves the two bookkeeping tensors alone (a caller whose copies stay on their source's pair).
+        Enqueued on the current stream; nothing synchronises.  Refused while per-lane speeds or a schedule are set."""
+        s = torch.as_tensor(src, device=self.device)
+        s = (s if s.dtype == torch.int32 else s.to(torch.int32)).contiguous()
+        if s.dim() != 1:
+            raise ValueError("src must be a 1-d tensor of lane indices")
+        d = None
+        if dst is not None:
+            d = torch.as_tensor(dst, device=self.device)
+            d = (d if d.dtype == torch.int32 else d.to(torch.int32)).contiguous()
+            if d.shape != s.shape:
+                raise ValueError(f"dst must have src's shape {tuple(s.shape)}, got {tuple(d.shape)}")
+        count = int(s.numel())
+        if count == 0:
+            return
+        need = C.c_size_t()
+        self._check(self.lib.abr_env_fork_scratch_bytes(self._h, count, C.byref(need)))
+        scratch = getattr(self, "_fork_scratch", None)
+        if scratch is None or scratch.numel() < need.value:
+            with torch.cuda.device(self.device):
+                scratch = self._fork_scratch = torch.empty(need.value, dtype=torch.uint8, device=self.device)
+        self._call(self.lib.abr_env_fork, self._h, _lib.ptr(s), _lib.ptr(d), count, _lib.ptr(scratch),
+                   C.c_size_t(scratch.numel()), _lib.ptr(self.obs))
+        if not update_pairs or self.trace_id is None or self.start_offset is None:
+            return
+        # the same pairs on the two bookkeeping tensors (fresh tensors: the old ones may be the caller's)
+        si = s.long()
+        ok = (si >= 0) & (si < self.n_lanes)
+        si = si.clamp(0, self.n_lanes - 1)
+        if d is None and count == self.n_lanes:                 # every lane names its source: one gather per tensor
+            self.trace_id = torch.where(ok, self.trace_id[si], self.trace_id)
+            self.start_offset = torch.where(ok, self.start_offset[si], self.start_offset)
+            return
+        di = torch.arange(count, device=self.device) if d is None else d.long()
+        ok &= (di >= 0) & (di < self.n_lanes)
+        di = torch.where(ok, di, self.n_lanes)                  # skipped pairs land in a spare slot
+        for name in ("trace_id", "start_offset"):
+            t = getattr(self, name)
+            new = torch.cat([t, t[:1]])
+            new[di] = t[si]
+            setattr(self, name, new[:self.n_lanes].contiguous())
+
     # -- checkpoint / resume ------------------------------------------------
-    TAG_BYTES = 256     # the workspace's last 256 bytes: its layout tag (include/abr_env.h, ABI 4)
+    TAG_BYTES = 256    # the workspace's last 256 bytes: its layout tag (include/abr_env.h, ABI 4)
 
     def state_dict(self):
         """All simulator state is the workspace tensor (the reference keeps it in

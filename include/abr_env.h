@@ -458,6 +458,61 @@ typedef struct abr_env_state_view {
 } abr_env_state_view;
 int abr_env_get_state(abr_env *env, abr_env_state_view *view_out);
 
+/*
+ * Lane fork (ABI 4, additive; BUILD-DEFINED: the reference runs one player).  All lane state between launches is the
+ * workspace, shared bit for bit by every implementation, so "lane d continues as lane s would have" is a copy of lane s's
+ * column of every per-lane region.  For every i < count with 0 <= src[i] < n_lanes and 0 <= dst[i] < n_lanes, lane dst[i]
+ * becomes a byte-for-byte copy of lane src[i] AS IT WAS BEFORE THE CALL; every other pair is skipped (src[i] = -1 is the
+ * documented "leave dst[i] alone").  src may repeat a lane; src and dst may overlap in any way, a permutation cycle
+ * included: the call is two kernels on `stream`, a gather of every source column into the caller's scratch ([row][i]) and a
+ * scatter from it.  dst values must be distinct: a duplicate makes one of its writers win, row by row, and never faults.
+ * dst_dev == NULL means dst[i] = i.  src_dev / dst_dev: device int32 [count].  Nothing synchronises.
+ *
+ * Copied: the 8 float64, 1 int64, 15 int32 and 2 uint8 state rows (the per-lane state of a speed rule among them),
+ * action_hist, bw_hist, the QoE terms of the last finished episode, the lane's slot of abr_env_step_mpc's action scratch;
+ * the installed quality model's q_run column (mid-episode state); and the same columns of obs_dev, float32
+ * [ABR_OBS_DIM][n_lanes], when it is not NULL.  NOT copied: the tick tables and the predictor scratch; the episode ledger's
+ * and the quality blob's count, totals, q_last and rings (the slot's history of finished episodes); a speed rule's log.
+ * The episode number IS copied, and so are the trace id and start offset: the copy runs the source's episode.  Under an
+ * episode sampler a re-arm is keyed by the GLOBAL LANE the copy lives in and by that copied episode number, so source and
+ * copy are identical up to their next re-arm and draw different pairs there.  Controller-side state the caller owns (a
+ * RobustMPC state, a GRU's hidden rows) is the caller's to move, with the same src / dst.
+ *
+ * abr_env_fork_scratch_bytes is pure arithmetic (video_length and count): for each region in the order above, then q_run,
+ * then obs -- reserved whether present or not -- rows * count * element bytes, rounded up to a multiple of 256.
+ * ABR_E_INVALID, the arguments before the handle: NULL src_dev, count < 0 or > 2^31 - 1, count > 0 with scratch_dev NULL or
+ * not 256-byte aligned, a NULL handle, scratch_bytes too small.  ABR_E_UNSUPPORTED: per-lane speeds or a speed schedule in
+ * force or pending (abr_env_set_lane_speeds / _speed_schedule: their columns are caller-owned and belong to the slot; a
+ * constant speed and a speed rule are fine), and the diagnostic pipelines 4, 6 and 7.
+ */
+int abr_env_fork_scratch_bytes(abr_env *env, int64_t count, size_t *bytes_out);
+int abr_env_fork(abr_env *env, const int32_t *src_dev, const int32_t *dst_dev, int64_t count, void *scratch_dev,
+                 size_t scratch_bytes, float *obs_dev, void *stream);
+
+/*
+ * Beam selection (ABI 4, additive): per-group top-`beam` of beam * n_rates candidates, for a search that keeps `beam`
+ * survivors per group and tries every rate on each (abr_env_fork moves the survivors).  Lanes are grouped as slots = beam *
+ * n_rates consecutive lanes per group, slots <= 1024; slot s = r * n_rates + m means "survivor r takes action m".  Group g
+ * owns lanes [g * slots, (g + 1) * slots); lanes beyond n_groups * slots are neither read nor written.  Per candidate slot
+ * s of a group, in float64, never fused:
+ *   R_new = R_in[s] + (double)reward[s]          the running sum of the float32 step rewards, in step order
+ *   key   = key_override ? key_override[s] : R_new + wl * lat[s]
+ *   valid = valid_in[s] != 0 && !(done[s] & ~ABR_DONE_EPISODE) && key == key     (NaN, timed-out and frozen lanes drop out)
+ *   rank  = #{ valid t : key[t] < key[s]  or  (key[t] == key[s] and t < s) }
+ * and for every slot s = r * n_rates + m:  src_out[s] = the LANE of the valid candidate with rank r, or -1 when fewer than
+ * r + 1 candidates are valid;  R_out[s] = that candidate's R_new (0.0 with none);  valid_out[s] = src_out[s] >= 0.
+ * The key adds the latency term the step reward leaves out: lat is abr_env_observe_f64's ABR_F64_AVERAGE_LATENCY row.
+ * Smaller keys win (the reward is a cost); -0.0 and +0.0 tie and the smaller slot wins.  One workgroup per group, ranks by
+ * counting in LDS: slots^2 compares, deterministic.  All arrays are device memory of at least n_groups * slots elements:
+ * R_in, lat, key_override (nullable), R_out float64; reward float32; done, valid_in, valid_out uint8; src_out int32.
+ * Outputs must not alias inputs.  ABR_E_INVALID: n_groups < 0, beam < 1, n_rates outside 1..ABR_MAX_RATES, a NULL array
+ * (lat_dev may be NULL with a key_override); ABR_E_UNSUPPORTED: beam * n_rates > 1024.  n_groups == 0 launches nothing.
+ */
+int abr_beam_select(int32_t n_groups, int32_t beam, int32_t n_rates, double wl, const double *R_in_dev,
+                    const float *reward_dev, const double *lat_dev, const uint8_t *done_dev, const uint8_t *valid_in_dev,
+                    const double *key_override_dev, int32_t *src_out_dev, double *R_out_dev, uint8_t *valid_out_dev,
+                    void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* MPC lookahead                                                            */
 /* ---------------------------------------------------------------------- */
