@@ -1758,6 +1758,21 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
     return ABR_OK;
 }
 
+// Row s of a [n_steps][words][n_lanes] output slab (NULL stays NULL): a rollout that takes its decisions one launch at a
+// time (mpc_rollout, policy_rollout) hands each launch its own row.
+template <class T>
+static inline T *slab_row(T *base, int32_t s, int64_t words, int64_t n_lanes) {
+    return base ? base + (int64_t)s * words * n_lanes : nullptr;
+}
+
+// The env half of decision s of such a rollout: K1 MODE 1 on `actions` [n_lanes], into row s of obs / rew / dn.
+static int step_row(const abr_env *env, int impl, hipStream_t st, int32_t s, const int32_t *actions, float *obs, float *rew,
+                    uint8_t *dn) {
+    const int64_t N = env->p.n_lanes;
+    return launch_env<1>(env, impl, st, actions, slab_row(obs, s, ABR_OBS_DIM, N), slab_row(rew, s, 1, N),
+                         slab_row(dn, s, 1, N), nullptr, 1, 0ull);
+}
+
 extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
                              const int32_t *start_offset_dev, const uint8_t *lane_mask_dev,
                              float *obs_out_dev, void *stream) {
@@ -1788,8 +1803,8 @@ extern "C" int abr_env_step(abr_env *env, const int32_t *actions_dev, float *obs
                             float *reward_out_dev, uint8_t *done_out_dev, void *stream) {
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if (!actions_dev) return fail(ABR_E_INVALID, "actions_dev is NULL");
-    return launch_env<1>(env, launch_impl<1>(env, 1), (hipStream_t)stream, actions_dev, obs_out_dev, reward_out_dev,
-                         done_out_dev, nullptr, 1, 0ull);
+    return step_row(env, launch_impl<1>(env, 1), (hipStream_t)stream, 0, actions_dev, obs_out_dev, reward_out_dev,
+                    done_out_dev);
 }
 
 // n_steps fused decisions per lane under the built-in random policy
@@ -2882,12 +2897,9 @@ static int mpc_rollout(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_ro
     void *scratch = robust && robust->scratch_dev ? robust->scratch_dev : env->mpc_scratch;
     const int impl = launch_impl<1>(env, 1);
     for (int32_t s = 0; s < n_steps; s++) {
-        p.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
+        p.action_out = actions_out_dev ? slab_row(actions_out_dev, s, 1, N) : env->mpc_action;
         if ((rc = launch_mpc_select(p, st, scratch, robust, e.bw_hist, N))) return rc;
-        rc = launch_env<1>(env, impl, st, p.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
+        if ((rc = step_row(env, impl, st, s, p.action_out, obs_out_dev, reward_out_dev, done_out_dev))) return rc;
     }
     return ABR_OK;
 }
@@ -3314,7 +3326,7 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(
     }
 }
 
-// the struct alone (before the handle): shape, window, reserved fields, pointers, threshold
+// the struct's shape alone: the size query checks no more, the entries go on to policy_fields (before the handle)
 static int validate_policy_shape(const abr_policy *pol) {
     if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
     if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
@@ -3330,20 +3342,9 @@ static int validate_policy_shape(const abr_policy *pol) {
     return ABR_OK;
 }
 
-static int validate_policy(const abr_policy *pol) {
-    int rc = validate_policy_shape(pol);
-    if (rc) return rc;
-    for (int32_t r : pol->reserved_)
-        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
-    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
-        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
-    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
-    if (pol->explore_threshold > (1ull << 32))
-        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
-    return ABR_OK;
-}
-
-static size_t policy_weights_bytes(const abr_policy *pol, int32_t M) {
+// an MLP's blob, which abr_policy and abr_policy_mx lay out alike: per layer W [out][in], then b [out]
+template <class Pol>
+static size_t policy_weights_bytes(const Pol *pol, int32_t M) {
     size_t in = 4 + (size_t)pol->window + (size_t)M, words = 0;
     for (int l = 0; l <= pol->n_hidden; l++) {
         const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
@@ -3370,216 +3371,79 @@ extern "C" int abr_policy_weights_bytes(const abr_policy *pol, int32_t n_rates, 
     return ABR_OK;
 }
 
-// after the handle: the blob's size for the environment's n_rates
-static int policy_args(const abr_env *env, const abr_policy *pol, PolicyArgs *a) {
-    const int32_t M = env->p.n_rates;
-    const size_t want = policy_weights_bytes(pol, M);
-    if (pol->weights_bytes != want)
-        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
-    *a = PolicyArgs{};
-    a->net.window = pol->window; a->net.n_hidden = pol->n_hidden;
-    a->net.w0 = pol->n_hidden >= 1 ? pol->width[0] : 0; a->net.w1 = pol->n_hidden >= 2 ? pol->width[1] : 0;
-    a->net.M = M; a->net.F = 4 + pol->window + M;
-    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
-    a->weights = pol->weights_dev;
+// What the three engines' argument builders (policy_lane_args, policy_mx_args, policy_gru_args) share.  A builder runs
+// after the handle: it checks the byte counts that depend on the environment, then fills its kernel's struct from the
+// policy struct and from smp / val / pop where the entry has them (NULL otherwise).
+template <class Pol>
+static abrx::PolicyNet policy_net(const Pol *pol, int32_t M) {
+    abrx::PolicyNet net{};
+    net.window = pol->window; net.M = M; net.F = 4 + pol->window + M;
+    net.norm = pol->norm_dev; net.seed = pol->seed; net.thr = pol->explore_threshold;
+    return net;
+}
+
+static int check_weights_bytes(size_t got, size_t want, int32_t M) {
+    if (got != want) return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", got, want, M);
     return ABR_OK;
 }
 
-template <bool SAMPLED = false>
-static void launch_policy(const abr_env *env, const PolicyArgs &a, hipStream_t st) {
-    const size_t lds = ((size_t)abrx::policy_layout(a.net).total + (SAMPLED ? (size_t)a.net.M * kPolicyBlock : 0)) *
-                       sizeof(float);
-    hipLaunchKernelGGL(policy_select_kernel<SAMPLED>, dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
-                       dim3(kPolicyBlock), lds, st, env->p, a);
-}
-
-template <bool SAMPLED>
-static void launch_policy_value(const abr_env *env, const PolicyValueArgs &a, hipStream_t st) {
-    const size_t lds = ((size_t)abrx::policy_layout<true>(a.net).total + (SAMPLED ? (size_t)a.net.M * kPolicyBlock : 0)) *
-                       sizeof(float);
-    hipLaunchKernelGGL((policy_select_kernel<SAMPLED, true>), dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
-                       dim3(kPolicyBlock), lds, st, env->p, a);
-}
-
-// the sampling struct alone (before the handle)
-static int validate_sampling(const abr_policy_sampling *smp) {
-    if (!smp) return fail(ABR_E_INVALID, "sampling is NULL");
-    if (smp->mode != ABR_POLICY_ARGMAX && smp->mode != ABR_POLICY_SOFTMAX)
-        return fail(ABR_E_INVALID, "sampling mode %d is neither ABR_POLICY_ARGMAX nor ABR_POLICY_SOFTMAX", smp->mode);
-    const float t = smp->inv_temperature;
-    if (!(t > 0.0f && t <= 0x1.fffffep127f)) return fail(ABR_E_INVALID, "sampling inv_temperature must be finite and > 0");
-    for (int32_t r : smp->reserved_)
-        if (r) return fail(ABR_E_INVALID, "sampling reserved_ must be 0");
-    return ABR_OK;
-}
-
-extern "C" int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_t *action_out_dev, float *features_out_dev,
-                                     float *scores_out_dev, void *stream) {
-    int rc = validate_policy(pol);
-    if (rc) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyArgs a;
-    if ((rc = policy_args(env, pol, &a))) return rc;
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    launch_policy(env, a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
-// per decision the policy kernel, then K1 MODE 1 on its actions, back to back on the stream (as mpc_rollout)
-template <bool SAMPLED>
-static int step_policy(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp, int32_t n_steps,
-                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
-                       float *features_out_dev, float *scores_out_dev, float *probs_out_dev, void *stream) {
-    int rc = validate_policy(pol);
-    if (rc) return rc;
-    if (SAMPLED && (rc = validate_sampling(smp))) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyArgs a;
-    if ((rc = policy_args(env, pol, &a))) return rc;
-    if (SAMPLED) { a.mode = smp->mode; a.inv_temperature = smp->inv_temperature; }
-    if ((rc = require(kPolicyRollout, env->impl))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
-        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        launch_policy<SAMPLED>(env, a, st);
-        HIP_TRY(hipGetLastError());
-        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
-    }
-    return ABR_OK;
-}
-
-extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev,
-                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
-                                   float *features_out_dev, float *scores_out_dev, void *stream) {
-    return step_policy<false>(env, pol, nullptr, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
-                              features_out_dev, scores_out_dev, nullptr, stream);
-}
-
-extern "C" int abr_env_step_policy_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
-                                           int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
-                                           uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
-                                           float *scores_out_dev, float *probs_out_dev, void *stream) {
-    return step_policy<true>(env, pol, smp, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
-                             features_out_dev, scores_out_dev, probs_out_dev, stream);
-}
-
-extern "C" int abr_env_policy_select_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
-                                             int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
-                                             float *probs_out_dev, void *stream) {
-    int rc = validate_policy(pol);
-    if (rc) return rc;
-    if ((rc = validate_sampling(smp))) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyArgs a;
-    if ((rc = policy_args(env, pol, &a))) return rc;
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    a.probs_out = probs_out_dev; a.mode = smp->mode; a.inv_temperature = smp->inv_temperature;
-    launch_policy<true>(env, a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Actor-critic rollouts (include/abr_env.h: abr_policy_value, abr_gae)
-// ---------------------------------------------------------------------------
-// the value struct alone (before the handle)
-static int validate_value(const abr_policy_value *val) {
-    if (!val) return fail(ABR_E_INVALID, "value is NULL");
-    if (!val->head_dev || ((uintptr_t)val->head_dev & 3))
-        return fail(ABR_E_INVALID, "value head must be non-NULL and 4-byte aligned");
-    for (int32_t r : val->reserved_)
-        if (r) return fail(ABR_E_INVALID, "value reserved_ must be 0");
-    return ABR_OK;
-}
-
-// after the handle: the policy's arguments, then the head's size for the policy's shape
-static int policy_value_args(const abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
-                             const abr_policy_value *val, PolicyValueArgs *a) {
-    PolicyArgs base;
-    int rc = policy_args(env, pol, &base);
-    if (rc) return rc;
-    const size_t in = pol->n_hidden == 0 ? (size_t)base.net.F : (size_t)pol->width[pol->n_hidden - 1];
-    if (val->head_bytes != (in + 1) * sizeof(float))
+// the value head over a layer of `in` units: Wv [in], then bv
+static int check_head_bytes(const abr_policy_value *val, size_t in) {
+    if (val && val->head_bytes != (in + 1) * sizeof(float))
         return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
-    *a = PolicyValueArgs{};
-    static_cast<PolicyArgs &>(*a) = base;
-    a->mode = smp->mode; a->inv_temperature = smp->inv_temperature;
-    a->head = val->head_dev;
     return ABR_OK;
 }
 
-// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
-static void launch_policy_ac(const abr_env *env, const PolicyValueArgs &a, hipStream_t st) {
-    if (a.mode == ABR_POLICY_ARGMAX && !a.probs_out) launch_policy_value<false>(env, a, st);
-    else launch_policy_value<true>(env, a, st);
-}
-
-extern "C" int abr_env_policy_select_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
-                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
-                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
-    int rc = validate_policy(pol);
-    if (rc) return rc;
-    if ((rc = validate_sampling(smp))) return rc;
-    if ((rc = validate_value(val))) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyValueArgs a;
-    if ((rc = policy_value_args(env, pol, smp, val, &a))) return rc;
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
-    launch_policy_ac(env, a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
+// after the one-member byte counts: a population's members cover the environment's lanes exactly
+static int pop_covers(const abr_env *env, const abr_policy_pop *pop) {
+    if (!pop) return ABR_OK;
+    const int64_t want = (env->p.n_lanes + pop->group - 1) / pop->group;
+    if ((int64_t)pop->n_members != want)
+        return fail(ABR_E_INVALID, "population n_members %d, %lld lanes in groups of %d need %lld", pop->n_members,
+                    (long long)env->p.n_lanes, pop->group, (long long)want);
     return ABR_OK;
 }
 
-// step_policy with the VALUE instances, then one value evaluation of the state the launch leaves behind
-extern "C" int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
-                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
-                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
-                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
-                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
-    int rc = validate_policy(pol);
+// The lane engine's struct is the widest one on the host whatever the entry: launch_policy_lane hands each instance the
+// base it was compiled for.
+static int policy_lane_args(const abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                            const abr_policy_value *val, const abr_policy_pop *pop, PolicyPopArgs *a) {
+    const int32_t M = env->p.n_rates;
+    int rc = check_weights_bytes(pol->weights_bytes, policy_weights_bytes(pol, M), M);
     if (rc) return rc;
-    if ((rc = validate_sampling(smp))) return rc;
-    if ((rc = validate_value(val))) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyValueArgs a;
-    if ((rc = policy_value_args(env, pol, smp, val, &a))) return rc;
-    if ((rc = require(kPolicyRollout, env->impl))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
-        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
-        launch_policy_ac(env, a, st);
-        HIP_TRY(hipGetLastError());
-        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
-    }
-    if (last_value_out_dev) {
-        // the bootstrap value: no decision is stored, so the workspace is left as the rollout left it
-        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
-        a.value_out = last_value_out_dev;
-        launch_policy_value<false>(env, a, st);
-        HIP_TRY(hipGetLastError());
+    *a = PolicyPopArgs{};
+    a->net = policy_net(pol, M);
+    a->net.n_hidden = pol->n_hidden;
+    a->net.w0 = pol->n_hidden >= 1 ? pol->width[0] : 0; a->net.w1 = pol->n_hidden >= 2 ? pol->width[1] : 0;
+    a->weights = pol->weights_dev;
+    if ((rc = check_head_bytes(val, pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1]))) return rc;
+    if ((rc = pop_covers(env, pop))) return rc;
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    if (val) a->head = val->head_dev;
+    if (pop) {       // the member stride of the blob and of the heads, in floats
+        a->group = pop->group;
+        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
     }
     return ABR_OK;
+}
+
+// The one chooser of policy_select_kernel's instances.  SAMPLED: a softmax draw or probs need the score columns in LDS;
+// the argmax without probs needs none, and the plain instance decides exactly as the sampled one in mode 0.  The _sampled
+// entries (ALWAYS_SAMPLED) run the sampled instances in every mode.  VALUE: the launch has a head.  POP: the entry's.
+// A rollout's bootstrap launch (argmax, no probs, a head) is therefore <false, true, POP> whatever the entry's mode.
+template <bool POP, bool ALWAYS_SAMPLED = false>
+static hipError_t launch_policy_lane(const abr_env *env, const PolicyPopArgs &a, hipStream_t st) {
+    const bool sampled = ALWAYS_SAMPLED || a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t words = value ? abrx::policy_layout<true>(a.net).total : abrx::policy_layout(a.net).total;
+    const size_t lds = (words + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
+    const dim3 grid((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), block(kPolicyBlock);
+    // a POP == false instance takes `a` sliced to its own argument struct (PolicyValueArgs or PolicyArgs)
+    if (sampled && value) hipLaunchKernelGGL((policy_select_kernel<true, true, POP>), grid, block, lds, st, env->p, a);
+    else if (sampled) hipLaunchKernelGGL((policy_select_kernel<true, false, POP>), grid, block, lds, st, env->p, a);
+    else if (value) hipLaunchKernelGGL((policy_select_kernel<false, true, POP>), grid, block, lds, st, env->p, a);
+    else hipLaunchKernelGGL((policy_select_kernel<false, false, POP>), grid, block, lds, st, env->p, a);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -3836,7 +3700,7 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p,
     a.action_out[i] = action;
 }
 
-static int validate_policy_mx(const abr_policy_mx *pol) {
+static int validate_policy_shape(const abr_policy_mx *pol) {
     if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
     if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
         return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
@@ -3851,339 +3715,49 @@ static int validate_policy_mx(const abr_policy_mx *pol) {
     return ABR_OK;
 }
 
-static size_t policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t M) {
-    size_t in = 4 + (size_t)pol->window + (size_t)M, words = 0;
-    for (int l = 0; l <= pol->n_hidden; l++) {
-        const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
-        words += out * in + out;
-        in = out;
-    }
-    return words * sizeof(float);
-}
-
 extern "C" int abr_policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_mx(pol);
+    int rc = validate_policy_shape(pol);
     if (rc) return rc;
     if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
     if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
-    *bytes_out = policy_mx_weights_bytes(pol, n_rates);
+    *bytes_out = policy_weights_bytes(pol, n_rates);
     return ABR_OK;
 }
 
-// everything that is checked before the handle: the structs, then the outputs that need a struct that is absent
-static int validate_policy_mx_call(const abr_policy_mx *pol, const abr_policy_sampling *smp, const abr_policy_value *val,
-                                   const float *probs_out, const float *values_out, const float *last_value_out) {
-    int rc = validate_policy_mx(pol);
-    if (rc) return rc;
-    for (int32_t r : pol->reserved_)
-        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
-    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
-        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
-    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
-    if (pol->explore_threshold > (1ull << 32))
-        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
-    if (smp && (rc = validate_sampling(smp))) return rc;
-    if (val && (rc = validate_value(val))) return rc;
-    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
-    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
-    return ABR_OK;
-}
-
-// after the handle: the blob's and the head's sizes for the environment's n_rates
+// the matrix engine's builder (as policy_lane_args: the widest struct, sliced at the launch)
 static int policy_mx_args(const abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
-                          const abr_policy_value *val, PolicyMxArgs *a) {
+                          const abr_policy_value *val, const abr_policy_pop *pop, PolicyMxPopArgs *a) {
     const int32_t M = env->p.n_rates;
-    const size_t want = policy_mx_weights_bytes(pol, M);
-    if (pol->weights_bytes != want)
-        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
-    *a = PolicyMxArgs{};
-    a->net.window = pol->window; a->net.M = M; a->net.F = 4 + pol->window + M;
-    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
+    int rc = check_weights_bytes(pol->weights_bytes, policy_weights_bytes(pol, M), M);
+    if (rc) return rc;
+    *a = PolicyMxPopArgs{};
+    a->net = policy_net(pol, M);
     a->n_hidden = pol->n_hidden;
     for (int l = 0; l < ABR_POLICY_MX_MAX_HIDDEN; l++) a->width[l] = pol->width[l];
     a->weights = pol->weights_dev;
-    if (val) {
-        const size_t in = pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1];
-        if (val->head_bytes != (in + 1) * sizeof(float))
-            return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
-        a->head = val->head_dev;
-    }
+    if ((rc = check_head_bytes(val, pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1]))) return rc;
+    if ((rc = pop_covers(env, pop))) return rc;
     if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    if (val) a->head = val->head_dev;
+    if (pop) {
+        a->group = pop->group;
+        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
+    }
     return ABR_OK;
 }
 
-// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
-static void launch_policy_mx(const abr_env *env, const PolicyMxArgs &a, hipStream_t st) {
+// the one chooser of policy_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_lane
+template <bool POP>
+static hipError_t launch_policy_mx(const abr_env *env, const PolicyMxPopArgs &a, hipStream_t st) {
     const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
     const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
     const dim3 grid((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)), block(kMxBlock);
-    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true>), grid, block, lds, st, env->p, a);
-    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false>), grid, block, lds, st, env->p, a);
-    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true>), grid, block, lds, st, env->p, a);
-    else hipLaunchKernelGGL((policy_mx_kernel<false, false>), grid, block, lds, st, env->p, a);
-}
-
-extern "C" int abr_env_policy_select_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
-                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
-                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
-    int rc = validate_policy_mx_call(pol, smp, val, probs_out_dev, value_out_dev, nullptr);
-    if (rc) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyMxArgs a;
-    if ((rc = policy_mx_args(env, pol, smp, val, &a))) return rc;
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
-    launch_policy_mx(env, a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
-// per decision the matrix kernel, then K1 MODE 1 on its actions (as abr_env_step_policy_ac, last_value included)
-extern "C" int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
-                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
-                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
-                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
-                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
-    int rc = validate_policy_mx_call(pol, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
-    if (rc) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyMxArgs a;
-    if ((rc = policy_mx_args(env, pol, smp, val, &a))) return rc;
-    if ((rc = require(kPolicyRollout, env->impl))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
-        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
-        launch_policy_mx(env, a, st);
-        HIP_TRY(hipGetLastError());
-        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
-    }
-    if (last_value_out_dev) {
-        // the bootstrap value: no decision is stored, so the workspace is left as the rollout left it
-        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
-        a.mode = ABR_POLICY_ARGMAX;
-        a.value_out = last_value_out_dev;
-        launch_policy_mx(env, a, st);
-        HIP_TRY(hipGetLastError());
-    }
-    return ABR_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Policy populations (include/abr_env.h: abr_policy_pop): one weight set per lane group, both engines
-// ---------------------------------------------------------------------------
-// the struct alone (before the handle)
-static int validate_pop(const abr_policy_pop *pop) {
-    if (!pop) return fail(ABR_E_INVALID, "population is NULL");
-    if (pop->n_members < 1) return fail(ABR_E_INVALID, "population n_members %d must be >= 1", pop->n_members);
-    if (pop->group < kPolicyBlock || pop->group % kPolicyBlock)
-        return fail(ABR_E_INVALID, "population group %d must be a positive multiple of %d", pop->group, kPolicyBlock);
-    for (int32_t r : pop->reserved_)
-        if (r) return fail(ABR_E_INVALID, "population reserved_ must be 0");
-    // a launch covers at most 2^32 - 1 workgroups of 256 lanes: no environment can have the lanes of a larger product
-    if ((int64_t)pop->n_members * (int64_t)pop->group > (int64_t)UINT32_MAX * kPolicyBlock)
-        return fail(ABR_E_INVALID, "population n_members %d x group %d overflows the lanes of a launch", pop->n_members,
-                    pop->group);
-    return ABR_OK;
-}
-
-// after the handle and the one-member byte counts: the members cover the environment's lanes exactly
-static int pop_covers(const abr_env *env, const abr_policy_pop *pop) {
-    const int64_t want = (env->p.n_lanes + pop->group - 1) / pop->group;
-    if ((int64_t)pop->n_members != want)
-        return fail(ABR_E_INVALID, "population n_members %d, %lld lanes in groups of %d need %lld", pop->n_members,
-                    (long long)env->p.n_lanes, pop->group, (long long)want);
-    return ABR_OK;
-}
-
-// everything the lane engine's population entries check before the handle, but n_steps
-static int validate_policy_pop_call(const abr_policy *pol, const abr_policy_pop *pop, const abr_policy_sampling *smp,
-                                    const abr_policy_value *val, const float *probs_out, const float *values_out,
-                                    const float *last_value_out) {
-    int rc = validate_policy(pol);
-    if (rc) return rc;
-    if (smp && (rc = validate_sampling(smp))) return rc;
-    if (val && (rc = validate_value(val))) return rc;
-    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
-    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
-    return validate_pop(pop);
-}
-
-static int policy_pop_args(const abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
-                           const abr_policy_sampling *smp, const abr_policy_value *val, PolicyPopArgs *a) {
-    PolicyArgs base;
-    int rc = policy_args(env, pol, &base);
-    if (rc) return rc;
-    *a = PolicyPopArgs{};
-    static_cast<PolicyArgs &>(*a) = base;
-    if (val) {
-        const size_t in = pol->n_hidden == 0 ? (size_t)base.net.F : (size_t)pol->width[pol->n_hidden - 1];
-        if (val->head_bytes != (in + 1) * sizeof(float))
-            return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, (in + 1) * sizeof(float));
-        a->head = val->head_dev;
-        a->head_words = (int32_t)(in + 1);
-    }
-    if ((rc = pop_covers(env, pop))) return rc;
-    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
-    a->group = pop->group;
-    a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-    return ABR_OK;
-}
-
-// the instance by what the launch needs, as launch_policy_ac and launch_policy_mx choose theirs
-static void launch_policy_pop(const abr_env *env, const PolicyPopArgs &a, hipStream_t st) {
-    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t total = value ? abrx::policy_layout<true>(a.net).total : abrx::policy_layout(a.net).total;
-    const size_t lds = (total + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
-    const dim3 grid((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), block(kPolicyBlock);
-    if (sampled && value) hipLaunchKernelGGL((policy_select_kernel<true, true, true>), grid, block, lds, st, env->p, a);
-    else if (sampled) hipLaunchKernelGGL((policy_select_kernel<true, false, true>), grid, block, lds, st, env->p, a);
-    else if (value) hipLaunchKernelGGL((policy_select_kernel<false, true, true>), grid, block, lds, st, env->p, a);
-    else hipLaunchKernelGGL((policy_select_kernel<false, false, true>), grid, block, lds, st, env->p, a);
-}
-
-static int validate_policy_mx_pop_call(const abr_policy_mx *pol, const abr_policy_pop *pop, const abr_policy_sampling *smp,
-                                       const abr_policy_value *val, const float *probs_out, const float *values_out,
-                                       const float *last_value_out) {
-    int rc = validate_policy_mx_call(pol, smp, val, probs_out, values_out, last_value_out);
-    if (rc) return rc;
-    return validate_pop(pop);
-}
-
-static int policy_mx_pop_args(const abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
-                              const abr_policy_sampling *smp, const abr_policy_value *val, PolicyMxPopArgs *a) {
-    PolicyMxArgs base;
-    int rc = policy_mx_args(env, pol, smp, val, &base);
-    if (rc) return rc;
-    if ((rc = pop_covers(env, pop))) return rc;
-    *a = PolicyMxPopArgs{};
-    static_cast<PolicyMxArgs &>(*a) = base;
-    a->group = pop->group;
-    a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-    a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
-    return ABR_OK;
-}
-
-static void launch_policy_mx_pop(const abr_env *env, const PolicyMxPopArgs &a, hipStream_t st) {
-    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
-    const dim3 grid((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)), block(kMxBlock);
-    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true, true>), grid, block, lds, st, env->p, a);
-    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false, true>), grid, block, lds, st, env->p, a);
-    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true, true>), grid, block, lds, st, env->p, a);
-    else hipLaunchKernelGGL((policy_mx_kernel<false, false, true>), grid, block, lds, st, env->p, a);
-}
-
-// one decision per lane on the current state, either engine's argument struct and launcher
-template <class Args, class Launch>
-static int select_pop(abr_env *env, Args &a, const Launch &launch, int32_t *action_out_dev, float *features_out_dev,
-                      float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    a.probs_out = probs_out_dev; a.value_out = value_out_dev;
-    launch(env, a, (hipStream_t)stream);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
-}
-
-// per decision the population's policy kernel, then K1 MODE 1 on its actions (as abr_env_step_policy_ac, last_value included)
-template <class Args, class Launch>
-static int step_pop(abr_env *env, Args &a, const Launch &launch, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
-                    uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
-                    float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, void *stream) {
-    int rc = require(kPolicyRollout, env->impl);
-    if (rc) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
-        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
-        launch(env, a, st);
-        HIP_TRY(hipGetLastError());
-        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
-    }
-    if (last_value_out_dev) {
-        // the bootstrap value, each lane's by its own member: no decision is stored, the workspace stays as it is
-        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
-        a.mode = ABR_POLICY_ARGMAX;
-        a.value_out = last_value_out_dev;
-        launch(env, a, st);
-        HIP_TRY(hipGetLastError());
-    }
-    return ABR_OK;
-}
-
-extern "C" int abr_env_policy_select_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
-                                         const abr_policy_sampling *smp, const abr_policy_value *val,
-                                         int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
-                                         float *probs_out_dev, float *value_out_dev, void *stream) {
-    int rc = validate_policy_pop_call(pol, pop, smp, val, probs_out_dev, value_out_dev, nullptr);
-    if (rc) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyPopArgs a;
-    if ((rc = policy_pop_args(env, pol, pop, smp, val, &a))) return rc;
-    return select_pop(env, a, launch_policy_pop, action_out_dev, features_out_dev, scores_out_dev, probs_out_dev,
-                      value_out_dev, stream);
-}
-
-extern "C" int abr_env_step_policy_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
-                                       const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
-                                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
-                                       int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
-                                       float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
-                                       void *stream) {
-    int rc = validate_policy_pop_call(pol, pop, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
-    if (rc) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyPopArgs a;
-    if ((rc = policy_pop_args(env, pol, pop, smp, val, &a))) return rc;
-    return step_pop(env, a, launch_policy_pop, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
-                    features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, last_value_out_dev, stream);
-}
-
-extern "C" int abr_env_policy_select_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
-                                            const abr_policy_sampling *smp, const abr_policy_value *val,
-                                            int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
-                                            float *probs_out_dev, float *value_out_dev, void *stream) {
-    int rc = validate_policy_mx_pop_call(pol, pop, smp, val, probs_out_dev, value_out_dev, nullptr);
-    if (rc) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyMxPopArgs a;
-    if ((rc = policy_mx_pop_args(env, pol, pop, smp, val, &a))) return rc;
-    return select_pop(env, a, launch_policy_mx_pop, action_out_dev, features_out_dev, scores_out_dev, probs_out_dev,
-                      value_out_dev, stream);
-}
-
-extern "C" int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
-                                          const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
-                                          float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
-                                          int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
-                                          float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
-                                          void *stream) {
-    int rc = validate_policy_mx_pop_call(pol, pop, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
-    if (rc) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyMxPopArgs a;
-    if ((rc = policy_mx_pop_args(env, pol, pop, smp, val, &a))) return rc;
-    return step_pop(env, a, launch_policy_mx_pop, n_steps, obs_out_dev, reward_out_dev, done_out_dev, actions_out_dev,
-                    features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, last_value_out_dev, stream);
+    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true, POP>), grid, block, lds, st, env->p, a);
+    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false, POP>), grid, block, lds, st, env->p, a);
+    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true, POP>), grid, block, lds, st, env->p, a);
+    else hipLaunchKernelGGL((policy_mx_kernel<false, false, POP>), grid, block, lds, st, env->p, a);
+    return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------
@@ -4312,7 +3886,7 @@ static size_t policy_gru_weights_bytes(int32_t W, int32_t H, int32_t M) {
     return (3 * h * (F + h + 2) + (size_t)M * (h + 1)) * sizeof(float);
 }
 
-static int validate_policy_gru_shape(const abr_policy_gru *pol) {
+static int validate_policy_shape(const abr_policy_gru *pol) {
     if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
     if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
         return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
@@ -4322,7 +3896,7 @@ static int validate_policy_gru_shape(const abr_policy_gru *pol) {
 }
 
 extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_gru_shape(pol);
+    int rc = validate_policy_shape(pol);
     if (rc) return rc;
     if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
     if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
@@ -4330,46 +3904,23 @@ extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n
     return ABR_OK;
 }
 
-// everything that is checked before the handle: the structs, then the outputs that need a struct that is absent
-static int validate_policy_gru_call(const abr_policy_gru *pol, const abr_policy_sampling *smp, const abr_policy_value *val,
-                                    const float *probs_out, const float *values_out, const float *last_value_out) {
-    int rc = validate_policy_gru_shape(pol);
-    if (rc) return rc;
-    for (int32_t r : pol->reserved_)
-        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
-    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
-        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
-    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
-    if (!pol->state_dev || ((uintptr_t)pol->state_dev & 3))
-        return fail(ABR_E_INVALID, "policy state must be non-NULL and 4-byte aligned");
-    if (pol->explore_threshold > (1ull << 32))
-        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
-    if (smp && (rc = validate_sampling(smp))) return rc;
-    if (val && (rc = validate_value(val))) return rc;
-    if (!smp && probs_out) return fail(ABR_E_INVALID, "probs need a sampling struct");
-    if (!val && (values_out || last_value_out)) return fail(ABR_E_INVALID, "values need a value struct");
-    return ABR_OK;
-}
-
-// after the handle: the blob's, the state's and the head's sizes for the environment
+// the recurrent engine's builder: the blob's, the state's and the head's sizes for the environment (it has no populations)
 static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
-                           const abr_policy_value *val, PolicyGruArgs *a) {
+                           const abr_policy_value *val, const abr_policy_pop *, PolicyGruArgs *a) {
     const int32_t M = env->p.n_rates, H = pol->hidden;
-    const size_t want = policy_gru_weights_bytes(pol->window, H, M);
-    if (pol->weights_bytes != want)
-        return fail(ABR_E_INVALID, "policy weights_bytes %zu, the shape needs %zu at n_rates %d", pol->weights_bytes, want, M);
+    int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
+    if (rc) return rc;
     const size_t state = (size_t)H * (size_t)env->p.n_lanes * sizeof(float);
     if (pol->state_bytes != state)
         return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
                     (long long)env->p.n_lanes, state);
-    if (val && val->head_bytes != ((size_t)H + 1) * sizeof(float))
-        return fail(ABR_E_INVALID, "value head_bytes %zu, the shape needs %zu", val->head_bytes, ((size_t)H + 1) * sizeof(float));
+    if ((rc = check_head_bytes(val, (size_t)H))) return rc;
     *a = PolicyGruArgs{};
-    a->net.window = pol->window; a->net.n_hidden = 1; a->net.w0 = H; a->net.M = M; a->net.F = 4 + pol->window + M;
-    a->net.norm = pol->norm_dev; a->net.seed = pol->seed; a->net.thr = pol->explore_threshold;
+    a->net = policy_net(pol, M);
+    a->net.n_hidden = 1; a->net.w0 = H;
     a->weights = pol->weights_dev; a->state = pol->state_dev;
-    if (val) a->head = val->head_dev;
     if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    if (val) a->head = val->head_dev;
     return ABR_OK;
 }
 
@@ -4393,7 +3944,7 @@ static hipError_t launch_policy_gru_instance(const abr_env *env, const PolicyGru
     return hipGetLastError();
 }
 
-// The argmax without probs needs no score columns: the plain instance decides exactly as the sampled one in mode 0.
+// the one chooser of policy_gru_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_lane
 static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruArgs &a, hipStream_t st) {
     const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
     const size_t words = value ? abrx::policy_gru_layout<true>(a.net).total : abrx::policy_gru_layout(a.net).total;
@@ -4404,62 +3955,283 @@ static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruArgs &a, 
     return launch_policy_gru_instance<false, false>(env, a, lds, st);
 }
 
+// ---------------------------------------------------------------------------
+// The host path of the learned-policy entries: one validator, one select, one rollout, whatever the engine
+// ---------------------------------------------------------------------------
+// An engine is an argument struct, a builder that fills it after the handle (policy_lane_args, policy_mx_args,
+// policy_gru_args) and a launcher that picks the kernel instance (launch_policy_lane, launch_policy_mx, launch_policy_gru),
+// next to its validate_policy_shape.  Everything below is shared.
+
+// the sampling struct alone
+static int validate_sampling(const abr_policy_sampling *smp) {
+    if (!smp) return fail(ABR_E_INVALID, "sampling is NULL");
+    if (smp->mode != ABR_POLICY_ARGMAX && smp->mode != ABR_POLICY_SOFTMAX)
+        return fail(ABR_E_INVALID, "sampling mode %d is neither ABR_POLICY_ARGMAX nor ABR_POLICY_SOFTMAX", smp->mode);
+    const float t = smp->inv_temperature;
+    if (!(t > 0.0f && t <= 0x1.fffffep127f)) return fail(ABR_E_INVALID, "sampling inv_temperature must be finite and > 0");
+    for (int32_t r : smp->reserved_)
+        if (r) return fail(ABR_E_INVALID, "sampling reserved_ must be 0");
+    return ABR_OK;
+}
+
+// the value struct alone
+static int validate_value(const abr_policy_value *val) {
+    if (!val) return fail(ABR_E_INVALID, "value is NULL");
+    if (!val->head_dev || ((uintptr_t)val->head_dev & 3))
+        return fail(ABR_E_INVALID, "value head must be non-NULL and 4-byte aligned");
+    for (int32_t r : val->reserved_)
+        if (r) return fail(ABR_E_INVALID, "value reserved_ must be 0");
+    return ABR_OK;
+}
+
+// the population struct alone
+static int validate_pop(const abr_policy_pop *pop) {
+    if (!pop) return fail(ABR_E_INVALID, "population is NULL");
+    if (pop->n_members < 1) return fail(ABR_E_INVALID, "population n_members %d must be >= 1", pop->n_members);
+    if (pop->group < kPolicyBlock || pop->group % kPolicyBlock)
+        return fail(ABR_E_INVALID, "population group %d must be a positive multiple of %d", pop->group, kPolicyBlock);
+    for (int32_t r : pop->reserved_)
+        if (r) return fail(ABR_E_INVALID, "population reserved_ must be 0");
+    // a launch covers at most 2^32 - 1 workgroups of 256 lanes: no environment can have the lanes of a larger product
+    if ((int64_t)pop->n_members * (int64_t)pop->group > (int64_t)UINT32_MAX * kPolicyBlock)
+        return fail(ABR_E_INVALID, "population n_members %d x group %d overflows the lanes of a launch", pop->n_members,
+                    pop->group);
+    return ABR_OK;
+}
+
+// what abr_policy, abr_policy_mx and abr_policy_gru hold past their shape: reserved words, pointers, threshold
+template <class Pol>
+static int validate_policy_fields(const Pol *pol) {
+    for (int32_t r : pol->reserved_)
+        if (r) return fail(ABR_E_INVALID, "policy reserved_ must be 0");
+    if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
+        return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
+    if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
+    if constexpr (std::is_same_v<Pol, abr_policy_gru>) {
+        if (!pol->state_dev || ((uintptr_t)pol->state_dev & 3))
+            return fail(ABR_E_INVALID, "policy state must be non-NULL and 4-byte aligned");
+    }
+    if (pol->explore_threshold > (1ull << 32))
+        return fail(ABR_E_INVALID, "explore_threshold %llu above 2^32", (unsigned long long)pol->explore_threshold);
+    return ABR_OK;
+}
+
+// The outputs of a select (one row of each) or of a rollout (n_steps rows; last_value one), nullable but a select's action.
+struct PolicyOut {
+    int32_t *action;
+    float *features, *scores, *probs, *value, *hidden;
+    float *last_value, *obs, *reward;   // rollouts only
+    uint8_t *done;
+};
+
+// the structs an entry cannot do without (the others are checked where they are given)
+enum : unsigned { kNeedsSmp = 1, kNeedsVal = 2, kNeedsPop = 4 };
+
+// Everything an entry checks before it reads the handle, in the order include/abr_env.h documents for each of them: the
+// policy struct, smp, val, the outputs that need a struct that is absent, pop, n_steps (NULL: a select), the handle.
+template <class Pol>
+static int validate_policy_call(const abr_env *env, const Pol *pol, unsigned needs, const abr_policy_sampling *smp,
+                                const abr_policy_value *val, const abr_policy_pop *pop, const int32_t *n_steps,
+                                const PolicyOut &o) {
+    int rc = validate_policy_shape(pol);
+    if (rc || (rc = validate_policy_fields(pol))) return rc;
+    if ((smp || (needs & kNeedsSmp)) && (rc = validate_sampling(smp))) return rc;
+    if ((val || (needs & kNeedsVal)) && (rc = validate_value(val))) return rc;
+    if (!smp && o.probs) return fail(ABR_E_INVALID, "probs need a sampling struct");
+    if (!val && (o.value || o.last_value)) return fail(ABR_E_INVALID, "values need a value struct");
+    if ((needs & kNeedsPop) && (rc = validate_pop(pop))) return rc;
+    if (!n_steps) return env && o.action ? ABR_OK : fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
+    if (*n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
+    return env ? ABR_OK : fail(ABR_E_INVALID, "env is NULL");
+}
+
+// the recurrent engine's part of a launch: where h_in is reported, and whether h' replaces it in the caller's slab
+template <class Args>
+static void set_recurrence(Args &, float *, int32_t) {}
+static void set_recurrence(PolicyGruArgs &a, float *hidden_out, int32_t commit) { a.hidden_out = hidden_out; a.commit = commit; }
+
+// one decision per lane on the current state
+template <class Args, class Launch>
+static int policy_select_once(const abr_env *env, Args &a, const Launch &launch, const PolicyOut &o, void *stream) {
+    a.action_out = o.action; a.features_out = o.features; a.scores_out = o.scores;
+    a.probs_out = o.probs; a.value_out = o.value;
+    HIP_TRY(launch(env, a, (hipStream_t)stream));
+    return ABR_OK;
+}
+
+// Per decision the policy kernel on row s of the outputs, then K1 MODE 1 on its actions, back to back on the stream (as
+// mpc_rollout); the recurrent kernel commits each h'.  Then, if asked for, the bootstrap value of the state the rollout
+// leaves behind, which has one form for every engine: an argmax launch that stores no decision, no feature, score or prob
+// and commits nothing, so the workspace and the state slab stay as the rollout left them.
+template <class Args, class Launch>
+static int policy_rollout(const abr_env *env, Args &a, const Launch &launch, int32_t n_steps, const PolicyOut &o,
+                          void *stream) {
+    int rc = require(kPolicyRollout, env->impl);
+    if (rc) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t N = env->p.n_lanes;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        a.action_out = o.action ? slab_row(o.action, s, 1, N) : env->mpc_action;
+        a.features_out = slab_row(o.features, s, a.net.F, N);
+        a.scores_out = slab_row(o.scores, s, a.net.M, N);
+        a.probs_out = slab_row(o.probs, s, a.net.M, N);
+        a.value_out = slab_row(o.value, s, 1, N);
+        set_recurrence(a, slab_row(o.hidden, s, a.net.w0, N), 1);
+        HIP_TRY(launch(env, a, st));
+        if ((rc = step_row(env, impl, st, s, a.action_out, o.obs, o.reward, o.done))) return rc;
+    }
+    if (o.last_value) {
+        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
+        a.mode = ABR_POLICY_ARGMAX;
+        a.value_out = o.last_value;
+        set_recurrence(a, nullptr, 0);
+        HIP_TRY(launch(env, a, st));
+    }
+    return ABR_OK;
+}
+
+// An entry: the checks before the handle, the engine's builder, then the rollout (n_steps given) or the one select.
+template <class Pol, class Args>
+static int policy_entry(const abr_env *env, const Pol *pol, unsigned needs, const abr_policy_sampling *smp,
+                        const abr_policy_value *val, const abr_policy_pop *pop,
+                        int (*build)(const abr_env *, const Pol *, const abr_policy_sampling *, const abr_policy_value *,
+                                     const abr_policy_pop *, Args *),
+                        hipError_t (*launch)(const abr_env *, const Args &, hipStream_t), const int32_t *n_steps,
+                        const PolicyOut &o, void *stream, int32_t commit = 0) {
+    int rc = validate_policy_call(env, pol, needs, smp, val, pop, n_steps, o);
+    if (rc) return rc;
+    Args a;
+    if ((rc = build(env, pol, smp, val, pop, &a))) return rc;
+    if (n_steps) return policy_rollout(env, a, launch, *n_steps, o, stream);
+    set_recurrence(a, o.hidden, commit);
+    return policy_select_once(env, a, launch, o, stream);
+}
+
+extern "C" int abr_env_policy_select(abr_env *env, const abr_policy *pol, int32_t *action_out_dev, float *features_out_dev,
+                                     float *scores_out_dev, void *stream) {
+    return policy_entry(env, pol, 0, nullptr, nullptr, nullptr, policy_lane_args, launch_policy_lane<false>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy(abr_env *env, const abr_policy *pol, int32_t n_steps, float *obs_out_dev,
+                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                   float *features_out_dev, float *scores_out_dev, void *stream) {
+    return policy_entry(env, pol, 0, nullptr, nullptr, nullptr, policy_lane_args, launch_policy_lane<false>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, nullptr, nullptr, nullptr, nullptr, obs_out_dev,
+                         reward_out_dev, done_out_dev}, stream);
+}
+
+extern "C" int abr_env_policy_select_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                             int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                             float *probs_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsSmp, smp, nullptr, nullptr, policy_lane_args, launch_policy_lane<false, true>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy_sampled(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                           int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                                           uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
+                                           float *scores_out_dev, float *probs_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsSmp, smp, nullptr, nullptr, policy_lane_args, launch_policy_lane<false, true>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, nullptr, nullptr, nullptr,
+                         obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// Actor-critic rollouts (include/abr_env.h: abr_policy_value, abr_gae): the VALUE instances, and last_value
+extern "C" int abr_env_policy_select_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsSmp | kNeedsVal, smp, val, nullptr, policy_lane_args, launch_policy_lane<false>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy_ac(abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
+                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsSmp | kNeedsVal, smp, val, nullptr, policy_lane_args, launch_policy_lane<false>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, nullptr,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// the matrix engine: one entry pair for every mode, smp and val nullable
+extern "C" int abr_env_policy_select_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                                        const abr_policy_value *val, int32_t *action_out_dev, float *features_out_dev,
+                                        float *scores_out_dev, float *probs_out_dev, float *value_out_dev, void *stream) {
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_mx_args, launch_policy_mx<false>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy_mx(abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
+                                      const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                      float *values_out_dev, float *last_value_out_dev, void *stream) {
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_mx_args, launch_policy_mx<false>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, nullptr,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// populations (include/abr_env.h: abr_policy_pop): one weight set per lane group, both engines' POP instances
+extern "C" int abr_env_policy_select_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                                         const abr_policy_sampling *smp, const abr_policy_value *val,
+                                         int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                         float *probs_out_dev, float *value_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_lane_args, launch_policy_lane<true>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy_pop(abr_env *env, const abr_policy *pol, const abr_policy_pop *pop,
+                                       const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                       int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                       float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                       void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_lane_args, launch_policy_lane<true>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, nullptr,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+extern "C" int abr_env_policy_select_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                                            const abr_policy_sampling *smp, const abr_policy_value *val,
+                                            int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                            float *probs_out_dev, float *value_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_mx_args, launch_policy_mx<true>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev}, stream);
+}
+
+extern "C" int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr_policy_pop *pop,
+                                          const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                          float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                          int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                          float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                          void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_mx_args, launch_policy_mx<true>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, nullptr,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// the recurrent engine: a select commits h' only when asked to, a rollout at every decision
 extern "C" int abr_env_policy_select_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
                                          const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
                                          float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                          float *value_out_dev, float *hidden_out_dev, void *stream) {
-    int rc = validate_policy_gru_call(pol, smp, val, probs_out_dev, value_out_dev, nullptr);
-    if (rc) return rc;
-    if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
-    PolicyGruArgs a;
-    if ((rc = policy_gru_args(env, pol, smp, val, &a))) return rc;
-    a.action_out = action_out_dev; a.features_out = features_out_dev; a.scores_out = scores_out_dev;
-    a.probs_out = probs_out_dev; a.value_out = value_out_dev; a.hidden_out = hidden_out_dev;
-    a.commit = commit != 0;
-    HIP_TRY(launch_policy_gru(env, a, (hipStream_t)stream));
-    return ABR_OK;
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
+                        stream, commit != 0);
 }
 
-// per decision the recurrent kernel (commit), then K1 MODE 1 on its actions (as abr_env_step_policy_mx, last_value included)
 extern "C" int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
                                        const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
                                        float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
                                        float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                        float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                        void *stream) {
-    int rc = validate_policy_gru_call(pol, smp, val, probs_out_dev, values_out_dev, last_value_out_dev);
-    if (rc) return rc;
-    if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
-    if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    PolicyGruArgs a;
-    if ((rc = policy_gru_args(env, pol, smp, val, &a))) return rc;
-    if ((rc = require(kPolicyRollout, env->impl))) return rc;
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    a.commit = 1;
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = actions_out_dev ? actions_out_dev + (int64_t)s * N : env->mpc_action;
-        a.features_out = features_out_dev ? features_out_dev + (int64_t)s * a.net.F * N : nullptr;
-        a.scores_out = scores_out_dev ? scores_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.probs_out = probs_out_dev ? probs_out_dev + (int64_t)s * a.net.M * N : nullptr;
-        a.value_out = values_out_dev ? values_out_dev + (int64_t)s * N : nullptr;
-        a.hidden_out = hidden_out_dev ? hidden_out_dev + (int64_t)s * a.net.w0 * N : nullptr;
-        HIP_TRY(launch_policy_gru(env, a, st));
-        rc = launch_env<1>(env, impl, st, a.action_out, obs_out_dev ? obs_out_dev + (int64_t)s * ABR_OBS_DIM * N : nullptr,
-                           reward_out_dev ? reward_out_dev + (int64_t)s * N : nullptr,
-                           done_out_dev ? done_out_dev + (int64_t)s * N : nullptr, nullptr, 1, 0ull);
-        if (rc) return rc;
-    }
-    if (last_value_out_dev) {
-        // the bootstrap value: no decision is stored and nothing is committed, so the workspace and the state slab are
-        // left as the rollout left them
-        a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = a.hidden_out = nullptr;
-        a.mode = ABR_POLICY_ARGMAX; a.commit = 0;
-        a.value_out = last_value_out_dev;
-        HIP_TRY(launch_policy_gru(env, a, st));
-    }
-    return ABR_OK;
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }
 
 // One thread per lane walks its column of the slabs from the last row to the first (abr_lane_jump.h: gae_lane): a row of

@@ -552,50 +552,26 @@ class BatchedABREnv:
                 out["last_value"] = torch.empty(N, dtype=torch.float32, device=dev)
             if want_hidden:
                 out["hidden"] = torch.empty(n, controller.hidden_size, N, dtype=torch.float32, device=dev)
-        if recurrent:                                                     # one entry for every mode (abr_policy_gru)
-            smp = controller.sampling()
-            self._call(self.lib.abr_env_step_policy_gru, self._h, C.byref(pol), C.byref(smp),
-                       C.byref(val) if val is not None else None, n,
-                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
-                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")),
-                       _lib.ptr(out.get("hidden")))
-            return out
-        if getattr(controller, "method", None) == "policy_population":    # one weight set per lane group (abr_policy_pop)
-            pop, smp = controller.population(), controller.sampling()
-            fn = (self.lib.abr_env_step_policy_mx_pop if controller.engine == "matrix" else
-                  self.lib.abr_env_step_policy_pop)
-            self._call(fn, self._h, C.byref(pol), C.byref(pop), C.byref(smp), C.byref(val) if val is not None else None,
-                       n, _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
-                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")))
-            return out
-        if getattr(controller, "engine", "lane") == "matrix":             # one entry for every mode (abr_env_step_policy_mx)
-            smp = controller.sampling()
-            self._call(self.lib.abr_env_step_policy_mx, self._h, C.byref(pol), C.byref(smp),
-                       C.byref(val) if val is not None else None, n,
-                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
-                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")))
-            return out
-        if val is not None:
-            smp = controller.sampling()
-            self._call(self.lib.abr_env_step_policy_ac, self._h, C.byref(pol), C.byref(smp), C.byref(val), n,
-                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
-                       _lib.ptr(out.get("probs")), _lib.ptr(out.get("values")), _lib.ptr(out.get("last_value")))
-            return out
-        if controller.uses_sampled_entries(out.get("probs") is not None):
-            smp = controller.sampling()
-            self._call(self.lib.abr_env_step_policy_sampled, self._h, C.byref(pol), C.byref(smp), n,
-                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")), _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")),
-                       _lib.ptr(out.get("probs")))
-            return out
-        self._call(self.lib.abr_env_step_policy, self._h, C.byref(pol), n, _lib.ptr(out.get("obs")),
-                   _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")),
-                   _lib.ptr(out.get("features")), _lib.ptr(out.get("scores")))
+        self._policy_call(controller, pol, val, out, n_steps=n)
         return out
+
+    _SELECT_OUT = ("actions", "features", "scores", "probs", "value", "hidden")
+    _STEP_OUT = ("obs", "reward", "done", "actions", "features", "scores", "probs", "values", "last_value", "hidden")
+
+    def _policy_call(self, controller, pol, val, out, n_steps=None, commit=None):
+        """The one call behind every learned-policy select (n_steps None) and every step_policy.  controller.entries(val,
+        probs wanted) names the (select, step) pair of C entry points it takes, the structs they take after the policy's,
+        and how many of the optional output groups -- probs; value(s); hidden -- they have; the rest is the same for all:
+        n_steps (or the recurrent select's commit), then the outputs in the header's order, None where not wanted."""
+        (select, step), structs, groups = controller.entries(val, out.get("probs") is not None)
+        lead = [C.byref(pol)] + [C.byref(s) if s is not None else None for s in structs]
+        if n_steps is None:
+            name, keys = select, self._SELECT_OUT[:3 + groups]
+            lead += [] if commit is None else [int(bool(commit))]
+        else:
+            name, keys = step, self._STEP_OUT[:6 + (0, 1, 3, 4)[groups]]
+            lead.append(n_steps)
+        self._call(getattr(self.lib, name), self._h, *lead, *(_lib.ptr(out.get(k)) for k in keys))
 
     # -- exact state -------------------------------------------------------
     def observe_f64(self):

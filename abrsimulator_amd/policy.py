@@ -77,6 +77,24 @@ def pack_gru(cell, head):
     return pack_layers([cell[:2], cell[2:], head])
 
 
+def _select(ctl, want_features, want_scores, want_probs, want_value, want_hidden=False, commit=None):
+    """The select of every controller: the outputs that are wanted, then the controller's select entry
+    (BatchedABREnv._policy_call, which asks ctl.entries() which one that is)."""
+    env = ctl.player.env
+    N, dev = env.n_lanes, env.device
+    f32 = lambda rows, want: torch.empty(rows, N, dtype=torch.float32, device=dev) if want else None
+    out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev), features=f32(ctl.feature_dim, want_features),
+               scores=f32(ctl.n_rates, want_scores), probs=f32(ctl.n_rates, want_probs))
+    pol = ctl.bound(env)
+    val = ctl.value() if want_value else None
+    if want_value:
+        out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
+    if want_hidden:
+        out["hidden"] = f32(ctl.hidden_size, True)
+    env._policy_call(ctl, pol, val, out, commit=commit)
+    return out
+
+
 class PolicyController:
     """An MLP policy over `player` (an EnvPlayer: the environment is player.env).
 
@@ -325,37 +343,20 @@ class PolicyController:
         [F, N], scores float32 [M, N], probs float32 [M, N] -- the policy's distribution before exploration); a lane
         whose done bits are set answers -1 with zero columns.  An entry that is not wanted is None.  want_value=True
         (a controller with a value head) adds value float32 [N], the critic's V of the current state, 0 on a done lane."""
-        env = self.player.env
-        N, dev = env.n_lanes, env.device
-        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
-                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
-                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
-                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
-        pol = self.bound(env)
-        if self.engine == "matrix":                                       # one entry for every mode
-            val, smp = (self.value() if want_value else None), self.sampling()
-            if want_value:
-                out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
-            env._call(env.lib.abr_env_policy_select_mx, env._h, C.byref(pol), C.byref(smp),
-                      C.byref(val) if val is not None else None, _lib.ptr(out["actions"]), _lib.ptr(out["features"]),
-                      _lib.ptr(out["scores"]), _lib.ptr(out["probs"]), _lib.ptr(out.get("value")))
-            return out
-        if want_value:
-            val, smp = self.value(), self.sampling()
-            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
-            env._call(env.lib.abr_env_policy_select_ac, env._h, C.byref(pol), C.byref(smp), C.byref(val),
-                      _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]),
-                      _lib.ptr(out["probs"]), _lib.ptr(out["value"]))
-            return out
+        return _select(self, want_features, want_scores, want_probs, want_value)
+
+    def entries(self, val, want_probs):
+        """What BatchedABREnv._policy_call asks a controller: the (select, step) pair of C entry points it takes with the
+        value struct `val` (None: no values) and with or without probs, the structs those take after the policy's, and
+        how many optional output groups they have (0: none, 1: probs, 2: and value(s), 3: and hidden)."""
+        smp = self.sampling()
+        if self.engine == "matrix":                                       # one entry pair for every mode
+            return ("abr_env_policy_select_mx", "abr_env_step_policy_mx"), (smp, val), 2
+        if val is not None:
+            return ("abr_env_policy_select_ac", "abr_env_step_policy_ac"), (smp, val), 2
         if self.uses_sampled_entries(want_probs):
-            smp = self.sampling()
-            env._call(env.lib.abr_env_policy_select_sampled, env._h, C.byref(pol), C.byref(smp),
-                      _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]),
-                      _lib.ptr(out["probs"]))
-        else:
-            env._call(env.lib.abr_env_policy_select, env._h, C.byref(pol), _lib.ptr(out["actions"]),
-                      _lib.ptr(out["features"]), _lib.ptr(out["scores"]))
-        return out
+            return ("abr_env_policy_select_sampled", "abr_env_step_policy_sampled"), (smp,), 1
+        return ("abr_env_policy_select", "abr_env_step_policy"), (), 0
 
     def uses_sampled_entries(self, want_probs):
         """An argmax policy without probs keeps the abr_policy entry points; anything else takes the sampled ones."""
@@ -596,21 +597,13 @@ class PolicyPopulation:
     def select(self, want_features=True, want_scores=True, want_probs=False, want_value=False):
         """One decision per lane on the environment's current state, every lane by its own member: the same dict as
         PolicyController.select."""
-        env = self.player.env
-        N, dev = env.n_lanes, env.device
-        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
-                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
-                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
-                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
-        pol, pop, smp = self.bound(env), self.population(), self.sampling()
-        val = self.value() if want_value else None
-        if want_value:
-            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
-        fn = env.lib.abr_env_policy_select_mx_pop if self.engine == "matrix" else env.lib.abr_env_policy_select_pop
-        env._call(fn, env._h, C.byref(pol), C.byref(pop), C.byref(smp), C.byref(val) if val is not None else None,
-                  _lib.ptr(out["actions"]), _lib.ptr(out["features"]), _lib.ptr(out["scores"]), _lib.ptr(out["probs"]),
-                  _lib.ptr(out.get("value")))
-        return out
+        return _select(self, want_features, want_scores, want_probs, want_value)
+
+    def entries(self, val, want_probs):
+        """As PolicyController.entries: one pair per engine, every mode (abr_policy_pop before smp)."""
+        names = (("abr_env_policy_select_mx_pop", "abr_env_step_policy_mx_pop") if self.engine == "matrix" else
+                 ("abr_env_policy_select_pop", "abr_env_step_policy_pop"))
+        return names, (self.population(), self.sampling(), val), 2
 
     def next_bitrate(self):
         """int32 [N]: each lane's action by its member's network (-1 for finished lanes)."""
@@ -791,23 +784,11 @@ class RecurrentPolicyController:
         with want_hidden=True hidden float32 [H, N], the state each decision was taken from (zeros at a lane's first
         chunk).  commit=False leaves `hidden` as it is, so that select can be called any number of times; commit=True
         advances it, which is right exactly when a step of the returned actions follows."""
-        env = self.player.env
-        N, dev = env.n_lanes, env.device
-        out = dict(actions=torch.empty(N, dtype=torch.int32, device=dev),
-                   features=torch.empty(self.feature_dim, N, dtype=torch.float32, device=dev) if want_features else None,
-                   scores=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_scores else None,
-                   probs=torch.empty(self.n_rates, N, dtype=torch.float32, device=dev) if want_probs else None)
-        pol, smp = self.bound(env), self.sampling()
-        val = self.value() if want_value else None
-        if want_value:
-            out["value"] = torch.empty(N, dtype=torch.float32, device=dev)
-        if want_hidden:
-            out["hidden"] = torch.empty(self.hidden_size, N, dtype=torch.float32, device=dev)
-        env._call(env.lib.abr_env_policy_select_gru, env._h, C.byref(pol), C.byref(smp),
-                  C.byref(val) if val is not None else None, int(bool(commit)), _lib.ptr(out["actions"]),
-                  _lib.ptr(out["features"]), _lib.ptr(out["scores"]), _lib.ptr(out["probs"]), _lib.ptr(out.get("value")),
-                  _lib.ptr(out.get("hidden")))
-        return out
+        return _select(self, want_features, want_scores, want_probs, want_value, want_hidden, commit)
+
+    def entries(self, val, want_probs):
+        """As PolicyController.entries: one pair for every mode, with the hidden outputs."""
+        return ("abr_env_policy_select_gru", "abr_env_step_policy_gru"), (self.sampling(), val), 3
 
     def next_bitrate(self):
         """int32 [N]: the policy's action for each lane (-1 for finished lanes).  It commits the new hidden state: the
