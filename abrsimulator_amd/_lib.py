@@ -146,6 +146,13 @@ class PolicyGru(C.Structure):
                 ("explore_threshold", C.c_uint64), ("reserved_", C.c_int32 * 4)]
 
 
+POLICY_GRU_MX_MAX_HIDDEN = 128
+
+
+class PolicyGruMx(C.Structure):       # abr_policy_gru_mx: a distinct type with abr_policy_gru's layout
+    _fields_ = list(PolicyGru._fields_)
+
+
 SPEED_RULE_MAX_THR = 4
 
 
@@ -269,6 +276,11 @@ SYMBOLS = [
                                             C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_env_step_policy_gru", C.c_int, [_P, C.POINTER(PolicyGru), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
                                           C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_policy_gru_mx_weights_bytes", C.c_int, [C.POINTER(PolicyGruMx), C.c_int32, C.POINTER(C.c_size_t)]),
+    ("abr_env_gru_mx_select", C.c_int, [_P, C.POINTER(PolicyGruMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                        C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_gru_mx_step", C.c_int, [_P, C.POINTER(PolicyGruMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
+                                      C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_trace_synth", C.c_int, [C.POINTER(TraceModel), C.c_uint64, C.c_uint32, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),

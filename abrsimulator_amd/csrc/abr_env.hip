@@ -3956,11 +3956,348 @@ static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruArgs &a, 
 }
 
 // ---------------------------------------------------------------------------
+// The matrix engine of the recurrent policy (include/abr_env.h: abr_policy_gru_mx): abr_policy_gru's chains on
+// v_mfma_f32_32x32x2_f32, H up to 128
+// ---------------------------------------------------------------------------
+// The prologue and the epilogue are policy_mx_kernel's: one thread per env lane, a wave's 64 env lanes as two column tiles
+// of 32.  In between (abr_lane_jump.h: gru_mx_*) the 3H gate rows are the rows of the product, 32 units at a time.  A
+// lane's B registers of h_in come straight from the slab -- input 2 s + (lane >> 5) of env lane 32 t + (lane & 31), all of
+// them before the first store of h' -- and register r of unit tile U's accumulators holds the unit that B register
+// 16 U + r holds, so the gates are element-wise on registers, the lane that loaded h_in[j] of a column is the lane that
+// stores its h'[j] (a commit in place is safe), and a tile's h' is as it stands the B operand of output steps
+// 16 U .. 16 U + 15: it is folded into the output accumulator at once, U ascending, so every output stays a k-ordered
+// chain.  The workgroup stages one unit tile at a time in LDS in operand order (gru_mx_staged_at: per gate the W_ih
+// steps, the W_hh steps, each padded to whole groups, then the tile's slice of the output rows; at most 68 608 B, one
+// ds_read_b32 per MFMA) between two barriers.  The column tiles are the outer loop and the unit tiles the inner one,
+// both rolled: one column tile's B operands are resident at a time (64 of h_in, 18 of x) and a unit tile is staged again
+// for the second column tile; the gates retire one after another (r, z, then n with h'), two accumulators live at a
+// time.  One wave per SIMD has the whole unified register file.  Biases are read from the blob when an accumulator is
+// initialised.  No thread leaves before the last MFMA; a lane past n_lanes or a finished lane carries a zero column and
+// is masked at every store.
+// The arguments are the lane engine's (PolicyGruArgs).
+// One chain of one accumulator: `steps` MFMAs, k ascending, a group of kGruMxGroup at a time.  at = the chain's first
+// staged row + lane, b[s] the B register of step s.  A step of the last group past `steps` reads a pad row (-0.0f) against a
+// B register that is +0.0f: an exact no-op, and no step needs a predicate of its own.
+static_assert(kMxGroup == abrx::kGruMxGroup, "one group size");
+template <int MAXS>
+__device__ __forceinline__ void gru_mx_chain(const float *__restrict__ at, int32_t steps, const float *b, mx_acc_t &acc) {
+#pragma unroll
+    for (int g = 0; g < MAXS / kMxGroup; g++) {
+        if (g * kMxGroup < steps) {
+            float av[kMxGroup];
+#pragma unroll
+            for (int j = 0; j < kMxGroup; j++) av[j] = at[(g * kMxGroup + j) * abrx::kMxWave];
+#pragma unroll
+            for (int j = 0; j < kMxGroup; j++)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[j], b[g * kMxGroup + j], acc, 0, 0, 0);
+        }
+    }
+}
+
+template <bool SAMPLED, bool VALUE>
+__global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(EnvParams p, PolicyGruArgs a) {
+    extern __shared__ float gmx_lds[];
+    constexpr int kHSteps = abrx::kGruMxMaxHidden / 2;
+    constexpr int kXSteps = (abrx::kPolicyMaxF / 2 + kMxGroup - 1) / kMxGroup * kMxGroup;   // whole groups
+    static_assert(kHSteps % kMxGroup == 0 && kHSteps == abrx::kGruMxMaxTiles * abrx::kMxRegs, "groups and tiles");
+    const int64_t N = p.n_lanes;
+    const int64_t i = (int64_t)blockIdx.x * kMxBlock + threadIdx.x;
+    const int32_t lane = threadIdx.x & (abrx::kMxWave - 1), half = abrx::mx_b_k(lane);
+    const abrx::PolicyNet &n = a.net;
+    const int32_t H = n.w0;
+    const bool inside = i < N;
+    int32_t c = 0;
+    bool live = false;
+    if (inside) {
+        c = p.chunk_id[i];
+        live = !(p.done[i] || c < 0 || c >= p.video_length);
+    }
+    const bool decide = !VALUE || a.action_out;              // false: a value evaluation only
+    float x[abrx::kPolicyMaxF];
+    if (live) {
+        const double G = p.G[p.k[i]];
+        const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
+        const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
+        const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+        abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    } else {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) x[f] = 0.0f;
+    }
+    // One column tile at a time (a loop, not an unrolled pair: the registers of one tile's B operands are live, 64 of
+    // h_in and 18 of x), and within it the unit tiles, each staged again for the second column tile from what the first
+    // left in the cache.  This lane's B registers for column tile t, whose env lane is `col`: xb[s] = x[2 s + half],
+    // h[s] = h_in[2 s + half] -- +0.0f where c == 0, where the column's lane takes no decision and past H.
+    const int32_t tiles = abrx::gru_mx_tiles(H);
+    const bool commit = a.commit != 0;
+    float sc[abrx::kPolicyMaxRates] = {};
+    [[maybe_unused]] float value = 0.0f;
+#pragma unroll 1
+    for (int32_t t = 0; t < 2; t++) {
+        // Ht and Nt are H and N behind an empty statement: what follows is the same for both column tiles and for every
+        // unit tile, and the compiler would otherwise compute its predicates, offsets and addresses once, ahead of the
+        // loops, and keep them all (the same again at the top of the unit-tile loop).
+        int32_t Ht = H;
+        int64_t Nt = N;
+        asm volatile("" : "+s"(Ht), "+s"(Nt));
+        const int32_t src = abrx::kMxTile * t + abrx::mx_b_col(lane);
+        const int64_t col = i - lane + src;
+        const bool col_live = __shfl((int32_t)live, src) != 0;
+        const bool col_read = col_live && __shfl(c, src) != 0;
+        float xb[kXSteps] = {}, h[kHSteps];
+#pragma unroll
+        for (int s = 0; s < abrx::kPolicyMaxF / 2; s++) {
+            const float k0 = __shfl(x[2 * s], src), k1 = __shfl(x[2 * s + 1], src);
+            xb[s] = half ? k1 : k0;
+        }
+        // The slab, a tile of units at a time (a uniform branch each, then a scheduling fence, so that the addresses of
+        // one tile's reads are in flight at a time).  Every read is unconditional and inside the slab -- a column past
+        // n_lanes reads column 0, the odd half past an odd H reads the even row -- and hmax discards what the lane may
+        // not use.  All of them are issued before this column tile's first store of h'.
+        {
+            const bool in = col < Nt, report = decide && a.hidden_out && in;
+            const int32_t hmax = col_read ? Ht : 0;
+            const int64_t hoff = half ? Nt : 0;
+            const float *row = a.state + (in ? col : 0);         // running pointers, two rows a step
+            float *orow = a.hidden_out + col + hoff;
+#pragma unroll
+            for (int T = 0; T < abrx::kGruMxMaxTiles; T++) {
+                if (abrx::kMxTile * T < Ht) {
+#pragma unroll
+                    for (int r = 0; r < abrx::kMxRegs; r++) {
+                        const int s = abrx::kMxRegs * T + r;
+                        const float v = row[2 * s + 1 < Ht ? hoff : 0];
+                        h[s] = 2 * s + half < hmax ? v : 0.0f;
+                        if (2 * s + 2 < Ht) row += 2 * Nt;
+                    }
+                    if (report) {
+#pragma unroll
+                        for (int r = 0; r < abrx::kMxRegs; r++) {
+                            const int s = abrx::kMxRegs * T + r;
+                            if (2 * s + half < Ht) {
+                                *orow = h[s];
+                            }
+                            orow += 2 * Nt;
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+#pragma unroll
+                    for (int r = 0; r < abrx::kMxRegs; r++) h[abrx::kMxRegs * T + r] = 0.0f;
+                }
+            }
+        }
+        mx_acc_t out;
+        {
+            const abrx::GruMx y = abrx::gru_mx(a.weights, VALUE ? a.head : nullptr, n.F, Ht, n.M);
+#pragma unroll
+            for (int r = 0; r < abrx::kMxRegs; r++) out[r] = abrx::gru_mx_b_out(y, abrx::mx_acc_unit(lane, r));
+        }
+#pragma unroll 1
+        for (int32_t U = 0; U < tiles; U++) {
+            int32_t Hu = H;
+            asm volatile("" : "+s"(Hu));
+            const abrx::GruMx y = abrx::gru_mx(a.weights, VALUE ? a.head : nullptr, n.F, Hu, n.M);
+            const int32_t rows = abrx::gru_mx_rows(n.F, Hu), sF = abrx::mx_steps(n.F), sH = abrx::mx_steps(Hu);
+            __syncthreads();                                 // every wave has left the tile staged before
+            {
+                // a wave takes kBatch consecutive rows at a time and issues their gathers before its first store
+                constexpr int kBatch = 8;
+                for (int32_t q0 = kBatch * (threadIdx.x / abrx::kMxWave); q0 < rows; q0 += kBatch * (kMxBlock / abrx::kMxWave)) {
+                    float v[kBatch];
+#pragma unroll
+                    for (int j = 0; j < kBatch; j++) v[j] = q0 + j < rows ? abrx::gru_mx_staged_at(y, U, q0 + j, lane) : 0.0f;
+#pragma unroll
+                    for (int j = 0; j < kBatch; j++) {
+                        if (q0 + j < rows) gmx_lds[(q0 + j) * abrx::kMxWave + lane] = v[j];
+                    }
+                }
+            }
+            __syncthreads();
+            const int32_t j0 = abrx::kMxTile * U;            // register r holds unit j0 + mx_acc_unit(lane, r)
+            // gate by gate, so that two accumulators are live at a time: r, z, then n and with it h'
+            float rz[2][abrx::kMxRegs];
+            mx_acc_t hp;
+#pragma unroll
+            for (int g = 0; g < 3; g++) {
+                mx_acc_t gi, gh;
+#pragma unroll
+                for (int r = 0; r < abrx::kMxRegs; r++) {
+                    gi[r] = abrx::gru_mx_b_ih(y, g, j0 + abrx::mx_acc_unit(lane, r));
+                    gh[r] = abrx::gru_mx_b_hh(y, g, j0 + abrx::mx_acc_unit(lane, r));
+                }
+                gru_mx_chain<kXSteps>(gmx_lds + abrx::gru_mx_ih_row(n.F, Hu, g) * abrx::kMxWave + lane, sF, xb, gi);
+                gru_mx_chain<kHSteps>(gmx_lds + abrx::gru_mx_hh_row(n.F, Hu, g) * abrx::kMxWave + lane, sH, h, gh);
+#pragma unroll
+                for (int r = 0; r < abrx::kMxRegs; r++) {
+                    if (g < 2) {
+                        rz[g][r] = abrx::gru_mx_gate(gi[r], gh[r]);
+                    } else {
+                        // h_in of the unit: B register 16 U + r (U is a loop counter: a select, not an index)
+                        const float hj = U == 0 ? h[r] : U == 1 ? h[abrx::kMxRegs + r]
+                                       : U == 2 ? h[2 * abrx::kMxRegs + r] : h[3 * abrx::kMxRegs + r];
+                        hp[r] = abrx::gru_mx_unit(rz[0][r], rz[1][r], gi[r], gh[r], hj, j0 + abrx::mx_acc_unit(lane, r) < Hu);
+                    }
+                }
+            }
+            if (commit && col_live) {
+                float *srow = a.state + col + (int64_t)(j0 + half) * Nt;
+#pragma unroll
+                for (int r = 0; r < abrx::kMxRegs; r++) {
+                    if (j0 + abrx::mx_acc_unit(lane, r) < Hu) {
+                        *srow = hp[r];
+                    }
+                    srow += 2 * Nt;
+                }
+            }
+            const float *ao = gmx_lds + abrx::gru_mx_out_row(n.F, Hu) * abrx::kMxWave + lane;
+            float av[abrx::kMxRegs];
+#pragma unroll
+            for (int s = 0; s < abrx::kMxRegs; s++) av[s] = ao[s * abrx::kMxWave];
+#pragma unroll
+            for (int s = 0; s < abrx::kMxRegs; s++) out = __builtin_amdgcn_mfma_f32_32x32x2f32(av[s], hp[s], out, 0, 0, 0);
+        }
+        // Unit u of env lane 32 t + j sits in register mx_unit_reg(u) of wave lane j + 32 mx_unit_half(u): back to the
+        // thread that owns the env lane, which is in this column tile when lane >> 5 == t.
+        const bool mine = (lane >> 5) == t;
+        const auto unit = [&](auto Uc, float old) {
+            constexpr int u = decltype(Uc)::value;
+            const float v = __shfl(out[abrx::mx_unit_reg(u)], abrx::mx_d_col(lane) + abrx::kMxTile * abrx::mx_unit_half(u));
+            return mine ? v : old;
+        };
+#define ABR_MX_UNIT(U) sc[U] = unit(std::integral_constant<int, U>{}, sc[U]);
+        ABR_MX_UNIT(0) ABR_MX_UNIT(1) ABR_MX_UNIT(2) ABR_MX_UNIT(3) ABR_MX_UNIT(4) ABR_MX_UNIT(5) ABR_MX_UNIT(6) ABR_MX_UNIT(7)
+        ABR_MX_UNIT(8) ABR_MX_UNIT(9) ABR_MX_UNIT(10) ABR_MX_UNIT(11) ABR_MX_UNIT(12) ABR_MX_UNIT(13) ABR_MX_UNIT(14) ABR_MX_UNIT(15)
+#undef ABR_MX_UNIT
+        if constexpr (VALUE) value = unit(std::integral_constant<int, abrx::kMxValueUnit>{}, value);
+    }
+    if (!inside) return;
+    // every output pointer is first read here, after the loops: none of them is live across the MFMAs
+    if (decide && a.features_out) {
+#pragma unroll
+        for (int f = 0; f < abrx::kPolicyMaxF; f++) {
+            if (f < n.F) {
+                a.features_out[f * N + i] = x[f];
+            }
+        }
+    }
+    if (!live) {
+        if constexpr (VALUE) {
+            if (a.value_out) a.value_out[i] = 0.0f;
+        }
+        if (!decide) return;
+        a.action_out[i] = -1;
+        if (a.scores_out)
+            for (int32_t m = 0; m < n.M; m++) a.scores_out[m * N + i] = 0.0f;
+        if constexpr (SAMPLED) {
+            if (a.probs_out)
+                for (int32_t m = 0; m < n.M; m++) a.probs_out[m * N + i] = 0.0f;
+        }
+        return;
+    }
+    if constexpr (VALUE) {
+        if (a.value_out) a.value_out[i] = value;
+    }
+    if (!decide) return;
+    float *so = a.scores_out;
+    [[maybe_unused]] float *scol = gmx_lds + abrx::gru_mx_score_offset(n.F, H) + threadIdx.x;
+    int32_t g = 0;
+    float best = 0.0f;
+#pragma unroll
+    for (int m = 0; m < abrx::kPolicyMaxRates; m++) {
+        if (m < n.M) {
+            const float v = sc[m];
+            if (so) so[m * N + i] = v;
+            if constexpr (SAMPLED) scol[m * kMxBlock] = v;
+            if (m == 0) best = v;
+            else if (v > best) { best = v; g = m; }
+        }
+    }
+    int32_t action;
+    if constexpr (!SAMPLED) {
+        action = abrx::policy_explore(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g);
+    } else {
+        float *po = a.probs_out;
+        const auto buf = [&](int32_t m) -> float & { return scol[m * kMxBlock]; };
+        const auto prob = [&](int32_t m, float v) { if (po) po[m * N + i] = v; };
+        action = abrx::policy_decide(n, (uint64_t)(p.lane_id_base + i), c, p.episode_no[i], g, a.mode, a.inv_temperature,
+                                     buf, prob);
+    }
+    a.action_out[i] = action;
+}
+
+static int validate_policy_shape(const abr_policy_gru_mx *pol) {
+    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
+    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
+        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
+    if (pol->hidden < 1 || pol->hidden > ABR_POLICY_GRU_MX_MAX_HIDDEN)
+        return fail(ABR_E_INVALID, "policy hidden %d outside 1..%d", pol->hidden, ABR_POLICY_GRU_MX_MAX_HIDDEN);
+    return ABR_OK;
+}
+
+extern "C" int abr_policy_gru_mx_weights_bytes(const abr_policy_gru_mx *pol, int32_t n_rates, size_t *bytes_out) {
+    int rc = validate_policy_shape(pol);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *bytes_out = policy_gru_weights_bytes(pol->window, pol->hidden, n_rates);
+    return ABR_OK;
+}
+
+// the builder: policy_gru_args' checks and fields for the wider struct (the kernels share PolicyGruArgs)
+static int policy_gru_mx_args(const abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
+                              const abr_policy_value *val, const abr_policy_pop *, PolicyGruArgs *a) {
+    const int32_t M = env->p.n_rates, H = pol->hidden;
+    int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
+    if (rc) return rc;
+    const size_t state = (size_t)H * (size_t)env->p.n_lanes * sizeof(float);
+    if (pol->state_bytes != state)
+        return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
+                    (long long)env->p.n_lanes, state);
+    if ((rc = check_head_bytes(val, (size_t)H))) return rc;
+    *a = PolicyGruArgs{};
+    a->net = policy_net(pol, M);
+    a->net.n_hidden = 1; a->net.w0 = H;
+    a->weights = pol->weights_dev; a->state = pol->state_dev;
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    if (val) a->head = val->head_dev;
+    return ABR_OK;
+}
+
+// A unit tile at H = 128, W = 16, 16 rates is 68 608 B, past the 64 KiB a kernel may take by default: each instance's
+// dynamic-LDS limit is raised once, to the largest launch the contract allows (with the score columns: 84 992 B).
+template <bool SAMPLED, bool VALUE>
+static hipError_t launch_policy_gru_mx_instance(const abr_env *env, const PolicyGruArgs &a, size_t lds, hipStream_t st) {
+    static bool raised = false;
+    if (!raised) {
+        const int most = (int)((size_t)abrx::gru_mx_lds_floats(abrx::kPolicyMaxF, ABR_POLICY_GRU_MX_MAX_HIDDEN, ABR_MAX_RATES,
+                                                               true, kMxBlock) * sizeof(float));
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_mx_kernel<SAMPLED, VALUE>),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e != hipSuccess) return e;
+        raised = true;
+    }
+    hipLaunchKernelGGL((policy_gru_mx_kernel<SAMPLED, VALUE>), dim3((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)),
+                       dim3(kMxBlock), lds, st, env->p, a);
+    return hipGetLastError();
+}
+
+// the one chooser of policy_gru_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_gru
+static hipError_t launch_policy_gru_mx(const abr_env *env, const PolicyGruArgs &a, hipStream_t st) {
+    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    const size_t lds = (size_t)abrx::gru_mx_lds_floats(a.net.F, a.net.w0, a.net.M, sampled, kMxBlock) * sizeof(float);
+    if (sampled && value) return launch_policy_gru_mx_instance<true, true>(env, a, lds, st);
+    if (sampled) return launch_policy_gru_mx_instance<true, false>(env, a, lds, st);
+    if (value) return launch_policy_gru_mx_instance<false, true>(env, a, lds, st);
+    return launch_policy_gru_mx_instance<false, false>(env, a, lds, st);
+}
+
+// ---------------------------------------------------------------------------
 // The host path of the learned-policy entries: one validator, one select, one rollout, whatever the engine
 // ---------------------------------------------------------------------------
 // An engine is an argument struct, a builder that fills it after the handle (policy_lane_args, policy_mx_args,
-// policy_gru_args) and a launcher that picks the kernel instance (launch_policy_lane, launch_policy_mx, launch_policy_gru),
-// next to its validate_policy_shape.  Everything below is shared.
+// policy_gru_args, policy_gru_mx_args) and a launcher that picks the kernel instance (launch_policy_lane, launch_policy_mx,
+// launch_policy_gru, launch_policy_gru_mx), next to its validate_policy_shape.  Everything below is shared.
 
 // the sampling struct alone
 static int validate_sampling(const abr_policy_sampling *smp) {
@@ -3999,7 +4336,7 @@ static int validate_pop(const abr_policy_pop *pop) {
     return ABR_OK;
 }
 
-// what abr_policy, abr_policy_mx and abr_policy_gru hold past their shape: reserved words, pointers, threshold
+// what abr_policy, abr_policy_mx, abr_policy_gru and abr_policy_gru_mx hold past their shape: reserved words, pointers, threshold
 template <class Pol>
 static int validate_policy_fields(const Pol *pol) {
     for (int32_t r : pol->reserved_)
@@ -4007,7 +4344,7 @@ static int validate_policy_fields(const Pol *pol) {
     if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
         return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
     if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
-    if constexpr (std::is_same_v<Pol, abr_policy_gru>) {
+    if constexpr (std::is_same_v<Pol, abr_policy_gru> || std::is_same_v<Pol, abr_policy_gru_mx>) {
         if (!pol->state_dev || ((uintptr_t)pol->state_dev & 3))
             return fail(ABR_E_INVALID, "policy state must be non-NULL and 4-byte aligned");
     }
@@ -4230,6 +4567,27 @@ extern "C" int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, 
                                        float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                        void *stream) {
     return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// the recurrent policy's matrix engine: the same pair, the wider struct
+extern "C" int abr_env_gru_mx_select(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
+                                     const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
+                                     float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                     float *value_out_dev, float *hidden_out_dev, void *stream) {
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
+                        stream, commit != 0);
+}
+
+extern "C" int abr_env_gru_mx_step(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
+                                   const abr_policy_value *val, int32_t n_steps, float *obs_out_dev,
+                                   float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                   float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
+                                   float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
+                                   void *stream) {
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }

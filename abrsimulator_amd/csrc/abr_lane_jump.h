@@ -1402,6 +1402,102 @@ ABR_HD int32_t mx_lds_floats(int32_t F, int32_t M, int32_t n_hidden, const int32
     return cap;
 }
 
+// ---------------------------------------------------------------------------
+// The matrix engine of the recurrent policy (include/abr_env.h: abr_policy_gru_mx; abr_env.hip: policy_gru_mx_kernel):
+// abr_policy_gru's chains on the same instruction.  The 3H gate rows are the rows of the product, a tile of 32 units at a
+// time: unit j = 32 U + u of EVERY gate sits in row mx_unit_row(u) of its gate's product, so the six accumulators of a
+// tile (gi and gh of r, z, n) hold unit 32 U + mx_acc_unit(l, r) in register r of lane l, and the gate arithmetic is
+// element-wise on registers.  That unit is also input 2 (16 U + r) + (l >> 5) of the recurrent chains: register r of
+// tile U sits where B register 16 U + r of h_in sits (d = h_in[j] - n needs no shuffle), and a tile's h' is, as it
+// stands, the B operand of steps 16 U .. 16 U + 15 of the output layer.
+//
+// The staged operands of one unit tile are gru_mx_rows() rows of 64 floats (the A registers of one step): per gate the
+// steps of W_ih then of W_hh, each rounded up to whole groups of kGruMxGroup steps (the kernel issues a group at a time
+// and asks nothing of a step but its number: the rows past a chain's last step are pads), then the kMxRegs steps of the
+// output layer (and the value head, row kMxValueUnit) that the tile's units feed.  Pads are -0.0f against +0.0f as
+// above; a unit past H has -0.0f weights and biases and its h' is forced to +0.0f before it is folded into the outputs.
+// ---------------------------------------------------------------------------
+constexpr int kGruMxMaxHidden = 128, kGruMxMaxTiles = kGruMxMaxHidden / kMxTile, kGruMxGroup = 4;
+
+// the blob of abr_policy_gru, by matrix; out is the output layer as the MLP's engine sees one (extra: the value head)
+struct GruMx { const float *Wih, *Whh, *bih, *bhh; MxLayer out; int32_t F, H; };
+
+ABR_HD GruMx gru_mx(const float *blob, const float *head, int32_t F, int32_t H, int32_t M) {
+    const float *Wih = blob, *Whh = Wih + (int64_t)3 * H * F, *bih = Whh + (int64_t)3 * H * H, *bhh = bih + 3 * H,
+                *Wout = bhh + 3 * H;
+    return GruMx{Wih, Whh, bih, bhh, MxLayer{Wout, Wout + (int64_t)M * H, H, M, head}, F, H};
+}
+
+ABR_HD int32_t gru_mx_tiles(int32_t H) { return (H + kMxTile - 1) / kMxTile; }
+// rows of one gate's staged operands (its W_ih steps, then its W_hh steps), and of a whole unit tile
+ABR_HD int32_t gru_mx_chain_rows(int32_t in) { return (mx_steps(in) + kGruMxGroup - 1) / kGruMxGroup * kGruMxGroup; }
+ABR_HD int32_t gru_mx_gate_rows(int32_t F, int32_t H) { return gru_mx_chain_rows(F) + gru_mx_chain_rows(H); }
+ABR_HD int32_t gru_mx_rows(int32_t F, int32_t H) { return 3 * gru_mx_gate_rows(F, H) + kMxRegs; }
+// the first row of gate g's W_ih steps, of its W_hh steps, and of the output steps
+ABR_HD int32_t gru_mx_ih_row(int32_t F, int32_t H, int32_t g) { return g * gru_mx_gate_rows(F, H); }
+ABR_HD int32_t gru_mx_hh_row(int32_t F, int32_t H, int32_t g) { return g * gru_mx_gate_rows(F, H) + gru_mx_chain_rows(F); }
+ABR_HD int32_t gru_mx_out_row(int32_t F, int32_t H) { return 3 * gru_mx_gate_rows(F, H); }
+
+// Gate g's weights and first terms for unit j (j >= H: a padded unit).  Every read is unconditional, from a clamped index,
+// and the pad is selected afterwards: no branch on the device, where a wave's lanes straddle the last unit and the last k.
+ABR_HD int32_t gru_mx_clamp(int32_t v, int32_t n) { return v < n ? v : n - 1; }
+ABR_HD float gru_mx_w_ih(const GruMx &y, int32_t g, int32_t j, int32_t k) {
+    const float w = y.Wih[((int64_t)g * y.H + gru_mx_clamp(j, y.H)) * y.F + gru_mx_clamp(k, y.F)];
+    return j < y.H && k < y.F ? w : -0.0f;
+}
+ABR_HD float gru_mx_w_hh(const GruMx &y, int32_t g, int32_t j, int32_t k) {
+    const float w = y.Whh[((int64_t)g * y.H + gru_mx_clamp(j, y.H)) * y.H + gru_mx_clamp(k, y.H)];
+    return j < y.H && k < y.H ? w : -0.0f;
+}
+ABR_HD float gru_mx_b_ih(const GruMx &y, int32_t g, int32_t j) {
+    const float b = y.bih[g * y.H + gru_mx_clamp(j, y.H)];
+    return j < y.H ? b : -0.0f;
+}
+ABR_HD float gru_mx_b_hh(const GruMx &y, int32_t g, int32_t j) {
+    const float b = y.bhh[g * y.H + gru_mx_clamp(j, y.H)];
+    return j < y.H ? b : -0.0f;
+}
+// the output tile's weight (mx_weight's) and first term (mx_bias's) for row unit u: scores 0 .. M-1, the value head at
+// kMxValueUnit, pads elsewhere
+ABR_HD float gru_mx_w_out(const GruMx &y, int32_t u, int32_t k) {
+    const bool score = u < y.out.out, value = y.out.extra && u == kMxValueUnit;
+    const float *row = value ? y.out.extra : y.out.W + (int64_t)gru_mx_clamp(u, y.out.out) * y.H;
+    const float w = row[gru_mx_clamp(k, y.H)];
+    return (score || value) && k < y.H ? w : -0.0f;
+}
+ABR_HD float gru_mx_b_out(const GruMx &y, int32_t u) {
+    const bool score = u < y.out.out, value = y.out.extra && u == kMxValueUnit;
+    const float *at = value ? y.out.extra + y.H : y.out.b + gru_mx_clamp(u, y.out.out);
+    const float b = *at;
+    return score || value ? b : -0.0f;
+}
+
+// the A register of lane l in row q (0 .. gru_mx_rows) of unit tile U's staged operands
+ABR_HD float gru_mx_staged_at(const GruMx &y, int32_t U, int32_t q, int32_t l) {
+    const int32_t P = gru_mx_gate_rows(y.F, y.H), sF = gru_mx_chain_rows(y.F);   // a pad row: k past F or H
+    const int32_t u = mx_row_unit(mx_a_row(l)), kk = mx_a_k(l);
+    if (q >= 3 * P) return gru_mx_w_out(y, u, 2 * (kMxRegs * U + (q - 3 * P)) + kk);
+    const int32_t g = (q >= P) + (q >= 2 * P), s = q - g * P, j = kMxTile * U + u;
+    return s < sF ? gru_mx_w_ih(y, g, j, 2 * s + kk) : gru_mx_w_hh(y, g, j, 2 * (s - sF) + kk);
+}
+
+// LDS floats of a launch: one unit tile's staged operands, then the SAMPLED instances' score columns ([M][block])
+ABR_HD int32_t gru_mx_score_offset(int32_t F, int32_t H) { return gru_mx_rows(F, H) * kMxWave; }
+ABR_HD int32_t gru_mx_lds_floats(int32_t F, int32_t H, int32_t M, bool sampled, int32_t block) {
+    return gru_mx_score_offset(F, H) + (sampled ? M * block : 0);
+}
+
+// The gates of one unit, in the order the engine retires its chains: r and z from their two chains each, then h' from
+// the n gate's two, r, z and h_in[j].  live = false (a unit past H): +0.0f whatever the chains made of their pads, so
+// that its term in every output chain is fmaf(-0, +0, acc) == acc.
+ABR_HD float gru_mx_gate(float gi, float gh) { return sig_c(gi + gh); }
+ABR_HD float gru_mx_unit(float r, float z, float gi_n, float gh_n, float hj, bool live) {
+    const float n = tanh_c(fmaf(r, gh_n, gi_n));
+    const float d = hj - n;
+    const float hp = fmaf(z, d, n);
+    return live ? hp : 0.0f;
+}
+
 // Policy populations (include/abr_env.h: abr_policy_pop): the member a workgroup serves and where its weights lie.
 // block_first_lane is the LOCAL index of the workgroup's first lane (blockIdx.x * 256); group is a multiple of the
 // workgroup size, so every lane of the workgroup has the same member.  Offsets are in floats from member 0.

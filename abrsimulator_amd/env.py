@@ -533,7 +533,8 @@ class BatchedABREnv:
         flags (abr_env_step_policy_pop, abr_env_step_policy_mx_pop).
         A policy.RecurrentPolicyController rolls out its GRU cell (abr_env_step_policy_gru): every decision advances
         controller.hidden, and want_hidden=True adds hidden[n,H,N], the state each decision was taken from (zeros at a
-        lane's first chunk) -- with features, what a trainer needs to recompute each step in torch."""
+        lane's first chunk) -- with features, what a trainer needs to recompute each step in torch.  Built with
+        engine="matrix" it rolls out on the MFMA kernel (abr_env_gru_mx_step), H up to 128, with the same outputs."""
         n = int(n_steps)
         recurrent = getattr(controller, "method", None) == "policy_gru"
         if want_hidden and not recurrent:

@@ -624,12 +624,16 @@ class RecurrentPolicyController:
         ctl.load_weights(cell, head)                              # in place, no sync
 
     cell: an nn.GRUCell(feature_dim, H) with bias, or (W_ih [3H, F], W_hh [3H, H], b_ih [3H], b_hh [3H]) in GRUCell's
-    layout and gate order (r, z, n); 1 <= H <= 64.  head: nn.Linear(H, n_rates) or (W [M, H], b [M]).  value_head: None,
-    nn.Linear(H, 1) or (Wv, bv), the critic's head over the new hidden state.  window, norm, explore, seed, sample and
-    temperature are PolicyController's.  It owns `weights` (the blob: the cell's four parameters, then the head's two,
-    concatenated) and `hidden`, float32 [H, N], which starts at zero.
+    layout and gate order (r, z, n); 1 <= H <= 64, or 128 with engine="matrix".  head: nn.Linear(H, n_rates) or
+    (W [M, H], b [M]).  value_head: None, nn.Linear(H, 1) or (Wv, bv), the critic's head over the new hidden state.
+    window, norm, explore, seed, sample and temperature are PolicyController's.  It owns `weights` (the blob: the cell's
+    four parameters, then the head's two, concatenated) and `hidden`, float32 [H, N], which starts at zero.
 
-    Not covered: the matrix engine, PolicyPopulation, ShardedABREnv, LSTM cells and stacked cells.  A checkpoint taken
+    engine: "lane" (the default: one thread per lane, abr_policy_gru) or "matrix" (the same chains as f32 MFMA products,
+    abr_policy_gru_mx: H up to 128, and bit for bit the lane engine's outputs and state where both run).  Everything
+    else -- the blob, `hidden`, load_weights, select, next_bitrate, value() -- is the same object either way.
+
+    Not covered: PolicyPopulation, ShardedABREnv, LSTM cells and stacked cells.  A checkpoint taken
     mid-episode (env.state_dict()) does not contain the policy's state: save ctl.hidden next to it."""
 
     method = "policy_gru"
@@ -644,7 +648,11 @@ class RecurrentPolicyController:
     _head_parts = PolicyController._head_parts
 
     def __init__(self, player, cell, head, window=8, norm="default", explore=0.0, seed=0, sample="argmax",
-                 temperature=1.0, value_head=None, device=None):
+                 temperature=1.0, value_head=None, device=None, engine="lane"):
+        if engine not in ("lane", "matrix"):
+            raise ValueError(f"engine must be 'lane' or 'matrix', got {engine!r}")
+        self.engine = engine
+        self.max_hidden = _lib.POLICY_GRU_MX_MAX_HIDDEN if engine == "matrix" else _lib.POLICY_GRU_MAX_HIDDEN
         self.player = player
         env = getattr(player, "env", None)
         if type(env).__name__ == "ShardedABREnv":
@@ -667,8 +675,9 @@ class RecurrentPolicyController:
         self.explore, self.seed, self.sample, self.temperature = explore, int(seed), sample, temperature
         norm = self._norm(norm, mpd)
         nbytes = C.c_size_t()
-        _lib.check(_lib.lib().abr_policy_gru_weights_bytes(C.byref(self._struct(None, 0, None, None, 0)), self.n_rates,
-                                                          C.byref(nbytes)))
+        weights_bytes = (_lib.lib().abr_policy_gru_mx_weights_bytes if engine == "matrix" else
+                         _lib.lib().abr_policy_gru_weights_bytes)
+        _lib.check(weights_bytes(C.byref(self._struct(None, 0, None, None, 0)), self.n_rates, C.byref(nbytes)))
         self.n_lanes = int(env.n_lanes) if env is not None else None
         if self.n_lanes is None:
             raise ValueError("RecurrentPolicyController needs player.env: the hidden state is [H, env.n_lanes]")
@@ -703,8 +712,8 @@ class RecurrentPolicyController:
             raise ValueError("cell is nn.GRUCell(F, H) or (W_ih, W_hh, b_ih, b_hh)") from None
         sh = tuple(np.shape(W_hh))
         H = sh[1] if len(sh) == 2 else -1
-        if not 1 <= H <= _lib.POLICY_GRU_MAX_HIDDEN:
-            raise ValueError(f"cell: W_hh must be [3H, H] with H in 1..{_lib.POLICY_GRU_MAX_HIDDEN}, got {sh}")
+        if not 1 <= H <= self.max_hidden:
+            raise ValueError(f"cell: W_hh must be [3H, H] with H in 1..{self.max_hidden}, got {sh}")
         if self.hidden_size is not None and H != self.hidden_size:
             raise ValueError(f"cell: {H} units, this policy has {self.hidden_size}")
         got = tuple(tuple(np.shape(t)) for t in (W_ih, W_hh, b_ih, b_hh))
@@ -758,7 +767,7 @@ class RecurrentPolicyController:
 
     # -- the C ABI ---------------------------------------------------------------
     def _struct(self, wptr, nbytes, norm, sptr, sbytes):
-        p = _lib.PolicyGru()
+        p = _lib.PolicyGruMx() if self.engine == "matrix" else _lib.PolicyGru()
         p.window, p.hidden = self.window, self.hidden_size
         p.weights_dev, p.weights_bytes = wptr, nbytes
         p.norm_dev = norm.data_ptr() if norm is not None else None
@@ -768,7 +777,7 @@ class RecurrentPolicyController:
         return p
 
     def bound(self, env=None):
-        """The abr_policy_gru struct (it points into this controller's tensors)."""
+        """The abr_policy_gru struct, or abr_policy_gru_mx with engine="matrix" (it points into this controller's tensors)."""
         env = env if env is not None else self.player.env
         if env.n_rates != self.n_rates:
             raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
@@ -787,8 +796,10 @@ class RecurrentPolicyController:
         return _select(self, want_features, want_scores, want_probs, want_value, want_hidden, commit)
 
     def entries(self, val, want_probs):
-        """As PolicyController.entries: one pair for every mode, with the hidden outputs."""
-        return ("abr_env_policy_select_gru", "abr_env_step_policy_gru"), (self.sampling(), val), 3
+        """As PolicyController.entries: one pair per engine for every mode, with the hidden outputs."""
+        names = (("abr_env_gru_mx_select", "abr_env_gru_mx_step") if self.engine == "matrix" else
+                 ("abr_env_policy_select_gru", "abr_env_step_policy_gru"))
+        return names, (self.sampling(), val), 3
 
     def next_bitrate(self):
         """int32 [N]: the policy's action for each lane (-1 for finished lanes).  It commits the new hidden state: the

@@ -1130,7 +1130,7 @@ int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr
  * Commit: with commit != 0 a lane that takes a decision has h' written over its column of state_dev.  A lane whose done
  * bits are set takes no decision: action -1, its feature, score, probs and hidden-out columns 0.0f, value 0.0f, and its
  * column of state_dev is NOT touched.
- * Not covered: the matrix engine, populations, sharded environments, LSTM cells and stacked cells.
+ * Not covered: populations, sharded environments, LSTM cells and stacked cells.  (H above 64: abr_policy_gru_mx, below.)
  */
 #define ABR_POLICY_GRU_MAX_HIDDEN 64
 typedef struct abr_policy_gru {           /* 80 bytes, no padding */
@@ -1174,6 +1174,52 @@ int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, const abr_p
                             uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev,
                             float *scores_out_dev, float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
                             float *hidden_out_dev, void *stream);
+
+/*
+ * The recurrent policy's matrix engine (ABI 4, additive; BUILD-DEFINED): a second engine with the arithmetic contract of
+ * abr_policy_gru, word for word -- the same features, the same blob (GRUCell's own layout and gate order, then the
+ * head, unpadded), the same state slab [H][n_lanes] and c == 0 rule, the same six k-ordered chains per unit (gi_g and
+ * gh_g separate accumulators, each from its own bias, added after the chains), the same sig_c / tanh_c /
+ * d = h_in[j] - n / h' = fmaf(z, d, n), the same output chains over h' and value head, the same argmax, exploration
+ * and softmax draw, the same rules for commit, done lanes and hidden_out.  Only the width limit is lifted:
+ * 1 <= H <= ABR_POLICY_GRU_MX_MAX_HIDDEN.  The chains are issued as v_mfma_f32_32x32x2_f32 (as abr_policy_mx's), whose
+ * accumulation is the fmaf chain in k order: on a shape inside both limits (H <= 64) a blob, a head and a state slab are
+ * interchangeable between the engines, and every output and the committed state are bit-identical.
+ * abr_policy_gru_mx is a distinct type with abr_policy_gru's layout, as abr_policy_mx is next to abr_policy.
+ * Not covered: populations, sharded environments, LSTM cells and stacked cells.
+ */
+#define ABR_POLICY_GRU_MX_MAX_HIDDEN 128
+typedef struct abr_policy_gru_mx {        /* 80 bytes, no padding: field for field abr_policy_gru */
+    int32_t window;                       /* W, 0..ABR_POLICY_MAX_WINDOW */
+    int32_t hidden;                       /* H, 1..ABR_POLICY_GRU_MX_MAX_HIDDEN */
+    const float *weights_dev;             /* the blob (device, 4-byte aligned) */
+    size_t weights_bytes;                 /* == abr_policy_gru_mx_weights_bytes(this, n_rates) */
+    const double *norm_dev;               /* float64 [2][F] (device, 8-byte aligned) or NULL */
+    float *state_dev;                     /* float32 [H][n_lanes] (device, 4-byte aligned, non-NULL) */
+    size_t state_bytes;                   /* == H * n_lanes * 4 */
+    uint64_t seed;                        /* philox key of the exploration draw */
+    uint64_t explore_threshold;           /* 0 .. 2^32 */
+    int32_t reserved_[4];                 /* set to 0 */
+} abr_policy_gru_mx;
+
+/* As abr_policy_gru_weights_bytes, the same formula: 4 * (3H (F + H + 2) + M (H + 1)). */
+int abr_policy_gru_mx_weights_bytes(const abr_policy_gru_mx *pol, int32_t n_rates, size_t *bytes_out);
+
+/* abr_env_policy_select_gru on the matrix engine: the same parameters, outputs, commit rule, validation order and
+ * messages. */
+int abr_env_gru_mx_select(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
+                          const abr_policy_value *val, int32_t commit, int32_t *action_out_dev, float *features_out_dev,
+                          float *scores_out_dev, float *probs_out_dev, float *value_out_dev, float *hidden_out_dev,
+                          void *stream);
+
+/* abr_env_step_policy_gru on the matrix engine: every decision commits, last_value_out_dev is a forward-only launch that
+ * commits nothing, byte for byte a loop of abr_env_gru_mx_select(commit = 1) then abr_env_step; ABR_E_UNSUPPORTED on
+ * tick. */
+int abr_env_gru_mx_step(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
+                        const abr_policy_value *val, int32_t n_steps, float *obs_out_dev, float *reward_out_dev,
+                        uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                        float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
+                        void *stream);
 
 /*
  * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
