@@ -13,7 +13,7 @@ from .fastmpc import FastMPCController
 from .ledger import EpisodeLedger
 from .quality import EpisodeQuality
 from .mpc import BatchedMPCController, EnvPlayer
-from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController
+from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController, RecurrentPolicyPopulation
 from .search import HindsightSearch
 from .rules import BolaController, BufferBasedController, RateBasedController
 from .sharding import ShardedABREnv, ShardStep
@@ -26,7 +26,7 @@ from .traces import (load_mpd_file, load_network_info, load_trace_file, save_mpd
 _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
-           "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
+           "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "RecurrentPolicyPopulation", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
            "HindsightSearch", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

@@ -281,6 +281,15 @@ SYMBOLS = [
                                         C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_env_gru_mx_step", C.c_int, [_P, C.POINTER(PolicyGruMx), C.POINTER(PolicySampling), C.POINTER(PolicyValue),
                                       C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_gru_select_pop", C.c_int, [_P, C.POINTER(PolicyGru), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                                C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_gru_step_pop", C.c_int, [_P, C.POINTER(PolicyGru), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                              C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                              _P]),
+    ("abr_env_gru_mx_select_pop", C.c_int, [_P, C.POINTER(PolicyGruMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                            C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
+    ("abr_env_gru_mx_step_pop", C.c_int, [_P, C.POINTER(PolicyGruMx), C.POINTER(PolicyPop), C.POINTER(PolicySampling),
+                                          C.POINTER(PolicyValue), C.c_int32, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_gae", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int64, C.c_float, C.c_float, _P, _P, _P]),
     ("abr_trace_synth", C.c_int, [C.POINTER(TraceModel), C.c_uint64, C.c_uint32, C.c_int64, _P, _P, _P, C.c_int32, _P]),
     ("abr_debug_chain", C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P]),

@@ -3780,13 +3780,28 @@ struct PolicyGruArgs {
     int32_t commit;
 };
 
-template <bool SAMPLED, bool VALUE>
-__global__ __launch_bounds__(kPolicyBlock, 2) void policy_gru_kernel(EnvParams p, PolicyGruArgs a) {
+// the POP instances' arguments (abr_policy_pop), as PolicyPopArgs: both recurrent kernels take them
+struct PolicyGruPopArgs : PolicyGruArgs {
+    int32_t group, blob_words, head_words;
+};
+
+// POP: the instances behind abr_env_gru_select_pop / abr_env_gru_step_pop (abr_policy_pop), as policy_select_kernel's.  The
+// workgroup computes the member it serves once, from its first lane, and stages that member's blob and head; the state
+// slab is one slab whatever the population (members own disjoint columns), and the rest is the single-network kernel.
+template <bool SAMPLED, bool VALUE, bool POP = false>
+__global__ __launch_bounds__(kPolicyBlock, 2) void policy_gru_kernel(
+    EnvParams p, std::conditional_t<POP, PolicyGruPopArgs, PolicyGruArgs> a) {
     extern __shared__ __attribute__((aligned(16))) float gru_lds[];   // rows are read as 128-bit quads
     float *w_lds = gru_lds;
     const abrx::PolicyGruLayout lay = abrx::policy_gru_layout<VALUE>(a.net);
+    [[maybe_unused]] const float *member_blob = nullptr, *member_head = nullptr;
+    if constexpr (POP) {
+        const int64_t member = abrx::pop_member((int64_t)blockIdx.x * kPolicyBlock, a.group);
+        member_blob = a.weights + abrx::pop_blob_offset(member, a.blob_words);
+        if constexpr (VALUE) member_head = a.head + abrx::pop_head_offset(member, a.head_words);
+    }
     for (int32_t d = threadIdx.x; d < lay.total; d += kPolicyBlock)
-        w_lds[d] = abrx::policy_gru_padded<VALUE>(a.net, lay, a.weights, d, a.head);
+        w_lds[d] = abrx::policy_gru_padded<VALUE>(a.net, lay, POP ? member_blob : a.weights, d, POP ? member_head : a.head);
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * kPolicyBlock + threadIdx.x;
     if (i >= p.n_lanes) return;
@@ -3904,9 +3919,10 @@ extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n
     return ABR_OK;
 }
 
-// the recurrent engine's builder: the blob's, the state's and the head's sizes for the environment (it has no populations)
+// The recurrent engine's builder: one member's blob and head and the whole state slab against the environment, then the
+// population's cover.  The struct is the widest one on the host whatever the entry, as policy_lane_args'.
 static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
-                           const abr_policy_value *val, const abr_policy_pop *, PolicyGruArgs *a) {
+                           const abr_policy_value *val, const abr_policy_pop *pop, PolicyGruPopArgs *a) {
     const int32_t M = env->p.n_rates, H = pol->hidden;
     int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
     if (rc) return rc;
@@ -3915,44 +3931,54 @@ static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const 
         return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
                     (long long)env->p.n_lanes, state);
     if ((rc = check_head_bytes(val, (size_t)H))) return rc;
-    *a = PolicyGruArgs{};
+    if ((rc = pop_covers(env, pop))) return rc;
+    *a = PolicyGruPopArgs{};
     a->net = policy_net(pol, M);
     a->net.n_hidden = 1; a->net.w0 = H;
     a->weights = pol->weights_dev; a->state = pol->state_dev;
     if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
     if (val) a->head = val->head_dev;
+    if (pop) {       // the member stride of the blob and of the heads, in floats
+        a->group = pop->group;
+        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
+    }
     return ABR_OK;
 }
 
 // The staged blob passes the 64 KiB a kernel may take by default, so each instance's dynamic-LDS limit is raised once,
 // to the largest launch the contract allows (H = 64, 16 rates, a value head, the score columns: 99 664 B).
-template <bool SAMPLED, bool VALUE>
-static hipError_t launch_policy_gru_instance(const abr_env *env, const PolicyGruArgs &a, size_t lds, hipStream_t st) {
+template <bool SAMPLED, bool VALUE, bool POP>
+static hipError_t launch_policy_gru_instance(const abr_env *env, const PolicyGruPopArgs &a, size_t lds, hipStream_t st) {
     static bool raised = false;
     if (!raised) {
         abrx::PolicyNet top{};
         top.w0 = ABR_POLICY_GRU_MAX_HIDDEN;
         const int most = (int)(((size_t)abrx::policy_gru_layout<true>(top).total + (size_t)ABR_MAX_RATES * kPolicyBlock) *
                                sizeof(float));
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_kernel<SAMPLED, VALUE>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_kernel<SAMPLED, VALUE, POP>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, most);
         if (e != hipSuccess) return e;
         raised = true;
     }
-    hipLaunchKernelGGL((policy_gru_kernel<SAMPLED, VALUE>), dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)),
-                       dim3(kPolicyBlock), lds, st, env->p, a);
+    // a POP == false instance takes `a` sliced to PolicyGruArgs
+    hipLaunchKernelGGL((policy_gru_kernel<SAMPLED, VALUE, POP>),
+                       dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), dim3(kPolicyBlock), lds, st, env->p,
+                       a);
     return hipGetLastError();
 }
 
-// the one chooser of policy_gru_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_lane
-static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruArgs &a, hipStream_t st) {
+// the one chooser of policy_gru_kernel's instances: SAMPLED and VALUE by what the launch needs, POP the entry's, as
+// launch_policy_lane
+template <bool POP>
+static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruPopArgs &a, hipStream_t st) {
     const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
     const size_t words = value ? abrx::policy_gru_layout<true>(a.net).total : abrx::policy_gru_layout(a.net).total;
     const size_t lds = (words + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
-    if (sampled && value) return launch_policy_gru_instance<true, true>(env, a, lds, st);
-    if (sampled) return launch_policy_gru_instance<true, false>(env, a, lds, st);
-    if (value) return launch_policy_gru_instance<false, true>(env, a, lds, st);
-    return launch_policy_gru_instance<false, false>(env, a, lds, st);
+    if (sampled && value) return launch_policy_gru_instance<true, true, POP>(env, a, lds, st);
+    if (sampled) return launch_policy_gru_instance<true, false, POP>(env, a, lds, st);
+    if (value) return launch_policy_gru_instance<false, true, POP>(env, a, lds, st);
+    return launch_policy_gru_instance<false, false, POP>(env, a, lds, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -3994,8 +4020,11 @@ __device__ __forceinline__ void gru_mx_chain(const float *__restrict__ at, int32
     }
 }
 
-template <bool SAMPLED, bool VALUE>
-__global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(EnvParams p, PolicyGruArgs a) {
+// POP: as policy_gru_kernel's -- the member's blob and head are what gru_mx() lays out at every unit tile, so the staged
+// operands, the biases and the output and value rows are all the member's.
+template <bool SAMPLED, bool VALUE, bool POP = false>
+__global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(
+    EnvParams p, std::conditional_t<POP, PolicyGruPopArgs, PolicyGruArgs> a) {
     extern __shared__ float gmx_lds[];
     constexpr int kHSteps = abrx::kGruMxMaxHidden / 2;
     constexpr int kXSteps = (abrx::kPolicyMaxF / 2 + kMxGroup - 1) / kMxGroup * kMxGroup;   // whole groups
@@ -4030,6 +4059,12 @@ __global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(EnvParams p, Po
     // h[s] = h_in[2 s + half] -- +0.0f where c == 0, where the column's lane takes no decision and past H.
     const int32_t tiles = abrx::gru_mx_tiles(H);
     const bool commit = a.commit != 0;
+    [[maybe_unused]] const float *member_blob = nullptr, *member_head = nullptr;
+    if constexpr (POP) {
+        const int64_t member = abrx::pop_member((int64_t)blockIdx.x * kMxBlock, a.group);
+        member_blob = a.weights + abrx::pop_blob_offset(member, a.blob_words);
+        if constexpr (VALUE) member_head = a.head + abrx::pop_head_offset(member, a.head_words);
+    }
     float sc[abrx::kPolicyMaxRates] = {};
     [[maybe_unused]] float value = 0.0f;
 #pragma unroll 1
@@ -4089,7 +4124,8 @@ __global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(EnvParams p, Po
         }
         mx_acc_t out;
         {
-            const abrx::GruMx y = abrx::gru_mx(a.weights, VALUE ? a.head : nullptr, n.F, Ht, n.M);
+            const abrx::GruMx y = abrx::gru_mx(POP ? member_blob : a.weights, VALUE ? (POP ? member_head : a.head) : nullptr,
+                                               n.F, Ht, n.M);
 #pragma unroll
             for (int r = 0; r < abrx::kMxRegs; r++) out[r] = abrx::gru_mx_b_out(y, abrx::mx_acc_unit(lane, r));
         }
@@ -4097,7 +4133,8 @@ __global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(EnvParams p, Po
         for (int32_t U = 0; U < tiles; U++) {
             int32_t Hu = H;
             asm volatile("" : "+s"(Hu));
-            const abrx::GruMx y = abrx::gru_mx(a.weights, VALUE ? a.head : nullptr, n.F, Hu, n.M);
+            const abrx::GruMx y = abrx::gru_mx(POP ? member_blob : a.weights, VALUE ? (POP ? member_head : a.head) : nullptr,
+                                               n.F, Hu, n.M);
             const int32_t rows = abrx::gru_mx_rows(n.F, Hu), sF = abrx::mx_steps(n.F), sH = abrx::mx_steps(Hu);
             __syncthreads();                                 // every wave has left the tile staged before
             {
@@ -4244,9 +4281,9 @@ extern "C" int abr_policy_gru_mx_weights_bytes(const abr_policy_gru_mx *pol, int
     return ABR_OK;
 }
 
-// the builder: policy_gru_args' checks and fields for the wider struct (the kernels share PolicyGruArgs)
+// the builder: policy_gru_args' checks and fields for the wider struct (the kernels share PolicyGruPopArgs)
 static int policy_gru_mx_args(const abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
-                              const abr_policy_value *val, const abr_policy_pop *, PolicyGruArgs *a) {
+                              const abr_policy_value *val, const abr_policy_pop *pop, PolicyGruPopArgs *a) {
     const int32_t M = env->p.n_rates, H = pol->hidden;
     int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
     if (rc) return rc;
@@ -4255,41 +4292,49 @@ static int policy_gru_mx_args(const abr_env *env, const abr_policy_gru_mx *pol, 
         return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
                     (long long)env->p.n_lanes, state);
     if ((rc = check_head_bytes(val, (size_t)H))) return rc;
-    *a = PolicyGruArgs{};
+    if ((rc = pop_covers(env, pop))) return rc;
+    *a = PolicyGruPopArgs{};
     a->net = policy_net(pol, M);
     a->net.n_hidden = 1; a->net.w0 = H;
     a->weights = pol->weights_dev; a->state = pol->state_dev;
     if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
     if (val) a->head = val->head_dev;
+    if (pop) {       // the member stride of the blob and of the heads, in floats
+        a->group = pop->group;
+        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
+        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
+    }
     return ABR_OK;
 }
 
 // A unit tile at H = 128, W = 16, 16 rates is 68 608 B, past the 64 KiB a kernel may take by default: each instance's
 // dynamic-LDS limit is raised once, to the largest launch the contract allows (with the score columns: 84 992 B).
-template <bool SAMPLED, bool VALUE>
-static hipError_t launch_policy_gru_mx_instance(const abr_env *env, const PolicyGruArgs &a, size_t lds, hipStream_t st) {
+template <bool SAMPLED, bool VALUE, bool POP>
+static hipError_t launch_policy_gru_mx_instance(const abr_env *env, const PolicyGruPopArgs &a, size_t lds, hipStream_t st) {
     static bool raised = false;
     if (!raised) {
         const int most = (int)((size_t)abrx::gru_mx_lds_floats(abrx::kPolicyMaxF, ABR_POLICY_GRU_MX_MAX_HIDDEN, ABR_MAX_RATES,
                                                                true, kMxBlock) * sizeof(float));
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_mx_kernel<SAMPLED, VALUE>),
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_mx_kernel<SAMPLED, VALUE, POP>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, most);
         if (e != hipSuccess) return e;
         raised = true;
     }
-    hipLaunchKernelGGL((policy_gru_mx_kernel<SAMPLED, VALUE>), dim3((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)),
+    hipLaunchKernelGGL((policy_gru_mx_kernel<SAMPLED, VALUE, POP>), dim3((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)),
                        dim3(kMxBlock), lds, st, env->p, a);
     return hipGetLastError();
 }
 
-// the one chooser of policy_gru_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_gru
-static hipError_t launch_policy_gru_mx(const abr_env *env, const PolicyGruArgs &a, hipStream_t st) {
+// the one chooser of policy_gru_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, POP the entry's, as
+// launch_policy_gru
+template <bool POP>
+static hipError_t launch_policy_gru_mx(const abr_env *env, const PolicyGruPopArgs &a, hipStream_t st) {
     const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
     const size_t lds = (size_t)abrx::gru_mx_lds_floats(a.net.F, a.net.w0, a.net.M, sampled, kMxBlock) * sizeof(float);
-    if (sampled && value) return launch_policy_gru_mx_instance<true, true>(env, a, lds, st);
-    if (sampled) return launch_policy_gru_mx_instance<true, false>(env, a, lds, st);
-    if (value) return launch_policy_gru_mx_instance<false, true>(env, a, lds, st);
-    return launch_policy_gru_mx_instance<false, false>(env, a, lds, st);
+    if (sampled && value) return launch_policy_gru_mx_instance<true, true, POP>(env, a, lds, st);
+    if (sampled) return launch_policy_gru_mx_instance<true, false, POP>(env, a, lds, st);
+    if (value) return launch_policy_gru_mx_instance<false, true, POP>(env, a, lds, st);
+    return launch_policy_gru_mx_instance<false, false, POP>(env, a, lds, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -4385,7 +4430,10 @@ static int validate_policy_call(const abr_env *env, const Pol *pol, unsigned nee
 // the recurrent engine's part of a launch: where h_in is reported, and whether h' replaces it in the caller's slab
 template <class Args>
 static void set_recurrence(Args &, float *, int32_t) {}
-static void set_recurrence(PolicyGruArgs &a, float *hidden_out, int32_t commit) { a.hidden_out = hidden_out; a.commit = commit; }
+static void set_recurrence(PolicyGruPopArgs &a, float *hidden_out, int32_t commit) {
+    a.hidden_out = hidden_out;
+    a.commit = commit;
+}
 
 // one decision per lane on the current state
 template <class Args, class Launch>
@@ -4555,7 +4603,7 @@ extern "C" int abr_env_policy_select_gru(abr_env *env, const abr_policy_gru *pol
                                          const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
                                          float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                          float *value_out_dev, float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru, nullptr,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru<false>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4566,7 +4614,7 @@ extern "C" int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, 
                                        float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                        float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                        void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru, &n_steps,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru<false>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }
@@ -4576,7 +4624,7 @@ extern "C" int abr_env_gru_mx_select(abr_env *env, const abr_policy_gru_mx *pol,
                                      const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                      float *value_out_dev, float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx, nullptr,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx<false>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4587,7 +4635,50 @@ extern "C" int abr_env_gru_mx_step(abr_env *env, const abr_policy_gru_mx *pol, c
                                    float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                    float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                    void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx, &n_steps,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx<false>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+// recurrent populations (include/abr_env.h: abr_policy_pop over abr_policy_gru / abr_policy_gru_mx): both engines' POP
+// instances, one state slab
+extern "C" int abr_env_gru_select_pop(abr_env *env, const abr_policy_gru *pol, const abr_policy_pop *pop,
+                                             const abr_policy_sampling *smp, const abr_policy_value *val, int32_t commit,
+                                             int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                             float *probs_out_dev, float *value_out_dev, float *hidden_out_dev,
+                                             void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args, launch_policy_gru<true>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
+                        stream, commit != 0);
+}
+
+extern "C" int abr_env_gru_step_pop(abr_env *env, const abr_policy_gru *pol, const abr_policy_pop *pop,
+                                           const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                           float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                           int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                           float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                           float *hidden_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args, launch_policy_gru<true>, &n_steps,
+                        {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
+                         last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
+}
+
+extern "C" int abr_env_gru_mx_select_pop(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_pop *pop,
+                                         const abr_policy_sampling *smp, const abr_policy_value *val, int32_t commit,
+                                         int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                         float *probs_out_dev, float *value_out_dev, float *hidden_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_mx_args, launch_policy_gru_mx<true>, nullptr,
+                        {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
+                        stream, commit != 0);
+}
+
+extern "C" int abr_env_gru_mx_step_pop(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_pop *pop,
+                                       const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                       float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev,
+                                       int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
+                                       float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
+                                       float *hidden_out_dev, void *stream) {
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_mx_args, launch_policy_gru_mx<true>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }

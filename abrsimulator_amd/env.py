@@ -534,11 +534,13 @@ class BatchedABREnv:
         A policy.RecurrentPolicyController rolls out its GRU cell (abr_env_step_policy_gru): every decision advances
         controller.hidden, and want_hidden=True adds hidden[n,H,N], the state each decision was taken from (zeros at a
         lane's first chunk) -- with features, what a trainer needs to recompute each step in torch.  Built with
-        engine="matrix" it rolls out on the MFMA kernel (abr_env_gru_mx_step), H up to 128, with the same outputs."""
+        engine="matrix" it rolls out on the MFMA kernel (abr_env_gru_mx_step), H up to 128, with the same outputs.
+        A policy.RecurrentPolicyPopulation rolls out P GRU cells at once, member m on its own lane group and its own
+        columns of the one hidden slab (abr_env_gru_step_pop, abr_env_gru_mx_step_pop), with the same dict and flags."""
         n = int(n_steps)
-        recurrent = getattr(controller, "method", None) == "policy_gru"
+        recurrent = getattr(controller, "method", None) in ("policy_gru", "policy_gru_population")
         if want_hidden and not recurrent:
-            raise ValueError("want_hidden needs a RecurrentPolicyController")
+            raise ValueError("want_hidden needs a RecurrentPolicyController or a RecurrentPolicyPopulation")
         pol = controller.bound(self)
         val = controller.value() if want_values or (out is not None and out.get("values") is not None) else None
         if out is None:

@@ -38,6 +38,13 @@ across decisions and launches and restarts with the lane's episode (include/abr_
 
     ctl = RecurrentPolicyController(EnvPlayer(env), nn.GRUCell(F, 32), nn.Linear(32, M), window=8, sample="softmax")
     out = env.step_policy(ctl, 48, want_features=True, want_hidden=True)   # hidden[t]: the state decision t started from
+
+RecurrentPolicyPopulation is the two together: P GRU cells of one shape, member m on its own lane group and its own
+columns of the one hidden slab (include/abr_env.h: abr_env_gru_step_pop) -- a recurrent actor for evolution
+strategies and population-based training, which need no backpropagation through time:
+
+    pop = RecurrentPolicyPopulation(EnvPlayer(env), [(cell_0, head_0), ..., (cell_63, head_63)], group=env.n_lanes // 64)
+    out = env.step_policy(pop, 48)                          # every member on its own lanes, one launch per decision
 """
 import copy
 import ctypes as C
@@ -633,7 +640,8 @@ class RecurrentPolicyController:
     abr_policy_gru_mx: H up to 128, and bit for bit the lane engine's outputs and state where both run).  Everything
     else -- the blob, `hidden`, load_weights, select, next_bitrate, value() -- is the same object either way.
 
-    Not covered: PolicyPopulation, ShardedABREnv, LSTM cells and stacked cells.  A checkpoint taken
+    Populations: RecurrentPolicyPopulation (PolicyPopulation's members are MLPs).  Not covered: ShardedABREnv, LSTM cells
+    and stacked cells.  A checkpoint taken
     mid-episode (env.state_dict()) does not contain the policy's state: save ctl.hidden next to it."""
 
     method = "policy_gru"
@@ -804,4 +812,218 @@ class RecurrentPolicyController:
     def next_bitrate(self):
         """int32 [N]: the policy's action for each lane (-1 for finished lanes).  It commits the new hidden state: the
         player's loop steps these actions next."""
+        return self.select(False, False, commit=True)["actions"]
+
+
+class RecurrentPolicyPopulation:
+    """P recurrent policies of ONE shape over `player`, each deciding for its own group of lanes in the same launch
+    (include/abr_env.h: abr_policy_pop over abr_policy_gru / abr_policy_gru_mx): local lane i belongs to member
+    i // group, group is a positive multiple of 256, and P == ceil(n_lanes / group) -- the last member may own fewer
+    lanes.  For every lane of member m every output and the committed column of `hidden` are bit for bit what a
+    RecurrentPolicyController over member_parts(m) gives on that lane.
+
+        pop = RecurrentPolicyPopulation(EnvPlayer(env), [(cell_m, head_m) for m in range(P)], group=env.n_lanes // P)
+        out = env.step_policy(pop, 48, want_obs=False, want_actions=False)
+        fitness = led.per_member(pop.group, pop.n_members)["qoe"]           # led = env.set_episode_ledger(rows)
+        pop.load_weights(next_generation)                                    # in place, no sync; hidden is left alone
+
+    members: a non-empty list of (cell, head) pairs, each what RecurrentPolicyController takes (an nn.GRUCell or
+    (W_ih, W_hh, b_ih, b_hh); an nn.Linear or (W, b)), or the six stacked tensors (W_ih [P, 3H, F], W_hh [P, 3H, H],
+    b_ih [P, 3H], b_hh [P, 3H], W [P, M, H], b [P, M]).  value_heads: None, a list of P heads (nn.Linear(H, 1) or
+    (Wv, bv)), or the stacked pair (Wv [P, H], bv [P]).  Every other argument is RecurrentPolicyController's and is shared
+    by all members, with the same H limit per engine; explore, sample, temperature and seed can be changed between
+    launches.  It owns weights float32 [P, words] (row m is pack_gru of member m), hidden float32 [H, N] -- ONE slab,
+    members own disjoint columns, zeros at construction -- and value_heads float32 [P, H + 1] (or None).
+
+    Not covered: ShardedABREnv, LSTM cells and stacked cells; per-member exploration, temperature or norm."""
+
+    method = "policy_gru_population"
+
+    def __init__(self, player, members, group, window=8, norm="default", explore=0.0, seed=0, sample="argmax",
+                 temperature=1.0, value_heads=None, engine="lane", device=None):
+        if engine not in ("lane", "matrix"):
+            raise ValueError(f"engine must be 'lane' or 'matrix', got {engine!r}")
+        if isinstance(group, bool) or int(group) != group or int(group) < _lib.POLICY_POP_BLOCK or \
+                int(group) % _lib.POLICY_POP_BLOCK:
+            raise ValueError(f"group must be a positive multiple of {_lib.POLICY_POP_BLOCK}, got {group!r}")
+        env = getattr(player, "env", None)
+        if type(env).__name__ == "ShardedABREnv":
+            raise ValueError("RecurrentPolicyPopulation does not run on a ShardedABREnv: the hidden state is one slab of "
+                             "one environment's lanes")
+        self.group = int(group)
+        self.player, self.engine = player, engine
+        pairs = self._member_pairs(members)
+        self.n_members = len(pairs)
+        heads = PolicyPopulation._member_heads(value_heads, self.n_members)
+        # member 0 through the controller's own checks: shape, H, window, norm, explore, sample, temperature, head
+        self._proto = RecurrentPolicyController(player, pairs[0][0], pairs[0][1], window=window, norm=norm, explore=explore,
+                                                seed=seed, sample=sample, temperature=temperature,
+                                                value_head=heads[0] if heads is not None else None, device=device,
+                                                engine=engine)
+        c = self._proto
+        self.device, self.window, self.n_rates, self.n_lanes = c.device, c.window, c.n_rates, c.n_lanes
+        self.feature_dim, self.hidden_size, self.value_in = c.feature_dim, c.hidden_size, c.value_in
+        self._check_cover(env)
+        for cell, head in pairs:                                            # every member has member 0's shape
+            c._parts(cell, head)
+        self.weights = torch.zeros(self.n_members, c.weights.numel(), dtype=torch.float32, device=self.device)
+        self.hidden = c.hidden
+        self.value_heads = (torch.zeros(self.n_members, self.value_in + 1, dtype=torch.float32, device=self.device)
+                            if heads is not None else None)
+        c.weights = self.weights[0]                                         # the prototype is member 0: no second copy
+        c.value_head = self.value_heads[0] if heads is not None else None
+        self.load_weights(members, value_heads=value_heads)
+
+    # -- the members' inputs -------------------------------------------------------
+    @staticmethod
+    def _stacked(members):
+        return (not isinstance(members, torch.nn.Module) and len(members) == 6 and
+                all(_is_array(t) for t in members) and np.ndim(members[0]) == 3)
+
+    @classmethod
+    def _member_pairs(cls, members):
+        """A list of P (cell, head) pairs from either form; ValueError for anything else."""
+        if isinstance(members, torch.nn.Module) or not isinstance(members, (list, tuple)) or len(members) == 0:
+            raise ValueError("members is a non-empty list of (cell, head) pairs, or the six stacked tensors")
+        if cls._stacked(members):
+            P = int(np.shape(members[0])[0])
+            if P < 1:
+                raise ValueError("a population has at least one member")
+            want = (3, 3, 2, 2, 3, 2)
+            if any(np.ndim(t) != d or np.shape(t)[0] != P for t, d in zip(members, want)):
+                raise ValueError(f"stacked members: W_ih [{P}, 3H, F], W_hh [{P}, 3H, H], b_ih [{P}, 3H], b_hh [{P}, 3H], "
+                                 f"W [{P}, M, H], b [{P}, M]; got {[tuple(np.shape(t)) for t in members]}")
+            return [(tuple(t[m] for t in members[:4]), tuple(t[m] for t in members[4:])) for m in range(P)]
+        out = []
+        for k, pair in enumerate(members):
+            try:
+                cell, head = pair
+            except (TypeError, ValueError):
+                raise ValueError(f"member {k} is not a (cell, head) pair") from None
+            out.append((cell, head))
+        return out
+
+    def _check_cover(self, env):
+        want = -(-int(env.n_lanes) // self.group)
+        if self.n_members != want:
+            raise ValueError(f"{self.n_members} members, {env.n_lanes} lanes in groups of {self.group} need {want}")
+
+    # -- what all members share (checked by the controller's own setters) ------------
+    explore = PolicyPopulation.explore
+    sample = PolicyPopulation.sample
+    temperature = PolicyPopulation.temperature
+    seed = PolicyPopulation.seed
+    norm = PolicyPopulation.norm
+    explore_threshold = PolicyPopulation.explore_threshold
+    inv_temperature = PolicyPopulation.inv_temperature
+    sampling = PolicyPopulation.sampling
+    feature_names = PolicyPopulation.feature_names
+    _index = PolicyPopulation._index
+    _n_lanes = PolicyPopulation._n_lanes
+    member_of_lane = PolicyPopulation.member_of_lane
+    lanes_of = PolicyPopulation.lanes_of
+    population = PolicyPopulation.population
+
+    # -- the weights -----------------------------------------------------------------
+    def _member(self, m):
+        """The prototype over row m of the weights and of the heads (the hidden slab is the population's)."""
+        c = copy.copy(self._proto)
+        c.weights = self.weights[m]
+        c.value_head = self.value_heads[m] if self.value_heads is not None else None
+        return c
+
+    def member_parts(self, m):
+        """(cell, head) of member m -- (W_ih, W_hh, b_ih, b_hh), (W, b) -- as VIEWS of row m of `weights`: what a
+        RecurrentPolicyController on another environment takes (it copies them)."""
+        row = self.weights[self._index(m)]
+        F, H, M = self.feature_dim, self.hidden_size, self.n_rates
+        out, o = [], 0
+        for shape in ((3 * H, F), (3 * H, H), (3 * H,), (3 * H,), (M, H), (M,)):
+            n = int(np.prod(shape))
+            out.append(row[o:o + n].view(*shape))
+            o += n
+        assert o == row.numel()
+        return tuple(out[:4]), tuple(out[4:])
+
+    def load_member(self, m, cell, head, value_head=None):
+        """Copy new weights for member m alone (as RecurrentPolicyController.load_weights) in place, on the current
+        stream, without synchronising.  `hidden` is not touched."""
+        self._member(self._index(m)).load_weights(cell, head, value_head=value_head)
+
+    def load_weights(self, members, value_heads=None):
+        """Copy new weights for EVERY member (either form the constructor takes, P unchanged) in place, on the current
+        stream, without synchronising.  Stacked tensors take one copy per tensor, whatever P is.  `hidden` is not
+        touched."""
+        pairs = self._member_pairs(members)
+        if len(pairs) != self.n_members:
+            raise ValueError(f"{len(pairs)} members, this population has {self.n_members}")
+        heads = PolicyPopulation._member_heads(value_heads, self.n_members)
+        if heads is not None and self.value_heads is None:
+            raise ValueError("this population was built without value heads")
+        parts = [self._proto._parts(cell, head) for cell, head in pairs]    # every shape, before anything is copied
+        if heads is not None:
+            heads = [self._proto._head_parts(h) for h in heads]
+        with torch.no_grad():
+            if self._stacked(members):
+                o = 0
+                for t in members:
+                    t = _as_f32(t, self.device).reshape(self.n_members, -1)
+                    self.weights[:, o:o + t.shape[1]].copy_(t, non_blocking=True)
+                    o += t.shape[1]
+                assert o == self.weights.shape[1]
+            else:
+                for m, p in enumerate(parts):
+                    o = 0
+                    for t in p:
+                        t = _as_f32(t, self.device).reshape(-1)
+                        self.weights[m, o:o + t.numel()].copy_(t, non_blocking=True)
+                        o += t.numel()
+                    assert o == self.weights.shape[1]
+            if heads is not None:
+                for m, (Wv, bv) in enumerate(heads):
+                    self.value_heads[m, :self.value_in].copy_(_as_f32(Wv, self.device).reshape(-1), non_blocking=True)
+                    self.value_heads[m, self.value_in:].copy_(_as_f32(bv, self.device).reshape(-1), non_blocking=True)
+
+    def reset_hidden(self, mask=None):
+        """Zero the hidden state of every lane, or of the lanes where mask (bool [N]) is set, whatever member owns them.
+        A new episode needs no call: a lane's first decision starts from zeros by the contract."""
+        self._proto.reset_hidden(mask)
+
+    # -- the C ABI ---------------------------------------------------------------------
+    def bound(self, env=None):
+        """abr_policy_gru / abr_policy_gru_mx over member 0's blob with ONE member's byte count and the whole slab (the
+        population entries' rule)."""
+        env = env if env is not None else self.player.env
+        if env.n_rates != self.n_rates:
+            raise ValueError(f"the policy is for {self.n_rates} bitrates, the environment has {env.n_rates}")
+        if int(env.n_lanes) != self.n_lanes:
+            raise ValueError(f"the hidden state is for {self.n_lanes} lanes, the environment has {env.n_lanes}")
+        self._check_cover(env)
+        return self._proto._struct(self.weights.data_ptr(), self.weights.shape[1] * 4, self._proto.norm,
+                                   self.hidden.data_ptr(), self.hidden.numel() * 4)
+
+    def value(self):
+        """abr_policy_value over member 0's head with ONE head's byte count; ValueError without heads."""
+        if self.value_heads is None:
+            raise ValueError("values need value heads: RecurrentPolicyPopulation(..., value_heads=[...])")
+        v = _lib.PolicyValue()
+        v.head_dev, v.head_bytes = self.value_heads.data_ptr(), self.value_heads.shape[1] * 4
+        return v
+
+    # -- decisions ---------------------------------------------------------------------
+    def select(self, want_features=True, want_scores=True, want_probs=False, want_value=False, want_hidden=False,
+               commit=False):
+        """One decision per lane on the environment's current state, every lane by its own member: the same dict, and the
+        same commit rule, as RecurrentPolicyController.select."""
+        return _select(self, want_features, want_scores, want_probs, want_value, want_hidden, commit)
+
+    def entries(self, val, want_probs):
+        """As RecurrentPolicyController.entries: one pair per engine, every mode (abr_policy_pop before smp)."""
+        names = (("abr_env_gru_mx_select_pop", "abr_env_gru_mx_step_pop") if self.engine == "matrix" else
+                 ("abr_env_gru_select_pop", "abr_env_gru_step_pop"))
+        return names, (self.population(), self.sampling(), val), 3
+
+    def next_bitrate(self):
+        """int32 [N]: each lane's action by its member's cell (-1 for finished lanes).  It commits the new hidden state:
+        the player's loop steps these actions next."""
         return self.select(False, False, commit=True)["actions"]

@@ -1130,7 +1130,8 @@ int abr_env_step_policy_mx_pop(abr_env *env, const abr_policy_mx *pol, const abr
  * Commit: with commit != 0 a lane that takes a decision has h' written over its column of state_dev.  A lane whose done
  * bits are set takes no decision: action -1, its feature, score, probs and hidden-out columns 0.0f, value 0.0f, and its
  * column of state_dev is NOT touched.
- * Not covered: populations, sharded environments, LSTM cells and stacked cells.  (H above 64: abr_policy_gru_mx, below.)
+ * Populations: abr_env_gru_select_pop / abr_env_gru_step_pop, below (one blob per lane group, one slab).
+ * Not covered: sharded environments, LSTM cells and stacked cells.  (H above 64: abr_policy_gru_mx, below.)
  */
 #define ABR_POLICY_GRU_MAX_HIDDEN 64
 typedef struct abr_policy_gru {           /* 80 bytes, no padding */
@@ -1186,7 +1187,8 @@ int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, const abr_p
  * accumulation is the fmaf chain in k order: on a shape inside both limits (H <= 64) a blob, a head and a state slab are
  * interchangeable between the engines, and every output and the committed state are bit-identical.
  * abr_policy_gru_mx is a distinct type with abr_policy_gru's layout, as abr_policy_mx is next to abr_policy.
- * Not covered: populations, sharded environments, LSTM cells and stacked cells.
+ * Populations: abr_env_gru_mx_select_pop / abr_env_gru_mx_step_pop, below (one blob per lane group, one slab).
+ * Not covered: sharded environments, LSTM cells and stacked cells.
  */
 #define ABR_POLICY_GRU_MX_MAX_HIDDEN 128
 typedef struct abr_policy_gru_mx {        /* 80 bytes, no padding: field for field abr_policy_gru */
@@ -1220,6 +1222,55 @@ int abr_env_gru_mx_step(abr_env *env, const abr_policy_gru_mx *pol, const abr_po
                         uint8_t *done_out_dev, int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
                         float *probs_out_dev, float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                         void *stream);
+
+/*
+ * Recurrent policy populations (ABI 4, additive; BUILD-DEFINED): abr_policy_pop, unchanged, over abr_policy_gru and
+ * abr_policy_gru_mx -- P GRU cells of ONE shape in a single launch, one weight set per group of lanes, for the trainers
+ * that need no backpropagation through time (evolution strategies, population-based training) and for leagues.
+ * Membership: exactly abr_policy_pop's.  LOCAL lane i belongs to member i / group, group is a multiple of 256 (the
+ * workgroup of both recurrent kernels), n_members == ceil(n_lanes / group), the last member may own fewer lanes, and
+ * lane_id_base takes no part.
+ * Weights: dense float32 [n_members][weights_bytes / 4]; pol->weights_dev points at member 0 and pol->weights_bytes is
+ * ONE member's size, abr_policy_gru_weights_bytes of the shape.  Member m's row is byte for byte the blob a single
+ * abr_policy_gru of that shape takes (GRUCell's layout, then the head, unpadded).  Value heads: float32
+ * [n_members][H + 1]; val->head_dev points at member 0's head and val->head_bytes is one head's size.
+ * State: still ONE slab, float32 [H][n_lanes], state_bytes == H * n_lanes * 4: members own disjoint columns.  The c == 0
+ * rule, commit, the done-lane rule and hidden_out are abr_policy_gru's, word for word.
+ * Numerics: on every lane of member m, every output (action, features, scores, probs, value, last_value, hidden_out),
+ * the committed column of the state slab, and the workspace are bit for bit what the single-network entry of the same
+ * engine gives on that lane with member m's blob and head.  That sentence is the whole numerical contract.
+ * Not covered: sharded environments, LSTM cells and stacked cells; per-member window, norm, seed, exploration or sampling.
+ */
+
+/* abr_env_policy_select_gru for a population.  Validation (ABR_E_INVALID, nothing launched): everything
+ * abr_env_policy_select_gru checks before the handle, then pop (non-NULL, n_members >= 1, group >= 256 and a multiple of
+ * 256, reserved_ zero, n_members * (int64)group representable), then the handle; then ONE member's weights_bytes, the
+ * slab's state_bytes and one head's head_bytes against the environment, then n_members == ceil(n_lanes / group). */
+int abr_env_gru_select_pop(abr_env *env, const abr_policy_gru *pol, const abr_policy_pop *pop,
+                                  const abr_policy_sampling *smp, const abr_policy_value *val, int32_t commit,
+                                  int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                                  float *probs_out_dev, float *value_out_dev, float *hidden_out_dev, void *stream);
+
+/* abr_env_step_policy_gru for a population: every decision commits, and the last_value launch (commit = 0) uses the same
+ * member mapping.  Validation as abr_env_gru_select_pop, with n_steps >= 1 after pop and before the handle;
+ * ABR_E_UNSUPPORTED on tick. */
+int abr_env_gru_step_pop(abr_env *env, const abr_policy_gru *pol, const abr_policy_pop *pop,
+                                const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                                float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                                float *features_out_dev, float *scores_out_dev, float *probs_out_dev, float *values_out_dev,
+                                float *last_value_out_dev, float *hidden_out_dev, void *stream);
+
+/* The same two entries on the matrix engine (abr_policy_gru_mx, H up to ABR_POLICY_GRU_MX_MAX_HIDDEN): the same
+ * parameters, validation order and messages; on H <= 64 bit for bit the lane engine's population. */
+int abr_env_gru_mx_select_pop(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_pop *pop,
+                              const abr_policy_sampling *smp, const abr_policy_value *val, int32_t commit,
+                              int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
+                              float *probs_out_dev, float *value_out_dev, float *hidden_out_dev, void *stream);
+int abr_env_gru_mx_step_pop(abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_pop *pop,
+                            const abr_policy_sampling *smp, const abr_policy_value *val, int32_t n_steps,
+                            float *obs_out_dev, float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev,
+                            float *features_out_dev, float *scores_out_dev, float *probs_out_dev, float *values_out_dev,
+                            float *last_value_out_dev, float *hidden_out_dev, void *stream);
 
 /*
  * Generalised advantage estimation over the slabs of a fused rollout (no handle).  Device pointers, row stride n_lanes:
