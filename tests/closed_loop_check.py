@@ -8,6 +8,9 @@ speed schedule, a LatencySpeedController), a per-chunk ladder or not, a lane cou
 combination is accepted by, and a launch split into pieces; every lane runs episode e over decisions [eV, (e+1)V).  The
 episode family (make_episode_case / check_episodes, further below) adds the learned policy as a seventh controller, an
 episode sampler, lane_id_base, and masked resets that stagger the lanes: each lane's run is a list of segments of its own.
+The learned family (make_learned_case / check_learned, at the end) runs the episode family's cases under the learned-policy
+engines -- MLP and GRU cell, lane and matrix engine, populations, softmax sampling, the value head and GAE -- with an
+episode ledger and a quality model, and checks every slab and record they produce (tests/test_closed_loop_learned_gpu.py).
 
 Why checking (a) and (b) together proves the closed loop.  Let F_i(s) be lane i's frame at its s-th call site of an
 episode.  (a) replays the device's actions A_i through the C oracle (with the speeds the lane played) and compares every
@@ -1038,7 +1041,7 @@ def _written(steps_row, fin_row, calls, seg):
     return int(steps_row["play_id"][c]) + int(steps_row["play_length"][c] > 0)
 
 
-def expected_layout(case, segs, after, res):
+def expected_layout(case, segs, after, res, reward_fn=None):
     """The device's outputs implied by per-segment results res[(lane, k)] = (steps row [V], bw [V], fin, acts [V], log
     row or None, calls): the `out` dict check_episodes compares (actions / reward / done / obs [T, ...], per op
     frames, episodes and speed logs, history, qoe with the lanes it is meaningful for)."""
@@ -1051,9 +1054,12 @@ def expected_layout(case, segs, after, res):
             steps, bw, fin, acts, _, _ = res[(i, sg.k)]
             if sg.n == 0:
                 continue
-            rw = oracle_rewards({k: steps[k][None] for k in ("rebuffer_time", "start_up_time")},
-                                {k: np.asarray([fin[k]]) for k in ("rebuffer_time", "start_up_time")}, acts[None],
-                                m["weights"], ladder=m["ladder"], br_table=case["br"])[0]
+            if reward_fn is not None:                          # the learned family: the reward with a quality term
+                rw = reward_fn(case, steps, fin, acts)
+            else:
+                rw = oracle_rewards({k: steps[k][None] for k in ("rebuffer_time", "start_up_time")},
+                                    {k: np.asarray([fin[k]]) for k in ("rebuffer_time", "start_up_time")}, acts[None],
+                                    m["weights"], ladder=m["ladder"], br_table=case["br"])[0]
             for s in range(sg.n):
                 t = sg.t0 + s
                 ex["actions"][t, i], ex["reward"][t, i] = acts[s], rw[s]
@@ -1160,12 +1166,15 @@ def _padded_actions(case, segs_k, acts_dev):
     return a
 
 
-def check_episodes(case, out, stats=None, pair_fn=None, run_batch=None):
+def check_episodes(case, out, stats=None, pair_fn=None, run_batch=None, ref=None, reward_fn=None,
+                   collect=None):
     """Compare one run of the episode family with the reference closed loop.  `out` (numpy): actions / reward / done
     [T, N], obs [T, 8, N]; per operation: frames (observe_f64 dicts), episodes (episodes() dicts) and speed_logs
     ([rows, N] or None); history (u8 [V, N], f64 [V, N]), qoe [N], entries (FastMPC) or None.  Returns the list of
     mismatches; `stats` collects the non-vacuity counters (assert_non_vacuous_ep).  pair_fn and run_batch replace the
-    sampler twin and the oracle replay (the checker's own tests)."""
+    sampler twin and the oracle replay (the checker's own tests).  ref, reward_fn and collect are the learned family's
+    hooks (check_learned): another reference controller, the reward under a quality model, and a dict that receives the
+    plan, the replay and the reference for the comparisons that family adds; the defaults are this family's behaviour."""
     mm = []
     m = case["meta"]
     V, N, T = m["video_length"], case["n_lanes"], case["n_steps"]
@@ -1176,7 +1185,7 @@ def check_episodes(case, out, stats=None, pair_fn=None, run_batch=None):
             _mm(mm, "timeout", t, i, int(done[t, i]), 0)
         return mm
     segs, after = episode_plan(case, pair_fn)
-    ref = make_reference(case, out.get("entries"))
+    ref = make_reference(case, out.get("entries")) if ref is None else ref
     res, prev_logs = {}, {}
     K_ = max(len(s) for s in segs)
     acts = out["actions"]
@@ -1200,7 +1209,9 @@ def check_episodes(case, out, stats=None, pair_fn=None, run_batch=None):
                 if acts[sg.t0 + s, i] != want:
                     _mm(mm, "action", sg.t0 + s, i, int(acts[sg.t0 + s, i]), int(want))
         _ep_stats(case, stats, segs_k, steps, fin, log, calls, prev_logs)
-    ex = expected_layout(case, segs, after, res)
+    ex = expected_layout(case, segs, after, res, reward_fn)
+    if collect is not None:
+        collect.update(segs=segs, after=after, res=res, ex=ex, ref=ref)
     # (a) the replay, (d) finished lanes idle until they are revived
     for t in range(T):
         _cmp(mm, "reward", t, out["reward"][t], ex["reward"][t])
@@ -1327,18 +1338,25 @@ def assert_non_vacuous_ep(stats, cases):
     return problems
 
 
-def _policy_closed_loop(case, segs_k, res, episode_fn=None):
+def _policy_closed_loop(case, segs_k, res, episode_fn=None, ref=None):
     """The policy's closed loop on a batch of segments: the policy is stateless and its answer at call site s depends on
     the actions before s only, so replaying and taking the answers up to the first disagreement converges in at most V
-    rounds.  Call sites past a segment's cut keep action 0 (no controller call happens there on the device)."""
+    rounds.  Call sites past a segment's cut keep action 0 (no controller call happens there on the device).  `ref`: the
+    learned family's reference (LearnedReference), which is told the actions of the round so that it evaluates no call
+    site whose frame is not final yet; the recurrent policy's answer at s depends on frames 0..s, so on the actions before
+    s only, and the same argument holds."""
     V = case["meta"]["video_length"]
-    ref = PolicyReference(case)
+    lazy = ref is not None
+    ref = PolicyReference(case) if ref is None else ref
     a = np.zeros((len(segs_k), V), np.int32)
     n = np.array([sg.n for sg in segs_k])
     while True:
         steps, bw, fin, log, calls = _run_batch(case, segs_k, a)
         eps = [sg.episode for sg in segs_k] if episode_fn is None else episode_fn(segs_k)
-        ref.prepare([sg.lane for sg in segs_k], eps, steps, bw)
+        if lazy:
+            ref.prepare([sg.lane for sg in segs_k], eps, steps, bw, n, k=segs_k[0].k, acts=a)
+        else:
+            ref.prepare([sg.lane for sg in segs_k], eps, steps, bw)
         want = np.stack([ref.ans[sg.lane] for sg in segs_k])
         bad = (want != a) & (np.arange(V)[None, :] < n[:, None])
         if not bad.any():
@@ -1422,3 +1440,809 @@ def subset_episode_case(case, out, pick):
     o["history"] = tuple(h[:, pick] for h in out["history"])
     o["qoe"] = out["qoe"][pick]
     return sub, o
+
+
+# =====================================================================================================================
+# The learned family: the learned-policy engines and the per-episode ledgers (make_learned_case / check_learned)
+#
+# A case of this family is an episode-family case (environment, speed feature, episode mode, sampler, lane_id_base,
+# operations, max_ticks: unchanged in kind) whose controller is one of eight learned policies (NETS): an MLP or a GRU
+# cell, on the lane engine or the matrix engine, alone or as a population with one weight set per lane group; with
+# arg-max or softmax sampling, an exploration coin, a value head or none, an episode ledger or none, a quality model or
+# none, and (`single`) launches of one decision taken through select(commit=True) + step instead of step_policy.
+#
+# check_learned is check_episodes with LearnedReference as the reference controller, plus the outputs this family adds.
+# The induction of the module docstring holds unchanged for the recurrent policy: its answer at call site s is a function
+# of the frames at call sites 0..s of the lane's segment (h = 0 at s = 0, then h = hp), which by (a) are the reference
+# closed loop's frames if the actions before s are the reference's answers.  The member of a population lane is
+# local lane // group -- abr_lane_jump.h: pop_member(block_first_lane, group) with block_first_lane = blockIdx.x * the
+# block size, an index into the environment's own lanes, and group a multiple of the block size -- never the global id.
+
+NETS = ("mlp", "mlp_mx", "gru", "gru_mx", "pop", "pop_mx", "gru_pop", "gru_pop_mx")
+LEARNED_CELLS = [(n, f) for n in NETS for f in SPEEDS]         # cell = seed % 32, mode = (seed // 32) % 4
+LEARNED_SLICE = len(LEARNED_CELLS) * len(EP_MODES)              # every (net, speed feature, mode) once
+POP_LANES = (300, 512, 600)                                     # 2 or 3 members of 256 lanes, the last partial in two
+POP_GROUP = 256
+GRU_H = dict(gru=(1, 7, 31, 32, 33, 64), gru_mx=(1, 31, 32, 33, 64, 65, 96, 127, 128))
+MX_WIDTHS = (1, 16, 32, 33, 64, 65, 96, 97, 128)
+LEDGER_FLOATS = ("rebuffer_time", "start_up_time", "average_latency", "variance", "qoe")
+LEDGER_INTS = ("episode", "trace_id", "start_offset", "chunks", "done")
+LEDGER_RTOL = dict(rebuffer_time=None, start_up_time=None, average_latency=1e-9, variance=None, qoe=1e-10)
+DONE_EPISODE = 1                                                # include/abr_env.h: ABR_DONE_EPISODE
+
+
+def net_is(case, what):
+    net = case["net"]
+    return dict(gru=net.startswith("gru"), pop="pop" in net, matrix=net.endswith("_mx"))[what]
+
+
+def _gru_parts(rng, F, H, M):
+    """GRUCell's four tensors and the head's two, scaled by fan-in as _policy_layers scales an MLP."""
+    n = lambda sd, *sh: rng.normal(0, sd, sh).astype(np.float32)
+    return (n(1.5 / np.sqrt(F), 3 * H, F), n(1.5 / np.sqrt(H), 3 * H, H), n(0.2, 3 * H), n(0.2, 3 * H),
+            n(1.5 / np.sqrt(H), M, H), n(0.2, M))
+
+
+def make_learned_case(seed, n_lanes=None, group=None):
+    """A deterministic case of the learned family.  n_lanes / group: smaller lane counts and lane groups for the host-only
+    tests (the device takes groups that are multiples of 256)."""
+    rng = np.random.default_rng(110_000 + seed)
+    net, feature = LEARNED_CELLS[seed % len(LEARNED_CELLS)]
+    mode = EP_MODES[(seed // len(LEARNED_CELLS)) % len(EP_MODES)]
+    rnd = seed // len(LEARNED_CELLS)
+    impls = accepted_impls_ep("policy", feature)
+    impl = impls[(rnd + seed // LEARNED_SLICE) % len(impls)]
+    pop = "pop" in net
+    vbr = rng.random() < 0.5
+    auto_reset = mode != "masked"
+    # the environment, as make_episode_case draws it
+    L = float(rng.choice([1.0, 2.0, 2.5, 3.0, 4.0, 6.0]))
+    interval = float(rng.choice([0.05, 0.25, 0.3, 0.5, 0.7, 1.0, 2.0, 3.7]))
+    B = int(rng.integers(1, 9)) if rng.random() < 0.8 else int(rng.integers(9, 17))
+    ladder = np.sort(rng.uniform(0.2, 8.0, B)).round(3)
+    ladder = np.maximum.accumulate(np.maximum(ladder, 0.2)).tolist()
+    if B >= 2 and rng.random() < 0.2:
+        ladder[1] = ladder[0]
+    max_buffer = float(rng.choice([L * 0.6, L * 1.2, L * 1.5, L * 1.9, L * 3, 7.3, 20.0]))
+    start_up = float(min(max_buffer, rng.choice([0.0, L, 1.7])))
+    speed = float(rng.choice([0.8, 1.0, 1.25]))
+    V = int(rng.integers(3, 19))
+    bw_lo = float(rng.choice([0.1, 0.5, 2.0] if feature != "rule" else [0.5, 2.0]))
+    bw_hi = bw_lo * float(rng.choice([3.0, 10.0, 40.0]))
+    own = POP_LANES[rnd % len(POP_LANES)] if pop else LANES[rnd % len(LANES)]
+    N = int(n_lanes if n_lanes is not None else own)
+    group = int(group if group is not None else POP_GROUP)
+    n_traces = 5
+    lens = rng.integers(40, 3000, n_traces)
+    lens[int(rng.integers(0, n_traces))] = int(rng.integers(8, 40))
+    traces = [rng.uniform(bw_lo, bw_hi, int(n)).astype(np.float32).astype(np.float64) for n in lens]
+    tid = rng.integers(0, n_traces, N).astype(np.int32)
+    off = np.array([rng.integers(0, lens[t]) for t in tid], np.int32)
+    br = np.tile(np.asarray(ladder, np.float64), (V, 1))
+    if vbr:
+        br = np.sort(br * rng.uniform(0.7, 1.3, (V, 1)) * rng.uniform(0.9, 1.1, (V, B)), axis=1)
+    case = dict(seed=seed, family="learned", mode=mode, ctl="policy", net=net, feature=feature, impl=impl, vbr=vbr,
+                auto_reset=auto_reset, n_lanes=N,
+                meta=dict(ladder=ladder, chunk_length=L, video_length=V, max_buffer=max_buffer, start_up_length=start_up,
+                          interval=interval, weights=[4.3, 1.0, 1.0, 0.1], speed=speed if feature == "config" else 1.0),
+                traces=traces, tid=tid, off=off, br=br if vbr else None)
+    # the policy
+    W = int(rng.integers(0, 17))
+    F = 4 + W + B
+    P = -(-N // group) if pop else 1
+    explore = float(rng.choice([0.0, 0.0, 0.3, 1.0]))
+    if net_is(case, "gru"):
+        H = int(rng.choice(GRU_H["gru_mx" if net_is(case, "matrix") else "gru"]))
+        p = policy_params(rng, case, W, [], explore)
+        del p["layers"]
+        p["hidden"] = H
+        members = [dict(parts=_gru_parts(rng, F, H, B)) for _ in range(P)]
+        vin = H
+    else:
+        if net_is(case, "matrix"):
+            widths = [int(x) for x in rng.choice(MX_WIDTHS, int(rng.integers(0, 4)))]
+            if rng.random() < 0.5:                              # at least one width past the lane engine's 64
+                widths = widths or [0]
+                widths[int(rng.integers(0, len(widths)))] = int(rng.choice([65, 96, 97, 128]))
+        else:
+            widths = [int(rng.integers(1, 65)) for _ in range(int(rng.integers(0, 3)))]
+        p = policy_params(rng, case, W, widths, explore)
+        members = [dict(layers=p.pop("layers"))] + [dict(layers=_policy_layers(rng, F, widths, B)) for _ in range(P - 1)]
+        p["widths"] = widths
+        vin = widths[-1] if widths else F
+    has_head = rng.random() < 2.0 / 3.0
+    for mb in members:
+        mb["head"] = ((rng.normal(0, 1.0 / np.sqrt(vin), vin).astype(np.float32),
+                       rng.normal(0, 0.2, 1).astype(np.float32)) if has_head else None)
+    p["sample"] = "softmax" if rng.random() < 0.6 else "argmax"
+    p["temperature"] = float(rng.choice([0.5, 0.7, 1.0, 2.0]))
+    p["members"], p["group"], p["value"] = members, group, has_head
+    case["params"] = p
+    # the ledgers
+    case["ledger"] = dict(rows=int(rng.choice([1, 2, 3]))) if rng.random() < 0.5 else None
+    case["quality"] = None
+    if rng.random() < 0.5:
+        k = int(rng.integers(0, 4))
+        util = ("identity", "log", "log_top")[k] if k < 3 else rng.uniform(-1.0, 3.0, (V, B)).round(3)
+        case["quality"] = dict(weight=float(rng.choice([0.37, 1.0, 3.0])), utility=util,
+                               rows=case["ledger"]["rows"] if case["ledger"] else 1)
+    case["single"] = bool(rng.random() < 0.25)
+    # the speed feature
+    if feature == "lanes":
+        case["lane_speeds"] = rng.choice([0.6, 0.8, 1.0, 1.25, 1.7, 0.9173], N)
+    elif feature == "schedule":
+        case["schedule"] = rng.choice([0.5, 0.75, 1.0, 1.1, 1.25, 1.5, 2.0], (N, int(rng.integers(2, 7))))
+    elif feature == "rule":
+        nl, nb = int(rng.integers(1, 3)), int(rng.integers(0, 3))
+        lat = np.sort(rng.choice(np.arange(0.5, 9.0, 0.5), nl, replace=False))
+        buf = np.sort(rng.choice(np.arange(0.25, max(max_buffer, 0.5) + 0.25, 0.25), min(nb, 2), replace=False))
+        sp = rng.choice([0.75, 0.9, 1.0, 1.1, 1.25, 1.5, 2.0], (nl + 1, len(buf) + 1))
+        case["rule"] = (tuple(float(x) for x in lat), tuple(float(x) for x in buf),
+                        tuple(tuple(float(x) for x in r) for r in sp))
+        case["log_rows"] = int(V + 4 if rng.random() < 0.7 else max(1, V // 2))
+    # the sampler and the global lane ids
+    sampler = None
+    if mode in ("sampled", "sampled_staggered") or (mode == "masked" and rng.random() < 0.5):
+        k = int(rng.integers(0, 3))
+        pool = None if k == 0 else ([int(rng.integers(0, n_traces))] if k == 1 else
+                                    rng.integers(0, n_traces, int(rng.integers(2, 9))).tolist())
+        span = int(rng.choice([0, 1, int(rng.integers(2, 40)), int(lens.max()) + int(rng.integers(1, 500))]))
+        sampler = dict(seed=int(rng.integers(0, 2 ** 63)) * 2 + int(rng.integers(0, 2)), pool=pool, span=span)
+    case["sampler"] = sampler
+    base = int(rng.choice(3))
+    case["lane_id_base"] = (0 if base == 0 else
+                            int(rng.integers(1, 2 ** 20)) * 64 + int(rng.integers(1, 64)) if base == 1 else
+                            2 ** 32 + int(rng.integers(0, 2 ** 40)))
+    # the operations: an initial reset, then launches with masked resets between them
+    ops = [("reset", None, "sample" if sampler is not None and rng.random() < 0.5 else "given")]
+    T = 2 * V + 1 + int(rng.integers(0, V + 1)) if auto_reset else 2 * V + 2 + int(rng.integers(0, V))
+    n_resets = 0 if mode == "sampled" else int(rng.integers(1, 4))
+    if mode == "masked":
+        at = sorted({int(rng.integers(1, V)), int(rng.integers(V, T - 1))} |
+                    {int(x) for x in rng.integers(1, T - 1, n_resets - 1)})
+    else:
+        at = sorted({int(x) for x in rng.integers(1, T - 1, n_resets)})
+    cuts = sorted(set(at) | {int(x) for x in rng.integers(1, T, max(1, T // 5))})
+    if case["single"]:                                          # a launch of one decision, split off a longer one
+        ends = [0] + cuts + [T]
+        if not any(b - a == 1 for a, b in zip(ends, ends[1:])):
+            a = max(zip(ends, ends[1:]), key=lambda x: x[1] - x[0])[0]
+            cuts = sorted(set(cuts) | {a + 1})
+    t = 0
+    for c in cuts + [T]:
+        if c <= t:
+            continue
+        ops.append(("launch", c - t))
+        t = c
+        if t in at:
+            ops.append(("reset", _wave_mask(rng, N), "sample" if sampler is not None and rng.random() < 0.6
+                        else "given"))
+    out_ops = []
+    for op in ops:
+        if op[0] == "reset" and op[2] == "given":
+            t_ = rng.integers(0, n_traces, N).astype(np.int32)
+            o_ = np.array([rng.integers(0, lens[x]) for x in t_], np.int32)
+            if op[1] is None:
+                t_, o_ = tid, off
+            out_ops.append(("reset", op[1], t_, o_))
+        elif op[0] == "reset":
+            out_ops.append(("reset", op[1], None, None))
+        else:
+            out_ops.append(op)
+    case["ops"] = out_ops
+    case["n_steps"] = T
+    slow = min(float(x.min()) for x in traces)
+    per_chunk = float(br.max()) * L / slow + L + (max_buffer + L) / 0.5
+    case["max_ticks"] = int(min(2 ** 31 - 1, 2 * V * per_chunk / 0.01 + 10_000))
+    return case
+
+
+def describe_learned(case):
+    p = case["params"]
+    shape = f"H={p['hidden']}" if net_is(case, "gru") else f"widths={p['widths']}"
+    q = case["quality"]
+    qs = "none" if q is None else f"{q['weight']}*{q['utility'] if isinstance(q['utility'], str) else 'table'}"
+    led = "none" if case["ledger"] is None else case["ledger"]["rows"]
+    return (f"learned seed={case['seed']} {case['net']}/{case['feature']}/{case['mode']}/{case['impl']} {shape} "
+            f"W={p['window']} {p['sample']} T={p['temperature']} explore={p['explore']} value={int(p['value'])} "
+            f"members={len(p['members'])} group={p['group']} ledger={led} quality={qs} single={int(case['single'])} "
+            + describe_ep(case))
+
+
+def quality_table(case):
+    """u float64 [V][M] of a case's quality model, from the definitions (README, DESIGN 4.8m): identity u = br[c][m];
+    log u = ln(br[c][m] / br[c][0]); log_top u = ln(br[c][m] / br[c][M - 1]); or the array as it is."""
+    import math
+    util, br = case["quality"]["utility"], br_table(case)
+    if not isinstance(util, str):
+        return np.asarray(util, np.float64)
+    if util == "identity":
+        return np.array(br, np.float64)
+    ref = br[:, 0] if util == "log" else br[:, -1]
+    return np.array([[math.log(br[c, m] / ref[c]) for m in range(br.shape[1])] for c in range(br.shape[0])])
+
+
+def launch_spans(case):
+    """[(operation index, first decision, decisions)] of the launches."""
+    out, t = [], 0
+    for oi, op in enumerate(case["ops"]):
+        if op[0] == "launch":
+            out.append((oi, t, op[1]))
+            t += op[1]
+    return out
+
+
+class LearnedReference(PolicyReference):
+    """The twins of the learned-policy engines as a reference controller.  MLP nets: policy_sample_twin.decide_sampled's
+    decision (the first arg-max, the softmax draw by word 2, the exploration coin by words 0 and 1 of the philox block
+    keyed by (seed, global lane id, chunk, the lane's own episode number)) on scores computed once with policy_twin.layer,
+    actor_critic_twin's value over the same hidden output.  GRU nets: policy_gru_twin.decide in a loop over the call site
+    s = 0..n, vectorised over the batch's segments, h = 0 at s = 0 and h = hp after.  Populations: each member's
+    segments with that member's weights, member = local lane // group.  Besides the answers it keeps every call site's
+    slabs (features, scores, probs, value, the state the decision started from and the one it left), for check_learned.
+    Call site n of a segment -- the frame its last decision left -- is evaluated too: last_value reads it.
+    mut: the perturbations of the checker's own tests (tests/test_closed_loop_learned_cpu.py)."""
+
+    def __init__(self, case, entries=None, mut=None):
+        super().__init__(case, entries)
+        self.mut = mut or {}
+        self.slabs, self.seen, self.col, self.segs = {}, {}, {}, None
+        self._k, self._P = None, None
+        p = case["params"]
+        self.gru = net_is(case, "gru")
+        self.iT = np.float32(1.0 / p["temperature"])
+        self.mode = 1 if p["sample"] == "softmax" else 0
+        t, self.launch_starts = 0, set()
+        for op in case["ops"]:
+            if op[0] == "launch":
+                self.launch_starts.add(t)
+                t += op[1]
+
+    def member_of(self, lanes):
+        p, N = self.case["params"], self.case["n_lanes"]
+        g, P = p["group"], len(p["members"])
+        lanes = np.asarray(lanes)
+        if P == 1:
+            return np.zeros(len(lanes), np.int64)
+        if self.mut.get("member") == "global":
+            return ((global_lanes(self.case)[lanes] // np.uint64(g)) % np.uint64(P)).astype(np.int64)
+        mb = lanes // g
+        if self.mut.get("member") == "partial_off_by_one" and N % g:
+            mb = np.where(mb == P - 1, P - 2, mb)
+        return mb
+
+    def _decide(self, mb, x, h, lane, c, ep):
+        """One member's decision on columns x [F, n] (h [H, n] for a GRU): dict(actions, scores, probs, value, hp, g,
+        coin)."""
+        import actor_critic_twin as AC
+        import policy_gru_twin as G
+        import policy_sample_twin as ST
+        import policy_twin as T
+        p = self.case["params"]
+        M = len(self.case["meta"]["ladder"])
+        if self.gru:
+            head = None if mb["head"] is None else np.concatenate([mb["head"][0], mb["head"][1]])
+            o = G.decide(mb["parts"], x, h, p["seed"], p["thr"], lane, c, ep, M, self.mode, self.iT, head)
+            o["g"] = T.argmax_first(o["scores"])
+            _, w1, _, _ = T.philox4(p["seed"], lane, c, ep)
+            o["coin"] = (w1 < np.uint64(p["thr"])) if p["thr"] < (1 << 32) else np.ones(len(c), bool)
+            return o
+        y = AC.hidden(mb["layers"], x)
+        s = T.layer(mb["layers"][-1][0], mb["layers"][-1][1], y)
+        g = T.argmax_first(s)
+        if self.mode == ST.ARGMAX:
+            pick, probs = g, (np.arange(M)[:, None] == g[None, :]).astype(np.float32)
+        else:
+            _, _, w2, _ = T.philox4(p["seed"], lane, c, ep)
+            pick, probs, _, _ = ST.softmax_sample(s, g, self.iT, w2)
+        a, coin = T.explore(p["seed"], p["thr"], lane, c, ep, M, pick)
+        v = None
+        if mb["head"] is not None:
+            v = T.layer(mb["head"][0].reshape(1, -1), mb["head"][1].reshape(1), y)[0]
+        return dict(actions=a, scores=s, probs=probs, value=v, hp=None, g=g, coin=coin)
+
+    def _eval(self, rows, sites, lanes, ks, feat, eps2, hcur):
+        """Evaluate call site sites[r] of batch rows `rows` and store the slabs; returns the actions."""
+        p = self.case["params"]
+        x = np.ascontiguousarray(feat[rows, sites].T)                      # [F, n]
+        ll = lanes[rows]
+        gl = global_lanes(self.case)[ll]
+        if self.mut.get("lane") == "mod_2_32":
+            gl = gl & np.uint64(0xFFFFFFFF)
+        ep = eps2[rows, sites].astype(np.int64)
+        if self.mut.get("episode") == "previous":
+            ep = np.maximum(ep - (ks[rows] > 0), 0)
+        h = None
+        if self.gru:
+            h = hcur[:, rows].copy()
+            for r, (j, s) in enumerate(zip(rows, sites)):
+                sg = self.segs[ll[r]][ks[j]] if self.segs is not None else None
+                if s == 0:
+                    stale = self.mut.get("gru") == "no_restart_at_masked_reset" and sg is not None and sg.reset_start \
+                        and sg.k > 0 and ll[r] in self.col
+                    h[:, r] = self.col[ll[r]] if stale else 0.0
+                elif self.mut.get("gru") == "restart_at_launch" and sg is not None and sg.t0 + s in self.launch_starts:
+                    h[:, r] = 0.0
+        mbs = self.member_of(ll)
+        acts = np.zeros(len(rows), np.int32)
+        for m in np.unique(mbs):
+            q = np.flatnonzero(mbs == m)
+            o = self._decide(p["members"][int(m)], x[:, q], None if h is None else h[:, q], gl[q], sites[q],
+                             ep[q].astype(np.uint64))
+            acts[q] = o["actions"]
+            for r_, a_ in zip(q, range(len(q))):
+                j, s = rows[r_], sites[r_]
+                sl = self.slabs[(int(ll[r_]), int(ks[j]))]
+                sl["features"][s], sl["scores"][s], sl["probs"][s] = x[:, r_], o["scores"][:, a_], o["probs"][:, a_]
+                sl["actions"][s], sl["g"][s], sl["coin"][s] = o["actions"][a_], o["g"][a_], o["coin"][a_]
+                if o["value"] is not None:
+                    sl["value"][s] = o["value"][a_]
+                if self.gru:
+                    sl["hin"][s], sl["hp"][s] = h[:, r_], o["hp"][:, a_]
+                    hcur[:, j] = o["hp"][:, a_]
+                sl["sites"] = max(sl["sites"], s + 1)
+        return acts
+
+    def prepare(self, lanes, eps, steps, bw, n=None, k=None, acts=None):
+        """As PolicyReference.prepare.  k: the batch's segment index (default: counted per lane).  acts [K, V]: the closed
+        loop's actions of this round (_policy_closed_loop): a segment is then evaluated only up to the first call site
+        whose answer differs from acts -- the frames behind it are not final -- and goes on from there in the next round."""
+        import policy_twin as T
+        p, m = self.case["params"], self.case["meta"]
+        V, M = m["video_length"], len(m["ladder"])
+        lanes = np.asarray(lanes)
+        K_ = len(lanes)
+        n = np.full(K_, V) if n is None else np.asarray(n)
+        if k is None:
+            ks = np.array([self.seen.get(int(i), 0) for i in lanes])
+            for i in lanes:
+                self.seen[int(i)] = self.seen.get(int(i), 0) + 1
+        else:
+            ks = np.full(K_, int(k))
+        table = br_table(self.case)
+        c = np.tile(np.arange(V), K_)
+        hist = np.repeat(bw, V, axis=0).T
+        feat = T.features(p["window"], M, V, c, steps["last_bitrate"].reshape(-1), steps["buffer_level"].reshape(-1),
+                          steps["global_time"].reshape(-1), steps["play_time"].reshape(-1), hist, lambda r: table[r],
+                          p["norm"]).T.reshape(K_, V, -1)
+        eps = np.asarray(eps, np.int64)
+        eps2 = np.repeat(eps[:, None], V, axis=1) if eps.ndim == 1 else eps
+        last = np.minimum(n, V - 1)                                        # call site n: the frame last_value reads
+        fresh = acts is None or self._k != (int(ks[0]), K_)
+        if fresh:
+            self._k = (int(ks[0]), K_)
+            self._P = np.zeros(K_, np.int64)
+            self._h = np.zeros((p.get("hidden", 1), K_), np.float32)
+            F, H = feat.shape[2], p.get("hidden", 0)
+            for j, i in enumerate(lanes):
+                self.slabs[(int(i), int(ks[j]))] = dict(
+                    features=np.zeros((V, F), np.float32), scores=np.zeros((V, M), np.float32),
+                    probs=np.zeros((V, M), np.float32), value=np.zeros(V, np.float32), hin=np.zeros((V, H), np.float32),
+                    hp=np.zeros((V, H), np.float32), actions=np.full(V, -9, np.int32), g=np.zeros(V, np.int64),
+                    coin=np.zeros(V, bool), sites=0)
+        P = self._P
+        if acts is None and not self.gru:                                  # stateless: every call site at once
+            rows = np.repeat(np.arange(K_), last + 1)
+            sites = np.concatenate([np.arange(x + 1) for x in last])
+            self._eval(rows, sites, lanes, ks, feat, eps2, self._h)
+            P[:] = last + 1
+        else:
+            stopped = np.zeros(K_, bool)
+            while ((P <= last) & ~stopped).any():
+                rows = np.flatnonzero((P <= last) & ~stopped)
+                sites = P[rows].copy()
+                a = self._eval(rows, sites, lanes, ks, feat, eps2, self._h)
+                P[rows] += 1
+                if acts is not None:                                       # a wrong guess: what follows is not final
+                    wrong = (sites < n[rows]) & (a != acts[rows, sites])
+                    stopped[rows[wrong]] = True
+        for j, i in enumerate(lanes):
+            sl = self.slabs[(int(i), int(ks[j]))]
+            ans = sl["actions"].copy()
+            if acts is not None:
+                ans[P[j]:] = acts[j, P[j]:]
+            self.ans[int(i)] = ans
+            done_all = P[j] > last[j]
+            if done_all:
+                if acts is None:
+                    self.coins.extend(sl["coin"][:n[j]].tolist())
+                if self.gru and n[j] > 0:
+                    self.col[int(i)] = sl["hp"][n[j] - 1].copy()           # the lane's state column after this segment
+
+
+def _site_index(case, segs):
+    """(segment index, call site) of every (decision, lane) of the run; -1 where the lane is idle."""
+    T, N = case["n_steps"], case["n_lanes"]
+    kk, ss = np.full((T, N), -1, np.int64), np.full((T, N), -1, np.int64)
+    for i in range(N):
+        for sg in segs[i]:
+            kk[sg.t0:sg.t0 + sg.n, i] = sg.k
+            ss[sg.t0:sg.t0 + sg.n, i] = np.arange(sg.n)
+    return kk, ss
+
+
+def _variance_in_order(case, acts):
+    """The sum over the episode of |br[c][a_c] - br[c + 1][a_(c + 1)]|, added in chunk order (the ledger's variance)."""
+    br = br_table(case)
+    v = 0.0
+    for c in range(len(acts) - 1):
+        v = v + abs(br[c][acts[c]] - br[c + 1][acts[c + 1]])
+    return v
+
+
+def learned_reward_fn(case, mut=None):
+    """expected_layout's reward of a segment under the case's quality model: float32(r64 - weight * u[c][a]) at every step
+    that completed a download -- every live step of a run without time-outs -- r64 the oracle's float64 reward."""
+    if case["quality"] is None:
+        return None
+    u, w = quality_table(case), np.float64(case["quality"]["weight"])
+    shift = 1 if (mut or {}).get("quality") == "next_chunk" else 0
+
+    def fn(case, steps, fin, acts):
+        m = case["meta"]
+        V = m["video_length"]
+        r64 = O.step_rewards(steps["rebuffer_time"][None], steps["start_up_time"][None],
+                             np.asarray([fin["rebuffer_time"]]), np.asarray([fin["start_up_time"]]), acts[None],
+                             m["weights"], ladder=m["ladder"], br_table=case["br"], dtype=np.float64)[0]
+        return (r64 - w * u[np.minimum(np.arange(V) + shift, V - 1), acts]).astype(np.float32)
+    return fn
+
+
+def learned_expected(case, segs, after, res, ref, mut=None):
+    """What the learned family adds to expected_layout, from the plan, the replay res and the reference's slabs:
+    launches (per launch: features / scores / probs / values / hidden [n, ., N], last_value [N]), hidden_after (per
+    operation: the controller's state slab [H, N], GRU nets), ledger and quality (the blobs' regions and records after
+    the last operation)."""
+    import ledger_twin
+    mut = mut or {}
+    p, m = case["params"], case["meta"]
+    V, N, M = m["video_length"], case["n_lanes"], len(m["ladder"])
+    F, H = 4 + p["window"] + M, p.get("hidden", 0)
+    gru = net_is(case, "gru")
+    kk, ss = _site_index(case, segs)
+    ex = dict(launches=[], hidden_after=[])
+    for oi, t0, n in launch_spans(case):
+        L = dict(features=np.zeros((n, F, N), np.float32), scores=np.zeros((n, M, N), np.float32),
+                 probs=np.zeros((n, M, N), np.float32), values=np.zeros((n, N), np.float32) if p["value"] else None,
+                 hidden=np.zeros((n, H, N), np.float32) if gru else None,
+                 last_value=np.zeros(N, np.float32) if p["value"] else None)
+        for t in range(t0, t0 + n):
+            for i in np.flatnonzero(kk[t] >= 0):                           # an idle (lane, step) keeps the zeros
+                sl, s = ref.slabs[(int(i), int(kk[t, i]))], ss[t, i]
+                L["features"][t - t0, :, i], L["scores"][t - t0, :, i] = sl["features"][s], sl["scores"][s]
+                L["probs"][t - t0, :, i] = sl["probs"][s]
+                if p["value"]:
+                    L["values"][t - t0, i] = sl["value"][s]
+                if gru:
+                    L["hidden"][t - t0, :, i] = sl["hp" if mut.get("hidden_out") == "hp" else "hin"][s]
+            if mut.get("idle_probs"):
+                L["probs"][t - t0, 0, kk[t] < 0] = 1.0
+        if p["value"]:
+            # last_value: V of the frame the launch leaves behind -- one more forward pass on it that stores no
+            # decision: call site c of the lane's current segment (c = 0 after a re-arm or a reset: the recurrent state
+            # restarts, so h_in = 0; else h_in is the hp of the decision before); 0.0 for a lane whose done bits are set
+            # (policy_gru_twin.select / the header's done-lane rule), which has no next decision.
+            ks, finished = after[oi]
+            for i in range(N):
+                if finished[i]:
+                    continue
+                sg = segs[i][ks[i]]
+                c = _n_at(case, sg, oi)
+                if mut.get("last_value") == "before_last_step" and kk[t0 + n - 1, i] >= 0:
+                    L["last_value"][i] = L["values"][n - 1, i]
+                else:
+                    L["last_value"][i] = ref.slabs[(i, sg.k)]["value"][c]
+        ex["launches"].append(L)
+    # the state slab after every operation: the hp of each lane's last live decision in the run so far; a reset does not
+    # touch it; a lane that has not decided yet holds the zeros the controller allocated
+    if gru:
+        t, cur = 0, np.zeros((H, N), np.float32)
+        for op in case["ops"]:
+            if op[0] == "launch":
+                for tt in range(t, t + op[1]):
+                    for i in np.flatnonzero(kk[tt] >= 0):
+                        cur[:, i] = ref.slabs[(int(i), int(kk[tt, i]))]["hp"][ss[tt, i]]
+                t += op[1]
+            ex["hidden_after"].append(cur.copy())
+    # the ledger and the quality records: one per finished episode and lane, in order; none for a segment a reset cut
+    rows = case["ledger"]["rows"] if case["ledger"] else (case["quality"]["rows"] if case["quality"] else None)
+    ex["ledger"] = ex["quality"] = None
+    if rows is None:
+        return ex
+    led = mut.get("ledger_cls", ledger_twin.TwinLedger)(N, rows)
+    u = quality_table(case) if case["quality"] else None
+    qrec, qtot, qlast = np.zeros((rows, N)), np.zeros(N), np.zeros(N)
+    recs = []
+    for i in range(N):
+        for sg in segs[i]:
+            if sg.end != "done" and not (mut.get("ledger") == "abandoned" and sg.end == "cut" and sg.n):
+                continue
+            steps, bw, fin, acts, _, _ = res[(i, sg.k)]
+            slot = int(led.count[i]) % rows
+            led.append(i, m["weights"], fin["rebuffer_time"], fin["start_up_time"], fin["average_latency"],
+                       _variance_in_order(case, acts), (sg.episode, sg.trace, sg.offset, V, DONE_EPISODE))
+            q = 0.0
+            if u is not None:
+                for c in range(V):                                         # the completed downloads, in call order
+                    q = q + u[c, acts[c]]
+                qrec[slot, i], qlast[i] = q, q
+                qtot[i] = qtot[i] + q
+            recs.append((i, sg.k, q))
+    count = led.count.copy()
+    keep = [r for r in recs if sum(1 for x in recs if x[0] == r[0] and x[1] > r[1]) < rows]      # the last `rows` per lane
+    rec = dict(lane=np.array([r[0] for r in keep], np.int64))
+    for f, k in enumerate(LEDGER_FLOATS):
+        rec[k] = np.array([_slot_of(led, segs, r, rows)[0][f] for r in keep], np.float64)
+    for f, k in enumerate(LEDGER_INTS):
+        rec[k] = np.array([_slot_of(led, segs, r, rows)[1][f] for r in keep], np.int64)
+    rec["quality"] = np.array([r[2] for r in keep], np.float64)
+    if case["ledger"]:
+        ex["ledger"] = dict(count=count, total=led.total.copy(), rf=led.rf.copy(), ri=led.ri.copy(), records=rec)
+    if case["quality"]:
+        ex["quality"] = dict(count=count, rec=qrec, total=qtot, last=qlast, records=rec)
+    return ex
+
+
+def _slot_of(led, segs, r, rows):
+    """(float fields, int fields) of record r = (lane, segment, quality) in the twin ledger's ring."""
+    i, k, _ = r
+    no = sum(1 for sg in segs[i] if sg.k < k and sg.end == "done")
+    return led.rf[no % rows, :, i], led.ri[no % rows, :, i]
+
+
+def _cmp_bits(out, name, step, got, want):
+    """Float32 arrays on the bit pattern."""
+    got, want = np.ascontiguousarray(got, np.float32), np.ascontiguousarray(want, np.float32)
+    if got.shape != want.shape:
+        _mm(out, name + ".shape", step, -1, list(got.shape), list(want.shape))
+        return
+    bad = got.view(np.uint32) != want.view(np.uint32)
+    for idx in np.argwhere(bad)[:8]:
+        _mm(out, name, step, idx[-1], dict(at=[int(x) for x in idx], value=float(got[tuple(idx)])),
+            float(want[tuple(idx)]))
+
+
+def check_learned(case, out, stats=None, pair_fn=None):
+    """Compare one run of the learned family with the reference closed loop: everything check_episodes compares, and
+    (float32 on the bit pattern) every slab the launches asked for, last_value, the controller's state slab after every
+    operation, the GAE kernel on each launch's own slabs, the quality term of every reward, and the ledger and quality
+    records after the last operation.  `out`: check_episodes' dict plus launches (per launch: features, scores, probs,
+    values, last_value, hidden, adv, ret), hidden_after (per operation), ledger and quality (dicts of numpy arrays:
+    count, total, rf, ri / rec, last; records, per_trace, per_member as the API returns them)."""
+    import actor_critic_twin as AC
+    stats = {} if stats is None else stats
+    ref = LearnedReference(case)
+    got = {}
+    ref.segs = episode_plan(case, pair_fn)[0]
+    mm = check_episodes(case, out, stats, pair_fn=pair_fn, ref=ref, reward_fn=learned_reward_fn(case), collect=got)
+    if not got:                                                           # a time-out: nothing to compare against
+        return mm
+    segs, after, res = got["segs"], got["after"], got["res"]
+    ex = learned_expected(case, segs, after, res, ref)
+    p = case["params"]
+    for li, ((oi, t0, n), L, E) in enumerate(zip(launch_spans(case), out["launches"], ex["launches"])):
+        for k in ("features", "scores", "probs", "values", "hidden", "last_value"):
+            if E[k] is not None:
+                _cmp_bits(mm, k, t0 if k != "last_value" else oi, L[k], E[k])
+        if p["value"]:
+            sl = slice(t0, t0 + n)
+            adv, ret = AC.gae(out["reward"][sl], L["values"], L["last_value"], out["done"][sl], out["actions"][sl],
+                              gamma=0.99, lam=0.95)
+            _cmp_bits(mm, "gae.adv", t0, L["adv"], adv)
+            _cmp_bits(mm, "gae.ret", t0, L["ret"], ret)
+    for oi, E in enumerate(ex["hidden_after"]):
+        _cmp_bits(mm, "ctl.hidden", oi, out["hidden_after"][oi], E)
+    N = case["n_lanes"]
+    P, g = len(p["members"]), p["group"]
+    if ex["ledger"] is not None:
+        G_, E = out["ledger"], ex["ledger"]
+        _cmp(mm, "ledger.count", -1, G_["count"], E["count"])
+        for f, k in enumerate(LEDGER_FLOATS):
+            _cmp(mm, "ledger.total." + k, -1, G_["total"][f], E["total"][f], rtol=1e-10)
+            _cmp(mm, "ledger.ring." + k, -1, G_["rf"][:, f].reshape(-1), E["rf"][:, f].reshape(-1),
+                 lanes=np.tile(np.arange(N), E["rf"].shape[0]), rtol=LEDGER_RTOL[k])
+        for f, k in enumerate(LEDGER_INTS):
+            _cmp(mm, "ledger.ring." + k, -1, G_["ri"][:, f].reshape(-1), E["ri"][:, f].reshape(-1),
+                 lanes=np.tile(np.arange(N), E["ri"].shape[0]))
+        _cmp_records(mm, "ledger.records", G_["records"], E["records"], LEDGER_INTS + LEDGER_FLOATS)
+        _cmp_groups(mm, "ledger.per_trace", G_["per_trace"], E["records"], E["records"]["trace_id"], len(case["traces"]),
+                    LEDGER_FLOATS)
+        if P > 1:
+            tot = {k: E["total"][f] for f, k in enumerate(LEDGER_FLOATS)}
+            _cmp_members(mm, "ledger.per_member", G_["per_member"], E["count"], tot, g, P)
+    if ex["quality"] is not None:
+        G_, E = out["quality"], ex["quality"]
+        _cmp(mm, "quality.count", -1, G_["count"], E["count"])
+        _cmp(mm, "quality.ring", -1, G_["rec"].reshape(-1), E["rec"].reshape(-1),
+             lanes=np.tile(np.arange(N), E["rec"].shape[0]))
+        _cmp(mm, "quality.last", -1, G_["last"], E["last"])
+        _cmp(mm, "quality.total", -1, G_["total"], E["total"], rtol=1e-10)
+        keys = ("quality",) + ((LEDGER_INTS + LEDGER_FLOATS) if case["ledger"] else ())
+        _cmp_records(mm, "quality.records", G_["records"], E["records"], keys)
+        if case["ledger"] and len(G_["records"]["qoe_q"]) == len(E["records"]["lane"]):
+            # qoe_q is qoe - weight * quality of the SAME record (tests/test_quality_gpu.py): `==` on the record's own
+            # fields, which are compared above (qoe at 1e-10, quality exactly).  Against the oracle's qoe the difference
+            # cancels -- the two terms are of one size -- so a relative bound on it would bound nothing.
+            want = G_["records"]["qoe"] - np.float64(case["quality"]["weight"]) * G_["records"]["quality"]
+            _cmp(mm, "quality.records.qoe_q", -1, G_["records"]["qoe_q"], want, lanes=E["records"]["lane"])
+    _learned_stats(case, stats, segs, after, ref, ex, out)
+    return mm
+
+
+def _cmp_records(mm, name, got, want, keys):
+    if not np.array_equal(np.asarray(got["lane"]), want["lane"]):
+        _mm(mm, name + ".lane", -1, -1, np.asarray(got["lane"]).tolist()[:8], want["lane"].tolist()[:8])
+        return
+    for k in keys:
+        _cmp(mm, f"{name}.{k}", -1, got[k], want[k], lanes=want["lane"], rtol=LEDGER_RTOL.get(k))
+
+
+def _cmp_groups(mm, name, got, rec, key, n, fields):
+    key = np.asarray(key, np.int64)
+    cnt = np.bincount(key, minlength=n)
+    _cmp(mm, name + ".count", -1, got["count"], cnt)
+    has = cnt > 0
+    for k in fields:
+        s = np.zeros(n)
+        np.add.at(s, key, rec[k])
+        _cmp(mm, f"{name}.{k}", -1, np.asarray(got[k])[has], (s[has] / cnt[has]), lanes=np.flatnonzero(has),
+             rtol=LEDGER_RTOL[k] or 1e-10)
+
+
+def _cmp_members(mm, name, got, count, totals, group, P):
+    mb = np.arange(len(count)) // group
+    cnt = np.bincount(mb, weights=count, minlength=P).astype(np.int64)
+    _cmp(mm, name + ".count", -1, got["count"], cnt)
+    for k, v in totals.items():
+        s = np.bincount(mb, weights=v, minlength=P)
+        _cmp(mm, f"{name}.{k}", -1, got[k], s / np.maximum(cnt, 1), rtol=LEDGER_RTOL[k] or 1e-10)
+
+
+def _learned_stats(case, stats, segs, after, ref, ex, out):
+    """The non-vacuity counters of one checked case (assert_non_vacuous_learned)."""
+    p, m = case["params"], case["meta"]
+    V, N, M = m["video_length"], case["n_lanes"], len(m["ladder"])
+    inc = lambda k, v=1: stats.__setitem__(k, stats.get(k, 0) + int(v))
+    stats.setdefault("net_impls", {}).setdefault(case["net"], set()).add(case["impl"])
+    kk, ss = _site_index(case, segs)
+    acts = out["actions"]
+    for (i, k), sl in ref.slabs.items():
+        n = segs[i][k].n
+        if p["sample"] == "softmax" and n:
+            own = ~sl["coin"][:n]
+            inc("soft_differs", (own & (sl["actions"][:n] != sl["g"][:n])).sum())
+            inc("soft_equals", (own & (sl["actions"][:n] == sl["g"][:n])).sum())
+    if M >= 6 and set(np.unique(acts[acts >= 0]).tolist()) == set(range(M)):
+        inc("all_actions")
+    gru = net_is(case, "gru")
+    if gru:
+        for i in range(N):
+            for sg in segs[i][1:]:
+                pv = segs[i][sg.k - 1]
+                if sg.reset_start and pv.end == "cut" and pv.n and sg.n and \
+                        ref.slabs[(i, pv.k)]["hp"][pv.n - 1].any():
+                    inc("gru_masked_rearm")
+        if case["impl"] in ("split", "split3", "auto"):
+            inner = set()
+            for _, t0, n in launch_spans(case):
+                inner |= set(range(t0 + 1, t0 + n))
+            inc("gru_mid_launch_rearm", any(sg.t0 in inner and not sg.reset_start and sg.k > 0 and sg.n
+                                            for s in segs for sg in s))
+    for t in range(kk.shape[0]):
+        for w in range(0, N, 64):
+            s = ss[t, w:w + 64]
+            if (s == 0).any() and (s > 0).any():
+                inc("wave_mixed_chunks")
+                break
+        else:
+            continue
+        break
+    P, g = len(p["members"]), p["group"]
+    if P > 1:
+        if N % g and (acts[:, (P - 1) * g:] >= 0).any():
+            inc("partial_group_decided")
+        mb = np.arange(N) // g
+        for c in range(V):
+            sets = [set(acts[(ss == c) & (mb[None, :] == q)].tolist()) for q in range(P)]
+            if sum(1 for x in sets if x) >= 2 and len(set().union(*sets)) > 1:
+                inc("members_differ")
+                break
+    cut_and_done = any({sg.end for sg in s if sg.n} >= {"cut", "done"} for s in segs)
+    if case["ledger"]:
+        inc("ledger_wrapped", (ex["ledger"]["count"] > case["ledger"]["rows"]).any())
+        inc("ledger_cut_and_done", cut_and_done)
+    if case["quality"]:
+        inc("quality_cut_and_done", cut_and_done)
+    if case["single"]:
+        inc("single_decisions", any(n == 1 and (kk[t0] >= 0).any() for _, t0, n in launch_spans(case)))
+    if case["lane_id_base"] >= 2 ** 32 and p["sample"] == "softmax":
+        inc("high_lane_ids_softmax")
+
+
+def assert_non_vacuous_learned(stats, cases):
+    """The learned family's aggregate over a slice: what the fuzz is meant to reach, it reached."""
+    problems = []
+    for net in NETS:
+        got = stats.get("net_impls", {}).get(net, set())
+        if got != set(accepted_impls_ep("policy", "config")):
+            problems.append(f"{net} ran on {sorted(got)} only")
+    for k, what in (("soft_differs", "no softmax pick differed from the arg-max"),
+                    ("soft_equals", "no softmax pick equalled the arg-max"),
+                    ("all_actions", "no case with M >= 6 answered every action"),
+                    ("gru_masked_rearm", "no running GRU lane with a nonzero state was re-armed by a masked reset and "
+                                         "decided afterwards"),
+                    ("gru_mid_launch_rearm", "no GRU lane was re-armed in the middle of a launch on a role-split impl"),
+                    ("wave_mixed_chunks", "no wave decided with lanes at chunk 0 and lanes past it"),
+                    ("partial_group_decided", "no population's partial last group took decisions"),
+                    ("members_differ", "no two members answered differently at call sites of one chunk index"),
+                    ("ledger_wrapped", "no ledger ring wrapped"),
+                    ("ledger_cut_and_done", "no ledger case had an abandoned and a finished episode on one lane"),
+                    ("quality_cut_and_done", "no quality case had an abandoned and a finished episode on one lane"),
+                    ("single_decisions", "no decision went through select + step"),
+                    ("high_lane_ids_softmax", "no lane_id_base >= 2^32 under softmax")):
+        if not stats.get(k):
+            problems.append(what)
+    if stats.get("explore") != {True, False}:
+        problems.append(f"the exploration coin fell {sorted(stats.get('explore', ()))}")
+    mx = [c["params"] for c in cases if net_is(c, "matrix")]
+    sizes = [w for q in mx for w in (q.get("widths") or []) + ([q["hidden"]] if "hidden" in q else [])]
+    if not any(w > 64 for w in sizes) or not any(w % 32 for w in sizes):
+        problems.append("no matrix-engine case past 64 units, or none off the 32-row tile")
+    return problems
+
+
+def oracle_run_learned(case, pair_fn=None, mut=None):
+    """The reference closed loop of a learned-family case on the host, laid out as a device run: the `out` dict
+    check_learned takes.  _policy_closed_loop's fixed-point iteration with LearnedReference (the recurrent policy's
+    answer at s depends on the actions before s only, so it converges in at most V rounds as well).  pair_fn and mut
+    (LearnedReference, learned_expected, learned_reward_fn) build the wrong runs of the checker's own tests."""
+    import actor_critic_twin as AC
+    mut = mut or {}
+    segs, after = episode_plan(case, pair_fn)
+    ref = LearnedReference(case, mut=mut)
+    ref.segs = segs
+    res = {}
+    for k in range(max(len(s) for s in segs)):
+        _policy_closed_loop(case, [s[k] for s in segs if len(s) > k], res, ref=ref)
+    ex = expected_layout(case, segs, after, res, learned_reward_fn(case, mut))
+    out = {k: ex[k] for k in ("actions", "reward", "done", "obs")}
+    out["frames"], out["episodes"], out["speed_logs"] = ex["frames"], ex["episodes"], ex["speed_logs"]
+    out["history"], out["qoe"], out["entries"] = ex["history"], ex["qoe"], None
+    if mut.get("quality") == "on_idle" and case["quality"]:             # the term applied where nothing was downloaded
+        u, w = quality_table(case), case["quality"]["weight"]
+        idle = out["actions"] < 0
+        out["reward"] = np.where(idle, np.float32(-w * u[-1, 0]), out["reward"]).astype(np.float32)
+    le = learned_expected(case, segs, after, res, ref, mut)
+    for (oi, t0, n), L in zip(launch_spans(case), le["launches"]):
+        if case["params"]["value"]:
+            sl = slice(t0, t0 + n)
+            L["adv"], L["ret"] = AC.gae(out["reward"][sl], L["values"], L["last_value"], out["done"][sl],
+                                        out["actions"][sl], gamma=0.99, lam=0.95)
+    out["launches"], out["hidden_after"] = le["launches"], le["hidden_after"]
+    N, p = case["n_lanes"], case["params"]
+    P, g = len(p["members"]), p["group"]
+    rec = le["ledger"]["records"] if le["ledger"] else (le["quality"]["records"] if le["quality"] else None)
+    out["ledger"] = out["quality"] = None
+    if le["ledger"]:
+        E = le["ledger"]
+        nt = len(case["traces"])
+        cnt = np.bincount(rec["trace_id"], minlength=nt)
+        per_trace = dict(count=cnt)
+        for k in LEDGER_FLOATS:
+            s = np.zeros(nt)
+            np.add.at(s, rec["trace_id"], rec[k])
+            with np.errstate(all="ignore"):
+                per_trace[k] = s / cnt
+        mb = np.arange(N) // g
+        mc = np.bincount(mb, weights=E["count"], minlength=P).astype(np.int64)
+        per_member = dict(count=mc)
+        for f, k in enumerate(LEDGER_FLOATS):
+            per_member[k] = np.bincount(mb, weights=E["total"][f], minlength=P) / np.maximum(mc, 1)
+        out["ledger"] = dict(E, per_trace=per_trace, per_member=per_member if P > 1 else None)
+    if le["quality"]:
+        E = le["quality"]
+        r = dict(rec)
+        if le["ledger"]:
+            r["qoe_q"] = rec["qoe"] - np.float64(case["quality"]["weight"]) * rec["quality"]
+        out["quality"] = dict(E, records=r)
+    return out

@@ -9,8 +9,28 @@ import numpy as np
 MASK32 = 0xFFFFFFFF
 
 
+F32_TINY = float(np.finfo(np.float32).tiny)
+
+
 def fmaf(a, b, c):
-    """Correctly rounded float32 fma, elementwise (numpy arrays or scalars of float32)."""
+    """Correctly rounded float32 fma, elementwise (numpy arrays or scalars of float32).  s = fl64(a*b + c) rounded to
+    float32 is already the correct result unless s lies exactly half way between two float32 values (for a normal float32
+    result: the low 29 bits of its significand are 1 followed by zeros) or in float32's subnormal range, where the
+    half-way points lie elsewhere; only those elements take fmaf_odd's rounding to odd."""
+    with np.errstate(all="ignore"):
+        a64, b64, c64 = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
+        s = np.asarray(a64 * b64 + c64)
+        r = s.astype(np.float32)
+        risky = ((s.view(np.int64) & 0x1FFFFFFF) == 0x10000000) | ((np.abs(s) < F32_TINY) & (s != 0))
+        if risky.any():
+            a64, b64, c64 = (np.broadcast_to(x, s.shape)[risky] for x in (a64, b64, c64))
+            r = np.array(r)
+            r[risky] = fmaf_odd(a64, b64, c64)
+        return r
+
+
+def fmaf_odd(a, b, c):
+    """fmaf by rounding to odd, on every element (the definition fmaf is checked against)."""
     with np.errstate(all="ignore"):
         a64, b64, c64 = (np.asarray(x, np.float32).astype(np.float64) for x in (a, b, c))
         p = a64 * b64
@@ -82,13 +102,11 @@ def features(W, M, V, c, a, B, G, P, hist, br, norm=None):
 def layer(W, b, x):
     """One layer in the contract's order: acc = b[j], then fmaf(W[j][k], x[k], acc) for k in order.  x [in, N]."""
     W = np.asarray(W, np.float32)
-    out = np.empty((W.shape[0], x.shape[1]), np.float32)
-    for j in range(W.shape[0]):
-        acc = np.full(x.shape[1], np.float32(b[j]), np.float32)
-        for k in range(W.shape[1]):
-            acc = fmaf(W[j, k], x[k], acc)
-        out[j] = acc
-    return out
+    x = np.asarray(x, np.float32)
+    acc = np.repeat(np.asarray(b, np.float32).reshape(-1, 1), x.shape[1], axis=1)
+    for k in range(W.shape[1]):                       # every row's chain at once: the same fmaf per element, in k order
+        acc = fmaf(W[:, k:k + 1], x[k][None, :], acc)
+    return acc
 
 
 def forward(layers, x):
