@@ -3233,6 +3233,9 @@ struct PolicyPopArgs : PolicyValueArgs {
     int32_t group, blob_words, head_words;
 };
 
+static_assert(sizeof(EnvParams) + sizeof(PolicyArgs) == 976 && sizeof(EnvParams) + sizeof(PolicyValueArgs) == 992 &&
+              sizeof(EnvParams) + sizeof(PolicyPopArgs) == 1008, "policy_select_kernel's kernarg segments");
+
 // SAMPLED: the instance behind abr_env_policy_select_sampled.  It keeps each lane's scores in its own column of LDS past
 // the weights (M * kPolicyBlock floats; the score loops run to a runtime M), where the draw turns them into e_m.
 // VALUE: the instances behind the _ac entries.  The value head is one more row of the staged layout and one more fmaf
@@ -3326,32 +3329,82 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(
     }
 }
 
-// the struct's shape alone: the size query checks no more, the entries go on to policy_fields (before the handle)
-static int validate_policy_shape(const abr_policy *pol) {
+// The struct's shape alone: the size query checks no more, the entries go on to policy_fields (before the handle).  The
+// two MLP structs share one set of checks and the two recurrent ones another; an engine's limits are the parameters.
+template <class Pol>
+constexpr bool kRecurrent = std::is_same_v<Pol, abr_policy_gru> || std::is_same_v<Pol, abr_policy_gru_mx>;
+
+template <class Pol>
+static int validate_window(const Pol *pol) {
     if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
     if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
         return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
-    if (pol->n_hidden < 0 || pol->n_hidden > ABR_POLICY_MAX_HIDDEN)
-        return fail(ABR_E_INVALID, "policy n_hidden %d outside 0..%d", pol->n_hidden, ABR_POLICY_MAX_HIDDEN);
-    for (int l = 0; l < ABR_POLICY_MAX_HIDDEN; l++) {
+    return ABR_OK;
+}
+
+// n_widths: how many width[] words the struct's contract covers
+template <class Pol>
+static int validate_mlp_shape(const Pol *pol, int max_hidden, int n_widths, int max_width) {
+    int rc = validate_window(pol);
+    if (rc) return rc;
+    if (pol->n_hidden < 0 || pol->n_hidden > max_hidden)
+        return fail(ABR_E_INVALID, "policy n_hidden %d outside 0..%d", pol->n_hidden, max_hidden);
+    for (int l = 0; l < n_widths; l++) {
         const int32_t wl = pol->width[l];
-        if (l < pol->n_hidden && (wl < 1 || wl > ABR_POLICY_MAX_WIDTH))
-            return fail(ABR_E_INVALID, "policy width[%d] = %d outside 1..%d", l, wl, ABR_POLICY_MAX_WIDTH);
+        if (l < pol->n_hidden && (wl < 1 || wl > max_width))
+            return fail(ABR_E_INVALID, "policy width[%d] = %d outside 1..%d", l, wl, max_width);
         if (l >= pol->n_hidden && wl != 0) return fail(ABR_E_INVALID, "policy width[%d] must be 0 past n_hidden", l);
     }
     return ABR_OK;
 }
 
-// an MLP's blob, which abr_policy and abr_policy_mx lay out alike: per layer W [out][in], then b [out]
+template <class Pol>
+static int validate_gru_shape(const Pol *pol, int max_hidden) {
+    int rc = validate_window(pol);
+    if (rc) return rc;
+    if (pol->hidden < 1 || pol->hidden > max_hidden)
+        return fail(ABR_E_INVALID, "policy hidden %d outside 1..%d", pol->hidden, max_hidden);
+    return ABR_OK;
+}
+
+static int validate_policy_shape(const abr_policy *pol) {
+    return validate_mlp_shape(pol, ABR_POLICY_MAX_HIDDEN, ABR_POLICY_MAX_HIDDEN, ABR_POLICY_MAX_WIDTH);
+}
+static int validate_policy_shape(const abr_policy_mx *pol) {
+    return validate_mlp_shape(pol, ABR_POLICY_MX_MAX_HIDDEN, ABR_POLICY_MX_MAX_HIDDEN + 1, ABR_POLICY_MX_MAX_WIDTH);
+}
+static int validate_policy_shape(const abr_policy_gru *pol) { return validate_gru_shape(pol, ABR_POLICY_GRU_MAX_HIDDEN); }
+static int validate_policy_shape(const abr_policy_gru_mx *pol) { return validate_gru_shape(pol, ABR_POLICY_GRU_MX_MAX_HIDDEN); }
+
+// One member's blob.  An MLP's, which abr_policy and abr_policy_mx lay out alike: per layer W [out][in], then b [out].
+// A GRU cell's, which abr_policy_gru and abr_policy_gru_mx lay out alike: the three gates' W_ih, W_hh, b_ih, b_hh, then
+// the output layer over h'.
 template <class Pol>
 static size_t policy_weights_bytes(const Pol *pol, int32_t M) {
-    size_t in = 4 + (size_t)pol->window + (size_t)M, words = 0;
-    for (int l = 0; l <= pol->n_hidden; l++) {
-        const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
-        words += out * in + out;
-        in = out;
+    const size_t F = 4 + (size_t)pol->window + (size_t)M;
+    if constexpr (kRecurrent<Pol>) {
+        const size_t h = (size_t)pol->hidden;
+        return (3 * h * (F + h + 2) + (size_t)M * (h + 1)) * sizeof(float);
+    } else {
+        size_t in = F, words = 0;
+        for (int l = 0; l <= pol->n_hidden; l++) {
+            const size_t out = l < pol->n_hidden ? (size_t)pol->width[l] : (size_t)M;
+            words += out * in + out;
+            in = out;
+        }
+        return words * sizeof(float);
     }
-    return words * sizeof(float);
+}
+
+// the four abr_policy_*_weights_bytes queries
+template <class Pol>
+static int policy_weights_query(const Pol *pol, int32_t n_rates, size_t *bytes_out) {
+    int rc = validate_policy_shape(pol);
+    if (rc) return rc;
+    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
+    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
+    *bytes_out = policy_weights_bytes(pol, n_rates);
+    return ABR_OK;
 }
 
 extern "C" int abr_policy_feature_dim(int32_t window, int32_t n_rates, int32_t *dim_out) {
@@ -3363,15 +3416,19 @@ extern "C" int abr_policy_feature_dim(int32_t window, int32_t n_rates, int32_t *
 }
 
 extern "C" int abr_policy_weights_bytes(const abr_policy *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_shape(pol);
-    if (rc) return rc;
-    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
-    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
-    *bytes_out = policy_weights_bytes(pol, n_rates);
-    return ABR_OK;
+    return policy_weights_query(pol, n_rates, bytes_out);
+}
+extern "C" int abr_policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t n_rates, size_t *bytes_out) {
+    return policy_weights_query(pol, n_rates, bytes_out);
+}
+extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n_rates, size_t *bytes_out) {
+    return policy_weights_query(pol, n_rates, bytes_out);
+}
+extern "C" int abr_policy_gru_mx_weights_bytes(const abr_policy_gru_mx *pol, int32_t n_rates, size_t *bytes_out) {
+    return policy_weights_query(pol, n_rates, bytes_out);
 }
 
-// What the three engines' argument builders (policy_lane_args, policy_mx_args, policy_gru_args) share.  A builder runs
+// What the engines' argument builders (policy_lane_args, policy_mx_args, policy_gru_args) share.  A builder runs
 // after the handle: it checks the byte counts that depend on the environment, then fills its kernel's struct from the
 // policy struct and from smp / val / pop where the entry has them (NULL otherwise).
 template <class Pol>
@@ -3404,6 +3461,48 @@ static int pop_covers(const abr_env *env, const abr_policy_pop *pop) {
     return ABR_OK;
 }
 
+// what every kernel's struct takes from smp / val / pop as they are: the draw, the head, the members' strides in floats
+template <class Args>
+static void policy_shared_args(Args *a, size_t weights_bytes, const abr_policy_sampling *smp, const abr_policy_value *val,
+                               const abr_policy_pop *pop) {
+    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
+    if (val) a->head = val->head_dev;
+    if (pop) {
+        a->group = pop->group;
+        a->blob_words = (int32_t)(weights_bytes / sizeof(float));
+        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
+    }
+}
+
+// The one chooser of a kernel's instances.  SAMPLED: a softmax draw or probs need the score columns in LDS; the argmax
+// without probs needs none, and the plain instance decides exactly as the sampled one in mode 0.  VALUE: the launch has a
+// head.  A rollout's bootstrap launch (argmax, no probs, a head) is therefore <false, true> whatever the entry's mode.
+// launch(S, V) gets the two as std::bool_constants.
+template <class Args, class Launch>
+static hipError_t policy_instance(const Args &a, bool always_sampled, const Launch &launch) {
+    const bool sampled = always_sampled || a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
+    if (sampled && value) return launch(std::true_type{}, std::true_type{});
+    if (sampled) return launch(std::true_type{}, std::false_type{});
+    if (value) return launch(std::false_type{}, std::true_type{});
+    return launch(std::false_type{}, std::false_type{});
+}
+
+// One workgroup of BLOCK per BLOCK lanes.  `a` is the widest struct of its engine on the host: an instance compiled for
+// a base of it takes `a` sliced.  most: the largest dynamic LDS the contract lets a launch of this kernel ask for, where
+// that passes the 64 KiB a kernel may take by default -- the instance's limit is then raised to it, once.
+template <auto Kernel, int BLOCK, class Args>
+static hipError_t policy_launch(const abr_env *env, const Args &a, size_t lds, hipStream_t st, int most = 0) {
+    static bool raised = false;
+    if (most && !raised) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
+        if (e != hipSuccess) return e;
+        raised = true;
+    }
+    hipLaunchKernelGGL(Kernel, dim3((unsigned)((env->p.n_lanes + BLOCK - 1) / BLOCK)), dim3(BLOCK), lds, st, env->p, a);
+    return hipGetLastError();
+}
+
 // The lane engine's struct is the widest one on the host whatever the entry: launch_policy_lane hands each instance the
 // base it was compiled for.
 static int policy_lane_args(const abr_env *env, const abr_policy *pol, const abr_policy_sampling *smp,
@@ -3418,32 +3517,19 @@ static int policy_lane_args(const abr_env *env, const abr_policy *pol, const abr
     a->weights = pol->weights_dev;
     if ((rc = check_head_bytes(val, pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1]))) return rc;
     if ((rc = pop_covers(env, pop))) return rc;
-    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
-    if (val) a->head = val->head_dev;
-    if (pop) {       // the member stride of the blob and of the heads, in floats
-        a->group = pop->group;
-        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
-    }
+    policy_shared_args(a, pol->weights_bytes, smp, val, pop);
     return ABR_OK;
 }
 
-// The one chooser of policy_select_kernel's instances.  SAMPLED: a softmax draw or probs need the score columns in LDS;
-// the argmax without probs needs none, and the plain instance decides exactly as the sampled one in mode 0.  The _sampled
-// entries (ALWAYS_SAMPLED) run the sampled instances in every mode.  VALUE: the launch has a head.  POP: the entry's.
-// A rollout's bootstrap launch (argmax, no probs, a head) is therefore <false, true, POP> whatever the entry's mode.
+// policy_select_kernel's instances.  The _sampled entries (ALWAYS_SAMPLED) run the sampled ones in every mode.
 template <bool POP, bool ALWAYS_SAMPLED = false>
 static hipError_t launch_policy_lane(const abr_env *env, const PolicyPopArgs &a, hipStream_t st) {
-    const bool sampled = ALWAYS_SAMPLED || a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t words = value ? abrx::policy_layout<true>(a.net).total : abrx::policy_layout(a.net).total;
-    const size_t lds = (words + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
-    const dim3 grid((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), block(kPolicyBlock);
-    // a POP == false instance takes `a` sliced to its own argument struct (PolicyValueArgs or PolicyArgs)
-    if (sampled && value) hipLaunchKernelGGL((policy_select_kernel<true, true, POP>), grid, block, lds, st, env->p, a);
-    else if (sampled) hipLaunchKernelGGL((policy_select_kernel<true, false, POP>), grid, block, lds, st, env->p, a);
-    else if (value) hipLaunchKernelGGL((policy_select_kernel<false, true, POP>), grid, block, lds, st, env->p, a);
-    else hipLaunchKernelGGL((policy_select_kernel<false, false, POP>), grid, block, lds, st, env->p, a);
-    return hipGetLastError();
+    return policy_instance(a, ALWAYS_SAMPLED, [&](auto S, auto V) {
+        constexpr bool sampled = decltype(S)::value, value = decltype(V)::value;
+        const size_t lds = ((size_t)abrx::policy_layout<value>(a.net).total + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) *
+                           sizeof(float);
+        return policy_launch<&policy_select_kernel<sampled, value, POP>, kPolicyBlock>(env, a, lds, st);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -3519,6 +3605,8 @@ __device__ __forceinline__ void mx_run_layer(const abrx::MxLayer &y, const float
 struct PolicyMxPopArgs : PolicyMxArgs {
     int32_t group, blob_words, head_words;
 };
+static_assert(sizeof(EnvParams) + sizeof(PolicyMxArgs) == 1008 && sizeof(EnvParams) + sizeof(PolicyMxPopArgs) == 1024,
+              "policy_mx_kernel's kernarg segments");
 
 // POP: as policy_select_kernel's -- one scalar adjustment of the blob and head pointers, made once, before the first
 // layer is staged; biases (mx_bias) and the head's row are read through the adjusted pointers as well.
@@ -3700,30 +3788,6 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p,
     a.action_out[i] = action;
 }
 
-static int validate_policy_shape(const abr_policy_mx *pol) {
-    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
-    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
-        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
-    if (pol->n_hidden < 0 || pol->n_hidden > ABR_POLICY_MX_MAX_HIDDEN)
-        return fail(ABR_E_INVALID, "policy n_hidden %d outside 0..%d", pol->n_hidden, ABR_POLICY_MX_MAX_HIDDEN);
-    for (int l = 0; l < ABR_POLICY_MX_MAX_HIDDEN + 1; l++) {
-        const int32_t wl = pol->width[l];
-        if (l < pol->n_hidden && (wl < 1 || wl > ABR_POLICY_MX_MAX_WIDTH))
-            return fail(ABR_E_INVALID, "policy width[%d] = %d outside 1..%d", l, wl, ABR_POLICY_MX_MAX_WIDTH);
-        if (l >= pol->n_hidden && wl != 0) return fail(ABR_E_INVALID, "policy width[%d] must be 0 past n_hidden", l);
-    }
-    return ABR_OK;
-}
-
-extern "C" int abr_policy_mx_weights_bytes(const abr_policy_mx *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_shape(pol);
-    if (rc) return rc;
-    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
-    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
-    *bytes_out = policy_weights_bytes(pol, n_rates);
-    return ABR_OK;
-}
-
 // the matrix engine's builder (as policy_lane_args: the widest struct, sliced at the launch)
 static int policy_mx_args(const abr_env *env, const abr_policy_mx *pol, const abr_policy_sampling *smp,
                           const abr_policy_value *val, const abr_policy_pop *pop, PolicyMxPopArgs *a) {
@@ -3737,27 +3801,18 @@ static int policy_mx_args(const abr_env *env, const abr_policy_mx *pol, const ab
     a->weights = pol->weights_dev;
     if ((rc = check_head_bytes(val, pol->n_hidden == 0 ? (size_t)a->net.F : (size_t)pol->width[pol->n_hidden - 1]))) return rc;
     if ((rc = pop_covers(env, pop))) return rc;
-    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
-    if (val) a->head = val->head_dev;
-    if (pop) {
-        a->group = pop->group;
-        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
-    }
+    policy_shared_args(a, pol->weights_bytes, smp, val, pop);
     return ABR_OK;
 }
 
-// the one chooser of policy_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, as launch_policy_lane
+// policy_mx_kernel's instances
 template <bool POP>
 static hipError_t launch_policy_mx(const abr_env *env, const PolicyMxPopArgs &a, hipStream_t st) {
-    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
-    const dim3 grid((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)), block(kMxBlock);
-    if (sampled && value) hipLaunchKernelGGL((policy_mx_kernel<true, true, POP>), grid, block, lds, st, env->p, a);
-    else if (sampled) hipLaunchKernelGGL((policy_mx_kernel<true, false, POP>), grid, block, lds, st, env->p, a);
-    else if (value) hipLaunchKernelGGL((policy_mx_kernel<false, true, POP>), grid, block, lds, st, env->p, a);
-    else hipLaunchKernelGGL((policy_mx_kernel<false, false, POP>), grid, block, lds, st, env->p, a);
-    return hipGetLastError();
+    return policy_instance(a, false, [&](auto S, auto V) {
+        constexpr bool sampled = decltype(S)::value, value = decltype(V)::value;
+        const size_t lds = (size_t)abrx::mx_lds_floats(a.net.F, a.net.M, a.n_hidden, a.width, sampled, kMxBlock) * sizeof(float);
+        return policy_launch<&policy_mx_kernel<sampled, value, POP>, kMxBlock>(env, a, lds, st);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -3784,6 +3839,8 @@ struct PolicyGruArgs {
 struct PolicyGruPopArgs : PolicyGruArgs {
     int32_t group, blob_words, head_words;
 };
+static_assert(sizeof(EnvParams) + sizeof(PolicyGruArgs) == 1016 && sizeof(EnvParams) + sizeof(PolicyGruPopArgs) == 1032,
+              "the kernarg segments of policy_gru_kernel and policy_gru_mx_kernel");
 
 // POP: the instances behind abr_env_gru_select_pop / abr_env_gru_step_pop (abr_policy_pop), as policy_select_kernel's.  The
 // workgroup computes the member it serves once, from its first lane, and stages that member's blob and head; the state
@@ -3896,35 +3953,14 @@ __global__ __launch_bounds__(kPolicyBlock, 2) void policy_gru_kernel(
     }
 }
 
-static size_t policy_gru_weights_bytes(int32_t W, int32_t H, int32_t M) {
-    const size_t F = 4 + (size_t)W + (size_t)M, h = (size_t)H;
-    return (3 * h * (F + h + 2) + (size_t)M * (h + 1)) * sizeof(float);
-}
-
-static int validate_policy_shape(const abr_policy_gru *pol) {
-    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
-    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
-        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
-    if (pol->hidden < 1 || pol->hidden > ABR_POLICY_GRU_MAX_HIDDEN)
-        return fail(ABR_E_INVALID, "policy hidden %d outside 1..%d", pol->hidden, ABR_POLICY_GRU_MAX_HIDDEN);
-    return ABR_OK;
-}
-
-extern "C" int abr_policy_gru_weights_bytes(const abr_policy_gru *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_shape(pol);
-    if (rc) return rc;
-    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
-    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
-    *bytes_out = policy_gru_weights_bytes(pol->window, pol->hidden, n_rates);
-    return ABR_OK;
-}
-
-// The recurrent engine's builder: one member's blob and head and the whole state slab against the environment, then the
-// population's cover.  The struct is the widest one on the host whatever the entry, as policy_lane_args'.
-static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const abr_policy_sampling *smp,
-                           const abr_policy_value *val, const abr_policy_pop *pop, PolicyGruPopArgs *a) {
+// The recurrent engines' builder (Pol: abr_policy_gru or abr_policy_gru_mx; the kernels share PolicyGruPopArgs): one
+// member's blob and head and the whole state slab against the environment, then the population's cover.  The struct is
+// the widest one on the host whatever the entry, as policy_lane_args'.
+template <class Pol>
+static int policy_gru_args(const abr_env *env, const Pol *pol, const abr_policy_sampling *smp, const abr_policy_value *val,
+                           const abr_policy_pop *pop, PolicyGruPopArgs *a) {
     const int32_t M = env->p.n_rates, H = pol->hidden;
-    int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
+    int rc = check_weights_bytes(pol->weights_bytes, policy_weights_bytes(pol, M), M);
     if (rc) return rc;
     const size_t state = (size_t)H * (size_t)env->p.n_lanes * sizeof(float);
     if (pol->state_bytes != state)
@@ -3936,49 +3972,24 @@ static int policy_gru_args(const abr_env *env, const abr_policy_gru *pol, const 
     a->net = policy_net(pol, M);
     a->net.n_hidden = 1; a->net.w0 = H;
     a->weights = pol->weights_dev; a->state = pol->state_dev;
-    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
-    if (val) a->head = val->head_dev;
-    if (pop) {       // the member stride of the blob and of the heads, in floats
-        a->group = pop->group;
-        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
-    }
+    policy_shared_args(a, pol->weights_bytes, smp, val, pop);
     return ABR_OK;
 }
 
-// The staged blob passes the 64 KiB a kernel may take by default, so each instance's dynamic-LDS limit is raised once,
-// to the largest launch the contract allows (H = 64, 16 rates, a value head, the score columns: 99 664 B).
-template <bool SAMPLED, bool VALUE, bool POP>
-static hipError_t launch_policy_gru_instance(const abr_env *env, const PolicyGruPopArgs &a, size_t lds, hipStream_t st) {
-    static bool raised = false;
-    if (!raised) {
+// policy_gru_kernel's instances.  The staged blob passes the 64 KiB a kernel may take by default; the largest launch the
+// contract allows is H = 64, 16 rates, a value head, the score columns: 99 664 B.
+template <bool POP>
+static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruPopArgs &a, hipStream_t st) {
+    return policy_instance(a, false, [&](auto S, auto V) {
+        constexpr bool sampled = decltype(S)::value, value = decltype(V)::value;
+        const size_t lds = ((size_t)abrx::policy_gru_layout<value>(a.net).total + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) *
+                           sizeof(float);
         abrx::PolicyNet top{};
         top.w0 = ABR_POLICY_GRU_MAX_HIDDEN;
         const int most = (int)(((size_t)abrx::policy_gru_layout<true>(top).total + (size_t)ABR_MAX_RATES * kPolicyBlock) *
                                sizeof(float));
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_kernel<SAMPLED, VALUE, POP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (e != hipSuccess) return e;
-        raised = true;
-    }
-    // a POP == false instance takes `a` sliced to PolicyGruArgs
-    hipLaunchKernelGGL((policy_gru_kernel<SAMPLED, VALUE, POP>),
-                       dim3((unsigned)((env->p.n_lanes + kPolicyBlock - 1) / kPolicyBlock)), dim3(kPolicyBlock), lds, st, env->p,
-                       a);
-    return hipGetLastError();
-}
-
-// the one chooser of policy_gru_kernel's instances: SAMPLED and VALUE by what the launch needs, POP the entry's, as
-// launch_policy_lane
-template <bool POP>
-static hipError_t launch_policy_gru(const abr_env *env, const PolicyGruPopArgs &a, hipStream_t st) {
-    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t words = value ? abrx::policy_gru_layout<true>(a.net).total : abrx::policy_gru_layout(a.net).total;
-    const size_t lds = (words + (sampled ? (size_t)a.net.M * kPolicyBlock : 0)) * sizeof(float);
-    if (sampled && value) return launch_policy_gru_instance<true, true, POP>(env, a, lds, st);
-    if (sampled) return launch_policy_gru_instance<true, false, POP>(env, a, lds, st);
-    if (value) return launch_policy_gru_instance<false, true, POP>(env, a, lds, st);
-    return launch_policy_gru_instance<false, false, POP>(env, a, lds, st);
+        return policy_launch<&policy_gru_kernel<sampled, value, POP>, kPolicyBlock>(env, a, lds, st, most);
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -4263,86 +4274,26 @@ __global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(
     a.action_out[i] = action;
 }
 
-static int validate_policy_shape(const abr_policy_gru_mx *pol) {
-    if (!pol) return fail(ABR_E_INVALID, "policy is NULL");
-    if (pol->window < 0 || pol->window > ABR_POLICY_MAX_WINDOW)
-        return fail(ABR_E_INVALID, "policy window %d outside 0..%d", pol->window, ABR_POLICY_MAX_WINDOW);
-    if (pol->hidden < 1 || pol->hidden > ABR_POLICY_GRU_MX_MAX_HIDDEN)
-        return fail(ABR_E_INVALID, "policy hidden %d outside 1..%d", pol->hidden, ABR_POLICY_GRU_MX_MAX_HIDDEN);
-    return ABR_OK;
-}
-
-extern "C" int abr_policy_gru_mx_weights_bytes(const abr_policy_gru_mx *pol, int32_t n_rates, size_t *bytes_out) {
-    int rc = validate_policy_shape(pol);
-    if (rc) return rc;
-    if (!bytes_out) return fail(ABR_E_INVALID, "bytes_out is NULL");
-    if (n_rates < 1 || n_rates > ABR_MAX_RATES) return fail(ABR_E_INVALID, "n_rates %d outside 1..%d", n_rates, ABR_MAX_RATES);
-    *bytes_out = policy_gru_weights_bytes(pol->window, pol->hidden, n_rates);
-    return ABR_OK;
-}
-
-// the builder: policy_gru_args' checks and fields for the wider struct (the kernels share PolicyGruPopArgs)
-static int policy_gru_mx_args(const abr_env *env, const abr_policy_gru_mx *pol, const abr_policy_sampling *smp,
-                              const abr_policy_value *val, const abr_policy_pop *pop, PolicyGruPopArgs *a) {
-    const int32_t M = env->p.n_rates, H = pol->hidden;
-    int rc = check_weights_bytes(pol->weights_bytes, policy_gru_weights_bytes(pol->window, H, M), M);
-    if (rc) return rc;
-    const size_t state = (size_t)H * (size_t)env->p.n_lanes * sizeof(float);
-    if (pol->state_bytes != state)
-        return fail(ABR_E_INVALID, "policy state_bytes %zu, %d units x %lld lanes need %zu", pol->state_bytes, H,
-                    (long long)env->p.n_lanes, state);
-    if ((rc = check_head_bytes(val, (size_t)H))) return rc;
-    if ((rc = pop_covers(env, pop))) return rc;
-    *a = PolicyGruPopArgs{};
-    a->net = policy_net(pol, M);
-    a->net.n_hidden = 1; a->net.w0 = H;
-    a->weights = pol->weights_dev; a->state = pol->state_dev;
-    if (smp) { a->mode = smp->mode; a->inv_temperature = smp->inv_temperature; }
-    if (val) a->head = val->head_dev;
-    if (pop) {       // the member stride of the blob and of the heads, in floats
-        a->group = pop->group;
-        a->blob_words = (int32_t)(pol->weights_bytes / sizeof(float));
-        a->head_words = val ? (int32_t)(val->head_bytes / sizeof(float)) : 0;
-    }
-    return ABR_OK;
-}
-
-// A unit tile at H = 128, W = 16, 16 rates is 68 608 B, past the 64 KiB a kernel may take by default: each instance's
-// dynamic-LDS limit is raised once, to the largest launch the contract allows (with the score columns: 84 992 B).
-template <bool SAMPLED, bool VALUE, bool POP>
-static hipError_t launch_policy_gru_mx_instance(const abr_env *env, const PolicyGruPopArgs &a, size_t lds, hipStream_t st) {
-    static bool raised = false;
-    if (!raised) {
-        const int most = (int)((size_t)abrx::gru_mx_lds_floats(abrx::kPolicyMaxF, ABR_POLICY_GRU_MX_MAX_HIDDEN, ABR_MAX_RATES,
-                                                               true, kMxBlock) * sizeof(float));
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(&policy_gru_mx_kernel<SAMPLED, VALUE, POP>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, most);
-        if (e != hipSuccess) return e;
-        raised = true;
-    }
-    hipLaunchKernelGGL((policy_gru_mx_kernel<SAMPLED, VALUE, POP>), dim3((unsigned)((env->p.n_lanes + kMxBlock - 1) / kMxBlock)),
-                       dim3(kMxBlock), lds, st, env->p, a);
-    return hipGetLastError();
-}
-
-// the one chooser of policy_gru_mx_kernel's instances: SAMPLED and VALUE by what the launch needs, POP the entry's, as
-// launch_policy_gru
+// policy_gru_mx_kernel's instances.  A unit tile at H = 128, W = 16, 16 rates is 68 608 B, past the 64 KiB a kernel may
+// take by default; the largest launch the contract allows has the score columns as well: 84 992 B.
 template <bool POP>
 static hipError_t launch_policy_gru_mx(const abr_env *env, const PolicyGruPopArgs &a, hipStream_t st) {
-    const bool sampled = a.mode != ABR_POLICY_ARGMAX || a.probs_out, value = a.head != nullptr;
-    const size_t lds = (size_t)abrx::gru_mx_lds_floats(a.net.F, a.net.w0, a.net.M, sampled, kMxBlock) * sizeof(float);
-    if (sampled && value) return launch_policy_gru_mx_instance<true, true, POP>(env, a, lds, st);
-    if (sampled) return launch_policy_gru_mx_instance<true, false, POP>(env, a, lds, st);
-    if (value) return launch_policy_gru_mx_instance<false, true, POP>(env, a, lds, st);
-    return launch_policy_gru_mx_instance<false, false, POP>(env, a, lds, st);
+    return policy_instance(a, false, [&](auto S, auto V) {
+        constexpr bool sampled = decltype(S)::value, value = decltype(V)::value;
+        const size_t lds = (size_t)abrx::gru_mx_lds_floats(a.net.F, a.net.w0, a.net.M, sampled, kMxBlock) * sizeof(float);
+        const int most = (int)((size_t)abrx::gru_mx_lds_floats(abrx::kPolicyMaxF, ABR_POLICY_GRU_MX_MAX_HIDDEN, ABR_MAX_RATES,
+                                                               true, kMxBlock) * sizeof(float));
+        return policy_launch<&policy_gru_mx_kernel<sampled, value, POP>, kMxBlock>(env, a, lds, st, most);
+    });
 }
 
 // ---------------------------------------------------------------------------
 // The host path of the learned-policy entries: one validator, one select, one rollout, whatever the engine
 // ---------------------------------------------------------------------------
 // An engine is an argument struct, a builder that fills it after the handle (policy_lane_args, policy_mx_args,
-// policy_gru_args, policy_gru_mx_args) and a launcher that picks the kernel instance (launch_policy_lane, launch_policy_mx,
-// launch_policy_gru, launch_policy_gru_mx), next to its validate_policy_shape.  Everything below is shared.
+// policy_gru_args for both recurrent engines) and a launcher that states its kernel template, LDS size and block
+// (launch_policy_lane, launch_policy_mx, launch_policy_gru, launch_policy_gru_mx), next to its validate_policy_shape's
+// limits.  Everything below is shared, as are policy_shared_args, policy_instance and policy_launch above.
 
 // the sampling struct alone
 static int validate_sampling(const abr_policy_sampling *smp) {
@@ -4389,7 +4340,7 @@ static int validate_policy_fields(const Pol *pol) {
     if (!pol->weights_dev || ((uintptr_t)pol->weights_dev & 3))
         return fail(ABR_E_INVALID, "policy weights must be non-NULL and 4-byte aligned");
     if ((uintptr_t)pol->norm_dev & 7) return fail(ABR_E_INVALID, "policy norm must be 8-byte aligned");
-    if constexpr (std::is_same_v<Pol, abr_policy_gru> || std::is_same_v<Pol, abr_policy_gru_mx>) {
+    if constexpr (kRecurrent<Pol>) {
         if (!pol->state_dev || ((uintptr_t)pol->state_dev & 3))
             return fail(ABR_E_INVALID, "policy state must be non-NULL and 4-byte aligned");
     }
@@ -4603,7 +4554,7 @@ extern "C" int abr_env_policy_select_gru(abr_env *env, const abr_policy_gru *pol
                                          const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
                                          float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                          float *value_out_dev, float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru<false>, nullptr,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args<abr_policy_gru>, launch_policy_gru<false>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4614,7 +4565,7 @@ extern "C" int abr_env_step_policy_gru(abr_env *env, const abr_policy_gru *pol, 
                                        float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                        float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                        void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args, launch_policy_gru<false>, &n_steps,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args<abr_policy_gru>, launch_policy_gru<false>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }
@@ -4624,7 +4575,7 @@ extern "C" int abr_env_gru_mx_select(abr_env *env, const abr_policy_gru_mx *pol,
                                      const abr_policy_value *val, int32_t commit, int32_t *action_out_dev,
                                      float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                      float *value_out_dev, float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx<false>, nullptr,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args<abr_policy_gru_mx>, launch_policy_gru_mx<false>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4635,7 +4586,7 @@ extern "C" int abr_env_gru_mx_step(abr_env *env, const abr_policy_gru_mx *pol, c
                                    float *features_out_dev, float *scores_out_dev, float *probs_out_dev,
                                    float *values_out_dev, float *last_value_out_dev, float *hidden_out_dev,
                                    void *stream) {
-    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_mx_args, launch_policy_gru_mx<false>, &n_steps,
+    return policy_entry(env, pol, 0, smp, val, nullptr, policy_gru_args<abr_policy_gru_mx>, launch_policy_gru_mx<false>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }
@@ -4647,7 +4598,7 @@ extern "C" int abr_env_gru_select_pop(abr_env *env, const abr_policy_gru *pol, c
                                              int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
                                              float *probs_out_dev, float *value_out_dev, float *hidden_out_dev,
                                              void *stream) {
-    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args, launch_policy_gru<true>, nullptr,
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args<abr_policy_gru>, launch_policy_gru<true>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4658,7 +4609,7 @@ extern "C" int abr_env_gru_step_pop(abr_env *env, const abr_policy_gru *pol, con
                                            int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
                                            float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
                                            float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args, launch_policy_gru<true>, &n_steps,
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args<abr_policy_gru>, launch_policy_gru<true>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }
@@ -4667,7 +4618,7 @@ extern "C" int abr_env_gru_mx_select_pop(abr_env *env, const abr_policy_gru_mx *
                                          const abr_policy_sampling *smp, const abr_policy_value *val, int32_t commit,
                                          int32_t *action_out_dev, float *features_out_dev, float *scores_out_dev,
                                          float *probs_out_dev, float *value_out_dev, float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_mx_args, launch_policy_gru_mx<true>, nullptr,
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args<abr_policy_gru_mx>, launch_policy_gru_mx<true>, nullptr,
                         {action_out_dev, features_out_dev, scores_out_dev, probs_out_dev, value_out_dev, hidden_out_dev},
                         stream, commit != 0);
 }
@@ -4678,7 +4629,7 @@ extern "C" int abr_env_gru_mx_step_pop(abr_env *env, const abr_policy_gru_mx *po
                                        int32_t *actions_out_dev, float *features_out_dev, float *scores_out_dev,
                                        float *probs_out_dev, float *values_out_dev, float *last_value_out_dev,
                                        float *hidden_out_dev, void *stream) {
-    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_mx_args, launch_policy_gru_mx<true>, &n_steps,
+    return policy_entry(env, pol, kNeedsPop, smp, val, pop, policy_gru_args<abr_policy_gru_mx>, launch_policy_gru_mx<true>, &n_steps,
                         {actions_out_dev, features_out_dev, scores_out_dev, probs_out_dev, values_out_dev, hidden_out_dev,
                          last_value_out_dev, obs_out_dev, reward_out_dev, done_out_dev}, stream);
 }

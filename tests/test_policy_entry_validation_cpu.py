@@ -1,9 +1,9 @@
 """Which check of a learned-policy entry point fails first, and with which message (include/abr_env.h documents the order
-entry by entry): one table over the 14 abr_env_policy_select* / abr_env_step_policy* entries, called on a NULL handle with
+entry by entry): one table over the 20 select and rollout entries of the four engines, called on a NULL handle with
 every single fault and every pair of simultaneous faults -- a bad reserved_ in the policy and in smp, a bad smp and
 n_steps = 0, probs without smp and a bad pop, n_steps = 0 and the NULL handle, a misaligned value head and probs without
 smp, and so on.  With several faults in one call the entry must report the one its order puts first.  The substrings and
-the order lists below are literals recorded from the library: the 14 entries share one host path, and this table is what
+the order lists below are literals recorded from the library: the 20 entries share one host path, and this table is what
 keeps a change to that path from moving a check for one of them."""
 import ctypes as C
 import itertools
@@ -71,7 +71,21 @@ ENTRIES = [
     ("abr_env_step_policy_mx_pop", "PolicyMx", "optional", "optional", True, MLP + SMP + VAL + ABSENT_STEP + POP + N),
     ("abr_env_policy_select_gru", "PolicyGru", "optional", "optional", False, GRU + SMP + VAL + ABSENT),
     ("abr_env_step_policy_gru", "PolicyGru", "optional", "optional", False, GRU + SMP + VAL + ABSENT_STEP + N),
+    ("abr_env_gru_mx_select", "PolicyGruMx", "optional", "optional", False, GRU + SMP + VAL + ABSENT),
+    ("abr_env_gru_mx_step", "PolicyGruMx", "optional", "optional", False, GRU + SMP + VAL + ABSENT_STEP + N),
+    ("abr_env_gru_select_pop", "PolicyGru", "optional", "optional", True, GRU + SMP + VAL + ABSENT + POP),
+    ("abr_env_gru_step_pop", "PolicyGru", "optional", "optional", True, GRU + SMP + VAL + ABSENT_STEP + POP + N),
+    ("abr_env_gru_mx_select_pop", "PolicyGruMx", "optional", "optional", True, GRU + SMP + VAL + ABSENT + POP),
+    ("abr_env_gru_mx_step_pop", "PolicyGruMx", "optional", "optional", True, GRU + SMP + VAL + ABSENT_STEP + POP + N),
 ]
+RECURRENT = ("PolicyGru", "PolicyGruMx")
+# each recurrent struct's own limit on `hidden`: every valid call is made at the limit, and
+# test_each_engine_has_its_own_limits calls one past it
+HIDDEN = {"PolicyGru": 64, "PolicyGruMx": 128}
+
+
+def _is_step(name):
+    return "_step" in name
 
 
 @pytest.fixture(scope="module")
@@ -85,8 +99,8 @@ def _valid(L, struct, smp, val, pop):
     """A call every check before the handle lets through: the arguments by name."""
     p = getattr(L, struct)()
     p.window, p.weights_dev, p.weights_bytes, p.seed = 8, 4096, 100, 1
-    if struct == "PolicyGru":
-        p.hidden, p.state_dev, p.state_bytes = 32, 8192, 100
+    if struct in RECURRENT:
+        p.hidden, p.state_dev, p.state_bytes = HIDDEN[struct], 8192, 100
     else:
         p.n_hidden, p.width[0], p.width[1] = 2, 64, 64
     a = dict(pol=p, smp=None, val=None, pop=None, n=4, probs=None, values=None, last=None)
@@ -166,15 +180,15 @@ def _compatible(f, g):
 def call(lib, entry, a):
     """The entry on a NULL handle: (return code, abr_last_error())."""
     name, struct, smp, val, pop, _ = entry
-    step, ref = "step_policy" in name, lambda s: C.byref(s) if s is not None else None
+    step, ref = _is_step(name), lambda s: C.byref(s) if s is not None else None
     args = [None, ref(a["pol"])] + ([ref(a["pop"])] if pop else []) + ([ref(a["smp"])] if smp else []) + \
         ([ref(a["val"])] if val else [])
     if step:
         args += [a["n"]] + [None] * 6                                       # obs, reward, done, actions, features, scores
     else:
-        args += ([0] if struct == "PolicyGru" else []) + [PTR, None, None]  # commit; action, features, scores
+        args += ([0] if struct in RECURRENT else []) + [PTR, None, None]  # commit; action, features, scores
     args += ([a["probs"]] if smp else []) + ([a["values"]] if val else []) + ([a["last"]] if val and step else [])
-    args += ([None] if struct == "PolicyGru" else []) + [None]              # hidden; stream
+    args += ([None] if struct in RECURRENT else []) + [None]              # hidden; stream
     rc = getattr(lib, name)(*args)
     return rc, lib.abr_last_error()
 
@@ -182,7 +196,7 @@ def call(lib, entry, a):
 def cases(entry):
     """(the optional structs left out, the faults injected, the fault that must be reported) for every call of `entry`."""
     name, _, smp, val, _, order = entry
-    handle = "handle.step" if "step_policy" in name else "handle.select"
+    handle = "handle.step" if _is_step(name) else "handle.select"
     variants = [()]
     if smp == "optional":
         variants += [("smp",), ("val",), ("smp", "val")]
@@ -216,9 +230,48 @@ def test_first_failing_check_and_its_message(L, entry):
     assert n > len(entry[5]) * (len(entry[5]) - 1) // 3                     # singles and most pairs ran
 
 
+LIMITS = [  # (entry, struct, size query, field, its limit, the message one past it)
+    ("abr_env_policy_select", "Policy", "abr_policy_weights_bytes", "n_hidden", 2, b"policy n_hidden 3 outside 0..2"),
+    ("abr_env_policy_select", "Policy", "abr_policy_weights_bytes", "width", 64, b"policy width[0] = 65 outside 1..64"),
+    ("abr_env_policy_select_mx", "PolicyMx", "abr_policy_mx_weights_bytes", "n_hidden", 3, b"policy n_hidden 4 outside 0..3"),
+    ("abr_env_policy_select_mx", "PolicyMx", "abr_policy_mx_weights_bytes", "width", 128,
+     b"policy width[0] = 129 outside 1..128"),
+    ("abr_env_policy_select_gru", "PolicyGru", "abr_policy_gru_weights_bytes", "hidden", 64, b"policy hidden 65 outside 1..64"),
+    ("abr_env_gru_mx_select", "PolicyGruMx", "abr_policy_gru_mx_weights_bytes", "hidden", 128,
+     b"policy hidden 129 outside 1..128"),
+]
+
+
+@pytest.mark.parametrize("limit", LIMITS, ids=lambda t: t[1] + "." + t[3])
+def test_each_engine_has_its_own_limits(L, limit):
+    """A shape at an engine's limit passes every check before the handle and its size query; one past the limit fails
+    with that engine's bound in the message, in the entry and in the query alike."""
+    name, struct, query, field, top, message = limit
+    entry = next(e for e in ENTRIES if e[0] == name)
+
+    def calls(value):
+        a = _valid(L, struct, entry[2], entry[3], entry[4])
+        if field == "n_hidden":
+            a["pol"].n_hidden = value
+            for l in range(min(value, len(a["pol"].width))):
+                a["pol"].width[l] = 32
+        elif field == "width":
+            a["pol"].width[0] = value
+        else:
+            setattr(a["pol"], field, value)
+        n = C.c_size_t(0)
+        rc = getattr(L.lib(), query)(C.byref(a["pol"]), 6, C.byref(n))
+        return call(L.lib(), entry, a), (rc, L.lib().abr_last_error())
+
+    (rc, err), (qrc, _) = calls(top)
+    assert rc == -1 and MESSAGE["handle.select"] in err and qrc == 0
+    (rc, err), (qrc, qerr) = calls(top + 1)
+    assert rc == -1 and message in err and qrc == -1 and message in qerr
+
+
 def test_table_covers_the_abi(L):
-    names = [s[0] for s in L.SYMBOLS if s[0].startswith(("abr_env_policy_select", "abr_env_step_policy"))]
-    assert sorted(names) == sorted(e[0] for e in ENTRIES) and len(names) == 14
+    names = [s[0] for s in L.SYMBOLS if s[0].startswith(("abr_env_policy_select", "abr_env_step_policy", "abr_env_gru_"))]
+    assert sorted(names) == sorted(e[0] for e in ENTRIES) and len(names) == 20
     assert set(FAULTS) | {"handle.select", "handle.step"} == set(MESSAGE)
     for f, g in (("pol.reserved", "smp.reserved"), ("smp.mode", "n_steps"), ("probs_without_smp", "pop.group"),
                  ("val.head", "probs_without_smp"), ("values_without_val", "pop.null")):
