@@ -276,3 +276,51 @@ def test_table_covers_the_abi(L):
     for f, g in (("pol.reserved", "smp.reserved"), ("smp.mode", "n_steps"), ("probs_without_smp", "pop.group"),
                  ("val.head", "probs_without_smp"), ("values_without_val", "pop.null")):
         assert _compatible(f, g)                                            # the pairs the order matters most for
+
+
+def test_the_python_engine_table_is_the_abi(L):
+    """policy.ENGINES, which every entries() reads, names exactly the 20 entries of the table above and the four size
+    queries, all of them bound symbols; and each entry is what exactly one (class, engine) pair launches -- one pair per
+    class and engine, but for the lane MLP, which has a pair per mode (plain, sampled, actor-critic)."""
+    import types
+
+    import numpy as np
+    import torch
+
+    import abrsimulator_amd as A
+    from abrsimulator_amd import policy
+    from abrsimulator_amd.datamodel import MPD, Chunk
+    rows = [row for family in policy.ENGINES.values() for row in family.values()]
+    assert [sorted(family) for family in policy.ENGINES.values()] == [["lane", "matrix"]] * 2
+    names = [n for row in rows for pair in row.single + (row.pop,) for n in pair]
+    assert sorted(names) == sorted(e[0] for e in ENTRIES) and len(set(names)) == 20
+    symbols = [s[0] for s in L.SYMBOLS]
+    assert all(n in symbols for n in names)
+    assert sorted(row.size_query for row in rows) == sorted(s for s in symbols if s.endswith("_weights_bytes"))
+    assert len(rows) == 4
+
+    class Player:
+        env = types.SimpleNamespace(n_lanes=256, n_rates=6, device=torch.device("cpu"))
+
+        def get_mpd(self):
+            return MPD(10, 4.0, 20.0, 4.0, Chunk([0.3, 0.75, 1.2, 1.85, 2.85, 4.3]))
+
+    F, M, z = 18, 6, lambda *shape: np.zeros(shape, np.float32)
+    mlp, gru, head = [(z(M, F), z(M))], ((z(3, F), z(3, 1), z(3), z(3)), (z(M, 1), z(M))), lambda n: (z(n), np.float32(0))
+    reached = {}
+    for engine in ("lane", "matrix"):
+        kw = dict(engine=engine, device="cpu")
+        for ctl in (A.PolicyController(Player(), mlp, value_head=head(F), **kw),
+                    A.PolicyPopulation(Player(), [mlp], 256, value_heads=[head(F)], **kw),
+                    A.RecurrentPolicyController(Player(), *gru, value_head=head(1), **kw),
+                    A.RecurrentPolicyPopulation(Player(), [gru], 256, value_heads=[head(1)], **kw)):
+            pairs = set()
+            for sample, val, probs in itertools.product(policy.SAMPLE_MODES, (None, ctl.value()), (False, True)):
+                ctl.sample = sample
+                pair, structs, groups = ctl.entries(val, probs)
+                assert "select" in pair[0] and "step" in pair[1] and (val is None or any(s is val for s in structs))
+                pairs.add(pair)
+            assert len(pairs) == (3 if (type(ctl), engine) == (A.PolicyController, "lane") else 1)
+            for n in (n for pair in pairs for n in pair):
+                assert reached.setdefault(n, (type(ctl).__name__, engine)) == (type(ctl).__name__, engine)
+    assert sorted(reached) == sorted(names)

@@ -430,3 +430,36 @@ def test_refusals():
     # PolicyPopulation keeps refusing a recurrent member
     with pytest.raises(ValueError, match="recurrent"):
         A.PolicyPopulation(_Player(700), [torch.nn.GRUCell(F, 5)], group=256)
+
+
+REFUSED_LOADS = ("stacked, bv of the wrong length", "stacked, Wv of the wrong width", "list, last member's hidden width",
+                 "list, last member's head", "list of P - 1 members")
+
+
+@pytest.mark.parametrize("case", REFUSED_LOADS)
+def test_a_refused_load_writes_nothing(case):
+    """load_weights is all or nothing: a generation with a fault anywhere -- in the last member, or in the heads, which
+    come after the weights -- raises ValueError and leaves weights and value_heads bit for bit as they were."""
+    import abrsimulator_amd as A
+    rng = np.random.default_rng(6)
+    P, H = 3, 5
+    head = lambda n=H: (rng.standard_normal(n).astype(f32), f32(rng.standard_normal()))
+    hstack = lambda hs: (np.stack([h[0] for h in hs]), np.array([h[1] for h in hs], f32))
+    pop = A.RecurrentPolicyPopulation(_Player(700), [_member(rng, H) for _ in range(P)], 256,
+                                      value_heads=[head() for _ in range(P)], device="cpu")
+    new, heads = [_member(rng, H) for _ in range(P)], [head() for _ in range(P)]
+    Wv, bv = hstack(heads)
+    members, value_heads = {
+        REFUSED_LOADS[0]: (_stack(new), (Wv, bv[:-1])),
+        REFUSED_LOADS[1]: (_stack(new), (np.concatenate([Wv, Wv[:, :1]], axis=1), bv)),
+        REFUSED_LOADS[2]: (new[:-1] + [_member(rng, H + 1)], heads),
+        REFUSED_LOADS[3]: (new, heads[:-1] + [head(H + 1)]),
+        REFUSED_LOADS[4]: (new[:-1], heads[:-1]),
+    }[case]
+    before, before_h = pop.weights.numpy().tobytes(), pop.value_heads.numpy().tobytes()
+    with pytest.raises(ValueError):
+        pop.load_weights(members, value_heads=value_heads)
+    assert pop.weights.numpy().tobytes() == before and pop.value_heads.numpy().tobytes() == before_h
+    assert not pop.hidden.any()
+    pop.load_weights(new, value_heads=heads)                                # the same generation without the fault loads
+    assert pop.weights.numpy().tobytes() != before and pop.value_heads.numpy().tobytes() != before_h

@@ -328,6 +328,40 @@ def test_refusals():
         pop.bound(types.SimpleNamespace(n_lanes=700, n_rates=5))
 
 
+REFUSED_LOADS = ("stacked, bv of the wrong length", "stacked, Wv of the wrong width", "list, last member's hidden width",
+                 "list, last member's head", "list of P - 1 members")
+
+
+@pytest.mark.parametrize("case", REFUSED_LOADS)
+def test_a_refused_load_writes_nothing(case):
+    """load_weights is all or nothing: a generation with a fault anywhere -- in the last member, or in the heads, which
+    come after the weights -- raises ValueError and leaves weights and value_heads bit for bit as they were."""
+    import abrsimulator_amd as A
+    rng = np.random.default_rng(6)
+    P, H = 3, 5
+    mk = lambda hidden=H: _layers(rng, 18, [hidden], 6)
+    head = lambda n=H: (rng.normal(0, 1, n).astype(np.float32), np.float32(rng.normal()))
+    stack = lambda ms: [(np.stack([m[l][0] for m in ms]), np.stack([m[l][1] for m in ms])) for l in range(2)]
+    hstack = lambda hs: (np.stack([h[0] for h in hs]), np.array([h[1] for h in hs], np.float32))
+    pop = A.PolicyPopulation(_Player(700), [mk() for _ in range(P)], 256, value_heads=[head() for _ in range(P)],
+                             device="cpu")
+    new, heads = [mk() for _ in range(P)], [head() for _ in range(P)]
+    Wv, bv = hstack(heads)
+    members, value_heads = {
+        REFUSED_LOADS[0]: (stack(new), (Wv, bv[:-1])),
+        REFUSED_LOADS[1]: (stack(new), (np.concatenate([Wv, Wv[:, :1]], axis=1), bv)),
+        REFUSED_LOADS[2]: (new[:-1] + [mk(H + 1)], heads),
+        REFUSED_LOADS[3]: (new, heads[:-1] + [head(H + 1)]),
+        REFUSED_LOADS[4]: (new[:-1], heads[:-1]),
+    }[case]
+    before, before_h = pop.weights.numpy().tobytes(), pop.value_heads.numpy().tobytes()
+    with pytest.raises(ValueError):
+        pop.load_weights(members, value_heads=value_heads)
+    assert pop.weights.numpy().tobytes() == before and pop.value_heads.numpy().tobytes() == before_h
+    pop.load_weights(new, value_heads=heads)                                # the same generation without the fault loads
+    assert pop.weights.numpy().tobytes() != before and pop.value_heads.numpy().tobytes() != before_h
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # EpisodeLedger.per_member
 
