@@ -9,6 +9,7 @@ from .advantage import gae
 from .datamodel import MPD, Chunk, ChunkInfo, NetworkInfo, QOEMetric
 from .env import BatchedABREnv, obs_dict, pack_traces
 from .episodes import EpisodeSampler
+from .expert import LookaheadExpert
 from .fastmpc import FastMPCController
 from .ledger import EpisodeLedger
 from .quality import EpisodeQuality
@@ -27,6 +28,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "RecurrentPolicyPopulation", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "HindsightSearch", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
+           "HindsightSearch", "LookaheadExpert", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

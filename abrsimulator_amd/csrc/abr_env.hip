@@ -2041,6 +2041,115 @@ extern "C" int abr_beam_select(int32_t n_groups, int32_t beam, int32_t n_rates, 
     return ABR_OK;
 }
 
+// ---------------------------------------------------------------------------
+// lookahead expert (include/abr_env.h: abr_env_lookahead_select): the exact tree of the next H decisions, per lane
+// ---------------------------------------------------------------------------
+// A workgroup is 64 lanes times n_rates waves: wave m walks the subtree a_0 = m of its 64 lanes (abr_lane_jump.h:
+// look_subtree), writes its q_out row, and the n_rates candidates meet in LDS for action and key.  One instance per horizon,
+// n_rates a run-time value.  The leaf cap bounds the waves an instance can be launched with -- the largest M with M^H <=
+// 65 536 -- and that is its __launch_bounds__: the deep instances, whose stack of saved lanes is what costs registers, are
+// the ones that never run more than a few waves per workgroup.  W halves the shallow instances once more: up to 8 rates (W
+// = 8, 512 threads, 256 registers per lane) and up to 16 (W = 16, 128 registers), because at 1 024 threads horizons 3 and 4
+// spilled 48 and 256 bytes per lane to scratch, which the 8-wave form does not (profiles/lookahead_resources.txt).
+constexpr int look_max_rates(int H) {
+    int m = 1;
+    while (m < ABR_MAX_RATES && abrx::look_leaves(m + 1, H) <= abrx::kLookMaxLeaves) m++;
+    return m;
+}
+static_assert(look_max_rates(1) == 16 && look_max_rates(4) == 16 && look_max_rates(5) == 9 && look_max_rates(6) == 6 &&
+              look_max_rates(7) == 4 && look_max_rates(8) == 4, "the leaf cap's wave counts");
+
+constexpr int look_waves(int H, int W) { return W < look_max_rates(H) ? W : look_max_rates(H); }
+
+template <int H, int W>
+__global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
+    EnvParams p, abrx::EpisodeQuality ql, int64_t lane0, int64_t lane_end, int32_t *__restrict__ action_out,
+    double *__restrict__ key_out, double *__restrict__ q_out) {
+    __shared__ double s_q[look_waves(H, W)][64];
+    const int32_t m = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));     // the wave's first digit, scalar
+    const int32_t l = (int32_t)(threadIdx.x & 63);
+    const int64_t i = lane0 + (int64_t)blockIdx.x * 64 + l;
+    const abrx::TablesT<false> tb = make_tables<false>(p);
+    LaneJ s{};
+    int32_t n_su_obs = 0, n_rb_obs = 0;
+    bool live = false;
+    if (i < lane_end && p.done[i] == 0) {      // a lane that was never reset carries ABR_DONE_EPISODE (abr_env_create)
+        live = true;
+        const int32_t t = p.trace_id[i];
+        s.cur.tlen = p.trace_len[t]; s.cur.trace = p.traces + p.trace_off[t];
+        lanej_load<false>(s, p, i);
+        n_su_obs = p.n_su_obs[i]; n_rb_obs = p.n_rb_obs[i];
+    }
+    abrx::LookWeights w;
+    w.wr = p.wr; w.ws = p.ws; w.wv = p.wv; w.wl = p.wl; w.M = p.n_rates; w.quality = ql.base != nullptr;
+    const auto br = [&](int32_t chunk, int32_t rate) { return chunk_bitrate(p, chunk, rate); };
+    const auto G = [&](int32_t n) { return p.G[n]; };
+    const auto lat = [&](const LaneJ &x) { return lane_avg_latency(p, x.sumk, x.n_play); };
+    const auto qt = [&](int32_t chunk, int32_t rate) { return abrx::quality_peek(ql, p.n_rates, chunk, rate); };
+    const auto any = [](bool f) { return __any(f) != 0; };
+    const double q = abrx::look_subtree<H>(w, tb, br, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
+    s_q[m][l] = q;
+    if (q_out && i < lane_end) ABR_OUT(q_out[(int64_t)m * p.n_lanes + i], q);
+    __syncthreads();
+    if (m == 0 && i < lane_end) {
+        int32_t action;
+        double key;
+        abrx::look_pick([&](int32_t r) { return s_q[r][l]; }, p.n_rates, action, key);
+        ABR_OUT(action_out[i], action);
+        if (key_out) ABR_OUT(key_out[i], key);
+    }
+}
+
+template <int H>
+static void launch_lookahead(const abr_env *env, int64_t lane0, int64_t lane_end, int32_t *action, double *key, double *q,
+                             hipStream_t st) {
+    const dim3 grid(grid64(lane_end - lane0)), block(64u * (unsigned)env->p.n_rates);
+    if (env->p.n_rates <= 8 || look_max_rates(H) <= 8)       // (the refusals have bounded n_rates by look_max_rates(H))
+        hipLaunchKernelGGL((lookahead_kernel<H, 8>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, action, key, q);
+    else if constexpr (look_max_rates(H) > 8)
+        hipLaunchKernelGGL((lookahead_kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, action, key, q);
+}
+
+extern "C" int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config *cfg, int32_t *action_out_dev,
+                                        double *key_out_dev, double *q_out_dev, void *stream) {
+    // the arguments before the handle: a CPU test drives these refusals with env == NULL
+    if (!cfg) return fail(ABR_E_INVALID, "lookahead: cfg is NULL");
+    if (!action_out_dev) return fail(ABR_E_INVALID, "lookahead: action_out_dev is NULL");
+    if (cfg->horizon < 1 || cfg->horizon > ABR_MAX_HORIZON)
+        return fail(ABR_E_INVALID, "lookahead: horizon %d outside 1..%d", cfg->horizon, ABR_MAX_HORIZON);
+    if (cfg->reserved_ != 0) return fail(ABR_E_INVALID, "lookahead: reserved_ must be 0, got %d", cfg->reserved_);
+    if (cfg->max_nodes_per_launch < 0)
+        return fail(ABR_E_INVALID, "lookahead: max_nodes_per_launch must be >= 0, got %lld", (long long)cfg->max_nodes_per_launch);
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    const EnvParams &p = env->p;
+    const int32_t H = cfg->horizon;
+    if (abrx::look_leaves(p.n_rates, H) > abrx::kLookMaxLeaves)
+        return fail(ABR_E_UNSUPPORTED, "lookahead: %d rates ^ horizon %d is more than %lld leaves; larger trees are the beam "
+                    "search's job", p.n_rates, H, (long long)abrx::kLookMaxLeaves);
+    if (p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on)))
+        return fail(ABR_E_UNSUPPORTED, "lookahead: per-lane speeds, a speed schedule or a speed rule are in force or pending: "
+                    "the walk is built from the one-speed tables only");
+    if (env->impl == 4 || env->impl == 6 || env->impl == 7)
+        return fail(ABR_E_UNSUPPORTED, "lookahead: the diagnostic pipelines (impl 4, 6, 7) keep lane state outside the workspace");
+    const int64_t per = abrx::look_lanes_per_launch(cfg->max_nodes_per_launch, p.n_rates, H);
+    const hipStream_t st = (hipStream_t)stream;
+    for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
+        const int64_t lane_end = lane0 + per < p.n_lanes ? lane0 + per : p.n_lanes;
+        switch (H) {
+        case 1: launch_lookahead<1>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 2: launch_lookahead<2>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 3: launch_lookahead<3>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 4: launch_lookahead<4>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 5: launch_lookahead<5>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 6: launch_lookahead<6>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        case 7: launch_lookahead<7>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        default: launch_lookahead<8>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
 #ifdef ABR_SPLIT_STAMPS
 extern "C" int abr_debug_read_stamps(unsigned long long *out32, int reset) {
     (void)hipDeviceSynchronize();

@@ -1881,5 +1881,107 @@ ABR_HD bool beam_before(double key_t, int32_t t, double key_s, int32_t s) {
     return key_t < key_s || (key_t == key_s && t < s);
 }
 
+// ---- the lookahead expert (include/abr_env.h: abr_env_lookahead_select) ----
+// The quality term of a step without quality_step's side effect: the weighted table entry a completed download of `chunk`
+// at rate `action` takes off the reward -- the same multiply on the same operands -- and q_run is left alone.
+ABR_HD double quality_peek(const EpisodeQuality &Q, int32_t n_rates, int32_t chunk, int32_t action) {
+    return Q.wq * Q.u[(int64_t)chunk * n_rates + action];
+}
+
+// Tree sizes.  M <= 16 and h <= 8: 16^8 fits an int64 with room to spare.
+constexpr int64_t kLookMaxLeaves = 65536;            // one launch walks one decision's tree; larger trees are a beam search's
+// Tree nodes one launch walks at most when the caller names no bound: 2^31.  Origin: at the 1.3e10 env-steps/s the README
+// records for the environment kernel, and a node being one lanej_step, that is about a sixth of a second per launch -- short
+// enough that the stream stays responsive.  The constant predates any measurement of this kernel's own rate.
+constexpr int64_t kLookDefaultNodes = (int64_t)1 << 31;
+ABR_HD constexpr int64_t look_leaves(int32_t M, int32_t h) {
+    int64_t n = 1;
+    for (int32_t j = 0; j < h; j++) n *= M;
+    return n;
+}
+ABR_HD constexpr int64_t look_nodes(int32_t M, int32_t h) {    // M + M^2 + ... + M^h
+    int64_t n = 0, pw = 1;
+    for (int32_t j = 0; j < h; j++) { pw *= M; n += pw; }
+    return n;
+}
+// lanes per launch: the largest multiple of 64 whose trees hold at most max_nodes nodes (0: the default), and at least 64
+ABR_HD int64_t look_lanes_per_launch(int64_t max_nodes, int32_t M, int32_t h) {
+    const int64_t lanes = (max_nodes > 0 ? max_nodes : kLookDefaultNodes) / look_nodes(M, h) / 64 * 64;
+    return lanes < 64 ? 64 : lanes;
+}
+
+struct LookWeights {
+    double wr, ws, wv, wl;
+    int32_t M;
+    bool quality;                  // a quality model is installed: the step reward carries its term
+};
+// One node of the tree: the lane after the node's step, the sum of the float32 rewards down to it, and whether anything is
+// left below (false: timed out, finished, or not a lane at all).  The two clocks a step's reward starts from are the
+// parent's own n_rb and n_su (what the kernels keep as n_rb_obs / n_su_obs after every step), so a node saves neither.
+struct LookNode {
+    LaneJ s;
+    double R;
+    bool live;
+};
+// candidate `key` replaces `best` when it is a number and smaller; equal keys (-0.0 and +0.0 among them) keep the earlier one
+ABR_HD bool look_better(double key, double best) { return key == key && !(best <= key); }
+
+// Depth first, one saved node per level, reached by template recursion: LVL is a compile-time index, so the stack is H
+// named objects (registers on the device) and never an array indexed at run time.  The digits of the sequence are the loop
+// counters m: the same in every lane of a wave (`any` folds the lanes' live flags, so the loops and the early-out are uniform
+// control flow); the only divergence is under `if (c.live)`.  Accessors: br(chunk, rate), G(n), lat(lane) = average_latency
+// of a lane state, qt(chunk, rate) = the weighted quality term, any(flag) = the flag in some lane of the wave (the host
+// harness: the flag itself).  Visits children in rate order and keeps the first least key: ties go to the
+// lexicographically smaller sequence.
+template <int LVL, int H, class TB, class BR, class GT, class LAT, class QT, class ANY>
+ABR_HD void look_visit(const LookWeights &w, const TB &t, const BR &br, const GT &G, const LAT &lat, const QT &qt,
+                       const ANY &any, const LookNode &par, int32_t n_rb_obs, int32_t n_su_obs, int32_t a, double &best) {
+    LookNode c = par;
+    if (c.live) {
+        const int32_t prev = c.s.last_action, chunk = c.s.chunk_id;
+        const double rate = br(chunk, a);
+        const StepResult r = lanej_step(c.s, t, rate * t.L, a);
+        const double g_rb = G(c.s.n_rb), g_su = G(c.s.n_su);
+        double var = 0.0;
+        if (r.hit && prev >= 0) var = fabs(rate - br(chunk - 1, prev));
+        double rew = w.wr * (g_rb - G(n_rb_obs)) + w.ws * (g_su - G(n_su_obs)) + w.wv * var;
+        if (w.quality) rew = rew - (r.hit ? qt(chunk, a) : 0.0);
+        c.R = c.R + (double)(float)rew;                  // reward_out's rounding: abr_beam_select's sum
+        const bool last = r.ended || LVL + 1 == H;       // h = min(H, V - chunk_id): the episode's end closes a sequence
+        c.live = !r.timeout && !last;
+        if (!r.timeout && last) {
+            const double key = c.R + w.wl * lat(c.s);
+            if (look_better(key, best)) best = key;
+        }
+    }
+    if constexpr (LVL + 1 < H) {
+        if (any(c.live))
+            for (int32_t m = 0; m < w.M; m++) look_visit<LVL + 1, H>(w, t, br, G, lat, qt, any, c, c.s.n_rb, c.s.n_su, m, best);
+    }
+}
+
+// q[a0] of one lane: the least key over the valid sequences that start with a0 from `root` (n_rb_obs / n_su_obs: the lane's
+// clocks at its last reported step), NaN when there is none or the lane is not live
+template <int H, class TB, class BR, class GT, class LAT, class QT, class ANY>
+ABR_HD double look_subtree(const LookWeights &w, const TB &t, const BR &br, const GT &G, const LAT &lat, const QT &qt,
+                           const ANY &any, const LaneJ &root, bool live, int32_t n_rb_obs, int32_t n_su_obs, int32_t a0) {
+    LookNode n;
+    n.s = root; n.R = 0.0; n.live = live;
+    double best = __builtin_nan("");
+    look_visit<0, H>(w, t, br, G, lat, qt, any, n, n_rb_obs, n_su_obs, a0, best);
+    return best;
+}
+
+// the lane's answer from its q column: the first least q(m), or -1 and NaN
+template <class Q>
+ABR_HD void look_pick(const Q &q, int32_t M, int32_t &action, double &key) {
+    action = -1; key = __builtin_nan("");
+    for (int32_t m = 0; m < M; m++) {
+        const double v = q(m);
+        const bool take = look_better(v, key);
+        action = take ? m : action; key = take ? v : key;
+    }
+}
+
 }  // namespace abrx
 #endif

@@ -513,6 +513,49 @@ int abr_beam_select(int32_t n_groups, int32_t beam, int32_t n_rates, double wl, 
                     const double *key_override_dev, int32_t *src_out_dev, double *R_out_dev, uint8_t *valid_out_dev,
                     void *stream);
 
+/*
+ * Lookahead expert (ABI 4, additive; BUILD-DEFINED: the reference has no teacher): for the state each lane is in NOW, the
+ * best next bitrate given the trace's real future, by exhaustive enumeration of the next decisions.  One call, read-only.
+ *
+ * The tree.  For every lane i whose done byte is 0 (a lane that was never reset carries ABR_DONE_EPISODE, as for
+ * abr_env_rule_select), with c = chunk_id[i] and h = min(horizon, video_length - c): every sequence a_0 .. a_{h-1} of rates
+ * is walked from the lane's state as it stands, by the step the environment kernels run.  A sequence ends at the step that
+ * ends the episode, whatever auto_reset says: the lookahead never re-arms and never looks into the next episode.
+ *
+ * The key.  All float64, never fused.  rew_j is step j's reward as the environment kernels form it,
+ *   rew = wr * (G[n_rb] - G[n_rb_obs]) + ws * (G[n_su] - G[n_su_obs]) + wv * var
+ *   var = |br(chunk, a) - br(chunk - 1, prev)| when the download completed and prev >= 0, else 0.0
+ *   rew = rew - wq * u[chunk][a]                 only while a quality model is installed (abr_env_set_episode_quality)
+ * R_0 = 0.0, R_{j+1} = R_j + (double)(float)rew_j -- the float32 rounding reward_out applies, so R is the sum abr_beam_select
+ * forms from reported rewards -- and key = R_h + wl * average_latency, the latency being that of the state after the last
+ * step: the value abr_env_observe_f64 would report there.  A sequence is dropped when any of its steps sets
+ * ABR_DONE_TIMEOUT or when its key is NaN.
+ *
+ * Outputs (device).  q_out[m][i] (float64 [n_rates][n_lanes], nullable) = the least key over the valid sequences with
+ * a_0 = m, NaN when there is none.  key_out[i] (float64 [n_lanes], nullable) = the least q_out[m][i]; action_out[i] (int32
+ * [n_lanes]) its m.  -0.0 and +0.0 tie; ties go to the smaller m, and inside a subtree to the lexicographically smaller
+ * sequence.  A lane whose done bits are set, or that has no valid sequence, gets action -1, key NaN and a NaN q column.
+ * The call reads the workspace, the traces, the tick tables and the quality table and writes only its three outputs: the
+ * workspace, q_run, the ledger, bw_hist and action_hist are untouched.  It is enqueued on `stream`; nothing synchronises.
+ *
+ * Launch splitting.  A lane's tree has n_rates + n_rates^2 + ... + n_rates^horizon nodes.  The call loops over ranges of
+ * lanes, each a multiple of 64 and at least 64, such that no launch walks more than max_nodes_per_launch nodes (0: the
+ * library's default, 2^31).
+ *
+ * Refusals, in this order, the arguments before the handle.  ABR_E_INVALID: NULL cfg; NULL action_out_dev; horizon outside
+ * 1..ABR_MAX_HORIZON; reserved_ != 0; max_nodes_per_launch < 0; a NULL handle.  ABR_E_UNSUPPORTED: n_rates^horizon > 65 536
+ * leaves (one launch walks one decision's tree; larger trees are the beam search's job); per-lane speeds, a speed schedule
+ * or a speed rule in force or pending (a constant play speed is fine); the diagnostic pipelines 4, 6 and 7.
+ */
+typedef struct abr_lookahead_config {
+    int32_t horizon;               /* 1..ABR_MAX_HORIZON */
+    int32_t reserved_;             /* 0 */
+    int64_t max_nodes_per_launch;  /* 0: the library's default */
+} abr_lookahead_config;
+
+int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config *cfg, int32_t *action_out_dev, double *key_out_dev,
+                             double *q_out_dev, void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* MPC lookahead                                                            */
 /* ---------------------------------------------------------------------- */
