@@ -14,6 +14,7 @@ from .fastmpc import FastMPCController
 from .ledger import EpisodeLedger
 from .quality import EpisodeQuality
 from .mpc import BatchedMPCController, EnvPlayer
+from .planner import ForecastMPCController
 from .policy import PolicyController, PolicyPopulation, RecurrentPolicyController, RecurrentPolicyPopulation
 from .search import HindsightSearch
 from .rules import BolaController, BufferBasedController, RateBasedController
@@ -28,6 +29,6 @@ _lib.lib()   # fail loudly at import time when libabr_hip.so is missing
 
 __all__ = ["MPD", "Chunk", "ChunkInfo", "NetworkInfo", "QOEMetric", "BatchedABREnv",
            "BatchedMPCController", "EnvPlayer", "FastMPCController", "PolicyController", "PolicyPopulation", "RecurrentPolicyController", "RecurrentPolicyPopulation", "BufferBasedController", "RateBasedController", "BolaController", "obs_dict", "pack_traces", "Simulator", "ShardedABREnv", "ShardStep", "LatencySpeedController",
-           "HindsightSearch", "LookaheadExpert", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
+           "HindsightSearch", "LookaheadExpert", "ForecastMPCController", "EpisodeSampler", "EpisodeLedger", "EpisodeQuality", "advantage", "gae", "TraceModel", "synth_traces",
            "load_trace_file", "load_network_info", "load_mpd_file", "save_trace_file",
            "save_mpd_file"]

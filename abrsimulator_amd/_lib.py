@@ -179,6 +179,12 @@ class LookaheadConfig(C.Structure):
     _fields_ = [("horizon", C.c_int32), ("reserved_", C.c_int32), ("max_nodes_per_launch", C.c_int64)]
 
 
+class PlanConfig(C.Structure):
+    _fields_ = [("horizon", C.c_int32), ("window", C.c_int32), ("robust", C.c_int32), ("reserved_", C.c_int32),
+                ("max_nodes_per_launch", C.c_int64), ("forecast_dev", C.c_void_p), ("state_dev", C.c_void_p),
+                ("state_bytes", C.c_size_t)]
+
+
 TRACE_MAX_STATES = 8
 
 
@@ -230,6 +236,8 @@ SYMBOLS = [
     ("abr_env_fork", C.c_int, [_P, _P, _P, C.c_int64, _P, C.c_size_t, _P, _P]),
     ("abr_beam_select", C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("abr_env_lookahead_select", C.c_int, [_P, C.POINTER(LookaheadConfig), _P, _P, _P, _P]),
+    ("abr_env_plan_select", C.c_int, [_P, C.POINTER(PlanConfig), _P, _P, _P, _P, _P]),
+    ("abr_env_step_plan", C.c_int, [_P, C.POINTER(PlanConfig), C.c_int32, _P, _P, _P, _P, _P]),
     ("abr_mpc_select", C.c_int, [C.POINTER(MpcConfig), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
                                  C.c_int64, _P]),
     ("abr_mpc_scratch_bytes", C.c_int, [C.POINTER(MpcConfig), C.c_int64, C.POINTER(C.c_size_t)]),

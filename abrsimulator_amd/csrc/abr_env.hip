@@ -2110,6 +2110,20 @@ static void launch_lookahead(const abr_env *env, int64_t lane0, int64_t lane_end
         hipLaunchKernelGGL((lookahead_kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, action, key, q);
 }
 
+// what the walk cannot serve (ABR_E_UNSUPPORTED), for the lookahead and for the forecast planner (`who` opens the message)
+static int look_supported(const abr_env *env, int32_t H, const char *who) {
+    const EnvParams &p = env->p;
+    if (abrx::look_leaves(p.n_rates, H) > abrx::kLookMaxLeaves)
+        return fail(ABR_E_UNSUPPORTED, "%s: %d rates ^ horizon %d is more than %lld leaves; larger trees are the beam "
+                    "search's job", who, p.n_rates, H, (long long)abrx::kLookMaxLeaves);
+    if (p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on)))
+        return fail(ABR_E_UNSUPPORTED, "%s: per-lane speeds, a speed schedule or a speed rule are in force or pending: "
+                    "the walk is built from the one-speed tables only", who);
+    if (env->impl == 4 || env->impl == 6 || env->impl == 7)
+        return fail(ABR_E_UNSUPPORTED, "%s: the diagnostic pipelines (impl 4, 6, 7) keep lane state outside the workspace", who);
+    return ABR_OK;
+}
+
 extern "C" int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config *cfg, int32_t *action_out_dev,
                                         double *key_out_dev, double *q_out_dev, void *stream) {
     // the arguments before the handle: a CPU test drives these refusals with env == NULL
@@ -2123,14 +2137,7 @@ extern "C" int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     const EnvParams &p = env->p;
     const int32_t H = cfg->horizon;
-    if (abrx::look_leaves(p.n_rates, H) > abrx::kLookMaxLeaves)
-        return fail(ABR_E_UNSUPPORTED, "lookahead: %d rates ^ horizon %d is more than %lld leaves; larger trees are the beam "
-                    "search's job", p.n_rates, H, (long long)abrx::kLookMaxLeaves);
-    if (p.lane_speeds || (env->speeds_dirty && (env->pending_speeds || env->pending_rule_on)))
-        return fail(ABR_E_UNSUPPORTED, "lookahead: per-lane speeds, a speed schedule or a speed rule are in force or pending: "
-                    "the walk is built from the one-speed tables only");
-    if (env->impl == 4 || env->impl == 6 || env->impl == 7)
-        return fail(ABR_E_UNSUPPORTED, "lookahead: the diagnostic pipelines (impl 4, 6, 7) keep lane state outside the workspace");
+    if (const int rc = look_supported(env, H, "lookahead")) return rc;
     const int64_t per = abrx::look_lanes_per_launch(cfg->max_nodes_per_launch, p.n_rates, H);
     const hipStream_t st = (hipStream_t)stream;
     for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
@@ -3039,6 +3046,167 @@ extern "C" int abr_env_step_mpc_robust(abr_env *env, const abr_mpc_config *cfg, 
     if (!br_table_dev || !sz_table_dev) return fail(ABR_E_INVALID, "NULL device pointer");
     return mpc_rollout(env, cfg, robust, br_table_dev, sz_table_dev, n_steps, obs_out_dev, reward_out_dev, done_out_dev,
                        actions_out_dev, (hipStream_t)stream);
+}
+
+// ===========================================================================
+// Forecast MPC (include/abr_env.h: abr_plan_config): the lookahead's walk on a predicted bandwidth
+// ===========================================================================
+// The built-in forecast, one thread per lane: RobustMPC's estimate on the environment's own chunk_id and bw_hist rows
+// (state != nullptr: the robust state, updated in place as mpc_robust_predict_kernel does; nullptr: no error is ever
+// stored, P = hm).  Every lane's P is written, 0.0 for "no decision" and for a lane whose done bits are set.
+__global__ __launch_bounds__(256) void plan_forecast_kernel(EnvParams p, int32_t window, uint8_t *__restrict__ state,
+                                                            double *__restrict__ P_out) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= p.n_lanes) return;
+    const auto hf = [&](int32_t j) { return p.bw_hist[(int64_t)j * p.n_lanes + i]; };
+    // read by the planning kernel that follows: a plain store
+    P_out[i] = abrx::plan_forecast(window, p.done[i] != 0, p.chunk_id[i], hf, state, p.n_lanes, i);
+}
+
+// lookahead_kernel with the cursor replaced at the root: lane i's trace is the one sample P[i].  A kernel of its own around
+// the shared look_subtree, so that the lookahead's instances stay what they are (profiles/plan_isa_diff.txt).  A P that
+// is not finite or not > 0 is "no decision"; forecast_out (nullable) receives the P the walk used, else 0.0.
+template <int H, int W>
+__global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
+    EnvParams p, abrx::EpisodeQuality ql, int64_t lane0, int64_t lane_end, const double *__restrict__ P, int32_t neg_to_zero,
+    int32_t *__restrict__ action_out, double *__restrict__ key_out, double *__restrict__ q_out,
+    double *__restrict__ forecast_out) {
+    __shared__ double s_q[look_waves(H, W)][64];
+    const int32_t m = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
+    const int32_t l = (int32_t)(threadIdx.x & 63);
+    const int64_t i = lane0 + (int64_t)blockIdx.x * 64 + l;
+    const abrx::TablesT<false> tb = make_tables<false>(p);
+    LaneJ s{};
+    int32_t n_su_obs = 0, n_rb_obs = 0;
+    bool live = false;
+    double f = 0.0;
+    if (i < lane_end && p.done[i] == 0) {
+        f = P[i];
+        if (abrx::plan_usable(f)) {
+            live = true;
+            lanej_load<false>(s, p, i);
+            abrx::plan_cursor(s.cur, P + i);
+            n_su_obs = p.n_su_obs[i]; n_rb_obs = p.n_rb_obs[i];
+        }
+    }
+    abrx::LookWeights w;
+    w.wr = p.wr; w.ws = p.ws; w.wv = p.wv; w.wl = p.wl; w.M = p.n_rates; w.quality = ql.base != nullptr;
+    const auto br = [&](int32_t chunk, int32_t rate) { return chunk_bitrate(p, chunk, rate); };
+    const auto G = [&](int32_t n) { return p.G[n]; };
+    const auto lat = [&](const LaneJ &x) { return lane_avg_latency(p, x.sumk, x.n_play); };
+    const auto qt = [&](int32_t chunk, int32_t rate) { return abrx::quality_peek(ql, p.n_rates, chunk, rate); };
+    const auto any = [](bool fl) { return __any(fl) != 0; };
+    const double q = abrx::look_subtree<H>(w, tb, br, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
+    s_q[m][l] = q;
+    if (q_out && i < lane_end) ABR_OUT(q_out[(int64_t)m * p.n_lanes + i], q);
+    __syncthreads();
+    if (m == 0 && i < lane_end) {
+        int32_t action;
+        double key;
+        abrx::look_pick([&](int32_t r) { return s_q[r][l]; }, p.n_rates, action, key);
+        ABR_OUT(action_out[i], (neg_to_zero && action < 0) ? 0 : action);
+        if (key_out) ABR_OUT(key_out[i], key);
+        if (forecast_out) ABR_OUT(forecast_out[i], live ? f : 0.0);
+    }
+}
+
+struct PlanOut {
+    int32_t *action;
+    double *key, *q, *forecast;
+    int32_t neg_to_zero;
+};
+
+template <int H>
+static void launch_plan(const abr_env *env, int64_t lane0, int64_t lane_end, const double *P, const PlanOut &o,
+                        hipStream_t st) {
+    const dim3 grid(grid64(lane_end - lane0)), block(64u * (unsigned)env->p.n_rates);
+    if (env->p.n_rates <= 8 || look_max_rates(H) <= 8)       // (the refusals have bounded n_rates by look_max_rates(H))
+        hipLaunchKernelGGL((plan_kernel<H, 8>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, P, o.neg_to_zero,
+                           o.action, o.key, o.q, o.forecast);
+    else if constexpr (look_max_rates(H) > 8)
+        hipLaunchKernelGGL((plan_kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, P, o.neg_to_zero,
+                           o.action, o.key, o.q, o.forecast);
+}
+
+// One decision of every lane: the built-in forecast into `scratch` (skipped when the caller brought one), then the walk in
+// launches of at most max_nodes_per_launch tree nodes, as abr_env_lookahead_select splits them.
+static int plan_decide(const abr_env *env, const abr_plan_config *cfg, double *scratch, PlanOut o, hipStream_t st) {
+    const EnvParams &p = env->p;
+    const int32_t H = cfg->horizon;
+    const double *P = cfg->forecast_dev;
+    if (!P) {
+        hipLaunchKernelGGL(plan_forecast_kernel, dim3((unsigned)((p.n_lanes + 255) / 256)), dim3(256), 0, st, p, cfg->window,
+                           cfg->robust ? (uint8_t *)cfg->state_dev : nullptr, scratch);
+        P = scratch;
+        if (o.forecast == scratch) o.forecast = nullptr;     // the forecast kernel has written the caller's copy already
+    }
+    const int64_t per = abrx::look_lanes_per_launch(cfg->max_nodes_per_launch, p.n_rates, H);
+    for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
+        const int64_t lane_end = lane0 + per < p.n_lanes ? lane0 + per : p.n_lanes;
+        switch (H) {
+        case 1: launch_plan<1>(env, lane0, lane_end, P, o, st); break;
+        case 2: launch_plan<2>(env, lane0, lane_end, P, o, st); break;
+        case 3: launch_plan<3>(env, lane0, lane_end, P, o, st); break;
+        case 4: launch_plan<4>(env, lane0, lane_end, P, o, st); break;
+        case 5: launch_plan<5>(env, lane0, lane_end, P, o, st); break;
+        case 6: launch_plan<6>(env, lane0, lane_end, P, o, st); break;
+        case 7: launch_plan<7>(env, lane0, lane_end, P, o, st); break;
+        default: launch_plan<8>(env, lane0, lane_end, P, o, st); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// The refusals of both entry points in the documented order; `select`: abr_env_plan_select (else abr_env_step_plan).
+static int validate_plan(const abr_env *env, const abr_plan_config *cfg, bool select, const void *action_out,
+                         int32_t n_steps) {
+    if (!cfg) return fail(ABR_E_INVALID, "plan: cfg is NULL");
+    if (select && !action_out) return fail(ABR_E_INVALID, "plan: action_out_dev is NULL");
+    if (cfg->horizon < 1 || cfg->horizon > ABR_MAX_HORIZON)
+        return fail(ABR_E_INVALID, "plan: horizon %d outside 1..%d", cfg->horizon, ABR_MAX_HORIZON);
+    if (cfg->reserved_ != 0) return fail(ABR_E_INVALID, "plan: reserved_ must be 0, got %d", cfg->reserved_);
+    if (cfg->max_nodes_per_launch < 0)
+        return fail(ABR_E_INVALID, "plan: max_nodes_per_launch must be >= 0, got %lld", (long long)cfg->max_nodes_per_launch);
+    if (cfg->robust != 0 && cfg->robust != 1) return fail(ABR_E_INVALID, "plan: robust must be 0 or 1, got %d", cfg->robust);
+    if (!cfg->forecast_dev && (cfg->window < 1 || cfg->window > ABR_ROBUST_MAX_WINDOW))
+        return fail(ABR_E_INVALID, "plan: window %d outside 1..%d", cfg->window, ABR_ROBUST_MAX_WINDOW);
+    if (!select && n_steps < 1) return fail(ABR_E_INVALID, "plan: n_steps must be >= 1");
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    if (cfg->robust == 1 && !cfg->forecast_dev) {
+        if (!cfg->state_dev) return fail(ABR_E_INVALID, "plan: robust state_dev is NULL");
+        if ((uintptr_t)cfg->state_dev & 7) return fail(ABR_E_INVALID, "plan: robust state must be 8-byte aligned");
+        if (cfg->state_bytes < robust_state_bytes(cfg->window, env->p.n_lanes))
+            return fail(ABR_E_INVALID, "plan: robust state has %zu bytes, need %zu", (size_t)cfg->state_bytes,
+                        robust_state_bytes(cfg->window, env->p.n_lanes));
+    }
+    return look_supported(env, cfg->horizon, "plan");
+}
+
+extern "C" int abr_env_plan_select(abr_env *env, const abr_plan_config *cfg, int32_t *action_out_dev, double *key_out_dev,
+                                   double *q_out_dev, double *forecast_out_dev, void *stream) {
+    if (const int rc = validate_plan(env, cfg, true, action_out_dev, 1)) return rc;
+    // the forecast's n_lanes doubles: the caller's output; the workspace's MPC scratch only when there is none
+    double *scratch = forecast_out_dev ? forecast_out_dev : (double *)env->mpc_scratch;
+    return plan_decide(env, cfg, scratch, PlanOut{action_out_dev, key_out_dev, q_out_dev, forecast_out_dev, 0},
+                       (hipStream_t)stream);
+}
+
+extern "C" int abr_env_step_plan(abr_env *env, const abr_plan_config *cfg, int32_t n_steps, float *obs_out_dev,
+                                 float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
+    int rc = validate_plan(env, cfg, false, nullptr, n_steps);
+    if (rc) return rc;
+    if ((rc = require(kMpcRollout, env->impl))) return rc;
+    const int64_t N = env->p.n_lanes;
+    const hipStream_t st = (hipStream_t)stream;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        int32_t *action = actions_out_dev ? slab_row(actions_out_dev, s, 1, N) : env->mpc_action;
+        if ((rc = plan_decide(env, cfg, (double *)env->mpc_scratch, PlanOut{action, nullptr, nullptr, nullptr, 1}, st)))
+            return rc;
+        if ((rc = step_row(env, impl, st, s, action, obs_out_dev, reward_out_dev, done_out_dev))) return rc;
+    }
+    return ABR_OK;
 }
 
 // ===========================================================================

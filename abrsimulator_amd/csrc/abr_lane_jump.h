@@ -870,6 +870,20 @@ ABR_HD double robust_estimate(int32_t W, int32_t c, const HIST &hist, int32_t &c
     return P > 0.0 ? P : 0.0;
 }
 
+// robust_estimate on lane `lane` of an N-lane state in the ABR_ROBUST_* layout (int32 [2][N], then float64 [1 + W][N]),
+// updated in place: what the predictor kernels run per thread
+template <class HIST>
+ABR_HD double robust_estimate_rows(int32_t W, int32_t c, const HIST &hist, uint8_t *state, int64_t N, int64_t lane) {
+    int32_t *cs1_row = (int32_t *)state, *cnt_row = cs1_row + N;
+    double *ps_row = (double *)(state + 2 * sizeof(int32_t) * N), *err_rows = ps_row + N;
+    int32_t cs1 = cs1_row[lane], cnt = cnt_row[lane];
+    double ps = ps_row[lane];
+    const auto ef = [&](int32_t k) -> double & { return err_rows[(int64_t)k * N + lane]; };
+    const double P = robust_estimate(W, c, hist, cs1, cnt, ps, ef);
+    cs1_row[lane] = cs1; cnt_row[lane] = cnt; ps_row[lane] = ps;
+    return P;
+}
+
 
 // ---------------------------------------------------------------------------
 // Learned policy (include/abr_env.h: abr_policy): features, the MLP forward pass as k-ordered fmaf chains, the decision.
@@ -1982,6 +1996,24 @@ ABR_HD void look_pick(const Q &q, int32_t M, int32_t &action, double &key) {
         action = take ? m : action; key = take ? v : key;
     }
 }
+
+// ---- forecast MPC (include/abr_env.h: abr_plan_config): the same walk on a predicted bandwidth ----
+// The built-in forecast of one lane at chunk c: RobustMPC's estimate on the lane's rows of `state`, or, with state ==
+// nullptr, the same arithmetic with no error ever stored (P = hm; nothing is read or written).  0.0: no decision, and a
+// finished lane takes none and keeps its state.
+template <class HIST>
+ABR_HD double plan_forecast(int32_t W, bool done, int32_t c, const HIST &hist, uint8_t *state, int64_t N, int64_t lane) {
+    if (done) return 0.0;
+    if (state) return robust_estimate_rows(W, c, hist, state, N, lane);
+    int32_t cs1 = 0, cnt = 0;
+    double ps = 0.0, none = 0.0;
+    return robust_estimate(W, c, hist, cs1, cnt, ps, [&](int32_t) -> double & { return none; });
+}
+// a forecast the walk can plan on: finite and > 0 (NaN fails both comparisons)
+ABR_HD bool plan_usable(double P) { return P > 0.0 && P <= 1.79769313486231570815e+308; }
+// the root's cursor: a one-sample trace at *P, so that every interval the walk downloads in has bandwidth *P (trace_wrap
+// folds the six-sample look-ahead of lanej_begin_load onto it); cur.j, the clock's interval index, stays the lane's
+ABR_HD void plan_cursor(Cursor &c, const double *P) { c.trace = P; c.tlen = 1; c.tpos = 0; }
 
 }  // namespace abrx
 #endif

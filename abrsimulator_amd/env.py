@@ -517,6 +517,20 @@ class BatchedABREnv:
                    _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
         return out
 
+    def step_plan(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, forecast=None):
+        """n_steps decisions per lane taken by forecast MPC (planner.py: ForecastMPCController) on the device: per decision
+        the throughput forecast, the exhaustive plan on it and the download, with no host work between decisions
+        (abr_env_step_plan).  `forecast` (float64 [N]) replaces the built-in forecast at every decision: a fixed belief.
+        Finished lanes take no decision; "no decision" downloads bitrate 0 and is reported as 0.  Every event-driven
+        kernel; 'tick' is refused.  Returns dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
+        n = int(n_steps)
+        cfg = controller.config(forecast)
+        if out is None:
+            out = self._rollout_out(n, want_obs, want_actions)
+        self._call(self.lib.abr_env_step_plan, self._h, C.byref(cfg), n, _lib.ptr(out.get("obs")),
+                   _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
+        return out
+
     def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
                     want_scores=False, want_probs=False, want_values=False, want_hidden=False):
         """n_steps decisions per lane taken by a learned policy (policy.py: PolicyController) on the device, each one the

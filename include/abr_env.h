@@ -556,6 +556,65 @@ typedef struct abr_lookahead_config {
 int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config *cfg, int32_t *action_out_dev, double *key_out_dev,
                              double *q_out_dev, void *stream);
 
+/*
+ * Forecast MPC (ABI 4, additive; BUILD-DEFINED: the reference has no such controller): the lookahead's exhaustive walk on a
+ * PREDICTED bandwidth instead of the trace's real future -- the MPC of the literature, with this environment's own step
+ * (live-edge gating, start-up, buffer cap, max_ticks) and the QoE the ledger reports, quality term included.  Deployable:
+ * it reads nothing a player could not know.
+ *
+ * The forecast P[i], float64, one per lane.
+ *  Without forecast_dev: for every lane whose done byte is 0, steps 1-5 of abr_mpc_robust's contract on the environment's
+ *  own chunk_id and previous_bandwidths rows (c = chunk_id, h = the lane's bw_hist rows, W = window).  robust == 1 reads and
+ *  updates state_dev exactly as abr_env_step_mpc_robust does (same layout, same bytes).  robust == 0 is the same arithmetic
+ *  with no error ever stored, P = hm; it needs no state and touches none.  "No decision" (chunk 0, a harmonic mean that is
+ *  not finite or not > 0) is P = 0.0.
+ *  With forecast_dev: P[i] = forecast_dev[i]; window, robust's state and state_dev are not looked at beyond the refusals
+ *  below, and no state is read or written.
+ *  Where P[i] is not finite or not > 0 the lane has no decision.  forecast_out_dev (float64 [n_lanes], nullable) receives
+ *  the P the walk used, 0.0 for a lane without a decision and for a lane whose done bits are set.
+ *
+ * The walk is abr_env_lookahead_select's with one change at the root: the lane's trace cursor points at its forecast --
+ * trace = &P[i], tlen = 1, tpos = 0 -- so every interval the walk downloads in has bandwidth P[i]; every other field of the
+ * lane is the workspace's.  The tree, the key, the dropped sequences (a time-out, a NaN key), the tie rules, the horizon's
+ * shrink at the episode's end, the shapes of action_out / key_out / q_out and the launch splitting are word for word the
+ * lookahead's.  A lane whose done bits are set, that has no decision or that has no valid sequence gets action -1, key NaN
+ * and a NaN q column.
+ *
+ * abr_env_plan_select writes its outputs and, with robust == 1 and no forecast_dev, the state: the workspace, q_run, the
+ * ledger, bw_hist and action_hist are untouched, and selecting twice on one state gives the same answer and the same state.
+ * P needs n_lanes float64 of device memory while the call runs: with the built-in forecast that is forecast_out_dev; only
+ * a caller that passes neither forecast_dev nor forecast_out_dev has P written to the workspace's MPC scratch (the region
+ * abr_env_step_mpc's predictor overwrites at every decision; it carries nothing between calls).
+ *
+ * abr_env_step_plan follows abr_env_step_mpc: per decision the forecast, the plan, then the download, enqueued back to back
+ * on `stream`; outputs (all nullable) as abr_env_step_mpc's.  Finished lanes take no decision and keep their state; action
+ * -1 downloads bitrate 0 and actions_out reports 0 for it.  A forecast_dev given here is used unchanged at every decision
+ * (a fixed belief).  The built-in forecast goes through the workspace's MPC scratch.  Kernel choice as abr_env_step_mpc.
+ *
+ * Refusals, in this order, the arguments before the handle.  ABR_E_INVALID: NULL cfg; NULL action_out_dev (select); horizon
+ * outside 1..ABR_MAX_HORIZON; reserved_ != 0; max_nodes_per_launch < 0; robust not 0 or 1; without forecast_dev, window
+ * outside 1..ABR_ROBUST_MAX_WINDOW; n_steps < 1 (step); a NULL handle; then, with robust == 1 and no forecast_dev, a NULL
+ * state_dev, one that is not 8-byte aligned, or state_bytes below abr_mpc_robust_state_bytes(window, n_lanes).
+ * ABR_E_UNSUPPORTED: the lookahead's three (the leaf cap; speed features in force or pending; impl 4 / 6 / 7), then, for
+ * abr_env_step_plan, impl 1 as abr_env_step_mpc.
+ */
+typedef struct abr_plan_config {
+    int32_t horizon;               /* 1..ABR_MAX_HORIZON */
+    int32_t window;                /* 1..ABR_ROBUST_MAX_WINDOW; ignored when forecast_dev is given */
+    int32_t robust;                /* 0: P = harmonic mean; 1: RobustMPC's discount P = hm / (1 + max error) */
+    int32_t reserved_;             /* 0 */
+    int64_t max_nodes_per_launch;  /* as abr_lookahead_config */
+    const double *forecast_dev;    /* nullable: float64 [n_lanes], the caller's forecast; skips the built-in one */
+    void *state_dev;               /* robust == 1 and no forecast_dev: abr_mpc_robust's state, same layout,
+                                      abr_mpc_robust_state_bytes(window, n_lanes), all-zero = empty; else ignored */
+    size_t state_bytes;
+} abr_plan_config;
+
+int abr_env_plan_select(abr_env *env, const abr_plan_config *cfg, int32_t *action_out_dev, double *key_out_dev,
+                        double *q_out_dev, double *forecast_out_dev, void *stream);
+int abr_env_step_plan(abr_env *env, const abr_plan_config *cfg, int32_t n_steps, float *obs_out_dev,
+                      float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream);
+
 /* ---------------------------------------------------------------------- */
 /* MPC lookahead                                                            */
 /* ---------------------------------------------------------------------- */
