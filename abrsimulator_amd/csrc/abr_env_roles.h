@@ -36,6 +36,16 @@
 #ifndef ABR_SPLIT3_CASCADE
 #define ABR_SPLIT3_CASCADE 0
 #endif
+// The lane functions' table for a role: make_tables' -- except that the three-wave kernel's speed instances get the type
+// whose chains settle their jumps by three candidates (abr_lane_jump.h: TablesCandidates; abr_exact_jump.h: SettleKind).
+template <bool THREE, bool SPEEDS>
+using RoleTables = std::conditional_t<THREE && SPEEDS, abrx::TablesCandidates, abrx::TablesT<SPEEDS>>;
+template <bool THREE, bool SPEEDS>
+__device__ __forceinline__ RoleTables<THREE, SPEEDS> role_tables(const EnvParams &p, bool cascade = true) {
+    RoleTables<THREE, SPEEDS> t;
+    static_cast<abrx::TablesT<SPEEDS> &>(t) = make_tables<SPEEDS>(p, cascade);
+    return t;
+}
 // the three-wave kernel's service role: re-read the parameter block every iteration (1, fresh_params) or use the kernel's
 // by-value copy like the download and player roles (0).  A/B knob; measured again with the no-speeds instances: 0 is
 // 1.05-1.2 % slower at 65 536 lanes in three interleaved pairs (profiles/speed_instances_ab.json: part4_fresh_params)
@@ -236,7 +246,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
     const int64_t i = (int64_t)blockIdx.x * 64 + l;
     const int32_t V = p.video_length;
     const int cb = t & 1;                      // this iteration's mailbox slot
-    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p);
+    const RoleTables<ACT_RING, SPEEDS> tb = role_tables<ACT_RING, SPEEDS>(p);   // ACT_RING: the three-wave kernel
     int32_t flags = 0;
     ABR_STAMP(0);
     if (v.d_alive && v.d_step < n_total) {
@@ -459,7 +469,7 @@ __device__ __forceinline__ void role_p3_pre(PVars &v, const EnvParams &p, SplitM
                                             int32_t n_total, int32_t t, int cb2) {
     const int l = threadIdx.x & 63;
     const int cb = t & 1, pb = (t + 1) & 1;    // this iteration's / the previous one's slot
-    const abrx::TablesT<SPEEDS> tb = make_tables<SPEEDS>(p, ABR_SPLIT3_CASCADE != 0);
+    const RoleTables<true, SPEEDS> tb = role_tables<true, SPEEDS>(p, ABR_SPLIT3_CASCADE != 0);
     const bool speeds = SpeedParams<SPEEDS>::lane_speeds(p) != nullptr;
     (void)speeds;
     LaneJ &s = v.s;
@@ -846,7 +856,7 @@ __global__ __launch_bounds__(192) __attribute__((amdgpu_waves_per_eu(1, 3))) voi
     else { __builtin_amdgcn_s_setprio(ABR_PRIO_S); SVars v; role_s_begin<SPEEDS>(v, p, ring); s_park<SPEEDS>(park.s, v); }
     for (int32_t t = 0;; t++) {
         if (role == 0) {
-            if (t > 0) role_d_validate<SAMPLE>(dv, m, make_tables<SPEEDS>(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
+            if (t > 0) role_d_validate<SAMPLE>(dv, m, role_tables<true, SPEEDS>(p, ABR_SPLIT3_CASCADE != 0), t - 1);      // against what P published before the previous barrier
             role_d_pre<MODE, true, SAMPLE, SPEEDS>(dv, p, m, &ring, actions, actions_out, n_total, seed, t, smp);
         } else if (role == 1) {
             PVars v; p_unpark<SPEEDS>(park.p, v, p);

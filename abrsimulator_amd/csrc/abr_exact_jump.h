@@ -130,13 +130,13 @@ ABR_HD bool jump_inside(double y, double lim, bool strict) {
     return strict ? (y > lim) : (y >= lim);
 }
 
-// Most additions one segment performs.  The jump-length estimate gap * v_rcp_f64(dm) carries the reciprocal's
-// relative error eps (the hardware's double-precision reciprocal is a seed, good to a few parts in 2^24 at worst); while
-// the true quotient is below 1 / (2 eps) the estimate is off by less than half a step, and a longer one is cut to the
-// segment's budget <= kJumpCap, which is then certainly not too long.  So candidate 0 of the settlement below is always
-// inside -- and because that is an argument about an estimate, the settlement still checks it (ok0) and repairs an
-// overshoot in line; correctness never rests on eps, only speed does.  A run of more than 2^20 equal additions inside one
-// binade (2.9 hours of 0.01 s ticks) takes one segment per 2^20 steps (tests/test_exact_jump_gpu.py: jumps of 2^27 steps).
+// Most additions one segment performs.  The jump-length guess gap * v_rcp_f64(dm) carries the reciprocal's relative
+// error eps (the hardware's double-precision reciprocal is a seed, good to a few parts in 2^24 at worst); while the true
+// quotient is below 1 / (2 eps) the guess is off by less than half a step, and a longer one is cut to the segment's budget
+// <= kJumpCap.  So the guess is within one of the answer, which is all the remainder settlement below needs -- and because
+// that is an argument about an estimate, the settlement still checks its result (ok) and repairs an overshoot in line;
+// correctness never rests on eps, only speed does.  A run of more than 2^20 equal additions inside one binade (2.9 hours
+// of 0.01 s ticks) takes one segment per 2^20 steps (tests/test_exact_jump_gpu.py: jumps of 2^27 steps).
 constexpr int32_t kJumpCap = 1 << 20;
 
 // min(max(v, 0), hi) for hi >= 0 in one instruction
@@ -148,6 +148,24 @@ ABR_HD uint32_t clamp0(int32_t v, int32_t hi) {
 #else
     v = (v > 0) ? v : 0;
     return (uint32_t)((v < hi) ? v : hi);
+#endif
+}
+
+// a + (double)q * b and a - (double)q * b.  One instruction on the device: the settlement only relies on these where
+// the product is exact, and there the fused and the two-step forms agree (the library builds with -ffp-contract=off, so
+// the fusion is spelled out).
+ABR_HD double mul_add_u32(uint32_t q, double b, double a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fma((double)q, b, a);
+#else
+    return a + (double)q * b;
+#endif
+}
+ABR_HD double mul_sub_u32(uint32_t q, double b, double a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_fma(-(double)q, b, a);
+#else
+    return a - (double)q * b;
 #endif
 }
 
@@ -172,7 +190,14 @@ ABR_HD bool any_lane(bool v) {
 // Straight-line selects on purpose: this is the body of the GPU hot loop.
 // BIAS (tests only) is added to the jump-length estimate: a non-zero value spoils it on purpose,
 // so that the repair path (estimate too long) and the short-jump path (estimate too short) run.
-template <int STOP, int BIAS = 0>
+// SETTLE: how the jump length is settled from its estimate.  SETTLE_REMAINDER is the form every caller gets by default.
+// SETTLE_CANDIDATES, the earlier and longer form (~9 vector instructions more per segment), is kept for ONE family of
+// kernels: the speed instances of the three-wave kernel, whose scalar register file is full -- with the remainder form
+// six (walk-back loop as here) or two (walk-back as two straight-line steps) of them come out with a 36 B private segment
+// for one more saved exec mask (profiles/chain_settle_resources.txt).  Both forms return the same jump for an estimate
+// within one of the answer (tests/test_chain_settle_cpu.py checks each against the longest legal jump).
+enum SettleKind { SETTLE_REMAINDER = 0, SETTLE_CANDIDATES = 1 };
+template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER>
 ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in, bool &hit_out) {
 #ifdef ABR_SEGMENT_HOOK
     ABR_SEGMENT_HOOK(STOP);              // host-side analysis builds count segments per chain kind
@@ -182,7 +207,7 @@ ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in,
     int32_t a = 0;
     const int e = expo(x);
     const bool normal = (e > 54) & (e < 2046);       // else: no jump; the values below are then unused (all stay finite
-    const int ec = e;                                // or NaN-free enough: base = 0 or tiny, d = |c|, and m0 is clamped to 0)
+    const int ec = e;                                // or NaN-free enough: base = 0 or tiny, d = |c|, and room = 0 clamps the jump to 0)
     const double ac = (STOP == STOP_GE) ? c : -c;    // |c|: the sign of c is fixed by the stop kind (see chain())
     // steady increment of this binade and the tie test (header comment)
     const double base = pow2_biased(ec);
@@ -213,39 +238,73 @@ ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in,
             gap = x - lim;
         }
         const int32_t room = can ? n - 1 : 0;        // the last addition of the budget is a real one
-        // Jump length: estimate gap / dm, clamped to [0, room] (NaN and negatives -> 0); room < kJumpCap.
-        int32_t m0s = sat_i32(gap * rcp_est(dm));
-        if (BIAS != 0) m0s = (m0s < 0x7fffff00 && m0s > -0x7fffff00) ? m0s + BIAS : m0s;
-        const uint32_t m0 = clamp0(m0s, room);
-        // Exact settlement (x + m*d is exact while it stays inside the binade).  With the answer
-        // m* = the longest jump that stays inside, the estimate satisfies m0 - 1 <= m* (see
-        // kJumpCap), so candidate bs = m0 - 1 is inside and the answer is the last of bs, bs + 1,
-        // bs + 2 that is: candidates 1 and 2 are formed by adding d to the previous one, identical
-        // to x + (bs+k)*d whenever the previous candidate is inside (both are then exact), and a
-        // candidate only counts if all before it are inside.  A jump SHORTER than m* is always
-        // legal -- the next segment carries on -- so nothing has to bound m* from above; only
-        // "candidate 0 is inside" is load-bearing, and it is not taken on trust: ok0 checks it,
-        // and a lane whose estimate overshot walks back to the last inside candidate.  The vote
-        // keeps that path out of the way (one compare and a scalar branch per segment).
-        const uint32_t bs = (m0 > 0) ? m0 - 1 : 0;   // a saturating subtraction
-        const double y0 = x + (double)bs * d;
-        const double y1 = y0 + d;
-        const double y2 = y1 + d;
-        const bool t1 = (bs + 1 <= (uint32_t)room) & jump_inside<STOP>(y1, lim, strict);
-        const bool t2 = (bs + 2 <= (uint32_t)room) & jump_inside<STOP>(y2, lim, strict) & t1;
-        int32_t m = (int32_t)(bs + (t1 ? 1 : 0) + (t2 ? 1 : 0));
-        double xj = t2 ? y2 : (t1 ? y1 : y0);
-        const bool ok0 = (bs == 0) | jump_inside<STOP>(y0, lim, strict);
+        // Jump length: a guess at gap / dm (NaN and negatives -> 0), cut to the budget; room < kJumpCap.
+        int32_t q0s = sat_i32(gap * rcp_est(dm));
+        if (BIAS != 0) q0s = (q0s < 0x7fffff00 && q0s > -0x7fffff00) ? q0s + BIAS : q0s;
+        const uint32_t q0 = clamp0(q0s, room);
+        int32_t m, back;                 // the jump, and where a lane whose jumped value is NOT inside starts walking back
+        double xj;
+        bool ok;
+        if (SETTLE == SETTLE_REMAINDER) {
+            // Exact settlement by the remainder of that guess (the form of drain_cascade below).  A jump of m steps is
+            // inside iff m*dm < gap (results strictly beyond lim) or m*dm <= gap (results may equal lim), in real
+            // numbers, and the three quantities involved are exact in float64 whenever the lane jumps at all:
+            //   * gap.  Going up x <= lim <= 2^(e+1) <= 2x, going down lim <= x < 2^(e+1) <= 2 lim, so the subtraction
+            //     is exact (Sterbenz); and gap is a multiple of u, because x is one and lim >= 2^e lies on u's grid or a
+            //     coarser one.  (A stop already behind x gives gap <= 0, possibly rounded: q0 = 0, r = gap <= 0, no jump.)
+            //   * q0*dm, for a guess within one of the answer: at most gap + dm <= 2^53 u and a multiple of u.  Hence
+            //     the remainder r = gap - q0*dm is exact as well.
+            //   * x + m*d for an m that is inside: every term is a multiple of u below 2^53 u (header comment).
+            // With m* the longest jump that stays inside, q0 == m* means 0 < r <= dm (strict) or 0 <= r < dm (not
+            // strict); a guess one short leaves more than that, a guess one long less, so one compare each way settles
+            // it -- and the guess IS within one while room < kJumpCap (see there).  A guess the budget cut to room can
+            // only be too short: it is lengthened to room + 1 and cut again.  A jump SHORTER than m* is always legal --
+            // the next segment carries on -- so nothing has to bound m from below; only "the jumped value is inside" is
+            // load-bearing, and it is not taken on trust, since it rests on an estimate: `ok` checks the value the lane
+            // is about to take, and a lane whose guess overshot by more than the settlement covers walks back to the
+            // last inside value.  (If q0*dm or m*d were too large to be exact the product would be >= 2^53 u = 2^(e+1),
+            // which no rounding moves back inside, so such a lane fails `ok` too.)  The vote keeps that path out of the
+            // way: one compare and a scalar branch per segment.
+            const double r = mul_sub_u32(q0, dm, gap);
+            bool longer, shorter;
+            if (STOP == STOP_LT) {
+                longer = strict ? (r > dm) : (r >= dm);
+                shorter = strict ? (r <= 0.0) : (r < 0.0);
+            } else {
+                longer = r > dm;
+                shorter = r <= 0.0;
+            }
+            m = (int32_t)clamp0((int32_t)q0 + (longer ? 1 : 0) - (shorter ? 1 : 0), room);
+            xj = mul_add_u32((uint32_t)m, d, x);
+            ok = (m == 0) | jump_inside<STOP>(xj, lim, strict);
+            back = m;
+        } else {
+            // Settlement by three chained candidates (SETTLE_CANDIDATES).  The guess satisfies q0 - 1 <= m*, so
+            // candidate bs = q0 - 1 is inside and the answer is the last of bs, bs + 1, bs + 2 that is: candidates 1
+            // and 2 are formed by adding d to the previous one, identical to x + (bs+k)*d whenever the previous
+            // candidate is inside (both are then exact), and a candidate only counts if all before it are inside.
+            // Only "candidate 0 is inside" is load-bearing, and `ok` checks it.
+            const uint32_t bs = (q0 > 0) ? q0 - 1 : 0;   // a saturating subtraction
+            const double y0 = x + (double)bs * d;
+            const double y1 = y0 + d;
+            const double y2 = y1 + d;
+            const bool t1 = (bs + 1 <= (uint32_t)room) & jump_inside<STOP>(y1, lim, strict);
+            const bool t2 = (bs + 2 <= (uint32_t)room) & jump_inside<STOP>(y2, lim, strict) & t1;
+            m = (int32_t)(bs + (t1 ? 1 : 0) + (t2 ? 1 : 0));
+            xj = t2 ? y2 : (t1 ? y1 : y0);
+            ok = (bs == 0) | jump_inside<STOP>(y0, lim, strict);
+            back = (int32_t)bs;
+        }
 #ifdef ABR_BRACKET_HOOK
-        ABR_BRACKET_HOOK(ok0);           // host-side analysis builds count overshooting estimates
+        ABR_BRACKET_HOOK(ok);            // host-side analysis builds count overshooting estimates
 #endif
-        if (any_lane(!ok0)) {
-            int32_t mm = ok0 ? 0 : (int32_t)bs;
+        if (any_lane(!ok)) {
+            int32_t mm = ok ? 0 : back;
 #if defined(__HIP_DEVICE_COMPILE__)
 #pragma clang loop unroll(disable) vectorize(disable)
 #endif
             while (mm > 0 && !jump_inside<STOP>(x + (double)mm * d, lim, strict)) mm--;
-            if (!ok0) { m = mm; xj = x + (double)mm * d; }
+            if (!ok) { m = mm; xj = x + (double)mm * d; }
         }
         x = xj;                          // == x when !can (m == 0)
         a = m;
@@ -270,13 +329,13 @@ ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in,
 // stopping one).  c > 0 requires STOP_GE; c < 0 requires STOP_LE or STOP_LT.
 // Bit-identical to the naive loop for every finite input (fuzzed in
 // tests/test_exact_jump.py).
-template <int STOP, int BIAS = 0>
+template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER>
 ABR_HD bool chain(double &x_io, double c, double thr, int32_t n, int32_t &a_out) {
     ChainState cs;
     cs.x = x_io; cs.eb = -1;
     int32_t a = 0;
     bool hit = false;
-    while (a < n && !hit) a += chain_segment<STOP, BIAS>(cs, c, thr, n - a, hit);
+    while (a < n && !hit) a += chain_segment<STOP, BIAS, SETTLE>(cs, c, thr, n - a, hit);
     x_io = cs.x;
     a_out = a;
     return hit;
@@ -295,8 +354,8 @@ ABR_HD bool chain(double &x_io, double c, double thr, int32_t n, int32_t &a_out)
 //     n_e = floor((x - B_e) / S_e) + 1   if x >= B_e := 2^e + T_e,   else 0.
 // S_e and B_e depend on the binade only and are wave-uniform: S_e = fl(2^e + sd) - 2^e as in the header comment, T_e = S_e
 // or S_e + u_e.  A stage is a handful of exact float64 operations -- x - B_e, n * S_e and the remainder are multiples of
-// u_e below 2^53 u_e -- against the ~58 vector instructions of a chain_segment (estimate, three candidates, one real
-// addition), and a buffer that runs dry (the player wave's slowest case: six segments and a 16-tick plain tail) is one
+// u_e below 2^53 u_e -- against the ~58 vector instructions a chain_segment had when this was built (estimate, three
+// candidates, one real addition), and a buffer that runs dry (the player wave's slowest case: six segments and a 16-tick plain tail) is one
 // pass over the binades and at most a few plain subtractions below them.  No table in memory: a first form read the stage
 // constants from one (scalar loads through the constant address space) and waited for a load in every stage -- the compiler
 // sinks a prefetch to its use -- which cost more than the six uniform instructions that compute them.

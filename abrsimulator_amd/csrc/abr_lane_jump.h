@@ -90,6 +90,7 @@ struct TablesT;
 template <>
 struct TablesT<true> {
     static constexpr bool kSpeeds = true;
+    static constexpr int kSettle = SETTLE_REMAINDER;   // how the chains settle a jump (abr_exact_jump.h: SettleKind)
     const double *G;               // G[n] = dt added n times to 0.0 (global_time, download_time, ...)
     const int32_t *interval_tick;  // first tick k with int(G[k]/interval) >= j          (:158)
     const int32_t *avail_tick;     // first tick k with int(G[k]/chunk_length) - 1 >= c  (:143)
@@ -114,6 +115,7 @@ struct TablesT<true> {
 template <>
 struct TablesT<false> {
     static constexpr bool kSpeeds = false;
+    static constexpr int kSettle = SETTLE_REMAINDER;
     const double *G;
     const int32_t *interval_tick;
     const int32_t *avail_tick;
@@ -128,6 +130,12 @@ struct TablesT<false> {
 };
 
 using Tables = TablesT<true>;
+
+// The table of the three-wave kernel's speed instances: the same fields, the chains settled by three candidates
+// (abr_exact_jump.h: SettleKind says why those kernels keep that form).
+struct TablesCandidates : TablesT<true> {
+    static constexpr int kSettle = SETTLE_CANDIDATES;
+};
 
 // Where a lane is in its bandwidth trace.  Only the download side (phase A) reads it.
 struct Cursor {
@@ -187,7 +195,7 @@ ABR_HD void lanej_play(LaneJ &s, const TB &t, int32_t a) {
     int32_t done = 0;
     double x = s.pt;
     // an unreachable threshold: the chain only counts
-    chain<STOP_GE>(x, s.sd, 1.0e300, a, done);
+    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, 1.0e300, a, done);
     s.pt = x;
 }
 
@@ -204,13 +212,14 @@ ABR_HD void lanej_play(LaneJ &s, const TB &t, int32_t a) {
 // a whole number exactly when it matters, and which side of zero the k-th result falls on is decided by the roundings
 // themselves.  Built and measured in round 5, profiles/r05_experiments_not_kept.txt.)
 constexpr int kDrainTail = ABR_K_DRAIN_TAIL;
+template <int SETTLE = SETTLE_REMAINDER>
 ABR_HD bool drain_to_zero(double &b_io, double sd, int32_t m, int32_t &a_out) {
     ChainState cs;
     cs.x = b_io; cs.eb = -1;
     const double tail = (double)kDrainTail * sd;
     int32_t a = 0;
     bool below = false;
-    while (a < m && !below) a += chain_segment<STOP_LE>(cs, -sd, tail, m - a, below);
+    while (a < m && !below) a += chain_segment<STOP_LE, 0, SETTLE>(cs, -sd, tail, m - a, below);
     double b = cs.x;
     ABR_STAMP(24);
 #ifdef ABR_DRAIN_HOOK
@@ -239,7 +248,7 @@ ABR_HD bool lanej_drain(const TB &t, double &b_io, double sd, int32_t m, int32_t
         ABR_STAMP(24);
         return zero;
     }
-    return drain_to_zero(b_io, sd, m, a_out);
+    return drain_to_zero<TB::kSettle>(b_io, sd, m, a_out);
 }
 
 // ---- speed schedule: the play speed changes at played-chunk boundaries ----
@@ -269,7 +278,7 @@ ABR_HD void sched_begin_chunk(LaneJ &s, const TB &t, int32_t k, double b) {
     s.sd = v * kTickDt;                                                      // play_speed * dt (:182)
     double x = 0.0;
     int32_t a = 0;
-    chain<STOP_GE>(x, s.sd, t.L, t.max_ticks + 1, a);
+    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, t.L, t.max_ticks + 1, a);
     s.pl_left = a > 0 ? a : 1;
 }
 
@@ -281,7 +290,7 @@ ABR_HD void sched_played(LaneJ &s, const TB &t, int32_t a) {
     s.pt_sum += (double)a * s.pt + s.sd * (double)(((long long)a * (a - 1)) / 2);
     int32_t done = 0;
     double x = s.pt;
-    chain<STOP_GE>(x, s.sd, 1.0e300, a, done);
+    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, 1.0e300, a, done);
     s.pt = x;
     s.pl_left -= a;
     if (s.pl_left == 0) s.play_id++;                                       // :185-187
@@ -297,8 +306,8 @@ ABR_HD bool sched_drain(LaneJ &s, const TB &t, double &b, double thr, int32_t m,
         if (s.pl_left == 0) sched_begin_chunk(s, t, s.k + a_tot, b);
         const int32_t run = (m - a_tot < s.pl_left) ? m - a_tot : s.pl_left;
         int32_t a = 0;
-        if (STOP == STOP_LE) hit = drain_to_zero(b, s.sd, run, a);
-        else hit = chain<STOP_LT>(b, -s.sd, thr, run, a);
+        if (STOP == STOP_LE) hit = drain_to_zero<TB::kSettle>(b, s.sd, run, a);
+        else hit = chain<STOP_LT, 0, TB::kSettle>(b, -s.sd, thr, run, a);
         sched_played(s, t, a);
         a_tot += a;
     }
@@ -362,9 +371,9 @@ ABR_HD bool lanej_wait_call(LaneJ &s, const TB &t) {
         bool cleared;
         if constexpr (TB::kSpeeds) {
             if (t.speed_rows >= 2) cleared = sched_drain<STOP_LT>(s, t, b, t.max_buffer, mt - s.k, a);
-            else { cleared = chain<STOP_LT>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
+            else { cleared = chain<STOP_LT, 0, TB::kSettle>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
         } else {
-            cleared = chain<STOP_LT>(b, -t.sd, t.max_buffer, mt - s.k, a);
+            cleared = chain<STOP_LT, 0, TB::kSettle>(b, -t.sd, t.max_buffer, mt - s.k, a);
         }
         s.n_play += a;
         s.sumk += (long long)a * s.k + ((long long)a * (a - 1)) / 2;
@@ -570,7 +579,7 @@ ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int3
         tn = (s.tpos + 1 == s.tlen) ? 0 : s.tpos + 1;
         bw_next = s.trace[(uint32_t)tn];
         ke_next = t.interval_tick[(uint32_t)(s.j + 2)];
-        kk += chain_segment<STOP_GE>(cs, c, target, ke - kk, hit);                // :160-163
+        kk += chain_segment<STOP_GE, 0, TB::kSettle>(cs, c, target, ke - kk, hit);                // :160-163
     }
     Download d;
     d.dl = cs.x; d.n_dl = kk - k; d.hit = hit;
@@ -675,7 +684,7 @@ ABR_HD bool lanej_predict_next_call(double buf, int32_t k, int32_t n_dl, int32_t
         if (k >= mt) return false;
         if (bf) {
             a = 0;
-            if (!chain<STOP_LT>(b, -t.sd, t.max_buffer, mt - k, a)) return false;
+            if (!chain<STOP_LT, 0, TB::kSettle>(b, -t.sd, t.max_buffer, mt - k, a)) return false;
             k += a;
             if (b <= 0.0) return false;
         }
