@@ -1773,6 +1773,22 @@ static int step_row(const abr_env *env, int impl, hipStream_t st, int32_t s, con
                          slab_row(dn, s, 1, N), nullptr, 1, 0ull);
 }
 
+// A rollout of n_steps decisions, one launch pair per decision on `st`: decide(s, action_row) enqueues the controller's
+// kernels, which write every lane's action into action_row (row s of actions_out, or the workspace's mpc_action when the
+// caller wants none), then K1 MODE 1 downloads it.  Refused on an env kernel that cannot serve `feature`.
+template <class Decide>
+static int rollout_per_launch(const abr_env *env, Feature feature, int32_t n_steps, int32_t *actions_out, hipStream_t st,
+                              float *obs, float *rew, uint8_t *dn, const Decide &decide) {
+    int rc = require(feature, env->impl);
+    if (rc) return rc;
+    const int impl = launch_impl<1>(env, 1);
+    for (int32_t s = 0; s < n_steps; s++) {
+        int32_t *action_row = actions_out ? slab_row(actions_out, s, 1, env->p.n_lanes) : env->mpc_action;
+        if ((rc = decide(s, action_row)) || (rc = step_row(env, impl, st, s, action_row, obs, rew, dn))) return rc;
+    }
+    return ABR_OK;
+}
+
 extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
                              const int32_t *start_offset_dev, const uint8_t *lane_mask_dev,
                              float *obs_out_dev, void *stream) {
@@ -1871,15 +1887,19 @@ __global__ __launch_bounds__(256) void rule_select_kernel(EnvParams p, abrx::Rul
     action_out[i] = p.done[i] ? -1 : rule_action(p, rule, i, p.chunk_id[i], p.last_action[i], p.buf[i]);
 }
 
+static int launch_rule_select(const abr_env *env, const abrx::RuleParams &rp, int32_t *action_out_dev, void *stream) {
+    hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
+                       (hipStream_t)stream, env->p, rp, action_out_dev);
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
 extern "C" int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, int32_t *action_out_dev, void *stream) {
     abrx::RuleParams rp;
     int rc = validate_rule(rule, &rp);
     if (rc) return rc;
     if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument");
-    hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, env->p, rp, action_out_dev);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    return launch_rule_select(env, rp, action_out_dev, stream);
 }
 
 extern "C" int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out) {
@@ -2100,14 +2120,52 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
     }
 }
 
-template <int H>
-static void launch_lookahead(const abr_env *env, int64_t lane0, int64_t lane_end, int32_t *action, double *key, double *q,
-                             hipStream_t st) {
+struct LookaheadKernels { template <int H, int W> static constexpr auto kernel = lookahead_kernel<H, W>; };
+
+// One launch of horizon H's instance of a kernel family on lanes [lane0, lane_end); `tail`: the kernel's arguments behind them.
+template <class Kernels, int H, class... Tail>
+static void launch_walk(const abr_env *env, int64_t lane0, int64_t lane_end, hipStream_t st, Tail... tail) {
     const dim3 grid(grid64(lane_end - lane0)), block(64u * (unsigned)env->p.n_rates);
     if (env->p.n_rates <= 8 || look_max_rates(H) <= 8)       // (the refusals have bounded n_rates by look_max_rates(H))
-        hipLaunchKernelGGL((lookahead_kernel<H, 8>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, action, key, q);
+        hipLaunchKernelGGL((Kernels::template kernel<H, 8>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, tail...);
     else if constexpr (look_max_rates(H) > 8)
-        hipLaunchKernelGGL((lookahead_kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, action, key, q);
+        hipLaunchKernelGGL((Kernels::template kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, tail...);
+}
+
+// The walk of every lane, in launches of at most max_nodes tree nodes each.
+template <class Kernels, class... Tail>
+static int launch_walks(const abr_env *env, int32_t H, int64_t max_nodes, hipStream_t st, Tail... tail) {
+    const EnvParams &p = env->p;
+    const int64_t per = abrx::look_lanes_per_launch(max_nodes, p.n_rates, H);
+    for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
+        const int64_t lane_end = lane0 + per < p.n_lanes ? lane0 + per : p.n_lanes;
+        switch (H) {
+        case 1: launch_walk<Kernels, 1>(env, lane0, lane_end, st, tail...); break;
+        case 2: launch_walk<Kernels, 2>(env, lane0, lane_end, st, tail...); break;
+        case 3: launch_walk<Kernels, 3>(env, lane0, lane_end, st, tail...); break;
+        case 4: launch_walk<Kernels, 4>(env, lane0, lane_end, st, tail...); break;
+        case 5: launch_walk<Kernels, 5>(env, lane0, lane_end, st, tail...); break;
+        case 6: launch_walk<Kernels, 6>(env, lane0, lane_end, st, tail...); break;
+        case 7: launch_walk<Kernels, 7>(env, lane0, lane_end, st, tail...); break;
+        default: launch_walk<Kernels, 8>(env, lane0, lane_end, st, tail...); break;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return ABR_OK;
+}
+
+// What a walk's config and decision output must be, whoever asks (`who` opens the message); action_out is looked at only
+// where the entry `wants_action`.  The arguments before the handle: a CPU test drives these refusals with env == NULL.
+template <class Cfg>
+static int validate_walk(const Cfg *cfg, bool wants_action, const void *action_out, const char *who) {
+    if (!cfg) return fail(ABR_E_INVALID, "%s: cfg is NULL", who);
+    if (wants_action && !action_out) return fail(ABR_E_INVALID, "%s: action_out_dev is NULL", who);
+    if (cfg->horizon < 1 || cfg->horizon > ABR_MAX_HORIZON)
+        return fail(ABR_E_INVALID, "%s: horizon %d outside 1..%d", who, cfg->horizon, ABR_MAX_HORIZON);
+    if (cfg->reserved_ != 0) return fail(ABR_E_INVALID, "%s: reserved_ must be 0, got %d", who, cfg->reserved_);
+    if (cfg->max_nodes_per_launch < 0)
+        return fail(ABR_E_INVALID, "%s: max_nodes_per_launch must be >= 0, got %lld", who, (long long)cfg->max_nodes_per_launch);
+    return ABR_OK;
 }
 
 // what the walk cannot serve (ABR_E_UNSUPPORTED), for the lookahead and for the forecast planner (`who` opens the message)
@@ -2126,35 +2184,12 @@ static int look_supported(const abr_env *env, int32_t H, const char *who) {
 
 extern "C" int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config *cfg, int32_t *action_out_dev,
                                         double *key_out_dev, double *q_out_dev, void *stream) {
-    // the arguments before the handle: a CPU test drives these refusals with env == NULL
-    if (!cfg) return fail(ABR_E_INVALID, "lookahead: cfg is NULL");
-    if (!action_out_dev) return fail(ABR_E_INVALID, "lookahead: action_out_dev is NULL");
-    if (cfg->horizon < 1 || cfg->horizon > ABR_MAX_HORIZON)
-        return fail(ABR_E_INVALID, "lookahead: horizon %d outside 1..%d", cfg->horizon, ABR_MAX_HORIZON);
-    if (cfg->reserved_ != 0) return fail(ABR_E_INVALID, "lookahead: reserved_ must be 0, got %d", cfg->reserved_);
-    if (cfg->max_nodes_per_launch < 0)
-        return fail(ABR_E_INVALID, "lookahead: max_nodes_per_launch must be >= 0, got %lld", (long long)cfg->max_nodes_per_launch);
+    int rc = validate_walk(cfg, true, action_out_dev, "lookahead");
+    if (rc) return rc;
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
-    const EnvParams &p = env->p;
-    const int32_t H = cfg->horizon;
-    if (const int rc = look_supported(env, H, "lookahead")) return rc;
-    const int64_t per = abrx::look_lanes_per_launch(cfg->max_nodes_per_launch, p.n_rates, H);
-    const hipStream_t st = (hipStream_t)stream;
-    for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
-        const int64_t lane_end = lane0 + per < p.n_lanes ? lane0 + per : p.n_lanes;
-        switch (H) {
-        case 1: launch_lookahead<1>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 2: launch_lookahead<2>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 3: launch_lookahead<3>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 4: launch_lookahead<4>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 5: launch_lookahead<5>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 6: launch_lookahead<6>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        case 7: launch_lookahead<7>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        default: launch_lookahead<8>(env, lane0, lane_end, action_out_dev, key_out_dev, q_out_dev, st); break;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    if ((rc = look_supported(env, cfg->horizon, "lookahead"))) return rc;
+    return launch_walks<LookaheadKernels>(env, cfg->horizon, cfg->max_nodes_per_launch, (hipStream_t)stream, action_out_dev,
+                                          key_out_dev, q_out_dev);
 }
 
 #ifdef ABR_SPLIT_STAMPS
@@ -3005,19 +3040,16 @@ static int mpc_rollout(abr_env *env, const abr_mpc_config *cfg, const abr_mpc_ro
                     cfg->video_length, cfg->n_rates, e.video_length, e.n_rates);
     int rc;
     if (robust && (rc = validate_robust_sizes(robust, cfg->horizon, N, true))) return rc;
-    if ((rc = require(kMpcRollout, env->impl))) return rc;
     MpcParams p = mpc_params(cfg, N, e.chunk_id, e.last_action, e.buf, robust ? nullptr : e.hist_n,
                              robust ? nullptr : e.hist_s, br_table_dev, sz_table_dev, e.done, nullptr, nullptr, nullptr);
     p.mask_is_done = 1; p.neg_to_zero = 1;
     if (robust) p.utility = robust->utility;
     void *scratch = robust && robust->scratch_dev ? robust->scratch_dev : env->mpc_scratch;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        p.action_out = actions_out_dev ? slab_row(actions_out_dev, s, 1, N) : env->mpc_action;
-        if ((rc = launch_mpc_select(p, st, scratch, robust, e.bw_hist, N))) return rc;
-        if ((rc = step_row(env, impl, st, s, p.action_out, obs_out_dev, reward_out_dev, done_out_dev))) return rc;
-    }
-    return ABR_OK;
+    return rollout_per_launch(env, kMpcRollout, n_steps, actions_out_dev, st, obs_out_dev, reward_out_dev, done_out_dev,
+                              [&](int32_t, int32_t *action) {
+        p.action_out = action;
+        return launch_mpc_select(p, st, scratch, robust, e.bw_hist, N);
+    });
 }
 
 extern "C" int abr_env_step_mpc(abr_env *env, const abr_mpc_config *cfg,
@@ -3110,29 +3142,17 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
     }
 }
 
+struct PlanKernels { template <int H, int W> static constexpr auto kernel = plan_kernel<H, W>; };
+
 struct PlanOut {
     int32_t *action;
     double *key, *q, *forecast;
     int32_t neg_to_zero;
 };
 
-template <int H>
-static void launch_plan(const abr_env *env, int64_t lane0, int64_t lane_end, const double *P, const PlanOut &o,
-                        hipStream_t st) {
-    const dim3 grid(grid64(lane_end - lane0)), block(64u * (unsigned)env->p.n_rates);
-    if (env->p.n_rates <= 8 || look_max_rates(H) <= 8)       // (the refusals have bounded n_rates by look_max_rates(H))
-        hipLaunchKernelGGL((plan_kernel<H, 8>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, P, o.neg_to_zero,
-                           o.action, o.key, o.q, o.forecast);
-    else if constexpr (look_max_rates(H) > 8)
-        hipLaunchKernelGGL((plan_kernel<H, 16>), grid, block, 0, st, env->p, env->quality, lane0, lane_end, P, o.neg_to_zero,
-                           o.action, o.key, o.q, o.forecast);
-}
-
-// One decision of every lane: the built-in forecast into `scratch` (skipped when the caller brought one), then the walk in
-// launches of at most max_nodes_per_launch tree nodes, as abr_env_lookahead_select splits them.
+// One decision of every lane: the built-in forecast into `scratch` (skipped when the caller brought one), then the walk.
 static int plan_decide(const abr_env *env, const abr_plan_config *cfg, double *scratch, PlanOut o, hipStream_t st) {
     const EnvParams &p = env->p;
-    const int32_t H = cfg->horizon;
     const double *P = cfg->forecast_dev;
     if (!P) {
         hipLaunchKernelGGL(plan_forecast_kernel, dim3((unsigned)((p.n_lanes + 255) / 256)), dim3(256), 0, st, p, cfg->window,
@@ -3140,34 +3160,14 @@ static int plan_decide(const abr_env *env, const abr_plan_config *cfg, double *s
         P = scratch;
         if (o.forecast == scratch) o.forecast = nullptr;     // the forecast kernel has written the caller's copy already
     }
-    const int64_t per = abrx::look_lanes_per_launch(cfg->max_nodes_per_launch, p.n_rates, H);
-    for (int64_t lane0 = 0; lane0 < p.n_lanes; lane0 += per) {
-        const int64_t lane_end = lane0 + per < p.n_lanes ? lane0 + per : p.n_lanes;
-        switch (H) {
-        case 1: launch_plan<1>(env, lane0, lane_end, P, o, st); break;
-        case 2: launch_plan<2>(env, lane0, lane_end, P, o, st); break;
-        case 3: launch_plan<3>(env, lane0, lane_end, P, o, st); break;
-        case 4: launch_plan<4>(env, lane0, lane_end, P, o, st); break;
-        case 5: launch_plan<5>(env, lane0, lane_end, P, o, st); break;
-        case 6: launch_plan<6>(env, lane0, lane_end, P, o, st); break;
-        case 7: launch_plan<7>(env, lane0, lane_end, P, o, st); break;
-        default: launch_plan<8>(env, lane0, lane_end, P, o, st); break;
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    return launch_walks<PlanKernels>(env, cfg->horizon, cfg->max_nodes_per_launch, st, P, o.neg_to_zero, o.action, o.key, o.q,
+                                     o.forecast);
 }
 
 // The refusals of both entry points in the documented order; `select`: abr_env_plan_select (else abr_env_step_plan).
 static int validate_plan(const abr_env *env, const abr_plan_config *cfg, bool select, const void *action_out,
                          int32_t n_steps) {
-    if (!cfg) return fail(ABR_E_INVALID, "plan: cfg is NULL");
-    if (select && !action_out) return fail(ABR_E_INVALID, "plan: action_out_dev is NULL");
-    if (cfg->horizon < 1 || cfg->horizon > ABR_MAX_HORIZON)
-        return fail(ABR_E_INVALID, "plan: horizon %d outside 1..%d", cfg->horizon, ABR_MAX_HORIZON);
-    if (cfg->reserved_ != 0) return fail(ABR_E_INVALID, "plan: reserved_ must be 0, got %d", cfg->reserved_);
-    if (cfg->max_nodes_per_launch < 0)
-        return fail(ABR_E_INVALID, "plan: max_nodes_per_launch must be >= 0, got %lld", (long long)cfg->max_nodes_per_launch);
+    if (const int rc = validate_walk(cfg, select, action_out, "plan")) return rc;
     if (cfg->robust != 0 && cfg->robust != 1) return fail(ABR_E_INVALID, "plan: robust must be 0 or 1, got %d", cfg->robust);
     if (!cfg->forecast_dev && (cfg->window < 1 || cfg->window > ABR_ROBUST_MAX_WINDOW))
         return fail(ABR_E_INVALID, "plan: window %d outside 1..%d", cfg->window, ABR_ROBUST_MAX_WINDOW);
@@ -3194,19 +3194,12 @@ extern "C" int abr_env_plan_select(abr_env *env, const abr_plan_config *cfg, int
 
 extern "C" int abr_env_step_plan(abr_env *env, const abr_plan_config *cfg, int32_t n_steps, float *obs_out_dev,
                                  float *reward_out_dev, uint8_t *done_out_dev, int32_t *actions_out_dev, void *stream) {
-    int rc = validate_plan(env, cfg, false, nullptr, n_steps);
-    if (rc) return rc;
-    if ((rc = require(kMpcRollout, env->impl))) return rc;
-    const int64_t N = env->p.n_lanes;
+    if (const int rc = validate_plan(env, cfg, false, nullptr, n_steps)) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        int32_t *action = actions_out_dev ? slab_row(actions_out_dev, s, 1, N) : env->mpc_action;
-        if ((rc = plan_decide(env, cfg, (double *)env->mpc_scratch, PlanOut{action, nullptr, nullptr, nullptr, 1}, st)))
-            return rc;
-        if ((rc = step_row(env, impl, st, s, action, obs_out_dev, reward_out_dev, done_out_dev))) return rc;
-    }
-    return ABR_OK;
+    return rollout_per_launch(env, kMpcRollout, n_steps, actions_out_dev, st, obs_out_dev, reward_out_dev, done_out_dev,
+                              [&](int32_t, int32_t *action) {
+        return plan_decide(env, cfg, (double *)env->mpc_scratch, PlanOut{action, nullptr, nullptr, nullptr, 1}, st);
+    });
 }
 
 // ===========================================================================
@@ -3358,6 +3351,11 @@ extern "C" int abr_fastmpc_build_scratch_bytes(const abr_mpc_config *cfg, const 
     return ABR_OK;
 }
 
+static int fastmpc_table_check(const void *table_dev) {
+    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    return ABR_OK;
+}
+
 // host array -> device, in kernel-argument slices on `st`
 static void fastmpc_copy(double *dst, const double *src, int32_t n, hipStream_t st) {
     for (int32_t k0 = 0; k0 < n; k0 += kFastMpcCopy) {
@@ -3373,7 +3371,7 @@ extern "C" int abr_fastmpc_build(const abr_mpc_config *cfg, const abr_fastmpc *f
                                  size_t scratch_bytes, void *stream) {
     int rc = validate_fastmpc(cfg, fm, true);
     if (rc) return rc;
-    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if ((rc = fastmpc_table_check(table_dev))) return rc;
     if (table_bytes < fastmpc_table_bytes(cfg, fm))
         return fail(ABR_E_INVALID, "fastmpc table has %zu bytes, need %zu", table_bytes, fastmpc_table_bytes(cfg, fm));
     if (!scratch_dev || ((uintptr_t)scratch_dev & 7))
@@ -3429,7 +3427,7 @@ extern "C" int abr_fastmpc_select(const abr_mpc_config *cfg, const abr_fastmpc *
                                   int64_t n_lanes, void *stream) {
     int rc = validate_fastmpc(cfg, fm, false);
     if (rc) return rc;
-    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if ((rc = fastmpc_table_check(table_dev))) return rc;
     if (table_bytes < fastmpc_table_bytes(cfg, fm))
         return fail(ABR_E_INVALID, "fastmpc table has %zu bytes, need %zu", table_bytes, fastmpc_table_bytes(cfg, fm));
     if (!hist_dev || hist_stride < 1) return fail(ABR_E_INVALID, "the lookup needs the history: hist_dev and hist_stride >= 1");
@@ -3458,7 +3456,7 @@ extern "C" int abr_env_step_fastmpc(abr_env *env, const abr_mpc_config *cfg, con
                                     int32_t *actions_out_dev, void *stream) {
     int rc = validate_fastmpc(cfg, fm, false);
     if (rc) return rc;
-    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if ((rc = fastmpc_table_check(table_dev))) return rc;
     if (n_steps < 1) return fail(ABR_E_INVALID, "n_steps must be >= 1");
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if ((rc = fastmpc_env_check(env, cfg, fm))) return rc;
@@ -3471,13 +3469,10 @@ extern "C" int abr_env_fastmpc_select(abr_env *env, const abr_mpc_config *cfg, c
                                       const void *table_dev, int32_t *action_out_dev, void *stream) {
     int rc = validate_fastmpc(cfg, fm, false);
     if (rc) return rc;
-    if (!table_dev || ((uintptr_t)table_dev & 7)) return fail(ABR_E_INVALID, "fastmpc table must be non-NULL and 8-byte aligned");
+    if ((rc = fastmpc_table_check(table_dev))) return rc;
     if (!env || !action_out_dev) return fail(ABR_E_INVALID, "NULL argument (env or action_out_dev)");
     if ((rc = fastmpc_env_check(env, cfg, fm))) return rc;
-    hipLaunchKernelGGL(rule_select_kernel, dim3((unsigned)((env->p.n_lanes + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, env->p, fastmpc_rule(cfg, fm, table_dev), action_out_dev);
-    HIP_TRY(hipGetLastError());
-    return ABR_OK;
+    return launch_rule_select(env, fastmpc_rule(cfg, fm, table_dev), action_out_dev, stream);
 }
 
 // ===========================================================================
@@ -4679,21 +4674,20 @@ static int policy_select_once(const abr_env *env, Args &a, const Launch &launch,
 template <class Args, class Launch>
 static int policy_rollout(const abr_env *env, Args &a, const Launch &launch, int32_t n_steps, const PolicyOut &o,
                           void *stream) {
-    int rc = require(kPolicyRollout, env->impl);
-    if (rc) return rc;
     const hipStream_t st = (hipStream_t)stream;
     const int64_t N = env->p.n_lanes;
-    const int impl = launch_impl<1>(env, 1);
-    for (int32_t s = 0; s < n_steps; s++) {
-        a.action_out = o.action ? slab_row(o.action, s, 1, N) : env->mpc_action;
+    const int rc = rollout_per_launch(env, kPolicyRollout, n_steps, o.action, st, o.obs, o.reward, o.done,
+                                      [&](int32_t s, int32_t *action) {
+        a.action_out = action;
         a.features_out = slab_row(o.features, s, a.net.F, N);
         a.scores_out = slab_row(o.scores, s, a.net.M, N);
         a.probs_out = slab_row(o.probs, s, a.net.M, N);
         a.value_out = slab_row(o.value, s, 1, N);
         set_recurrence(a, slab_row(o.hidden, s, a.net.w0, N), 1);
         HIP_TRY(launch(env, a, st));
-        if ((rc = step_row(env, impl, st, s, a.action_out, o.obs, o.reward, o.done))) return rc;
-    }
+        return ABR_OK;
+    });
+    if (rc) return rc;
     if (o.last_value) {
         a.action_out = nullptr; a.features_out = a.scores_out = a.probs_out = nullptr;
         a.mode = ABR_POLICY_ARGMAX;

@@ -359,6 +359,13 @@ class BatchedABREnv:
             out["actions"] = torch.empty(n, N, dtype=torch.int32, device=dev) if want_actions else None
         return out
 
+    def _rollout(self, fn, head, n, out, want_obs, want_actions):
+        """A rollout entry fn(handle, *head, n, obs, reward, done, actions) into `out` (None: a fresh _rollout_out)."""
+        if out is None:
+            out = self._rollout_out(n, want_obs, want_actions)
+        self._call(fn, self._h, *head, n, *(_lib.ptr(out.get(k)) for k in ("obs", "reward", "done", "actions")))
+        return out
+
     # -- the step surface --------------------------------------------------
     def reset(self, trace_id=None, start_offset=None, mask=None, check=False, sample=False):
         """Simulator.py:95-133 + idle ticks to the first ABR call.  Default assignment: lane i -> trace
@@ -481,19 +488,13 @@ class BatchedABREnv:
                              f"controller has method={method!r}, utility={utility!r}")
         br, sz = controller._tables()
         cfg = controller.config()
-        if out is None:
-            out = self._rollout_out(n, want_obs, want_actions)
-        if getattr(controller, "method", None) == "robust":
+        if method == "robust":
             # RobustMPC: the controller's per-lane state rides along; the estimates go through the workspace's scratch
             rob = controller.robust_options(self.n_lanes)
-            self._call(self.lib.abr_env_step_mpc_robust, self._h, C.byref(cfg), C.byref(rob), _lib.ptr(br),
-                       _lib.ptr(sz), n, _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")),
-                       _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
-            return out
-        self._call(self.lib.abr_env_step_mpc, self._h, C.byref(cfg), _lib.ptr(br), _lib.ptr(sz), n,
-                   _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                   _lib.ptr(out.get("actions")))
-        return out
+            return self._rollout(self.lib.abr_env_step_mpc_robust, (C.byref(cfg), C.byref(rob), _lib.ptr(br), _lib.ptr(sz)),
+                                 n, out, want_obs, want_actions)
+        return self._rollout(self.lib.abr_env_step_mpc, (C.byref(cfg), _lib.ptr(br), _lib.ptr(sz)), n, out, want_obs,
+                             want_actions)
 
     def step_rule(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True):
         """n_steps decisions per lane taken by a bitrate rule (rules.py: BufferBasedController, RateBasedController,
@@ -504,18 +505,9 @@ class BatchedABREnv:
         n = int(n_steps)
         if getattr(controller, "method", None) == "fastmpc":
             cfg, fm, table = controller.bound()
-            if out is None:
-                out = self._rollout_out(n, want_obs, want_actions)
-            self._call(self.lib.abr_env_step_fastmpc, self._h, C.byref(cfg), C.byref(fm), _lib.ptr(table), n,
-                       _lib.ptr(out.get("obs")), _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")),
-                       _lib.ptr(out.get("actions")))
-            return out
-        cfg = controller.config()
-        if out is None:
-            out = self._rollout_out(n, want_obs, want_actions)
-        self._call(self.lib.abr_env_step_rule, self._h, C.byref(cfg), n, _lib.ptr(out.get("obs")),
-                   _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
-        return out
+            return self._rollout(self.lib.abr_env_step_fastmpc, (C.byref(cfg), C.byref(fm), _lib.ptr(table)), n, out,
+                                 want_obs, want_actions)
+        return self._rollout(self.lib.abr_env_step_rule, (C.byref(controller.config()),), n, out, want_obs, want_actions)
 
     def step_plan(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, forecast=None):
         """n_steps decisions per lane taken by forecast MPC (planner.py: ForecastMPCController) on the device: per decision
@@ -524,12 +516,8 @@ class BatchedABREnv:
         Finished lanes take no decision; "no decision" downloads bitrate 0 and is reported as 0.  Every event-driven
         kernel; 'tick' is refused.  Returns dict(obs[n,OBS_DIM,N], reward[n,N], done[n,N], actions[n,N])."""
         n = int(n_steps)
-        cfg = controller.config(forecast)
-        if out is None:
-            out = self._rollout_out(n, want_obs, want_actions)
-        self._call(self.lib.abr_env_step_plan, self._h, C.byref(cfg), n, _lib.ptr(out.get("obs")),
-                   _lib.ptr(out.get("reward")), _lib.ptr(out.get("done")), _lib.ptr(out.get("actions")))
-        return out
+        return self._rollout(self.lib.abr_env_step_plan, (C.byref(controller.config(forecast)),), n, out, want_obs,
+                             want_actions)
 
     def step_policy(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True, want_features=False,
                     want_scores=False, want_probs=False, want_values=False, want_hidden=False):
