@@ -200,6 +200,8 @@ struct abr_env {
     abrx::EpisodeSampler sampler;
     abrx::EpisodeLedger ledger;     // abr_env_set_episode_ledger: base == nullptr while none is installed
     abrx::EpisodeQuality quality;   // abr_env_set_episode_quality: likewise
+    bool chains_proven;             // abr_env_create: abrx::chains_proven() holds for this handle's tables and config, so its
+                                    // launches may run the no-speeds instances, whose chains carry no per-segment guards
 };
 
 // A handle on which no reset has run has no episode to protect: the setters take effect at once
@@ -738,9 +740,10 @@ struct SpeedParams<false> {
     static __device__ __forceinline__ constexpr int32_t speed_rows(const EnvParams &) { return 1; }
 };
 
-template <bool SPEEDS = true>
-__device__ inline abrx::TablesT<SPEEDS> make_tables(const EnvParams &p, bool cascade = true) {
-    abrx::TablesT<SPEEDS> t;
+// TB: the table type filled in -- TablesT<SPEEDS>, or a type derived from it that only changes a trait (abr_lane_jump.h)
+template <bool SPEEDS = true, class TB = abrx::TablesT<SPEEDS>>
+__device__ inline TB make_tables(const EnvParams &p, bool cascade = true) {
+    TB t;
     t.G = p.G; t.interval_tick = p.interval_tick; t.avail_tick = p.avail_tick;
     t.L = p.chunk_length; t.sd = p.sd; t.max_buffer = p.max_buffer;
     t.start_up_length = p.start_up_length; t.V = p.video_length; t.max_ticks = p.max_ticks;
@@ -1234,6 +1237,8 @@ extern "C" int abr_env_create(const abr_env_config *cfg, const double *traces_de
     memset(e, 0, sizeof(*e));
     e->cfg = *cfg;
     e->impl = 3;
+    e->chains_proven = abrx::chains_proven(itick.data(), itick.size(), mt, sd, cfg->chunk_length, cfg->max_buffer, cfg->ladder,
+                                           cfg->n_rates);
     e->workspace_bytes = L.total;
     EnvParams &p = e->p;
     p.n_rates = cfg->n_rates; p.video_length = cfg->video_length; p.max_ticks = mt;
@@ -1715,7 +1720,9 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
     // nor a quality model's download: a reset has no QUALITY instance (abr_env_reset clears the running sums behind it)
     const bool quality = MODE != 0 && env->quality.base;
     // speeds are latched at a full reset (apply_pending), so the handle knows at every launch whether any lane has one
-    const bool speeds_on = env->p.lane_speeds != nullptr;
+    // ... and a handle whose tables fail the chains' proof (an interval shorter than a tick, more than 2^20 ticks: abr_lane_jump.h,
+    // chains_proven) runs the SPEEDS form as well: it accepts the no-speed case, and its chains test their guards per segment
+    const bool speeds_on = env->p.lane_speeds != nullptr || !env->chains_proven;
     // (never with the tick kernel: the speed setters and abr_env_set_impl refuse that pair, kFeatures)
     const auto go = [&](auto smp_on, auto led_on, auto ql_on) {
         // The no-speeds instances exist for handles WITHOUT an episode sampler.  With the sampler's draw in them, four of
@@ -1904,7 +1911,10 @@ extern "C" int abr_env_rule_select(abr_env *env, const abr_rule_config *rule, in
 
 extern "C" int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out) {
     if (!env || !impl_out) return fail(ABR_E_INVALID, "NULL argument");
-    *impl_out = effective_impl(env, fused != 0);
+    *impl_out = effective_impl(env, (fused & 1) != 0);
+    // bit 1 of `fused` asks for the instance as well: 0x100 is added when a step launch runs the SPEEDS == true form
+    // (launch_env: a latched speed feature, a sampler, a quality model, or tables that fail the chains' proof)
+    if ((fused & 2) && (env->p.lane_speeds || !env->chains_proven || env->sampler_on || env->quality.base)) *impl_out |= 0x100;
     return ABR_OK;
 }
 
@@ -2089,7 +2099,7 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
     const int32_t m = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));     // the wave's first digit, scalar
     const int32_t l = (int32_t)(threadIdx.x & 63);
     const int64_t i = lane0 + (int64_t)blockIdx.x * 64 + l;
-    const abrx::TablesT<false> tb = make_tables<false>(p);
+    const abrx::TablesChecked tb = make_tables<false, abrx::TablesChecked>(p);   // any handle: the checked chains
     LaneJ s{};
     int32_t n_su_obs = 0, n_rb_obs = 0;
     bool live = false;
@@ -3107,7 +3117,7 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
     const int32_t m = __builtin_amdgcn_readfirstlane((int32_t)(threadIdx.x >> 6));
     const int32_t l = (int32_t)(threadIdx.x & 63);
     const int64_t i = lane0 + (int64_t)blockIdx.x * 64 + l;
-    const abrx::TablesT<false> tb = make_tables<false>(p);
+    const abrx::TablesChecked tb = make_tables<false, abrx::TablesChecked>(p);   // any handle: the checked chains
     LaneJ s{};
     int32_t n_su_obs = 0, n_rb_obs = 0;
     bool live = false;
@@ -5052,23 +5062,25 @@ template <int STOP, int BIAS>
 __global__ void chain_debug_kernel(const double *__restrict__ x0, const double *__restrict__ c,
                                    const double *__restrict__ thr, const int32_t *__restrict__ n,
                                    int64_t count, double *__restrict__ x_out,
-                                   int32_t *__restrict__ a_out, uint8_t *__restrict__ hit_out) {
+                                   int32_t *__restrict__ a_out, uint8_t *__restrict__ hit_out, int32_t proven) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count) return;
     double x = x0[i];
     int32_t a = 0;
-    const bool hit = abrx::chain<STOP, BIAS>(x, c[i], thr[i], n[i], a);
+    // proven: the form of the chains without per-segment guards (abr_exact_jump.h: GUARDS_PROVEN); the caller keeps to P1-P3
+    const bool hit = proven ? abrx::chain<STOP, BIAS, abrx::SETTLE_REMAINDER, abrx::GUARDS_PROVEN>(x, c[i], thr[i], n[i], a)
+                            : abrx::chain<STOP, BIAS>(x, c[i], thr[i], n[i], a);
     x_out[i] = x; a_out[i] = a; hit_out[i] = hit ? 1 : 0;
 }
 
 template <int STOP>
 static int launch_chain_debug(int32_t bias, const double *x0, const double *c, const double *thr,
                               const int32_t *n, int64_t count, double *x_out, int32_t *a_out,
-                              uint8_t *hit_out, hipStream_t st) {
+                              uint8_t *hit_out, hipStream_t st, int32_t proven) {
     const dim3 g((unsigned)((count + 63) / 64)), b(64);
-    if (bias == 0) hipLaunchKernelGGL((chain_debug_kernel<STOP, 0>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out);
-    else if (bias == 4) hipLaunchKernelGGL((chain_debug_kernel<STOP, 4>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out);
-    else if (bias == -4) hipLaunchKernelGGL((chain_debug_kernel<STOP, -4>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out);
+    if (bias == 0) hipLaunchKernelGGL((chain_debug_kernel<STOP, 0>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out, proven);
+    else if (bias == 4) hipLaunchKernelGGL((chain_debug_kernel<STOP, 4>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out, proven);
+    else if (bias == -4) hipLaunchKernelGGL((chain_debug_kernel<STOP, -4>), g, b, 0, st, x0, c, thr, n, count, x_out, a_out, hit_out, proven);
     else return fail(ABR_E_INVALID, "estimate_bias must be 0, 4 or -4");
     HIP_TRY(hipGetLastError());
     return ABR_OK;
@@ -5082,10 +5094,14 @@ extern "C" int abr_debug_chain(int32_t stop_kind, int32_t estimate_bias, const d
         return fail(ABR_E_INVALID, "NULL device pointer");
     if (count < 1) return fail(ABR_E_INVALID, "count must be >= 1");
     hipStream_t st = (hipStream_t)stream;
+    // bit 8 of stop_kind: the proven form of the chains.  Its preconditions are the caller's (every budget in 1..2^20,
+    // finite values); the budgets are not readable here (device memory), so they are not checked.
+    const int32_t proven = (stop_kind & 0x100) ? 1 : 0;
+    stop_kind &= ~0x100;
     switch (stop_kind) {
-        case abrx::STOP_GE: return launch_chain_debug<abrx::STOP_GE>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st);
-        case abrx::STOP_LE: return launch_chain_debug<abrx::STOP_LE>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st);
-        case abrx::STOP_LT: return launch_chain_debug<abrx::STOP_LT>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st);
+        case abrx::STOP_GE: return launch_chain_debug<abrx::STOP_GE>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st, proven);
+        case abrx::STOP_LE: return launch_chain_debug<abrx::STOP_LE>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st, proven);
+        case abrx::STOP_LT: return launch_chain_debug<abrx::STOP_LT>(estimate_bias, x0_dev, c_dev, thr_dev, n_dev, count, x_out_dev, a_out_dev, hit_out_dev, st, proven);
         default: return fail(ABR_E_INVALID, "stop_kind must be 0 (>=), 1 (<=) or 2 (<)");
     }
 }

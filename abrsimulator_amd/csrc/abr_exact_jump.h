@@ -197,16 +197,36 @@ ABR_HD bool any_lane(bool v) {
 // for one more saved exec mask (profiles/chain_settle_resources.txt).  Both forms return the same jump for an estimate
 // within one of the answer (tests/test_chain_settle_cpu.py checks each against the longest legal jump).
 enum SettleKind { SETTLE_REMAINDER = 0, SETTLE_CANDIDATES = 1 };
-template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER>
+// GUARDS: who establishes the three facts a segment needs before it may jump.  GUARDS_CHECKED (the default) tests them in
+// every segment: the budget is cut to kJumpCap, a budget of 0 performs nothing (`go`), and a value outside the binades
+// 55..2045 does not jump (`normal`).  GUARDS_PROVEN tests none of them: its CALLER guarantees, for every call,
+//   (P1)  1 <= n_in             -- so `go` is the constant true: its selects and `& go` terms are gone;
+//   (P2)  n_in <= kJumpCap      -- so there is no clamp;
+//   (P3)  cs.x and thr are finite -- the only thing the high half of `normal` (e < 2046) protects: in binade 2046 the
+//         binade's top 2^(e+1) overflows, but lim = min(thr, inf) = thr is still a finite bound on u's grid, 2^e + |c| cannot
+//         overflow for expo(|c|) < e, and every step of the derivation below holds.  (So a value of 2^1023 or more may jump
+//         here where the checked form does not: same results, fewer trips.)
+// The low half of `normal` stays, folded into the test `can` already makes: expo(|c|) < e becomes max(expo(|c|), 54) < e,
+// which is `(e > 54) & (expo(|c|) < e)` in one instruction less (and loop-invariant wherever c is).  So under P1-P3, and
+// below 2^1023, `can` is the SAME predicate as in the checked form -- a zero constant jumps whole budgets, a subnormal
+// value or constant does not jump -- every jump has the same length, and results and trip counts are those of the checked
+// form, bit for bit.  The callers' side: abr_lane_jump.h (chains_proven: what a handle establishes once on the host; each
+// chain loop's own condition gives P1).  Who gets it: the tables without play-speed features (TablesT<false>::kGuards).
+enum GuardKind { GUARDS_CHECKED = 0, GUARDS_PROVEN = 1 };
+template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER, int GUARDS = GUARDS_CHECKED>
 ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in, bool &hit_out) {
 #ifdef ABR_SEGMENT_HOOK
     ABR_SEGMENT_HOOK(STOP);              // host-side analysis builds count segments per chain kind
 #endif
-    const int32_t n = (n_in < kJumpCap) ? n_in : kJumpCap;   // see kJumpCap; callers loop until their budget is spent
+    constexpr bool kProven = GUARDS == GUARDS_PROVEN;
+#ifdef ABR_PROVEN_HOOK
+    if (kProven) ABR_PROVEN_HOOK(STOP, n_in, cs.x);   // host-side test builds check P1-P3 on every call of the proven form
+#endif
+    const int32_t n = (kProven || n_in < kJumpCap) ? n_in : kJumpCap;   // see kJumpCap; callers loop until their budget is spent
     double x = cs.x;
     int32_t a = 0;
     const int e = expo(x);
-    const bool normal = (e > 54) & (e < 2046);       // else: no jump; the values below are then unused (all stay finite
+    const bool normal = kProven | ((e > 54) & (e < 2046));   // else: no jump; the values below are then unused (all stay finite
     const int ec = e;                                // or NaN-free enough: base = 0 or tiny, d = |c|, and room = 0 clamps the jump to 0)
     const double ac = (STOP == STOP_GE) ? c : -c;    // |c|: the sign of c is fixed by the stop kind (see chain())
     // steady increment of this binade and the tie test (header comment)
@@ -215,8 +235,9 @@ ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in,
     const double rem = ac - dm;                      // exact, in [-u/2, u/2]
     const double half_u = base * 0x1p-53;            // u/2 = 2^(e-53): exact (ec > 54)
     const bool tie = ((rem < 0.0) ? -rem : rem) == half_u;
-    const bool go = n > 0;
-    const bool can = normal & go & (expo(ac) < e) & (!tie | (cs.eb == e));
+    const bool go = kProven | (n > 0);
+    const int ea = expo(ac), ea_lo = (kProven && ea < 54) ? 54 : ea;    // proven: the low half of `normal` rides on this test
+    const bool can = normal & go & (ea_lo < e) & (!tie | (cs.eb == e));
     const double d = (STOP == STOP_GE) ? dm : -dm;
     {
         // `lim` bounds the jumped results: they must stay inside the binade and before
@@ -329,13 +350,14 @@ ABR_HD int32_t chain_segment(ChainState &cs, double c, double thr, int32_t n_in,
 // stopping one).  c > 0 requires STOP_GE; c < 0 requires STOP_LE or STOP_LT.
 // Bit-identical to the naive loop for every finite input (fuzzed in
 // tests/test_exact_jump.py).
-template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER>
+// GUARDS_PROVEN: the loop condition gives P1 of every segment; the caller guarantees n <= kJumpCap (P2) and finite inputs (P3).
+template <int STOP, int BIAS = 0, int SETTLE = SETTLE_REMAINDER, int GUARDS = GUARDS_CHECKED>
 ABR_HD bool chain(double &x_io, double c, double thr, int32_t n, int32_t &a_out) {
     ChainState cs;
     cs.x = x_io; cs.eb = -1;
     int32_t a = 0;
     bool hit = false;
-    while (a < n && !hit) a += chain_segment<STOP, BIAS, SETTLE>(cs, c, thr, n - a, hit);
+    while (a < n && !hit) a += chain_segment<STOP, BIAS, SETTLE, GUARDS>(cs, c, thr, n - a, hit);
     x_io = cs.x;
     a_out = a;
     return hit;

@@ -91,6 +91,7 @@ template <>
 struct TablesT<true> {
     static constexpr bool kSpeeds = true;
     static constexpr int kSettle = SETTLE_REMAINDER;   // how the chains settle a jump (abr_exact_jump.h: SettleKind)
+    static constexpr int kGuards = GUARDS_CHECKED;     // who establishes the segments' guards (abr_exact_jump.h: GuardKind)
     const double *G;               // G[n] = dt added n times to 0.0 (global_time, download_time, ...)
     const int32_t *interval_tick;  // first tick k with int(G[k]/interval) >= j          (:158)
     const int32_t *avail_tick;     // first tick k with int(G[k]/chunk_length) - 1 >= c  (:143)
@@ -116,6 +117,9 @@ template <>
 struct TablesT<false> {
     static constexpr bool kSpeeds = false;
     static constexpr int kSettle = SETTLE_REMAINDER;
+    // The chains of these tables run without their per-segment guards: whoever fills one in for a handle has checked
+    // chains_proven() for it (below); a handle that fails runs the TablesT<true> instances, which accept the no-speed case.
+    static constexpr int kGuards = GUARDS_PROVEN;
     const double *G;
     const int32_t *interval_tick;
     const int32_t *avail_tick;
@@ -136,6 +140,40 @@ using Tables = TablesT<true>;
 struct TablesCandidates : TablesT<true> {
     static constexpr int kSettle = SETTLE_CANDIDATES;
 };
+
+// The no-speeds table with the checked chains: for code that runs on ANY handle and has no TablesT<true> form to fall back
+// to (the tree walks of lookahead_kernel and plan_kernel).
+struct TablesChecked : TablesT<false> {
+    static constexpr int kGuards = GUARDS_CHECKED;
+};
+
+// The handle's side of GUARDS_PROVEN (abr_exact_jump.h: P1-P3), checked ONCE on the host where the tick tables are built.
+// With it, every chain loop of the lane functions hands chain_segment a budget in 1..kJumpCap:
+//   * lanej_drain, lanej_wait_call, lanej_predict_next_call: budgets are tick counts of one episode, m <= max_ticks, and
+//     the loops run while `a < m` (chain(), drain_to_zero), so each segment's budget m - a is in 1..max_ticks;
+//   * lanej_download: the loop runs while kk < mt and hands over ke - kk, where ke = min(end of the cursor's interval, mt).
+//     kk <= ke always (a segment performs at most its budget), and when kk == ke the trip first moves to the next interval,
+//     whose end is strictly later because every interval up to the sentinel spans at least one tick: 1 <= ke - kk; and
+//     ke - kk <= mt - 0.
+// So: max_ticks <= kJumpCap, and interval_tick strictly increasing up to its first sentinel (the spans then are below
+// 2^20 as well; the test is kept because it is what the download loop's argument reads).  P3 (finite values) for what the
+// handle itself contributes: chunk_length, sd, max_buffer and ladder x chunk_length finite and below 2^960 -- buffer_level
+// stays below max_buffer + chunk_length, downloaded_size below target + one tick's bytes; trace samples and a per-chunk
+// bitrate table are the caller's finite inputs.
+inline bool chains_proven(const int32_t *interval_tick, size_t n_interval_tick, int32_t max_ticks, double sd,
+                          double chunk_length, double max_buffer, const double *ladder, int32_t n_rates) {
+    if (max_ticks < 1 || max_ticks > kJumpCap) return false;
+    for (size_t j = 0; j + 1 < n_interval_tick && interval_tick[j] != 0x7fffffff; j++) {
+        if (interval_tick[j + 1] == 0x7fffffff) break;
+        const int64_t span = (int64_t)interval_tick[j + 1] - interval_tick[j];
+        if (span < 1 || span >= kJumpCap) return false;
+    }
+    const auto bounded = [](double v) { return v == v && v > -0x1p960 && v < 0x1p960; };
+    if (!bounded(sd) || !bounded(chunk_length) || !bounded(max_buffer)) return false;
+    for (int32_t r = 0; r < n_rates; r++)
+        if (!bounded(ladder[r] * chunk_length)) return false;
+    return true;
+}
 
 // Where a lane is in its bandwidth trace.  Only the download side (phase A) reads it.
 struct Cursor {
@@ -195,7 +233,7 @@ ABR_HD void lanej_play(LaneJ &s, const TB &t, int32_t a) {
     int32_t done = 0;
     double x = s.pt;
     // an unreachable threshold: the chain only counts
-    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, 1.0e300, a, done);
+    chain<STOP_GE, 0, TB::kSettle, TB::kGuards>(x, s.sd, 1.0e300, a, done);
     s.pt = x;
 }
 
@@ -212,14 +250,14 @@ ABR_HD void lanej_play(LaneJ &s, const TB &t, int32_t a) {
 // a whole number exactly when it matters, and which side of zero the k-th result falls on is decided by the roundings
 // themselves.  Built and measured in round 5, profiles/r05_experiments_not_kept.txt.)
 constexpr int kDrainTail = ABR_K_DRAIN_TAIL;
-template <int SETTLE = SETTLE_REMAINDER>
+template <int SETTLE = SETTLE_REMAINDER, int GUARDS = GUARDS_CHECKED>
 ABR_HD bool drain_to_zero(double &b_io, double sd, int32_t m, int32_t &a_out) {
     ChainState cs;
     cs.x = b_io; cs.eb = -1;
     const double tail = (double)kDrainTail * sd;
     int32_t a = 0;
     bool below = false;
-    while (a < m && !below) a += chain_segment<STOP_LE, 0, SETTLE>(cs, -sd, tail, m - a, below);
+    while (a < m && !below) a += chain_segment<STOP_LE, 0, SETTLE, GUARDS>(cs, -sd, tail, m - a, below);
     double b = cs.x;
     ABR_STAMP(24);
 #ifdef ABR_DRAIN_HOOK
@@ -248,7 +286,7 @@ ABR_HD bool lanej_drain(const TB &t, double &b_io, double sd, int32_t m, int32_t
         ABR_STAMP(24);
         return zero;
     }
-    return drain_to_zero<TB::kSettle>(b_io, sd, m, a_out);
+    return drain_to_zero<TB::kSettle, TB::kGuards>(b_io, sd, m, a_out);
 }
 
 // ---- speed schedule: the play speed changes at played-chunk boundaries ----
@@ -278,7 +316,7 @@ ABR_HD void sched_begin_chunk(LaneJ &s, const TB &t, int32_t k, double b) {
     s.sd = v * kTickDt;                                                      // play_speed * dt (:182)
     double x = 0.0;
     int32_t a = 0;
-    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, t.L, t.max_ticks + 1, a);
+    chain<STOP_GE, 0, TB::kSettle, TB::kGuards>(x, s.sd, t.L, t.max_ticks + 1, a);
     s.pl_left = a > 0 ? a : 1;
 }
 
@@ -290,7 +328,7 @@ ABR_HD void sched_played(LaneJ &s, const TB &t, int32_t a) {
     s.pt_sum += (double)a * s.pt + s.sd * (double)(((long long)a * (a - 1)) / 2);
     int32_t done = 0;
     double x = s.pt;
-    chain<STOP_GE, 0, TB::kSettle>(x, s.sd, 1.0e300, a, done);
+    chain<STOP_GE, 0, TB::kSettle, TB::kGuards>(x, s.sd, 1.0e300, a, done);
     s.pt = x;
     s.pl_left -= a;
     if (s.pl_left == 0) s.play_id++;                                       // :185-187
@@ -306,8 +344,8 @@ ABR_HD bool sched_drain(LaneJ &s, const TB &t, double &b, double thr, int32_t m,
         if (s.pl_left == 0) sched_begin_chunk(s, t, s.k + a_tot, b);
         const int32_t run = (m - a_tot < s.pl_left) ? m - a_tot : s.pl_left;
         int32_t a = 0;
-        if (STOP == STOP_LE) hit = drain_to_zero<TB::kSettle>(b, s.sd, run, a);
-        else hit = chain<STOP_LT, 0, TB::kSettle>(b, -s.sd, thr, run, a);
+        if (STOP == STOP_LE) hit = drain_to_zero<TB::kSettle, TB::kGuards>(b, s.sd, run, a);
+        else hit = chain<STOP_LT, 0, TB::kSettle, TB::kGuards>(b, -s.sd, thr, run, a);
         sched_played(s, t, a);
         a_tot += a;
     }
@@ -371,9 +409,9 @@ ABR_HD bool lanej_wait_call(LaneJ &s, const TB &t) {
         bool cleared;
         if constexpr (TB::kSpeeds) {
             if (t.speed_rows >= 2) cleared = sched_drain<STOP_LT>(s, t, b, t.max_buffer, mt - s.k, a);
-            else { cleared = chain<STOP_LT, 0, TB::kSettle>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
+            else { cleared = chain<STOP_LT, 0, TB::kSettle, TB::kGuards>(b, -s.sd, t.max_buffer, mt - s.k, a); lanej_play(s, t, a); }
         } else {
-            cleared = chain<STOP_LT, 0, TB::kSettle>(b, -t.sd, t.max_buffer, mt - s.k, a);
+            cleared = chain<STOP_LT, 0, TB::kSettle, TB::kGuards>(b, -t.sd, t.max_buffer, mt - s.k, a);
         }
         s.n_play += a;
         s.sumk += (long long)a * s.k + ((long long)a * (a - 1)) / 2;
@@ -579,7 +617,7 @@ ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int3
         tn = (s.tpos + 1 == s.tlen) ? 0 : s.tpos + 1;
         bw_next = s.trace[(uint32_t)tn];
         ke_next = t.interval_tick[(uint32_t)(s.j + 2)];
-        kk += chain_segment<STOP_GE, 0, TB::kSettle>(cs, c, target, ke - kk, hit);                // :160-163
+        kk += chain_segment<STOP_GE, 0, TB::kSettle, TB::kGuards>(cs, c, target, ke - kk, hit);                // :160-163
     }
     Download d;
     d.dl = cs.x; d.n_dl = kk - k; d.hit = hit;
@@ -684,7 +722,7 @@ ABR_HD bool lanej_predict_next_call(double buf, int32_t k, int32_t n_dl, int32_t
         if (k >= mt) return false;
         if (bf) {
             a = 0;
-            if (!chain<STOP_LT, 0, TB::kSettle>(b, -t.sd, t.max_buffer, mt - k, a)) return false;
+            if (!chain<STOP_LT, 0, TB::kSettle, TB::kGuards>(b, -t.sd, t.max_buffer, mt - k, a)) return false;
             k += a;
             if (b <= 0.0) return false;
         }

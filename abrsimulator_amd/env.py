@@ -474,6 +474,15 @@ class BatchedABREnv:
         self._check(self.lib.abr_env_get_effective_impl(self._h, int(bool(fused)), C.byref(v)))
         return {0: "jump", 1: "tick", 2: "split", 4: "async", 5: "split3", 6: "ring3", 7: "pair3"}[v.value]
 
+    def general_instance(self, fused: bool = False) -> bool:
+        """True while the handle's step launches run the kernels' general instances (the per-lane play-speed code, chains
+        that test their guards in every segment) and not the slimmer no-speeds ones: a latched speed feature, an episode
+        sampler, a quality model, or a configuration that fails the host's proof for the unguarded chains -- a trace
+        interval shorter than one 0.01 s tick, max_ticks above 2^20 (include/abr_env.h: abr_env_get_effective_impl)."""
+        v = C.c_int32()
+        self._check(self.lib.abr_env_get_effective_impl(self._h, int(bool(fused)) | 2, C.byref(v)))
+        return bool(v.value & 0x100)
+
     def step_mpc(self, controller, n_steps: int, out=None, want_obs=True, want_actions=True):
         """n_steps decisions per lane taken by `controller` (a BatchedMPCController whose
         tables match this environment) on the device: next_bitrate() on each lane's own

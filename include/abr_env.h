@@ -251,7 +251,11 @@ int abr_env_has_impl(int32_t impl);
 
 /* The implementation (0, 1, 2 or 5; never 3) the handle resolves to right now: fused != 0 for
  * abr_env_step_random / abr_env_step_script with more than one decision per call, 0 for launches of
- * one decision (abr_env_step, abr_env_step_mpc, n_steps == 1). */
+ * one decision (abr_env_step, abr_env_step_mpc, n_steps == 1).  `fused` is 0 or 1; with 2 added to it, 0x100 is added to
+ * the answer when the handle's step launches run the kernels' general instances (the form with the per-lane play-speed code
+ * and the per-segment chain guards) and not the slimmer no-speeds ones: while a speed feature is latched, a sampler or a
+ * quality model is installed, or the configuration fails the host's proof for the unguarded chains (a trace interval
+ * shorter than one 0.01 s tick, max_ticks above 2^20, a non-finite or absurd ladder x chunk_length, speed or max_buffer). */
 int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out);
 
 /*
@@ -1453,7 +1457,9 @@ int abr_mpc_objective_grid(const abr_mpc_config *cfg, int32_t chunk, int32_t pre
  * the float64 sequences of Simulator.py:160-163 and :184,:190-194 -- advanced by the kernels'
  * exact closed form (csrc/abr_exact_jump.h) on the device.  estimate_bias 0 is the product
  * path; +4 / -4 spoil the jump-length estimate so that the exact fallback search runs.
- * Outputs per case: final x, additions performed, 1 if it stopped on the predicate. */
+ * Outputs per case: final x, additions performed, 1 if it stopped on the predicate.
+ * stop_kind + 0x100 runs the form of the chains that the no-speeds kernel instances use, which tests no guard per segment
+ * (abr_exact_jump.h: GUARDS_PROVEN); every n must then be in 1..2^20 and every x0, c, thr finite (not checked). */
 int abr_debug_chain(int32_t stop_kind, int32_t estimate_bias, const double *x0_dev,
                     const double *c_dev, const double *thr_dev, const int32_t *n_dev, int64_t count,
                     double *x_out_dev, int32_t *a_out_dev, uint8_t *hit_out_dev, void *stream);

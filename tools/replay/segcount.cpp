@@ -40,10 +40,10 @@ extern "C" int seg_episode(double interval, double L, int32_t V, double max_buff
         tt = abrx::build_tick_tables(interval, L, 1.0, V, max_ticks, (int32_t)(max_ticks * 0.01 / interval + 4.0));
         have = true;
     }
-    abrx::Tables t;
+    abrx::TablesT<false> t;              // the tables of the bench's launch: no play-speed features (their chains: kGuards)
     t.G = tt.G.data(); t.interval_tick = tt.interval_tick.data(); t.avail_tick = tt.avail_tick.data();
     t.L = L; t.sd = tt.sd; t.max_buffer = max_buffer; t.start_up_length = start_up; t.V = V;
-    t.max_ticks = max_ticks; t.per_lane_speed = false; t.speed_rows = 0; t.speed_stride = 0; t.speeds = nullptr;
+    t.max_ticks = max_ticks;
     abrx::LaneJ s;
     s.cur.trace = trace; s.cur.tlen = tlen; s.sd = t.sd;
     abrx::lanej_init(s, t, offset);
