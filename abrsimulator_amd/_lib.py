@@ -214,6 +214,7 @@ SYMBOLS = [
     ("abr_env_has_impl", C.c_int, [C.c_int32]),
     ("abr_env_set_lane_speeds", C.c_int, [_P, _P]),
     ("abr_env_set_bitrate_table", C.c_int, [_P, _P]),
+    ("abr_env_set_size_table", C.c_int, [_P, _P]),
     ("abr_env_set_speed_schedule", C.c_int, [_P, _P, C.c_int32]),
     ("abr_env_set_speed_rule", C.c_int, [_P, C.POINTER(SpeedRule), _P, C.c_int32]),
     ("abr_env_set_episode_sampler", C.c_int, [_P, C.POINTER(EpisodeSampler)]),

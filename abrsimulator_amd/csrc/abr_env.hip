@@ -137,9 +137,12 @@ struct EnvParams {
     // sd_lane -- non-null, so that every "per-lane speeds" test holds, and never read as speeds.  The kernels read this
     // block from the kernarg segment only when a played chunk begins (abr_lane_jump.h: sched_begin_chunk).
     abrx::SpeedRuleBlock speed_rule;
+    // abr_env_set_size_table (appended likewise: 880 -> 888 bytes): caller-owned [video_length][n_rates] sizes of what is
+    // DOWNLOADED, or nullptr: bitrate x chunk_length.  Read by chunk_target, chunk_next_size, rule_action and the walks' sz.
+    const double *sz_table;
 };
 static_assert(offsetof(EnvParams, speed_rule) == ABR_RULE_KERNARG_OFFSET, "abr_lane_jump.h reads the rule at this offset");
-static_assert(sizeof(EnvParams) == 880, "the parameter block: 592 bytes + 288 of the speed rule");
+static_assert(sizeof(EnvParams) == 888, "the parameter block: 592 bytes + 288 of the speed rule + the size table");
 static_assert(sizeof(abrx::SpeedRule) == sizeof(abr_speed_rule) &&
               offsetof(abrx::SpeedRule, lat_thr) == offsetof(abr_speed_rule, lat_thr) &&
               offsetof(abrx::SpeedRule, buf_thr) == offsetof(abr_speed_rule, buf_thr) &&
@@ -195,6 +198,8 @@ struct abr_env {
     bool speeds_dirty;
     const double *pending_br_table; // abr_env_set_bitrate_table: latched the same way
     bool br_table_dirty;
+    const double *pending_sz_table; // abr_env_set_size_table: likewise
+    bool sz_table_dirty;
     bool armed;                     // abr_env_reset has run at least once: episodes may be in flight
     bool sampler_on;                // abr_env_set_episode_sampler: launches run the SAMPLE instances with `sampler`
     abrx::EpisodeSampler sampler;
@@ -208,6 +213,7 @@ struct abr_env {
 // (a freshly built handle that receives a checkpointed workspace must already carry them).
 static void apply_pending(abr_env *env) {
     if (env->br_table_dirty) { env->p.br_table = env->pending_br_table; env->br_table_dirty = false; }
+    if (env->sz_table_dirty) { env->p.sz_table = env->pending_sz_table; env->sz_table_dirty = false; }
     if (env->speeds_dirty) {
         env->p.lane_speeds = env->pending_speeds; env->p.speed_rows = env->pending_speed_rows;
         env->p.speed_rule = env->pending_rule;
@@ -220,6 +226,21 @@ static void apply_pending(abr_env *env) {
 // the evident intent of set_mpd's one-ladder-per-line file (Simulator.py:71-76) -- chunk's own
 __device__ inline double chunk_bitrate(const EnvParams &p, int32_t chunk, int32_t rate) {
     return p.br_table ? p.br_table[(int64_t)chunk * p.n_rates + rate] : p.ladder[rate];
+}
+
+// target_size of chunk's download at `rate` (Simulator.py:156: bitrate x chunk_length), or -- while a size table is in
+// force (include/abr_env.h: abr_env_set_size_table) -- the table's entry.  SIZED == false is the form of the no-speeds
+// instances, which a handle with a size table never launches (launch_env): they hold no test of the pointer.
+template <bool SIZED>
+__device__ __forceinline__ double chunk_target(const EnvParams &p, int32_t chunk, int32_t rate) {
+    if constexpr (SIZED) {
+        if (p.sz_table) return p.sz_table[(int64_t)chunk * p.n_rates + rate];
+    }
+    return chunk_bitrate(p, chunk, rate) * p.chunk_length;
+}
+// what the learned policy's features 4 + W + m hold: chunk's bitrates, or under a size table its sizes (next_chunk_sizes)
+__device__ __forceinline__ double chunk_next_size(const EnvParams &p, int32_t chunk, int32_t rate) {
+    return p.sz_table ? p.sz_table[(int64_t)chunk * p.n_rates + rate] : chunk_bitrate(p, chunk, rate);
 }
 
 // ---------------------------------------------------------------------------
@@ -381,10 +402,20 @@ __device__ inline void write_obs(const Lane &s, const EnvParams &p, int64_t i, f
 // MODE 4's action: a standard bitrate rule (abr_lane_jump.h: rule_select) on the lane's call-site state -- chunk_id,
 // buffer_level, and previous_bandwidths read back from the lane's bw_hist rows (coalesced: row stride n_lanes; the rows
 // of this launch's earlier decisions are the lane's own stores); FastMPC also reads previous_bitrates[-1] (pv)
+// Under a size table RATE and BOLA read the effective bitrates (abr_lane_jump.h: rule_cost).  SIZED: as chunk_target.
+template <bool SIZED = true>
 __device__ inline int32_t rule_action(const EnvParams &p, const abrx::RuleParams &rule, int64_t i, int32_t c, int32_t pv,
                                       double B) {
-    const auto br = [&](int32_t m) { return chunk_bitrate(p, c, m); };
     const auto hist = [&](int32_t j) { return p.bw_hist[(int64_t)j * p.n_lanes + i]; };
+    if constexpr (SIZED) {
+        // a branch of its own around the whole rule, so that the unsized path's accessor stays the plain one
+        if (p.sz_table && abrx::rule_reads_cost(rule.kind)) {
+            const double *row = p.sz_table + (int64_t)c * p.n_rates;
+            const auto e = [&](int32_t m) { return abrx::rule_cost(row, p.chunk_length, m); };
+            return abrx::rule_select_at(rule, e, hist, p.n_rates, p.video_length, c, pv, B);
+        }
+    }
+    const auto br = [&](int32_t m) { return chunk_bitrate(p, c, m); };
     return abrx::rule_select_at(rule, br, hist, p.n_rates, p.video_length, c, pv, B);
 }
 
@@ -602,7 +633,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                 int32_t a;
                 if (MODE == 1) a = actions[i];
                 else if (MODE == 3) a = actions[(int64_t)step_idx * p.n_lanes + i];
-                else if (MODE == 4) a = rule_action(p, rule, i, s.chunk_id, s.last_action, s.buf);
+                else if (MODE == 4) a = rule_action<true>(p, rule, i, s.chunk_id, s.last_action, s.buf);
                 else a = (int32_t)philox_action(seed, (uint64_t)(p.lane_id_base + i),
                                                 (uint32_t)s.chunk_id, (uint32_t)episode_no,
                                                 (uint32_t)p.n_rates);
@@ -619,7 +650,7 @@ __global__ __launch_bounds__(64) void env_advance_kernel(
                 } else {
                     prev_action = s.last_action;
                     s.cur_action = a;
-                    s.target = chunk_bitrate(p, s.chunk_id, a) * L;   // :156
+                    s.target = chunk_target<true>(p, s.chunk_id, a);   // :156 (the kernel's one form: the pointer is tested)
                     s.dl = 0.0; s.n_dl = 0; s.done_dl = false;
                     s.avail_next = p.avail_tick[s.chunk_id + 1];
                     s.running = true;          // T4 of this very tick comes next
@@ -923,7 +954,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
             if (active) {
                 // MODE 4: the rule runs BEFORE the step's burst of loads, so that its loops do not hold the burst's
                 // registers live (it decides chunk_id's download: nothing of the step is needed)
-                const int32_t a_rule = (MODE == 4) ? rule_action(p, rule, i, s.chunk_id, s.last_action, s.buf) : 0;
+                const int32_t a_rule = (MODE == 4) ? rule_action<SPEEDS>(p, rule, i, s.chunk_id, s.last_action, s.buf) : 0;
                 // one burst of loads for everything the step needs (issued before the
                 // policy arithmetic so that the two overlap)
                 const abrx::StepStart st = abrx::lanej_begin_step(s.cur, tb, s.k, s.chunk_id);
@@ -946,7 +977,7 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
                     const int32_t prev_action = s.last_action;
                     const int32_t chunk = s.chunk_id;
                     const abrx::StepResult r = abrx::lanej_download_and_wait(
-                        s, tb, st, chunk_bitrate(p, chunk, a) * p.chunk_length /* :156 */, a);
+                        s, tb, st, chunk_target<SPEEDS>(p, chunk, a) /* :156 */, a);
                     // the reward's two clocks and the observation's four tick-table values in ONE burst of loads
                     const double g_rb = p.G[s.n_rb], g_su = p.G[s.n_su];
                     double o_k = p.G[s.k], o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
@@ -1454,6 +1485,15 @@ extern "C" int abr_env_set_bitrate_table(abr_env *env, const double *br_table_de
     return ABR_OK;
 }
 
+// per-chunk sizes [video_length][n_rates] of what is downloaded (include/abr_env.h); nullptr restores bitrate x chunk_length
+extern "C" int abr_env_set_size_table(abr_env *env, const double *sz_table_dev) {
+    if (!env) return fail(ABR_E_INVALID, "env is NULL");
+    env->pending_sz_table = sz_table_dev;
+    env->sz_table_dirty = true;
+    if (!env->armed) apply_pending(env);
+    return ABR_OK;
+}
+
 // the caller has copied a checkpointed workspace into this handle's workspace: episodes are in flight.  The copy must be what
 // this handle's abr_env_create would have laid out: the tag in its last 256 bytes says so (read back here: this call
 // synchronises the device, once per restore).
@@ -1696,6 +1736,8 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
         return fail(ABR_E_UNSUPPORTED, "the episode ledger runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
     if (env->quality.base && impl != 0 && impl != 1 && impl != 2 && impl != 5)
         return fail(ABR_E_UNSUPPORTED, "the quality model runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
+    if (env->p.sz_table && impl != 0 && impl != 1 && impl != 2 && impl != 5)
+        return fail(ABR_E_UNSUPPORTED, "a size table runs on impl 0, 1, 2, 3 and 5, not on the diagnostic impl %d", impl);
     (void)N;
 #ifdef ABR_WITH_ASYNC
     if constexpr (MODE == 2 || MODE == 3) {
@@ -1722,7 +1764,8 @@ static int launch_env(const abr_env *env, int impl, hipStream_t st, const int32_
     // speeds are latched at a full reset (apply_pending), so the handle knows at every launch whether any lane has one
     // ... and a handle whose tables fail the chains' proof (an interval shorter than a tick, more than 2^20 ticks: abr_lane_jump.h,
     // chains_proven) runs the SPEEDS form as well: it accepts the no-speed case, and its chains test their guards per segment
-    const bool speeds_on = env->p.lane_speeds != nullptr || !env->chains_proven;
+    // ... and a handle with a size table (abr_env_set_size_table): the lookup lives in the SPEEDS form only (chunk_target)
+    const bool speeds_on = env->p.lane_speeds != nullptr || !env->chains_proven || env->p.sz_table != nullptr;
     // (never with the tick kernel: the speed setters and abr_env_set_impl refuse that pair, kFeatures)
     const auto go = [&](auto smp_on, auto led_on, auto ql_on) {
         // The no-speeds instances exist for handles WITHOUT an episode sampler.  With the sampler's draw in them, four of
@@ -1806,6 +1849,9 @@ extern "C" int abr_env_reset(abr_env *env, const int32_t *trace_id_dev,
         return fail(ABR_E_INVALID, "a sampled reset (trace_id_dev NULL) takes no start_offset_dev");
     if (env->br_table_dirty && lane_mask_dev)
         return fail(ABR_E_INVALID, "abr_env_set_bitrate_table takes effect at a reset of ALL lanes "
+                    "(lane_mask_dev must be NULL for the first reset after it)");
+    if (env->sz_table_dirty && lane_mask_dev)
+        return fail(ABR_E_INVALID, "abr_env_set_size_table takes effect at a reset of ALL lanes "
                     "(lane_mask_dev must be NULL for the first reset after it)");
     if (env->speeds_dirty && lane_mask_dev)
         return fail(ABR_E_INVALID, "abr_env_set_lane_speeds takes effect at a reset of ALL lanes "
@@ -1891,7 +1937,7 @@ extern "C" int abr_env_step_rule(abr_env *env, const abr_rule_config *rule, int3
 __global__ __launch_bounds__(256) void rule_select_kernel(EnvParams p, abrx::RuleParams rule, int32_t *__restrict__ action_out) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= p.n_lanes) return;
-    action_out[i] = p.done[i] ? -1 : rule_action(p, rule, i, p.chunk_id[i], p.last_action[i], p.buf[i]);
+    action_out[i] = p.done[i] ? -1 : rule_action<true>(p, rule, i, p.chunk_id[i], p.last_action[i], p.buf[i]);
 }
 
 static int launch_rule_select(const abr_env *env, const abrx::RuleParams &rp, int32_t *action_out_dev, void *stream) {
@@ -1913,8 +1959,11 @@ extern "C" int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *
     if (!env || !impl_out) return fail(ABR_E_INVALID, "NULL argument");
     *impl_out = effective_impl(env, (fused & 1) != 0);
     // bit 1 of `fused` asks for the instance as well: 0x100 is added when a step launch runs the SPEEDS == true form
-    // (launch_env: a latched speed feature, a sampler, a quality model, or tables that fail the chains' proof)
-    if ((fused & 2) && (env->p.lane_speeds || !env->chains_proven || env->sampler_on || env->quality.base)) *impl_out |= 0x100;
+    // (launch_env: a latched speed feature, a sampler, a quality model, tables that fail the chains' proof, or a size table
+    // in force or pending)
+    const bool sized = env->p.sz_table || (env->sz_table_dirty && env->pending_sz_table);
+    if ((fused & 2) && (env->p.lane_speeds || !env->chains_proven || env->sampler_on || env->quality.base || sized))
+        *impl_out |= 0x100;
     return ABR_OK;
 }
 
@@ -2091,7 +2140,11 @@ static_assert(look_max_rates(1) == 16 && look_max_rates(4) == 16 && look_max_rat
 
 constexpr int look_waves(int H, int W) { return W < look_max_rates(H) ? W : look_max_rates(H); }
 
-template <int H, int W>
+// SIZED: the instance that runs while a size table is in force (abr_env_set_size_table): a step's target is the table's
+// entry.  An instance of its own, as the quality model's are in the env kernels: with a run-time test of the pointer in
+// the one form, nine of the walks' instances gained 12-40 B of scratch per lane and plan_kernel<2> lost a wave of
+// occupancy (profiles/chunk_sizes_resources.txt); the <false> instances hold no trace of the table.
+template <int H, int W, bool SIZED>
 __global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
     EnvParams p, abrx::EpisodeQuality ql, int64_t lane0, int64_t lane_end, int32_t *__restrict__ action_out,
     double *__restrict__ key_out, double *__restrict__ q_out) {
@@ -2113,11 +2166,16 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
     abrx::LookWeights w;
     w.wr = p.wr; w.ws = p.ws; w.wv = p.wv; w.wl = p.wl; w.M = p.n_rates; w.quality = ql.base != nullptr;
     const auto br = [&](int32_t chunk, int32_t rate) { return chunk_bitrate(p, chunk, rate); };
+    // the step's target: the size table's entry (abr_env_set_size_table), else rate x chunk_length
+    const auto sz = [&](int32_t chunk, int32_t a, double rate) {
+        if constexpr (SIZED) return p.sz_table[(int64_t)chunk * p.n_rates + a];
+        else return rate * tb.L;
+    };
     const auto G = [&](int32_t n) { return p.G[n]; };
     const auto lat = [&](const LaneJ &x) { return lane_avg_latency(p, x.sumk, x.n_play); };
     const auto qt = [&](int32_t chunk, int32_t rate) { return abrx::quality_peek(ql, p.n_rates, chunk, rate); };
     const auto any = [](bool f) { return __any(f) != 0; };
-    const double q = abrx::look_subtree<H>(w, tb, br, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
+    const double q = abrx::look_subtree<H>(w, tb, br, sz, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
     s_q[m][l] = q;
     if (q_out && i < lane_end) ABR_OUT(q_out[(int64_t)m * p.n_lanes + i], q);
     __syncthreads();
@@ -2130,7 +2188,8 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void lookahead_kernel(
     }
 }
 
-struct LookaheadKernels { template <int H, int W> static constexpr auto kernel = lookahead_kernel<H, W>; };
+template <bool SIZED>
+struct LookaheadKernels { template <int H, int W> static constexpr auto kernel = lookahead_kernel<H, W, SIZED>; };
 
 // One launch of horizon H's instance of a kernel family on lanes [lane0, lane_end); `tail`: the kernel's arguments behind them.
 template <class Kernels, int H, class... Tail>
@@ -2198,8 +2257,12 @@ extern "C" int abr_env_lookahead_select(abr_env *env, const abr_lookahead_config
     if (rc) return rc;
     if (!env) return fail(ABR_E_INVALID, "env is NULL");
     if ((rc = look_supported(env, cfg->horizon, "lookahead"))) return rc;
-    return launch_walks<LookaheadKernels>(env, cfg->horizon, cfg->max_nodes_per_launch, (hipStream_t)stream, action_out_dev,
-                                          key_out_dev, q_out_dev);
+    const hipStream_t st = (hipStream_t)stream;
+    if (env->p.sz_table)
+        return launch_walks<LookaheadKernels<true>>(env, cfg->horizon, cfg->max_nodes_per_launch, st, action_out_dev,
+                                                    key_out_dev, q_out_dev);
+    return launch_walks<LookaheadKernels<false>>(env, cfg->horizon, cfg->max_nodes_per_launch, st, action_out_dev, key_out_dev,
+                                                 q_out_dev);
 }
 
 #ifdef ABR_SPLIT_STAMPS
@@ -3108,7 +3171,7 @@ __global__ __launch_bounds__(256) void plan_forecast_kernel(EnvParams p, int32_t
 // lookahead_kernel with the cursor replaced at the root: lane i's trace is the one sample P[i].  A kernel of its own around
 // the shared look_subtree, so that the lookahead's instances stay what they are (profiles/plan_isa_diff.txt).  A P that
 // is not finite or not > 0 is "no decision"; forecast_out (nullable) receives the P the walk used, else 0.0.
-template <int H, int W>
+template <int H, int W, bool SIZED>
 __global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
     EnvParams p, abrx::EpisodeQuality ql, int64_t lane0, int64_t lane_end, const double *__restrict__ P, int32_t neg_to_zero,
     int32_t *__restrict__ action_out, double *__restrict__ key_out, double *__restrict__ q_out,
@@ -3134,11 +3197,16 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
     abrx::LookWeights w;
     w.wr = p.wr; w.ws = p.ws; w.wv = p.wv; w.wl = p.wl; w.M = p.n_rates; w.quality = ql.base != nullptr;
     const auto br = [&](int32_t chunk, int32_t rate) { return chunk_bitrate(p, chunk, rate); };
+    // the step's target: the size table's entry (abr_env_set_size_table), else rate x chunk_length
+    const auto sz = [&](int32_t chunk, int32_t a, double rate) {
+        if constexpr (SIZED) return p.sz_table[(int64_t)chunk * p.n_rates + a];
+        else return rate * tb.L;
+    };
     const auto G = [&](int32_t n) { return p.G[n]; };
     const auto lat = [&](const LaneJ &x) { return lane_avg_latency(p, x.sumk, x.n_play); };
     const auto qt = [&](int32_t chunk, int32_t rate) { return abrx::quality_peek(ql, p.n_rates, chunk, rate); };
     const auto any = [](bool fl) { return __any(fl) != 0; };
-    const double q = abrx::look_subtree<H>(w, tb, br, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
+    const double q = abrx::look_subtree<H>(w, tb, br, sz, G, lat, qt, any, s, live, n_rb_obs, n_su_obs, m);
     s_q[m][l] = q;
     if (q_out && i < lane_end) ABR_OUT(q_out[(int64_t)m * p.n_lanes + i], q);
     __syncthreads();
@@ -3152,7 +3220,8 @@ __global__ __launch_bounds__(64 * look_waves(H, W)) void plan_kernel(
     }
 }
 
-struct PlanKernels { template <int H, int W> static constexpr auto kernel = plan_kernel<H, W>; };
+template <bool SIZED>
+struct PlanKernels { template <int H, int W> static constexpr auto kernel = plan_kernel<H, W, SIZED>; };
 
 struct PlanOut {
     int32_t *action;
@@ -3170,8 +3239,11 @@ static int plan_decide(const abr_env *env, const abr_plan_config *cfg, double *s
         P = scratch;
         if (o.forecast == scratch) o.forecast = nullptr;     // the forecast kernel has written the caller's copy already
     }
-    return launch_walks<PlanKernels>(env, cfg->horizon, cfg->max_nodes_per_launch, st, P, o.neg_to_zero, o.action, o.key, o.q,
-                                     o.forecast);
+    if (env->p.sz_table)
+        return launch_walks<PlanKernels<true>>(env, cfg->horizon, cfg->max_nodes_per_launch, st, P, o.neg_to_zero, o.action,
+                                               o.key, o.q, o.forecast);
+    return launch_walks<PlanKernels<false>>(env, cfg->horizon, cfg->max_nodes_per_launch, st, P, o.neg_to_zero, o.action, o.key,
+                                            o.q, o.forecast);
 }
 
 // The refusals of both entry points in the documented order; `select`: abr_env_plan_select (else abr_env_step_plan).
@@ -3515,8 +3587,8 @@ struct PolicyPopArgs : PolicyValueArgs {
     int32_t group, blob_words, head_words;
 };
 
-static_assert(sizeof(EnvParams) + sizeof(PolicyArgs) == 976 && sizeof(EnvParams) + sizeof(PolicyValueArgs) == 992 &&
-              sizeof(EnvParams) + sizeof(PolicyPopArgs) == 1008, "policy_select_kernel's kernarg segments");
+static_assert(sizeof(EnvParams) + sizeof(PolicyArgs) == 984 && sizeof(EnvParams) + sizeof(PolicyValueArgs) == 1000 &&
+              sizeof(EnvParams) + sizeof(PolicyPopArgs) == 1016, "policy_select_kernel's kernarg segments");
 
 // SAMPLED: the instance behind abr_env_policy_select_sampled.  It keeps each lane's scores in its own column of LDS past
 // the weights (M * kPolicyBlock floats; the score loops run to a runtime M), where the draw turns them into e_m.
@@ -3569,8 +3641,9 @@ __global__ __launch_bounds__(kPolicyBlock) void policy_select_kernel(
     const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
     const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
     const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+    const auto nx = [&](int32_t r, int32_t m) { return chunk_next_size(p, r, m); };
     float x[abrx::kPolicyMaxF];
-    abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    abrx::policy_features(n, hist, br, nx, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
     if (a.features_out) {
 #pragma unroll
         for (int f = 0; f < abrx::kPolicyMaxF; f++) {
@@ -3887,7 +3960,7 @@ __device__ __forceinline__ void mx_run_layer(const abrx::MxLayer &y, const float
 struct PolicyMxPopArgs : PolicyMxArgs {
     int32_t group, blob_words, head_words;
 };
-static_assert(sizeof(EnvParams) + sizeof(PolicyMxArgs) == 1008 && sizeof(EnvParams) + sizeof(PolicyMxPopArgs) == 1024,
+static_assert(sizeof(EnvParams) + sizeof(PolicyMxArgs) == 1016 && sizeof(EnvParams) + sizeof(PolicyMxPopArgs) == 1032,
               "policy_mx_kernel's kernarg segments");
 
 // POP: as policy_select_kernel's -- one scalar adjustment of the blob and head pointers, made once, before the first
@@ -3916,7 +3989,8 @@ __global__ __launch_bounds__(kMxBlock) void policy_mx_kernel(EnvParams p,
         const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
         const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
         const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
-        abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+        const auto nx = [&](int32_t r, int32_t m) { return chunk_next_size(p, r, m); };
+        abrx::policy_features(n, hist, br, nx, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
     } else {
 #pragma unroll
         for (int f = 0; f < abrx::kPolicyMaxF; f++) x[f] = 0.0f;
@@ -4121,7 +4195,7 @@ struct PolicyGruArgs {
 struct PolicyGruPopArgs : PolicyGruArgs {
     int32_t group, blob_words, head_words;
 };
-static_assert(sizeof(EnvParams) + sizeof(PolicyGruArgs) == 1016 && sizeof(EnvParams) + sizeof(PolicyGruPopArgs) == 1032,
+static_assert(sizeof(EnvParams) + sizeof(PolicyGruArgs) == 1024 && sizeof(EnvParams) + sizeof(PolicyGruPopArgs) == 1040,
               "the kernarg segments of policy_gru_kernel and policy_gru_mx_kernel");
 
 // POP: the instances behind abr_env_gru_select_pop / abr_env_gru_step_pop (abr_policy_pop), as policy_select_kernel's.  The
@@ -4196,8 +4270,9 @@ __global__ __launch_bounds__(kPolicyBlock, 2) void policy_gru_kernel(
     const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
     const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
     const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
+    const auto nx = [&](int32_t r, int32_t m) { return chunk_next_size(p, r, m); };
     float x[abrx::kPolicyMaxF];
-    abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+    abrx::policy_features(n, hist, br, nx, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
     if (a.features_out) {
 #pragma unroll
         for (int f = 0; f < abrx::kPolicyMaxF; f++) {
@@ -4341,7 +4416,8 @@ __global__ __launch_bounds__(kMxBlock) void policy_gru_mx_kernel(
         const double P = p.lane_speeds ? p.pt_lane[i] : p.GP[p.n_play[i]];   // play_time as abr_env_observe_f64
         const auto hist = [&](int32_t j) { return p.bw_hist[j * N + i]; };
         const auto br = [&](int32_t r, int32_t m) { return chunk_bitrate(p, r, m); };
-        abrx::policy_features(n, hist, br, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
+        const auto nx = [&](int32_t r, int32_t m) { return chunk_next_size(p, r, m); };
+        abrx::policy_features(n, hist, br, nx, p.video_length, c, p.last_action[i], p.buf[i], G, P, x);
     } else {
 #pragma unroll
         for (int f = 0; f < abrx::kPolicyMaxF; f++) x[f] = 0.0f;

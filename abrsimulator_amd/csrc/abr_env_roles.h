@@ -279,7 +279,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
         ABR_STAMP(2);
         if (a < 0 || a >= p.n_rates) flags |= kRecBadAct;
         else d = abrx::lanej_download(v.cur, tb, st, v.d_k,
-                                      chunk_bitrate(p, v.d_chunk, a) * p.chunk_length /* :156 */);
+                                      chunk_target<SPEEDS>(p, v.d_chunk, a) /* :156 */);
         ABR_STAMP(3);
         if (d.hit) flags |= kRecHit;
         m.dl[cb][l] = d.dl; m.n_dl[cb][l] = d.n_dl; m.k_start[cb][l] = v.d_k;

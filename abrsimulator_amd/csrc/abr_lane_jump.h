@@ -158,8 +158,9 @@ struct TablesChecked : TablesT<false> {
 // So: max_ticks <= kJumpCap, and interval_tick strictly increasing up to its first sentinel (the spans then are below
 // 2^20 as well; the test is kept because it is what the download loop's argument reads).  P3 (finite values) for what the
 // handle itself contributes: chunk_length, sd, max_buffer and ladder x chunk_length finite and below 2^960 -- buffer_level
-// stays below max_buffer + chunk_length, downloaded_size below target + one tick's bytes; trace samples and a per-chunk
-// bitrate table are the caller's finite inputs.
+// stays below max_buffer + chunk_length, downloaded_size below target + one tick's bytes; trace samples, a per-chunk
+// bitrate table and a size table (abr_env_set_size_table: finite, > 0 and below 2^960, never read on the host) are the
+// caller's finite inputs.  A handle with a size table runs the TablesT<true> instances in any case.
 inline bool chains_proven(const int32_t *interval_tick, size_t n_interval_tick, int32_t max_ticks, double sd,
                           double chunk_length, double max_buffer, const double *ladder, int32_t n_rates) {
     if (max_ticks < 1 || max_ticks > kJumpCap) return false;
@@ -860,6 +861,12 @@ ABR_HD int32_t fastmpc_lookup(const RuleParams &r, const HIST &hist, int32_t M, 
     return r.fm_table[(((int64_t)row * M + pv) * r.fm_nb + bi) * r.fm_nq + qi];
 }
 
+// Under the environment's size table (include/abr_env.h: abr_env_set_size_table) RATE and BOLA compare and divide by what
+// a rung costs to fetch: their br(m) is the effective bitrate e[m] = sz[c][m] / chunk_length, one float64 division.  BBA-0's
+// map lives on the nominal ladder, and FastMPC reads no br at all.
+ABR_HD bool rule_reads_cost(int32_t kind) { return kind == kRuleRate || kind == kRuleBola; }
+ABR_HD double rule_cost(const double *sz_row, double L, int32_t m) { return sz_row[m] / L; }
+
 // rule_select with the call-site arguments only FastMPC reads (V, the previous bitrate)
 template <class BR, class HIST>
 ABR_HD int32_t rule_select_at(const RuleParams &r, const BR &br, const HIST &hist, int32_t M, int32_t V, int32_t c,
@@ -964,9 +971,11 @@ ABR_HD void philox4(uint64_t seed, uint64_t lane, uint32_t step, uint32_t episod
 
 // The features of one lane at a call site: chunk c (0 <= c < V), buffer B, previous bitrate a, latency G - P,
 // h(j) = previous_bandwidths[j], br(r, m) = chunk r's bitrate m.  x[i] = (float)((raw_i - shift_i) * scale_i).
-template <class Hist, class Br>
-ABR_HD void policy_features(const PolicyNet &n, const Hist &h, const Br &br, int32_t V, int32_t c, int32_t a, double B,
-                            double G, double P, float x[kPolicyMaxF]) {
+// nx(r, m) = what features 4 + W + m hold of chunk r: its bitrates, or -- while the environment has a size table
+// (include/abr_env.h: abr_env_set_size_table) -- its sizes, Pensieve's next_chunk_sizes.
+template <class Hist, class Br, class Nx>
+ABR_HD void policy_features(const PolicyNet &n, const Hist &h, const Br &br, const Nx &nx, int32_t V, int32_t c, int32_t a,
+                            double B, double G, double P, float x[kPolicyMaxF]) {
     const int32_t W = n.window;
 #pragma unroll
     for (int i = 0; i < kPolicyMaxF; i++) {
@@ -977,13 +986,20 @@ ABR_HD void policy_features(const PolicyNet &n, const Hist &h, const Br &br, int
             else if (i == 2) raw = (double)(V - c);
             else if (i == 3) raw = G - P;
             else if (i < 4 + W) { const int32_t j = c - W + (i - 4); raw = j >= 0 ? h(j) : 0.0; }
-            else raw = br(c, i - 4 - W);
+            else raw = nx(c, i - 4 - W);
             const double sh = n.norm ? n.norm[i] : 0.0, sc = n.norm ? n.norm[n.F + i] : 1.0;
             x[i] = (float)((raw - sh) * sc);
         } else {
             x[i] = 0.0f;
         }
     }
+}
+
+// without a size table: features 4 + W + m are chunk c's bitrates
+template <class Hist, class Br>
+ABR_HD void policy_features(const PolicyNet &n, const Hist &h, const Br &br, int32_t V, int32_t c, int32_t a, double B,
+                            double G, double P, float x[kPolicyMaxF]) {
+    policy_features(n, h, br, br, V, c, a, B, G, P, x);
 }
 
 ABR_HD float relu_f32(float v) { return v > 0.0f ? v : 0.0f; }   // NaN and -0 -> +0
@@ -1994,14 +2010,17 @@ ABR_HD bool look_better(double key, double best) { return key == key && !(best <
 // of a lane state, qt(chunk, rate) = the weighted quality term, any(flag) = the flag in some lane of the wave (the host
 // harness: the flag itself).  Visits children in rate order and keeps the first least key: ties go to the
 // lexicographically smaller sequence.
-template <int LVL, int H, class TB, class BR, class GT, class LAT, class QT, class ANY>
-ABR_HD void look_visit(const LookWeights &w, const TB &t, const BR &br, const GT &G, const LAT &lat, const QT &qt,
-                       const ANY &any, const LookNode &par, int32_t n_rb_obs, int32_t n_su_obs, int32_t a, double &best) {
+// sz(chunk, a, rate) = the step's target_size, rate being br(chunk, a): rate * t.L, or the environment's size table's entry
+// (include/abr_env.h: abr_env_set_size_table), which decides what is downloaded while `rate` keeps deciding what is scored.
+template <int LVL, int H, class TB, class BR, class SZ, class GT, class LAT, class QT, class ANY>
+ABR_HD void look_visit(const LookWeights &w, const TB &t, const BR &br, const SZ &sz, const GT &G, const LAT &lat,
+                       const QT &qt, const ANY &any, const LookNode &par, int32_t n_rb_obs, int32_t n_su_obs, int32_t a,
+                       double &best) {
     LookNode c = par;
     if (c.live) {
         const int32_t prev = c.s.last_action, chunk = c.s.chunk_id;
         const double rate = br(chunk, a);
-        const StepResult r = lanej_step(c.s, t, rate * t.L, a);
+        const StepResult r = lanej_step(c.s, t, sz(chunk, a, rate), a);
         const double g_rb = G(c.s.n_rb), g_su = G(c.s.n_su);
         double var = 0.0;
         if (r.hit && prev >= 0) var = fabs(rate - br(chunk - 1, prev));
@@ -2017,20 +2036,28 @@ ABR_HD void look_visit(const LookWeights &w, const TB &t, const BR &br, const GT
     }
     if constexpr (LVL + 1 < H) {
         if (any(c.live))
-            for (int32_t m = 0; m < w.M; m++) look_visit<LVL + 1, H>(w, t, br, G, lat, qt, any, c, c.s.n_rb, c.s.n_su, m, best);
+            for (int32_t m = 0; m < w.M; m++) look_visit<LVL + 1, H>(w, t, br, sz, G, lat, qt, any, c, c.s.n_rb, c.s.n_su, m, best);
     }
 }
 
 // q[a0] of one lane: the least key over the valid sequences that start with a0 from `root` (n_rb_obs / n_su_obs: the lane's
 // clocks at its last reported step), NaN when there is none or the lane is not live
-template <int H, class TB, class BR, class GT, class LAT, class QT, class ANY>
-ABR_HD double look_subtree(const LookWeights &w, const TB &t, const BR &br, const GT &G, const LAT &lat, const QT &qt,
-                           const ANY &any, const LaneJ &root, bool live, int32_t n_rb_obs, int32_t n_su_obs, int32_t a0) {
+template <int H, class TB, class BR, class SZ, class GT, class LAT, class QT, class ANY>
+ABR_HD double look_subtree(const LookWeights &w, const TB &t, const BR &br, const SZ &sz, const GT &G, const LAT &lat,
+                           const QT &qt, const ANY &any, const LaneJ &root, bool live, int32_t n_rb_obs, int32_t n_su_obs,
+                           int32_t a0) {
     LookNode n;
     n.s = root; n.R = 0.0; n.live = live;
     double best = __builtin_nan("");
-    look_visit<0, H>(w, t, br, G, lat, qt, any, n, n_rb_obs, n_su_obs, a0, best);
+    look_visit<0, H>(w, t, br, sz, G, lat, qt, any, n, n_rb_obs, n_su_obs, a0, best);
     return best;
+}
+// without a size table: every target is bitrate x chunk_length
+template <int H, class TB, class BR, class GT, class LAT, class QT, class ANY>
+ABR_HD double look_subtree(const LookWeights &w, const TB &t, const BR &br, const GT &G, const LAT &lat, const QT &qt,
+                           const ANY &any, const LaneJ &root, bool live, int32_t n_rb_obs, int32_t n_su_obs, int32_t a0) {
+    const auto sz = [&](int32_t, int32_t, double rate) { return rate * t.L; };
+    return look_subtree<H>(w, t, br, sz, G, lat, qt, any, root, live, n_rb_obs, n_su_obs, a0);
 }
 
 // the lane's answer from its q column: the first least q(m), or -1 and NaN

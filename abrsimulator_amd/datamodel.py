@@ -56,6 +56,14 @@ class MPD:
         """[video_length][n_rates] bitrates, one row per chunk."""
         return [[float(b) for b in c.bitrates] for c in self.chunk_list()]
 
+    def size_table(self) -> List[List[float]]:
+        """[video_length][n_rates] chunk sizes, one row per chunk: Chunk.sizes where given, else bitrate *
+        chunk_length in float64 (the constant-bitrate relation, Simulator.py:156).  What BatchedMPCController plans on,
+        and what BatchedABREnv(chunk_sizes="mpd") downloads."""
+        L = float(self.chunk_length)
+        return [[float(s) for s in c.sizes] if c.sizes is not None else [float(b) * L for b in c.bitrates]
+                for c in self.chunk_list()]
+
     def chunk_list(self) -> List[Chunk]:
         if isinstance(self.chunks, (list, tuple)):
             return list(self.chunks)

@@ -56,7 +56,7 @@ class BatchedABREnv:
 
     def __init__(self, mpd: MPD, qoe_metric: QOEMetric, network_info: NetworkInfo, n_lanes: int,
                  device="cuda", speed=1.0, auto_reset: bool = False, max_ticks: int = 0,
-                 lane_id_base: int = 0, impl: str = "auto", library: Optional[str] = None):
+                 lane_id_base: int = 0, impl: str = "auto", library: Optional[str] = None, chunk_sizes=None):
         # `library`: a diagnostic build of the same ABI (tools/diag/csrc/Makefile -> tools/diag/lib), by path or file
         # name.  The product library holds only what `auto` can select plus the jump / split / tick cross-checks;
         # impl="async" / "ring3" (pipelines that were measured slower, kept for the parity tests and the records)
@@ -156,6 +156,12 @@ class BatchedABREnv:
             self.set_speed_controller(self.speed_controller)
         if self.br_table is not None:
             self._check(self.lib.abr_env_set_bitrate_table(self._h, _lib.ptr(self.br_table)))
+        # variable-bitrate video: what each chunk weighs (set_chunk_sizes).  None: bitrate * chunk_length, and Chunk.sizes
+        # stays ignored -- MPDs with sizes are handed to the MPC controllers by callers that expect CBR downloads
+        self.sz_table = None
+        self._sz_keep = []
+        if chunk_sizes is not None:
+            self.set_chunk_sizes(chunk_sizes)
         self.obs = torch.zeros(OBS_DIM, self.n_lanes, dtype=torch.float32, device=self.device)
         self.reward = torch.zeros(self.n_lanes, dtype=torch.float32, device=self.device)
         self.done = torch.zeros(self.n_lanes, dtype=torch.uint8, device=self.device)
@@ -207,6 +213,36 @@ class BatchedABREnv:
         # the library holds the table's and the blob's addresses: the model must live as long as it is installed
         self.quality = q
         return q
+
+    def set_chunk_sizes(self, table):
+        """Variable-bitrate video (include/abr_env.h: abr_env_set_size_table): a size table decides what is DOWNLOADED,
+        the bitrates keep deciding what is SCORED.  table: "mpd" (mpd.size_table(): Chunk.sizes where given -- what
+        BatchedMPCController and FastMPCController plan on, so this is what makes them and the environment agree), an
+        array-like [video_length][n_rates] in the ladder's unit x seconds, or None (back to bitrate * chunk_length).
+        Checked on the host: shape, finite, > 0, < 2**960.  Latched like the bitrate table: the next reset of ALL lanes
+        adopts it (a masked reset before that raises); at once on an env that has not been reset yet.  env.sz_table
+        holds the device tensor the library reads."""
+        if table is None:
+            self._check(self.lib.abr_env_set_size_table(self._h, None))
+            self.sz_table = None
+            return None
+        if isinstance(table, str):
+            if table != "mpd":
+                raise ValueError("chunk_sizes must be None, 'mpd' or a [video_length][n_rates] table")
+            table = self.mpd.size_table()
+            if any(len(r) != self.n_rates for r in table):
+                raise ValueError(f"every chunk's sizes must have {self.n_rates} entries")
+        t = torch.as_tensor(table, dtype=torch.float64)
+        if tuple(t.shape) != (self.video_length, self.n_rates):
+            raise ValueError(f"the size table must be [{self.video_length}][{self.n_rates}], got {tuple(t.shape)}")
+        if not bool(torch.isfinite(t).all()) or not bool((t > 0).all()) or not bool((t < 2.0 ** 960).all()):
+            raise ValueError("chunk sizes must be finite, > 0 and below 2**960")
+        t = t.to(self.device).contiguous().clone()
+        self._check(self.lib.abr_env_set_size_table(self._h, _lib.ptr(t)))
+        # the library holds the table's address, and running episodes keep reading the one they started with
+        self._sz_keep.append(t)
+        self.sz_table = t
+        return t
 
     def set_episode_ledger(self, rows):
         """Record every finished episode on the device (include/abr_env.h: abr_episode_ledger): while a ledger is
@@ -477,7 +513,7 @@ class BatchedABREnv:
     def general_instance(self, fused: bool = False) -> bool:
         """True while the handle's step launches run the kernels' general instances (the per-lane play-speed code, chains
         that test their guards in every segment) and not the slimmer no-speeds ones: a latched speed feature, an episode
-        sampler, a quality model, or a configuration that fails the host's proof for the unguarded chains -- a trace
+        sampler, a quality model, a size table in force or pending (set_chunk_sizes), or a configuration that fails the host's proof for the unguarded chains -- a trace
         interval shorter than one 0.01 s tick, max_ticks above 2^20 (include/abr_env.h: abr_env_get_effective_impl)."""
         v = C.c_int32()
         self._check(self.lib.abr_env_get_effective_impl(self._h, int(bool(fused)) | 2, C.byref(v)))

@@ -166,10 +166,11 @@ class ShardedABREnv:
 
     lanes_per_rank: weak scaling instead -- every rank gets that many lanes (total = world * lanes_per_rank).
     `env`: the per-rank stepper (default: a BatchedABREnv on `device`); anything with n_lanes, reset(trace_id, offset),
-    step_random / step_script(out=) works -- the gloo tests put a CPU stand-in there."""
+    step_random / step_script(out=) works -- the gloo tests put a CPU stand-in there.  Further keywords (impl, speed,
+    chunk_sizes, ...) go to that BatchedABREnv as they are: every rank downloads the same size table."""
 
     def __init__(self, mpd, qoe_metric, network_info, total_lanes=None, lanes_per_rank=None, fuse=48, device="cuda",
-                 group=None, rank=None, world=None, gather=True, obs_dim=8, env=None, **env_kw):
+                 group=None, rank=None, world=None, gather=True, obs_dim=8, env=None, chunk_sizes=None, **env_kw):
         if world is None:
             world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         if rank is None:
@@ -189,7 +190,7 @@ class ShardedABREnv:
         if env is None:
             from .env import BatchedABREnv
             env = BatchedABREnv(mpd, qoe_metric, network_info, self.n_lanes, device=self.device,
-                                lane_id_base=self.lane0, **env_kw)
+                                lane_id_base=self.lane0, chunk_sizes=chunk_sizes, **env_kw)
         self.env = env
         # the collective runs whenever a process group exists (a ONE-rank group too: the same code path as N ranks)
         self._do_gather = bool(gather) and dist.is_available() and dist.is_initialized()

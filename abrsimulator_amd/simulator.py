@@ -32,7 +32,10 @@ class _UnitSpeed:
 
 
 class Simulator(object):
-    def __init__(self, AbrController, SpeedController=None, n_lanes=1, device="cuda", speed_controller=None):
+    def __init__(self, AbrController, SpeedController=None, n_lanes=1, device="cuda", speed_controller=None,
+                 chunk_sizes=None):
+        # chunk_sizes: BatchedABREnv's (None, "mpd" or a [video_length][n_rates] table) -- variable-bitrate video
+        self.chunk_sizes = chunk_sizes
         if speed_controller is not None:
             if SpeedController is not None:
                 raise TypeError("give the speed controller once (SpeedController or speed_controller)")
@@ -96,7 +99,7 @@ class Simulator(object):
         speed = (self.speed_controller if isinstance(self.speed_controller, LatencySpeedController)
                  else self._speeds())
         self.env = BatchedABREnv(self.mpd, self.qoe_metric, self.network_info, self.n_lanes,
-                                 device=self.device, speed=speed)
+                                 device=self.device, speed=speed, chunk_sizes=self.chunk_sizes)
         env = self.env
         env.reset(self.trace_id, self.start_offset)
         chunk_id, _, buffer_level, _, _, done = env.mpc_inputs()

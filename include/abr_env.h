@@ -220,9 +220,39 @@ int abr_env_set_speed_rule(abr_env *env, const abr_speed_rule *rule, double *spe
  * chunk's ladder.  Latched like abr_env_set_lane_speeds: picked up by the next reset of ALL lanes. */
 int abr_env_set_bitrate_table(abr_env *env, const double *br_table_dev);
 
+/* Per-chunk SIZES (ABI 4, additive; BUILD-DEFINED: run() knows bitrate x chunk_length only): variable-bitrate video, where
+ * a rung is a nominal quality and its chunks weigh more or less with the scene.  sz_table_dev: float64
+ * [video_length][n_rates], caller-owned device memory, valid from this call until the handle is destroyed or another call
+ * replaces it; unit: the ladder's unit x seconds, what abr_mpc_select's sz_table_dev holds.  NULL restores bitrate x
+ * chunk_length.  The size table decides WHAT IS DOWNLOADED; the bitrate table (or config.ladder) keeps deciding WHAT IS
+ * SCORED.  Below, br(c, a) is the abr_env_set_bitrate_table row, else config.ladder, and sz(c, a) this table.
+ *   The one change: at a call site with chunk c and action a, target_size = sz(c, a) in place of br(c, a) *
+ *     chunk_length (Simulator.py:156).  The bandwidth appended to previous_bandwidths is, as ever, the downloaded size over
+ *     the download time (:164).
+ *   Nothing that reads a bitrate changes: the variance term of the reward and of abr_env_episode_qoe, the episode
+ *     ledger's record, the quality model's u, observation row 1 and abr_mpc_* keep reading br.
+ *   Coverage: every launch kind on implementations 0, 1, 2, 3 and 5.  The diagnostic pipelines 4, 6 and 7 refuse a launch
+ *     with a size table (ABR_E_UNSUPPORTED), as they do a sampler.
+ *   Tree walks: abr_env_lookahead_select, abr_env_plan_select and abr_env_step_plan walk with sz(chunk, a) as each step's
+ *     target; their variance keeps br.
+ *   Rules: ABR_RULE_RATE and ABR_RULE_BOLA compare and divide by what a chunk costs to fetch: while a size table is in
+ *     force their br[m] is e[m] = sz(c, m) / chunk_length, one float64 division, nothing else.  ABR_RULE_BUFFER is
+ *     untouched (its map lives on the nominal ladder), and so is FastMPC's lookup (its table was built from the caller's sz).
+ *   Learned policy (all four engines, both populations): while a size table is in force features 4 + W + m are sz(c, m) in
+ *     place of br(c, m) -- the sizes of the next chunk.  F, feature 1 (br(c - 1, a)), norm_dev and everything downstream
+ *     are unchanged.
+ *   abr_env_fork needs nothing: there is no per-lane state.
+ * Latched exactly like abr_env_set_bitrate_table: the next abr_env_reset of all lanes adopts it, a masked reset while one is
+ * pending is ABR_E_INVALID, on a handle with no episode in flight it takes effect at once, and abr_env_notify_restore expects
+ * the same table to be set.  A handle with a size table runs the kernels' general instances (abr_env_get_effective_impl).
+ * Values must be finite, > 0 and below 2^960.  The library never reads the table on the host, so it cannot refuse a value
+ * outside that range: this is the caller's promise, as for the traces and the bitrate table, and a binding checks it
+ * itself, as abrsimulator_amd.env.BatchedABREnv does.  NULL handle: ABR_E_INVALID. */
+int abr_env_set_size_table(abr_env *env, const double *sz_table_dev);
+
 /* Resume: the whole simulator state is the workspace, so a checkpoint is a copy of it.  After copying
  * a checkpointed workspace into the workspace of a handle built with the same config, lane count
- * and (already set) speeds / bitrate table, call this: it marks the handle as carrying episodes in
+ * and (already set) speeds / bitrate table / size table, call this: it marks the handle as carrying episodes in
  * flight, so that later setter calls are latched again.  It first reads the workspace's layout tag back
  * (ABI 4; one device synchronisation) and returns ABR_E_WORKSPACE -- the handle then stays as it was, the
  * workspace holds the foreign bytes and must be re-initialised by abr_env_reset of all lanes or restored
@@ -254,7 +284,7 @@ int abr_env_has_impl(int32_t impl);
  * one decision (abr_env_step, abr_env_step_mpc, n_steps == 1).  `fused` is 0 or 1; with 2 added to it, 0x100 is added to
  * the answer when the handle's step launches run the kernels' general instances (the form with the per-lane play-speed code
  * and the per-segment chain guards) and not the slimmer no-speeds ones: while a speed feature is latched, a sampler or a
- * quality model is installed, or the configuration fails the host's proof for the unguarded chains (a trace interval
+ * quality model is installed, a size table (abr_env_set_size_table) is in force or pending, or the configuration fails the host's proof for the unguarded chains (a trace interval
  * shorter than one 0.01 s tick, max_ticks above 2^20, a non-finite or absurd ladder x chunk_length, speed or max_buffer). */
 int abr_env_get_effective_impl(abr_env *env, int32_t fused, int32_t *impl_out);
 
@@ -480,7 +510,8 @@ int abr_env_get_state(abr_env *env, abr_env_state_view *view_out);
  * The episode number IS copied, and so are the trace id and start offset: the copy runs the source's episode.  Under an
  * episode sampler a re-arm is keyed by the GLOBAL LANE the copy lives in and by that copied episode number, so source and
  * copy are identical up to their next re-arm and draw different pairs there.  Controller-side state the caller owns (a
- * RobustMPC state, a GRU's hidden rows) is the caller's to move, with the same src / dst.
+ * RobustMPC state, a GRU's hidden rows) is the caller's to move, with the same src / dst.  A size table
+ * (abr_env_set_size_table) needs nothing: it is the handle's, with no per-lane state.
  *
  * abr_env_fork_scratch_bytes is pure arithmetic (video_length and count): for each region in the order above, then q_run,
  * then obs -- reserved whether present or not -- rows * count * element bytes, rounded up to a multiple of 256.
