@@ -117,6 +117,8 @@ struct EnvParams {
     double *sd_lane, *pt_lane;     // per-lane speed*dt and play_time (only touched when lane_speeds != nullptr)
     const double *lane_speeds;     // caller-owned per-lane play speeds [speed_rows][n_lanes], or nullptr: one speed for all lanes
     int32_t speed_rows;            // 1: one constant speed per lane; >= 2: a schedule, one row per played chunk
+    int32_t avail_j_blocks;        // avail_j -- the trace interval avail_tick[c] lies in (abr_tick_tables.h) -- starts this many
+                                   // 256-byte blocks after avail_tick (in the four bytes that were padding: no offset moves)
     int32_t *pl_left, *play_id;    // speed schedule only: playing ticks left in the played chunk, chunks played
     double *pt_sum;                // speed schedule only: sum of play_time over the playing ticks
     const double *br_table;        // caller-owned [video_length][n_rates] per-chunk ladders, or nullptr: `ladder`
@@ -154,7 +156,7 @@ static_assert(sizeof(abrx::SpeedRule) == sizeof(abr_speed_rule) &&
 // restoring a workspace of another version, lane count or configuration would otherwise be reinterpreted with shifted
 // offsets and no error -- sizes can coincide.  kLayoutRev counts layout changes inside one ABI version.
 constexpr uint32_t kTagMagic = 0x57524241u;          // "ABRW"
-constexpr uint32_t kLayoutRev = 1;
+constexpr uint32_t kLayoutRev = 2;                  // 2: the avail_j table, a region of its own in front of the tag
 struct WorkspaceTag {
     uint32_t magic, abi_version, layout_rev, n_rates;
     int64_t n_lanes;
@@ -776,6 +778,7 @@ template <bool SPEEDS = true, class TB = abrx::TablesT<SPEEDS>>
 __device__ inline TB make_tables(const EnvParams &p, bool cascade = true) {
     TB t;
     t.G = p.G; t.interval_tick = p.interval_tick; t.avail_tick = p.avail_tick;
+    t.avail_j = p.avail_tick + (int64_t)p.avail_j_blocks * 64;
     t.L = p.chunk_length; t.sd = p.sd; t.max_buffer = p.max_buffer;
     t.start_up_length = p.start_up_length; t.V = p.video_length; t.max_ticks = p.max_ticks;
     using SP = SpeedParams<SPEEDS>;
@@ -948,6 +951,12 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
     }
 
     if (MODE != 0) {
+        // the fused rollouts know which trace interval every call site but a launch's first lies in (abr_lane_jump.h:
+        // lanej_begin_step_at); a launch of one decision starts from the workspace, so it searches.  Not the rule rollout
+        // (MODE 4) and not the SPEEDS instances: the carried index cost the first a wave per SIMD and the others private
+        // segment (profiles/step_start_resources.txt).
+        constexpr bool kSiteKnown = (MODE == 2 || MODE == 3) && !SPEEDS;
+        int32_t j_site = abrx::kSiteSearch;
         for (int32_t step = 0; step < n_total; step++) {
             const int64_t o = (int64_t)step * p.n_lanes + i;
             float *obs = obs_out ? obs_out + (int64_t)step * ABR_OBS_DIM * p.n_lanes : nullptr;
@@ -957,7 +966,8 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
                 const int32_t a_rule = (MODE == 4) ? rule_action<SPEEDS>(p, rule, i, s.chunk_id, s.last_action, s.buf) : 0;
                 // one burst of loads for everything the step needs (issued before the
                 // policy arithmetic so that the two overlap)
-                const abrx::StepStart st = abrx::lanej_begin_step(s.cur, tb, s.k, s.chunk_id);
+                const abrx::StepStart st = kSiteKnown ? abrx::lanej_begin_step_at(s.cur, tb, s.k, s.chunk_id, j_site)
+                                                      : abrx::lanej_begin_step(s.cur, tb, s.k, s.chunk_id);
                 // ---- the call site: get_next_bitrate's return value (Simulator.py:155-156) ----
                 int32_t a;
                 if (MODE == 1) a = actions[i];
@@ -976,8 +986,9 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
                 } else {
                     const int32_t prev_action = s.last_action;
                     const int32_t chunk = s.chunk_id;
-                    const abrx::StepResult r = abrx::lanej_download_and_wait(
-                        s, tb, st, chunk_target<SPEEDS>(p, chunk, a) /* :156 */, a);
+                    const abrx::StepResult r = kSiteKnown
+                        ? abrx::lanej_download_and_wait_site(s, tb, st, chunk_target<SPEEDS>(p, chunk, a) /* :156 */, a, j_site)
+                        : abrx::lanej_download_and_wait(s, tb, st, chunk_target<SPEEDS>(p, chunk, a) /* :156 */, a);
                     // the reward's two clocks and the observation's four tick-table values in ONE burst of loads
                     const double g_rb = p.G[s.n_rb], g_su = p.G[s.n_su];
                     double o_k = p.G[s.k], o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play], o_rb = g_rb, o_su = g_su;
@@ -1035,6 +1046,8 @@ __global__ ABR_JUMP_BOUNDS(MODE, SAMPLE || LEDGER || QUALITY) void env_jump_kern
                             last_bw = 0.0; hist_n = 0.0; hist_s = 0.0; var_run = 0.0;
                             done = 0;
                             if (!abrx::lanej_wait_call(s, tb)) done |= ABR_DONE_TIMEOUT;
+                            // a fresh cursor, and a call site at the first chunk's availability
+                            if (kSiteKnown) j_site = s.k == tb.avail_tick[0] ? tb.avail_j[0] : abrx::kSiteSearch;
                             o_k = p.G[s.k]; o_pl = SP::lane_speeds(p) ? s.pt : p.GP[s.n_play];
                             o_rb = p.G[s.n_rb]; o_su = p.G[s.n_su];
                         }
@@ -1150,6 +1163,7 @@ struct Layout {
     size_t G, GP, interval_tick, avail_tick;        // table offsets
     size_t f64_state, i64_state, i32_state, u8_state, action_hist, bw_hist, ep_terms;
     size_t mpc_action, mpc_scratch;
+    size_t avail_j;                                  // table (appended: layout 2)
     size_t tag;                                      // the layout tag: the workspace's LAST 256 bytes (WorkspaceTag)
     size_t total;
     int32_t max_ticks, n_intervals;
@@ -1220,6 +1234,7 @@ static int compute_layout(const abr_env_config *c, int64_t n_lanes, Layout *L) {
     L->ep_terms = o; o = align_up(o + sizeof(double) * 4 * N, A);
     L->mpc_action = o; o = align_up(o + sizeof(int32_t) * N, A);
     L->mpc_scratch = o; o = align_up(o + mpc_scratch_bytes_max(N), A);
+    L->avail_j = o; o = align_up(o + sizeof(int32_t) * (V + 2), A);
     L->tag = o; o = align_up(o + sizeof(WorkspaceTag), A);
     L->total = o;
     return ABR_OK;
@@ -1285,6 +1300,7 @@ extern "C" int abr_env_create(const abr_env_config *cfg, const double *traces_de
     p.G = (const double *)(w + L.G); p.GP = (const double *)(w + L.GP);
     p.interval_tick = (const int32_t *)(w + L.interval_tick);
     p.avail_tick = (const int32_t *)(w + L.avail_tick);
+    p.avail_j_blocks = (int32_t)((L.avail_j - L.avail_tick) / 256);   // both 256-byte aligned
     // buffer_level never exceeds max_buffer + chunk_length (a download only starts below max_buffer, :144); a level above
     // the cascade would send its wave through the general chains (abr_lane_jump.h: lanej_drain)
     p.drain = abrx::make_drain_tab(sd, cfg->max_buffer + cfg->chunk_length);
@@ -1316,8 +1332,9 @@ extern "C" int abr_env_create(const abr_env_config *cfg, const double *traces_de
                         hipMemcpyHostToDevice, st);                                            \
     if (he != hipSuccess) { delete e; return fail(ABR_E_HIP, "table upload: %s", hipGetErrorString(he)); }
     UP(p.G, G) UP(p.GP, GP) UP(p.interval_tick, itick) UP(p.avail_tick, atick)
-#undef UP
     he = hipMemsetAsync(w + L.f64_state, 0, L.total - L.f64_state, st);
+    if (he == hipSuccess) { UP(w + L.avail_j, tt.avail_j) }
+#undef UP
     if (he == hipSuccess) he = hipMemsetAsync(p.done, ABR_DONE_EPISODE, N, st);  // not reset yet
     {
         WorkspaceTag &tg = e->tag;

@@ -213,6 +213,7 @@ struct DVars {
     int32_t snap_j, snap_tpos;                 // cursor before the download just issued
     int32_t d_step, d_k, d_chunk, d_ep, offset0, issued_step, issued_k;
     int32_t issued_ndl, issued_avail;          // the download just issued took this many ticks; avail_tick of the chunk after it
+    int32_t d_site;                            // the trace interval d_k lies in, or abrx::kSiteSearch (abr_lane_jump.h: lanej_begin_step_at)
     bool d_alive, was_alive;
     const double *snap_trace;                  // SAMPLE instances only: the cursor's trace before the download just issued
     int32_t snap_tlen;                         // (a speculative re-arm may have moved the cursor to another trace)
@@ -223,6 +224,7 @@ __device__ __forceinline__ void role_d_begin(DVars &v, const EnvParams &p) {
     v.cur.j = 0; v.cur.tpos = 0; v.cur.tlen = 1; v.cur.trace = p.traces;
     v.snap_j = 0; v.snap_tpos = 0; v.d_step = 0; v.d_k = 0; v.d_chunk = 0; v.d_ep = 0; v.offset0 = 0;
     v.issued_step = -1; v.issued_k = -1; v.issued_ndl = 0; v.issued_avail = 0; v.d_alive = false; v.was_alive = false;
+    v.d_site = abrx::kSiteSearch;              // the workspace does not say: a launch's first decision searches
     if (i < p.n_lanes) {
         const int32_t t = p.trace_id[i];
         v.offset0 = p.offset0[i];
@@ -256,7 +258,15 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
         // two-wave kernel -1.6 %, profiles/r02_ab_prefetch.txt; three-wave kernel -3 %, profiles/r03_ab_split3.txt (6);
         // the one-barrier form of round 4 -2 %, profiles/r04_experiments_not_kept.txt (6): 133 VGPRs, and the download
         // wave's 1.4 k cycles move into the player wave's share of the SIMD)
-        const abrx::StepStart st = abrx::lanej_begin_step(v.cur, tb, v.d_k, v.d_chunk);
+        // a fused rollout knows the interval of every call site it forms itself (below); what role_d_validate takes from the
+        // player, and a launch's first, it searches.  One decision per launch always starts from the workspace.  The two-wave
+        // kernel only: the three-wave kernel measured 0.2-1.6 % SLOWER with it (profiles/step_start_ab.json), so its
+        // instances keep the search, and their code is the parent's.
+        constexpr bool kSiteKnown = MODE >= 2 && !ACT_RING;
+        const abrx::StepStart st = kSiteKnown ? abrx::lanej_begin_step_at(v.cur, tb, v.d_k, v.d_chunk, v.d_site)
+                                              : abrx::lanej_begin_step(v.cur, tb, v.d_k, v.d_chunk);
+        // (in the same burst: the interval the NEXT chunk becomes available in)
+        const int32_t avail_j_next = kSiteKnown ? tb.avail_j[v.d_chunk + 1] : abrx::kSiteSearch;
         ABR_STAMP(1);
         int32_t a = -1;
         bool drawn = false;
@@ -275,7 +285,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
                                        (uint32_t)v.d_ep, (uint32_t)p.n_rates);
         if (MODE == 2 && actions_out) actions_out[(int64_t)v.d_step * p.n_lanes + i] = a;
         flags = kRecValid;
-        abrx::Download d; d.dl = 0.0; d.n_dl = 0; d.hit = false;
+        abrx::Download d; d.dl = 0.0; d.n_dl = 0; d.hit = false; d.closed = false; d.next_known = false;
         ABR_STAMP(2);
         if (a < 0 || a >= p.n_rates) flags |= kRecBadAct;
         else d = abrx::lanej_download(v.cur, tb, st, v.d_k,
@@ -291,7 +301,9 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
         else {
             v.d_step++;
             v.d_chunk++;
-            v.d_k = max(v.d_k + d.n_dl, st.avail_next);     // completing tick + 1, or availability (:143)
+            const int32_t k_done = v.d_k + d.n_dl;
+            v.d_k = max(k_done, st.avail_next);             // completing tick + 1, or availability (:143)
+            if (kSiteKnown) v.d_site = k_done >= st.avail_next ? abrx::lanej_site_next(v.cur, d) : avail_j_next;   // ... and the interval that tick lies in
             if (v.d_chunk >= V) {
                 if (p.auto_reset) {            // a fresh episode: clock, cursor and chunk ids restart
                     v.d_chunk = 0; v.d_ep++; v.d_k = tb.avail_tick[0];
@@ -301,6 +313,7 @@ __device__ __forceinline__ void role_d_pre(DVars &v, const EnvParams &p, SplitMa
                         v.cur.tlen = p.trace_len[tr]; v.cur.trace = p.traces + p.trace_off[tr];
                     }
                     abrx::cursor_init(v.cur, v.offset0);
+                    if (kSiteKnown) v.d_site = tb.avail_j[0];
                 } else v.d_alive = false;
             }
             // a call site at or past max_ticks never happens (the player times the lane out,
@@ -338,6 +351,7 @@ __device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const TB
             if constexpr (SAMPLE) { v.cur.trace = v.snap_trace; v.cur.tlen = v.snap_tlen; }
         }
         v.issued_step = -1;
+        v.d_site = abrx::kSiteSearch;          // the player's call site: buffer_full moved it
     } else if (v.d_alive && v.issued_ndl > 0 && v.d_chunk > 0) {
         // (Having the PLAYER flag "within chunk_length of max_buffer" in a spare bit of fb_alive, so that this wave reads
         // nothing more in the common case, lost 0.8 %: the player wave is as critical as this one.  profiles/r05_experiments_not_kept.txt)
@@ -352,6 +366,7 @@ __device__ __forceinline__ void role_d_validate(DVars &v, SplitMail &m, const TB
             int32_t kn;
             if (abrx::lanej_predict_next_call(buf, v.issued_k, v.issued_ndl, v.issued_avail, tb, kn)) {
                 v.d_k = kn;
+                v.d_site = abrx::kSiteSearch;
                 if (kn >= tb.max_ticks) v.d_alive = false;
             }
         }

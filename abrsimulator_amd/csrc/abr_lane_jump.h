@@ -95,6 +95,7 @@ struct TablesT<true> {
     const double *G;               // G[n] = dt added n times to 0.0 (global_time, download_time, ...)
     const int32_t *interval_tick;  // first tick k with int(G[k]/interval) >= j          (:158)
     const int32_t *avail_tick;     // first tick k with int(G[k]/chunk_length) - 1 >= c  (:143)
+    const int32_t *avail_j = nullptr;   // the trace interval avail_tick[c] lies in, -1 where not known; only lanej_begin_step_at reads it
     double L, sd, max_buffer, start_up_length;
     int32_t V, max_ticks;
     bool per_lane_speed;           // each lane carries its own speed*dt and play_time (8f rank 3)
@@ -123,6 +124,7 @@ struct TablesT<false> {
     const double *G;
     const int32_t *interval_tick;
     const int32_t *avail_tick;
+    const int32_t *avail_j = nullptr;
     double L, sd, max_buffer, start_up_length;
     int32_t V, max_ticks;
     static constexpr bool per_lane_speed = false;
@@ -388,15 +390,22 @@ ABR_HD void lanej_idle(LaneJ &s, const TB &t, int32_t m) {
 
 // From a post-head state that is not downloading: advance to the next call site
 // (returns true) or to max_ticks (returns false).
+// how: which of lanej_begin_step_at's cases the call site is -- reached without a wait (kWaitNone), by waiting for the
+// chunk to become available and for nothing else (kWaitAvail: s.k == s.avail_k), or moved by buffer_full (kWaitGated, also
+// when no call site is reached)
+enum { kWaitNone = 0, kWaitAvail = 1, kWaitGated = 2 };
 template <class TB>
-ABR_HD bool lanej_wait_call(LaneJ &s, const TB &t) {
+ABR_HD bool lanej_wait_call(LaneJ &s, const TB &t, int32_t *how = nullptr) {
     const int32_t mt = t.max_ticks;
+    if (how) *how = kWaitNone;
     if (s.k >= s.avail_k && !s.bf) return true;
+    if (how) *how = kWaitGated;
     int32_t w = s.avail_k - s.k;
     if (w < 0) w = 0;
     if (w > mt - s.k) w = mt - s.k;
     lanej_idle(s, t, w);
     if (s.k >= mt) return false;
+    if (how) *how = s.bf ? kWaitGated : kWaitAvail;     // (buffer_full only ever clears during the wait: not full means w > 0)
     if (s.bf) {
         // buffer_full gates the next download (:144): drain until buffer_level < max_buffer
         if (s.su || s.be) {
@@ -439,6 +448,7 @@ struct StepResult {
 // behind; the candidates for all those cases are loaded at once and selected in
 // registers.  The caller can issue this before it computes the action.
 constexpr int kCatch = 4;
+constexpr int32_t kSiteSearch = -1;         // lanej_begin_step_at: the call site's interval is not known
 struct StepStart {
     double c;          // bandwidth * dt of the interval the call site is in (:160)
     double bw_next;    // bandwidth of the next interval
@@ -528,6 +538,39 @@ ABR_HD StepStart lanej_begin_step(Cursor &s, const TB &t, int32_t k, int32_t chu
     return lanej_begin_select(s, t, ld, k);
 }
 
+// The step start of a lane that KNOWS which interval its call site k lies in.  Inside a rollout that is nearly every
+// decision, because a call site is reached in one of three ways:
+//   A  no wait: k is the tick after the completing one.  The cursor is in k's interval already, or exactly one behind when
+//      the completing tick was the last of its interval -- the download knows which (Download::j_next);
+//   B  the lane waited for the chunk to become available (:143) and nothing else: k = avail_tick[c], whose interval depends
+//      on the chunk alone (Tables::avail_j, abr_tick_tables.h);
+//   C  anything else -- buffer_full moved the call site (:144), the first decision after the state was loaded, a call site
+//      the download side took from the player or predicted: not known.
+// j_site >= 0 says "interval_tick[j_site] <= k < interval_tick[j_site + 1]" (the cursor's invariant, and the caller's
+// promise); the trace position follows from the cursor's, which is never ahead of k.  Then the two interval ends and the
+// two samples the step uses are loaded directly: five loads with per-lane addresses in one burst, against the thirteen of
+// lanej_begin_load, no candidate arrays and no select chain.  j_site < 0 (case C) is the search of lanej_begin_step, which
+// defines the result; one such lane sends only itself there, behind a wave-uniform branch that the others skip.
+template <class TB>
+ABR_HD StepStart lanej_begin_step_at(Cursor &s, const TB &t, int32_t k, int32_t chunk_id, int32_t j_site) {
+    const bool search = j_site < 0;
+    const int32_t j = search ? s.j : j_site;                  // (a searching lane loads from its own cursor: in bounds, unused)
+    const int32_t tp = trace_wrap(s.tpos + (j - s.j), s.tlen);
+    const int32_t tn = (tp + 1 == s.tlen) ? 0 : tp + 1;
+    StepStart st;
+    st.ke = t.interval_tick[j + 1];
+    st.ke_next = t.interval_tick[j + 2];
+    st.c = s.trace[tp] * kTickDt;
+    st.bw_next = s.trace[tn];
+    st.tn = tn;
+    st.avail_next = t.avail_tick[chunk_id + 1];
+    if (wave_any(search)) {
+        if (search) return lanej_begin_step(s, t, k, chunk_id);
+    }
+    s.j = j; s.tpos = tp;
+    return st;
+}
+
 // Phase A of one decision: the download side.  Needs nothing of the player state but
 // the call-site tick k: the download cannot pause before it completes, so it is a pure
 // function of (k, cursor, target) -- which is what lets a second thread run the player
@@ -536,7 +579,14 @@ struct Download {
     double dl;        // downloaded_size at the completing tick (:160-163)
     int32_t n_dl;     // ticks it took: download_time = G[n_dl] (:161)
     bool hit;         // false: max_ticks reached first
+    // where the tick after the completing one lies, for lanej_begin_step_at: in the cursor's interval or (closed) in the
+    // next one; next_known == false: in neither for sure (an interval shorter than a tick; no completing tick at all)
+    bool closed, next_known;
 };
+// ... as an interval index
+ABR_HD int32_t lanej_site_next(const Cursor &s, const Download &d) {
+    return d.next_known ? s.j + (d.closed ? 1 : 0) : kSiteSearch;
+}
 
 template <class TB>
 ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int32_t k,
@@ -622,6 +672,12 @@ ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int3
     }
     Download d;
     d.dl = cs.x; d.n_dl = kk - k; d.hit = hit;
+    // Where the tick after the completing one lies: in the cursor's interval, or -- the completing tick was the last of its
+    // interval -- in the next one, provided that one is not empty (an interval shorter than a tick: the search then).  The
+    // proven tables' intervals span at least a tick each (chains_proven), so they do not wait for the look-ahead's last load.
+    // ke is clamped to max_ticks: a download that ends there has no next call site.
+    d.closed = kk >= ke;
+    d.next_known = hit && (TB::kGuards == GUARDS_PROVEN || !d.closed || kk < ke_next);
     return d;
 }
 
@@ -630,7 +686,8 @@ ABR_HD Download lanej_download(Cursor &s, const TB &t, const StepStart &st, int3
 // avail_next = avail_tick[chunk_id + 1].
 template <class TB>
 ABR_HD StepResult lanej_after_download(LaneJ &s, const TB &t, const Download &d,
-                                       int32_t avail_next, int32_t action) {
+                                       int32_t avail_next, int32_t action, int32_t *how = nullptr) {
+    if (how) *how = kWaitGated;               // (lanej_wait_call's, when it runs)
     StepResult r;
     r.bw = 0.0; r.hit = false; r.ended = false; r.timeout = false;
     const int32_t mt = t.max_ticks;
@@ -673,7 +730,7 @@ ABR_HD StepResult lanej_after_download(LaneJ &s, const TB &t, const Download &d,
     if (!r.ended && !r.timeout) {
         s.n_su += s.su ? 1 : 0;                                              // T1 of the next tick
         s.n_rb += (!s.su && s.be) ? 1 : 0;
-        r.timeout = !lanej_wait_call(s, t);                                  // phase B
+        r.timeout = !lanej_wait_call(s, t, how);                             // phase B
     }
     ABR_STAMP(12);
     return r;
@@ -740,6 +797,22 @@ ABR_HD StepResult lanej_download_and_wait(LaneJ &s, const TB &t, const StepStart
                                           double target, int32_t action) {
     const Download d = lanej_download(s.cur, t, st, s.k, target);
     return lanej_after_download(s, t, d, st.avail_next, action);
+}
+// The interval of the call site a step stopped at, for lanej_begin_step_at: how = lanej_wait_call's word, the cursor and the
+// download as the step left them, avail_j_here = avail_j[s.chunk_id] of the chunk that call site downloads.
+ABR_HD int32_t lanej_site_reached(int32_t how, const Cursor &cur, const Download &d, int32_t avail_j_here) {
+    return how == kWaitNone ? lanej_site_next(cur, d) : (how == kWaitAvail ? avail_j_here : kSiteSearch);
+}
+// lanej_download_and_wait that also says which interval the call site it stops at lies in.  avail_j is loaded here, after
+// the chains: one step ahead of its use, and in no register while they run.
+template <class TB>
+ABR_HD StepResult lanej_download_and_wait_site(LaneJ &s, const TB &t, const StepStart &st, double target, int32_t action,
+                                               int32_t &j_site) {
+    const Download d = lanej_download(s.cur, t, st, s.k, target);
+    int32_t how;
+    const StepResult r = lanej_after_download(s, t, d, st.avail_next, action, &how);
+    j_site = lanej_site_reached(how, s.cur, d, t.avail_j[s.chunk_id]);
+    return r;
 }
 
 // begin + download + wait in one call (host harness)

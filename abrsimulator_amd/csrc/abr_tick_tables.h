@@ -21,6 +21,7 @@ struct TickTables {
     std::vector<double> G, GP;            // n-fold sums of dt and of speed*dt
     std::vector<int32_t> interval_tick;   // first tick k with int(G[k]/interval) >= j, INT_MAX past the end
     std::vector<int32_t> avail_tick;      // first tick k with int(G[k]/L) - 1 >= c,    INT_MAX past the end
+    std::vector<int32_t> avail_j;         // the j with interval_tick[j] <= avail_tick[c] < interval_tick[j + 1], -1 past the end
     int32_t play_ticks_per_chunk;         // first n with GP[n] >= L (:185), INT_MAX if none
     int32_t min_interval_ticks;           // shortest interval, in ticks (>= 0)
     double sd;                            // speed * dt as the reference forms it (:182)
@@ -60,6 +61,20 @@ inline TickTables build_tick_tables(double interval, double chunk_length, double
         for (int32_t k = 0; k <= mt && ccur < video_length; k++) {
             int64_t avail = (int64_t)(t.G[k] / chunk_length) - 1;          // :143
             while (ccur <= avail && ccur < video_length) t.avail_tick[ccur++] = k;
+        }
+    }
+    // The trace interval a chunk becomes available in depends on the chunk alone: a lane that waited for availability
+    // (:143) starts its download in interval avail_j[c] whatever it did before (abr_lane_jump.h: lanej_begin_step_at).
+    // -1 -- "not known: search" -- past the end of avail_tick, and where the look-ahead of two interval ends would leave
+    // the table.
+    t.avail_j.assign(t.avail_tick.size(), -1);
+    {
+        size_t j = 0;
+        for (size_t c = 0; c < t.avail_tick.size() && t.avail_tick[c] != INT_MAX; c++) {
+            const int32_t k = t.avail_tick[c];
+            while (j + 1 < t.interval_tick.size() && t.interval_tick[j + 1] <= k) j++;
+            if (j + 2 < t.interval_tick.size() && t.interval_tick[j] <= k && k < t.interval_tick[j + 1])
+                t.avail_j[c] = (int32_t)j;
         }
     }
     t.play_ticks_per_chunk = INT_MAX;
